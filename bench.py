@@ -16,6 +16,9 @@ already resident in HBM.  `roofline` prices the dominant kernel (k_score)
 against HBM bandwidth using ALGORITHMIC bytes and its average
 duration measured with HIP events on the launch stream.  `cpu_baseline` is the
 oracle's restatement of utils/index-search timed on this host (N = 1, rank 0).
+`--dump-outputs DIR`: rank 0 also writes the top-k of the last timed step
+(scores, docs, counts; segments where merged) as DIR/<name>.npy, so that two builds
+run with the same arguments (same seeded inputs) can be compared output for output.
 """
 from __future__ import annotations
 
@@ -192,7 +195,14 @@ def main():
                     help="a task list in the harness's grammar (default: the reference's own, "
                          "tests/golden/benchmark_tasks.json)")
     ap.add_argument("--scorer", default="bm25", choices=["bm25", "tfidf"])
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the results of the last timed step (the "
+                         "merged top-k a caller receives) as DIR/<name>.npy (configs 3 and 5)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.tasks:
+        ap.error("--dump-outputs applies to configs 3 and 5, not to --tasks")
     if args.tasks:
         return main_tasks(args)
     if args.config == 5:
@@ -445,12 +455,21 @@ def main():
     state["work"] = []
     for _ in range(args.steps):
         step()
-    flush()
+    merged = flush()
     state["collect"] = None
     sync()
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        # the last timed step's top-k, before the host-results steps below reuse the buffers:
+        # merged over the segments (multi), else as delivered into the one exchange slot
+        if multi:
+            dump = topk_arrays(merged[0], merged[2], merged[1])
+        else:
+            ex = exchange.ex[(state["it"] - 1) & 1]
+            dump = topk_arrays(ex.send[:nq * k].view(nq, k), ex.send[ex.hit_words:].view(torch.int32)[:nq])
+        write_outputs(args.dump_outputs, dump)
     reruns_timed = total_reruns() - reruns_warm
     # the same steps with the hits copied to host memory in every step (not `value`)
     host_elapsed = None
@@ -735,10 +754,12 @@ def main_config5(args):
         prev = it.pop("prev", None)
         if prev is not None:
             deliver(prev)
+        merged = {}
         for name, e in ex.items():
             with on(name):
-                e.finish(sptrs[name])
+                merged[name] = e.finish(sptrs[name])
         sync()
+        return merged
 
     for _ in range(max(1, args.warmup)):
         step()
@@ -753,11 +774,17 @@ def main_config5(args):
     for _ in range(args.steps):
         step()
         marks.append(time.perf_counter())   # (host clock after each step's submissions: where a stall sits)
-    flush()
+    merged = flush()
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
     marks.append(time.perf_counter())
+    if args.dump_outputs and rank == 0:
+        # the last timed step's two batches, merged over the segments
+        dump = {}
+        for name, (h, s, c) in merged.items():
+            dump.update(topk_arrays(h, c, s, prefix=name + "_"))
+        write_outputs(args.dump_outputs, dump)
     step_marks_ms = [round(1e3 * (b - a), 2) for a, b in zip([t0] + marks[:-1], marks)]
     for b in it["retire"]:
         it["reruns"] = it.get("reruns", 0) + b.reruns()
@@ -1068,6 +1095,46 @@ def kernel_sources_sha():
         if os.path.isfile(p) and n.endswith((".h", ".hip")):
             h.update(open(p, "rb").read())
     return h.hexdigest()[:16]
+
+
+DUMP_MAX_BYTES = 64 << 20
+DUMP_SEED = 7
+
+
+def topk_arrays(hits, counts, segments=None, prefix=""):
+    """A top-k result as plain arrays: hits (int64 tensor [nq][k], one irs_hip_hit each),
+    counts [nq] and, merged over segments, the segment of every hit.  Slots past a query's
+    count hold score 0 and doc / segment -1 (what the buffers keep there is not a result)."""
+    from iresearch_amd import _lib
+    h = hits.cpu().numpy().view(_lib.HIT).reshape(hits.shape)
+    c = counts.cpu().numpy().astype(np.int64)
+    pad = np.arange(h.shape[1])[None, :] >= c[:, None]
+    out = {prefix + "scores": np.where(pad, 0, h["score"]).astype(np.float32),
+           prefix + "docs": np.where(pad, -1, h["doc"].astype(np.int64)).astype(np.float64),
+           prefix + "counts": c.astype(np.float64)}
+    if segments is not None:
+        s = segments.cpu().numpy().astype(np.int64)
+        out[prefix + "segments"] = np.where(pad, -1, s).astype(np.float64)
+    return out
+
+
+def write_outputs(path, arrays):
+    """--dump-outputs: DIR/<name>.npy per array (float32 / float64), each of shape [nq, ...].
+    Over DUMP_MAX_BYTES in all, the same fixed, seeded sample of queries is kept of every
+    array; query_rows.npy says which (all of them otherwise)."""
+    nq = len(next(iter(arrays.values())))
+    per_query = sum(a[0].nbytes if a.ndim > 1 else a.itemsize for a in arrays.values()) + 8
+    budget = DUMP_MAX_BYTES - 4096 * (len(arrays) + 1)      # (room for the .npy headers)
+    rows = np.arange(nq)
+    if nq * per_query > budget:
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(
+            nq, max(1, budget // per_query), replace=False))
+    os.makedirs(path, exist_ok=True)
+    for name, a in list(arrays.items()) + [("query_rows", rows.astype(np.float64))]:
+        a = a if name == "query_rows" else a[rows]
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(path, name + ".npy"), a)
+    log("wrote %d arrays of %d / %d queries to %s" % (len(arrays) + 1, len(rows), nq, path))
 
 
 def measured_traffic(name="traffic_latest.json"):

@@ -7,6 +7,7 @@ enforces it).  See oracle/oracle.h for what is pinned against what.
 from __future__ import annotations
 
 import ctypes as C
+import os
 import subprocess
 from pathlib import Path
 
@@ -158,7 +159,8 @@ def ref():
     global _ref
     if _ref is None:
         so = HERE / "_ref" / "libref_codec.so"
-        if not so.exists() and Path("/root/reference/core/utils").is_dir():
+        # (os.path.isdir: an unreadable parent is "absent", where Path.is_dir raises)
+        if not so.exists() and os.path.isdir("/root/reference/core/utils"):
             subprocess.run(["make", "-C", str(HERE), "ref"], check=True, capture_output=True)
         if not so.exists():
             return None

@@ -431,3 +431,43 @@ def test_bench_config5_is_launchable_on_two_ranks(simlib):
     assert 0 < t["and_doc_and_norm"] <= a["and"] and t["phrase_doc"] > 0
     assert d["config"]["collective"].startswith("irs_hip_topk_allgather")
     assert d["config"]["ranks_seen"] == 2 and d["config"]["rccl_library"]
+
+
+def test_bench_dumps_the_last_timed_step(simlib, tmp_path):
+    """`bench.py --dump-outputs DIR` (one rank, emulator dry run): DIR holds the top-k of the
+    LAST timed step, as float32 / float64 arrays — the same hits and counts as that step's
+    queries run as a batch of their own."""
+    import subprocess
+    import sys
+    from iresearch_amd import search, synth
+    from iresearch_amd.search import BM25
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, IRS_BENCH_SIM=simlib._name, OMP_NUM_THREADS="1")
+    docs, nq, k, warmup, steps = 48_000, 5, 20, 1, 2
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(steps),
+           "--warmup", str(warmup), "--docs", str(docs), "--queries", str(nq), "--k", str(k),
+           "--no-cpu", "--dump-outputs", str(tmp_path / "out")]
+    out = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=900)
+    assert out.returncode == 0, out.stderr[-3000:]
+    got = {n: np.load(tmp_path / "out" / (n + ".npy")) for n in ("scores", "docs", "counts", "query_rows")}
+    assert got["scores"].dtype == np.float32 and got["scores"].shape == (nq, k)
+    assert all(got[n].dtype == np.float64 for n in ("docs", "counts", "query_rows"))
+    assert np.array_equal(got["query_rows"], np.arange(nq))
+    # bench.py's step i runs query set i (seeded): 3 isolated probe steps, the warm-up, the timed
+    # steps; the last timed one is set 3 + warmup + steps - 1
+    i = 3 + warmup + steps - 1
+    seg = synth.build_segment(docs, 4096, first_doc=0)
+    stats = [search.SegmentStats(seg.docs_with_field, seg.total_term_freq,
+                                 np.asarray(seg.metas["docs_count"]))]
+    reader = search.SegmentReader.from_synth(seg, device=0, L=simlib)
+    rows = synth.make_queries(nq, 8, 16, 4096, synth.SEED + 12 + i).astype(np.int64) - 1
+    b = search.QueryBatch(reader, search.prepare_disjunctions(rows, BM25(), stats, [reader], k))
+    hits, counts, _ = b.run().results()
+    b.close()
+    reader.close()
+    assert np.array_equal(got["counts"], counts)
+    for q in range(nq):
+        n = int(counts[q])
+        assert np.array_equal(got["scores"][q, :n], hits["score"][q, :n]), q
+        assert np.array_equal(got["docs"][q, :n], hits["doc"][q, :n]), q
+        assert (got["docs"][q, n:] == -1).all() and (got["scores"][q, n:] == 0).all(), q

@@ -1,0 +1,254 @@
+// batch.h — the state of a batch: what every execution path reads at the top level, and one record
+// per path (work items in doc tiles, joined posting streams, block-driven conjunctions and phrases),
+// for thresholds shared across segments and for a run's place on the streams.
+// Included by irs_hip.hip (one translation unit).
+#pragma once
+
+// (a named namespace: the batch record, at global scope, holds these)
+namespace irs_hip {
+
+constexpr uint32_t kDefaultStride = 64;
+constexpr uint32_t kPilotMargin = 3;   // estimated threshold: aim at margin * k candidates
+constexpr uint32_t kDefaultWgThreads = 512;  // 8 wavefronts share one tile (measured best)
+
+// Tuning and test knobs (environment), read once by irs_hip_batch_create on the caller's thread:
+// a batch keeps what was set when it was created.  (IRS_HIP_POOL_MB, IRS_HIP_PINNED_POOL_MB,
+// IRS_HIP_TRACE and IRS_HIP_ASYNC_RUN are process-wide settings, not batch knobs.)
+struct Knobs {
+  bool join_off = false;     // IRS_HIP_JOIN=0: no joined streams unless irs_hip_batch_set_path asks
+  bool join_counts = true;   // IRS_HIP_JOIN_COUNTS=0: no match counts in joined accumulators
+  int join_and = -1;         // IRS_HIP_JOIN_AND: conjunctions joined never (0) / wherever possible (1)
+  int join_or = -1;          // IRS_HIP_JOIN_OR: the same for plain disjunctions (-1: by cost)
+  int join_half = -1;        // IRS_HIP_JOIN_HALF: paired tiles never (0) / whatever the size (1)
+  uint32_t join_chunk = 0;   // IRS_HIP_JOIN_CHUNK: tiles per k_join_score chunk at most (0: by size)
+  uint32_t join_split_log2 = ~0u;   // IRS_HIP_JOIN_SPLIT_LOG2: a tile's entries among the first 2^v wavefronts only
+  int conj_split_log2 = -1;  // IRS_HIP_CONJ_SPLIT_LOG2: every lead block cut into 2^v pieces
+  uint32_t wg_threads = kDefaultWgThreads;   // IRS_HIP_WG_THREADS: threads per k_pilot / k_score workgroup
+  uint32_t join_threads = 1024;   // IRS_HIP_JOIN_THREADS: ... per k_join_pilot / k_join_score workgroup
+  bool acc64 = false;        // IRS_HIP_ACC=64: 64-bit accumulators whatever the queries
+  static Knobs from_env() {
+    Knobs k;
+    int v = 0;
+    auto set = [&v](const char* name) {
+      const char* e = std::getenv(name);
+      if (e) v = std::atoi(e);
+      return e != nullptr;
+    };
+    if (set("IRS_HIP_JOIN")) k.join_off = v == 0;
+    if (set("IRS_HIP_JOIN_COUNTS")) k.join_counts = v != 0;
+    if (set("IRS_HIP_JOIN_AND")) k.join_and = v != 0;
+    if (set("IRS_HIP_JOIN_OR")) k.join_or = v != 0;
+    if (set("IRS_HIP_JOIN_HALF") && (v == 0 || v == 1)) k.join_half = v;
+    if (set("IRS_HIP_JOIN_CHUNK") && v >= 1 && uint32_t(v) <= kJoinChunkTiles) k.join_chunk = uint32_t(v);
+    if (set("IRS_HIP_JOIN_SPLIT_LOG2")) k.join_split_log2 = uint32_t(v);
+    if (set("IRS_HIP_CONJ_SPLIT_LOG2") && v >= 0 && v <= int(kConjSplitMax)) k.conj_split_log2 = v;
+    if (set("IRS_HIP_WG_THREADS") && (v == 256 || v == 512 || v == 1024)) k.wg_threads = uint32_t(v);
+    if (set("IRS_HIP_JOIN_THREADS") && (v == 256 || v == 512 || v == 1024)) k.join_threads = uint32_t(v);
+    if (set("IRS_HIP_ACC")) k.acc64 = v == 64;
+    return k;
+  }
+};
+
+// A HIP event, created on first use and destroyed with its owner (sync / wait fail on one that
+// was never created)
+struct Event {
+  rt::event_t e{};
+  bool made = false;
+  Event() = default;
+  Event(const Event&) = delete;
+  Event& operator=(const Event&) = delete;
+  ~Event() { if (made) rt::event_destroy(e); }
+  bool create() { return made || (made = rt::event_create(&e)); }
+  bool record(rt::stream_t st) { return create() && rt::event_record(e, st); }
+  bool sync() const { return made && rt::event_sync(e); }
+  bool wait(rt::stream_t st) const { return made && rt::stream_wait(st, e); }   // st waits for it
+};
+
+// Doc-tile units as work items (score.h): k_plan's tables -> work-item lists -> k_pilot -> k_score
+struct TileWork {
+  std::vector<uint32_t> units;
+  DevBuf d_units;
+  // work-item lists of the doc tiles: per-tile item offsets (+ scan scratch) and the 32-byte
+  // records themselves
+  DevBuf d_off, d_scan_parts, d_items, d_args, d_ub;
+  DevBuf d_work;   // k_score's work counter
+  ScoreArgs args{}, args_sent{};
+  bool args_valid = false;
+  uint32_t docs = 0 /* docs per tile, 0 = pick by accumulator width */;
+  uint32_t asked = 0;      // irs_hip_batch_configure's tile (0: ensure_scratch picks one per deal)
+  bool any_and = false;    // some unit counts matches per doc in the tile kernels (min-match)
+  uint32_t n_total = 0;    // doc tiles of all units
+  uint32_t n_max = 0;      // ... of the unit with the most (chunk ids per unit)
+  uint32_t threads = 0;    // threads per k_pilot / k_score workgroup (power of two x 64)
+  uint32_t nw_log2 = 3;    // log2(wavefronts per such workgroup)
+};
+
+// Joined posting streams (join.h): every distinct (segment, term) of the batch decoded once per run
+struct JoinWork {
+  std::vector<uint32_t> units;
+  bool on() const { return !units.empty(); }   // some unit runs on joined streams
+  DevBuf d_streams, d_wgs, d_jterms, d_entries, d_bounds, d_args, d_units, d_order;
+  uint32_t n_max = 0;   // doc tiles of the unit with the most
+  uint32_t n_streams = 0, n_wgs = 0;
+  uint32_t threads = 1024, nw_log2 = 4;   // threads per k_join_pilot / k_join_score workgroup
+  uint64_t entries = 0;
+  bool slack_zeroed = false;   // the readable slack behind d_entries
+  JoinArgs args[2]{};   // plain disjunctions / units with match counts
+  JoinArgs args_sent[2]{};   // ... as the device last got them
+  bool args_valid[2] = {false, false};
+  uint32_t n_plain = 0; // units in d_order: the plain ones first
+  uint32_t first[2][kJoinQueues + 1]{};   // [launch] the queues' first slots in d_order
+  DevBuf d_ctr;                           // [launch][kJoinQueues] work counters
+  uint32_t ctr_init[2][kJoinQueues]{};
+  bool pairs_allowed = true;   // irs_hip_batch_set_paired_tiles (0: never; 1: by size; 2: whatever the size)
+  bool pairs_forced = false;
+  bool pairs_used = false;     // ... and whether the last run's plain disjunctions took them
+};
+
+// Block-driven conjunctions (conj.h) and phrases (phrase.h): a wavefront per block of a unit's lead term
+struct BlockWork {
+  std::vector<uint32_t> units;
+  std::vector<uint32_t> items;   // lead items of every unit
+  uint32_t n_items = 0;
+  uint32_t n_wgs = 0;          // k_conj workgroups
+  uint32_t n_phrase_wgs = 0;   // k_phrase workgroups: kPhraseWaves lead blocks each
+  DevBuf d_units, d_items, d_hist;
+  DevBuf d_item_base, d_unit_items, d_seek, d_recs;   // k_conj_seek
+  DevBuf d_lg;   // [unit] log2 of the pieces a lead block is cut into (ConjItem)
+  DevBuf d_item_hits;   // [lead item] matches (ConjArgs::item_hits, k_conj_hits)
+  DevBuf d_lead_of;   // by_phrase: slot of every unit's lead term
+  DevBuf d_pilot;             // the lead items the pilot pass samples, {unit, item} each
+  uint32_t n_pilot = 0, pilot_stride = 0;
+};
+
+// One threshold per query for its units on the batch's segments (irs_hip_batch_set_shared_threshold)
+// ... across ranks (irs_hip_batch_set_comm): the group histograms and the group sums are summed
+// over the communicator's ranks inside every run
+struct Groups {
+  bool shared = false;
+  uint32_t n = 0;       // groups in force this run (0: none)
+  DevBuf d_of;          // [unit] group + 1, 0: a threshold of its own
+  DevBuf d_members;     // [nq_user][n_segs] unit or 0xFFFFFFFF
+  DevBuf d_hist;        // [nq_user][kBins + 2]
+  DevBuf d_sums;        // [nq_user][kGroupSumWords] + 2 status counters (k_group_sums)
+  DevBuf d_agree;   // one word: the ranks' vote before a collective re-run (all_ranks_can)
+  std::vector<double> upper;   // [unit] a score bound that is the same on every segment, 0: none
+};
+
+// A run's place on the streams, what waits for it, and where its results land on the host
+struct RunSync {
+  // what verify_run waits for: the batch's OWN last run (not whatever else the caller has
+  // queued on the stream since), and the status word that run left in page-locked memory
+  Event done;
+  PinBuf h_status;
+  // irs_hip_batch_plan: the planning stage of the NEXT run was queued ahead (on another stream)
+  Event plan;
+  bool planned = false;        // ... and the next run may use it (same geometry)
+  // a plan stage is queued on some stream and may still be running — whether or not the next run
+  // will use its tables (`planned` is dropped by every setter that re-deals the units; the kernels
+  // it queued keep reading and writing the batch's buffers until `plan`)
+  bool plan_pending = false;
+  // the last copy OUT of the batch's buffers queued by irs_hip_batch_results_to_device (destroy
+  // waits for it and for `done` — never for the stream, which may hold other batches' work)
+  Event used;
+  bool used_pending = false;
+  Event uploaded;   // the first run's table uploads (the device's copy stream)
+  Event prof[2 * IRS_HIP_K_COUNT];   // irs_hip_batch_profile: around every stage of a run
+  PinBuf h_pin;                // page-locked staging for irs_hip_batch_results
+  // irs_hip_batch_results_to_host: hits, counts and totals in page-locked memory of the batch
+  PinBuf h_res;
+  Event host;
+  bool host_pending = false;
+  // irs_hip_batch_run hands the host half of a run (units dealt, streams and work lists built,
+  // uploads and launches queued: ~1 ms for 1000 queries) to the device's worker thread and returns;
+  // every other entry point waits here for it first.  async_rc: what that run returned.
+  std::mutex m;
+  std::condition_variable cv;
+  bool async_pending = false;
+  int async_rc = 0;
+  int async_pref = -1;   // irs_hip_batch_set_async: -1 the process default (IRS_HIP_ASYNC_RUN), 0 / 1
+};
+
+}  // namespace irs_hip
+
+struct irs_hip_comm {
+  int device = 0;
+  int n_ranks = 1, rank = 0;
+  rt::comm::handle_t h = nullptr;
+};
+
+struct irs_hip_batch {
+  irs_hip_segment* seg = nullptr;          // segs[0]: device, CU count
+  std::vector<irs_hip_segment*> segs;      // a batch spans one or more segments of one device
+  uint32_t nq_user = 0;                    // queries per segment
+  uint32_t nq = 0 /* execution units = segments x queries */, jt = 0, k_max = 0;
+  uint32_t stride = kDefaultStride, cand_cap = 0;
+  bool estimate = true;  // k_pilot picks an estimated threshold (falls back to the sound one)
+  uint32_t reruns = 0;   // recoveries so far (underflow or overflow re-runs)
+  uint32_t n_tiles = 0;     // of the segment with the FEWEST tiles (pilot stride, recovery)
+  uint32_t stride_eff = 1;  // pilot stride actually used (>= 2 pilot tiles per segment when possible)
+  bool wand = false;       // irs_hip_batch_set_wand
+  Knobs knobs;             // the environment's tuning / test knobs at create
+  // units by the kernels that execute them: doc tiles (Or, min-match) / lead blocks (And)
+  // (all_tile_units: every doc-tile unit, fixed at create; ensure_scratch deals them to
+  // join.units — plain disjunctions run as joined posting streams, join.h — and tiles.units —
+  // the rest, score.h's work items)
+  // (all_conj_units: every conjunction, fixed at create; ensure_scratch deals them to
+  // join.units — accumulators with match counts, join.h — and blocks.units — block driven, conj.h)
+  std::vector<uint32_t> all_tile_units, all_conj_units;
+  std::vector<uint8_t> count_precise;   // [unit] match counts may share its 32-bit accumulators
+  DevBuf d_min_bin;   // [unit] score bin of the caller's irs::score::Min (irs_hip_batch_set_min_scores)
+  DevBuf d_min_score; // [unit] ... and the score itself (k_select's exact filter)
+  bool has_min = false;
+  // the caller's scores themselves: their bins are worked out when a run's tables go out — AFTER
+  // ensure_scratch, which may change a unit's bin_scale (build_groups across ranks)
+  std::vector<float> min_scores;   // [unit]
+  bool min_dirty = false;
+  bool phrase = false;  // a batch of by_phrase queries (k_phrase instead of k_pilot + k_score)
+  bool acc32 = true;   // 32-bit fixed-point accumulators are precise enough for every query
+  bool scratch_ready = false;
+  std::vector<DevQuery> queries;
+  std::vector<DevQTerm> qterms;
+  DevBuf d_segs, d_queries, d_qterms, d_first, d_tails, d_bstar, d_cands, d_cand_count, d_hits,
+    d_out, d_out_count, d_status;
+  DevBuf d_pruned;    // [unit] u32: block-max pruning skipped something of the unit in this run
+  DevBuf d_zeroed;    // owns d_status, d_bstar, d_cand_count, d_hits, d_touched, d_pruned (views): one fill per run
+  DevBuf d_touched;   // [unit][2] u64: bytes decoded / positions read by the block-driven kernels
+  uint64_t alg_bytes = 0, postings = 0;
+  int path_pref = 0;   // irs_hip_batch_set_path (0 auto, 1 work items, 2 joined streams)
+  irs_hip_comm* comm = nullptr;   // irs_hip_batch_set_comm
+  bool profile = false;
+  bool count_touched = false;   // irs_hip_batch_profile bit 1: the kernels count what they decode
+  rt::stream_t stream = nullptr;
+  bool ran = false;
+  // host -> device tables of the batch: built in page-locked memory, sent with the next run
+  Stager up;
+  TileWork tiles;
+  JoinWork join;
+  BlockWork blocks;
+  Groups groups;
+  RunSync sync;
+};
+
+namespace {
+
+template<typename K>
+bool big_smem(K kernel, size_t bytes) {
+  return rt::allow_dynamic_smem(reinterpret_cast<const void*>(kernel), bytes);
+}
+
+// Candidate slots per query.  An estimated threshold aims at kPilotMargin * k
+// candidates; the sound one admits about k * (pilot stride).
+static const uint32_t* min_bins(const irs_hip_batch* b) {
+  return b->has_min ? b->d_min_bin.as<uint32_t>() : nullptr;
+}
+
+static uint32_t default_cand_cap(const irs_hip_batch* b) {
+  const uint64_t per_k = b->estimate ? 16ull : 4ull * b->stride_eff;
+  uint64_t learned = 0;   // (block-driven units only: tile units cut ties by their per-tile staging)
+  if (b->phrase || !b->all_conj_units.empty())
+    for (const irs_hip_segment* sg : b->segs) learned = std::max<uint64_t>(learned, sg->cand_cap_hint.load());
+  return uint32_t(std::min<uint64_t>(std::max<uint64_t>({per_k * b->k_max, 16384, learned}), 262144));
+}
+
+}  // namespace

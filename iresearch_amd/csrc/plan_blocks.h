@@ -1,0 +1,257 @@
+// plan_blocks.h — host half of the block-driven units (conj.h conjunctions, phrase.h phrases): the
+// lead-item work lists, the pilot pass's sample of them, the k_conj / k_phrase launches.
+// Included by irs_hip.hip (one translation unit).
+#pragma once
+
+namespace {
+
+// The rows of the seek table — the lead items of blocks.units, unit after unit — and the tables of
+// the block-driven kernels; `per_unit` goes to `d_per_unit` (a conjunction's lead-block cut /
+// a phrase's lead term)
+int stage_lead_items(irs_hip_batch* b, DevBuf& d_per_unit, const std::vector<uint32_t>& per_unit) {
+  const uint32_t nq = b->nq;
+  std::vector<uint32_t> item_base(b->blocks.units.size() + 1, 0), unit_items(nq, 0);
+  uint64_t total = 0;
+  for (size_t c = 0; c < b->blocks.units.size(); ++c) {
+    item_base[c] = uint32_t(total);
+    unit_items[b->blocks.units[c]] = uint32_t(total);
+    total += b->blocks.items[c];
+  }
+  if (total > 0x7FFFFFFFull) return IRS_HIP_EUNSUPPORTED;
+  item_base[b->blocks.units.size()] = uint32_t(total);
+  b->blocks.n_items = uint32_t(total);
+  if (!b->blocks.d_item_base.alloc(item_base.size() * 4) ||
+      !b->blocks.d_unit_items.alloc(unit_items.size() * 4) ||
+      !b->blocks.d_seek.alloc((total + 2) * uint64_t(kMaxTerms) * 4) ||
+      !b->blocks.d_recs.alloc((total + 1) * sizeof(ConjItem)) ||
+      !b->blocks.d_item_hits.alloc((total + 1) * 4) ||
+      !b->blocks.d_units.alloc(b->blocks.units.size() * 4) ||
+      !b->blocks.d_items.alloc(b->blocks.items.size() * 4) ||
+      !d_per_unit.alloc(per_unit.size() * 4) ||
+      !b->blocks.d_hist.alloc(uint64_t(nq) * kBins * 4))
+    return IRS_HIP_ENOMEM;
+  if (!b->up.copy(b->blocks.d_item_base.p, item_base.data(), item_base.size() * 4) ||
+      !b->up.copy(b->blocks.d_unit_items.p, unit_items.data(), unit_items.size() * 4) ||
+      !b->up.copy(b->blocks.d_units.p, b->blocks.units.data(), b->blocks.units.size() * 4) ||
+      !b->up.copy(b->blocks.d_items.p, b->blocks.items.data(), b->blocks.items.size() * 4) ||
+      !b->up.copy(d_per_unit.p, per_unit.data(), per_unit.size() * 4))
+    return IRS_HIP_ENOMEM;
+  return IRS_HIP_OK;
+}
+
+// k_phrase work of a phrase batch, built at create: the lead term of a unit is its rarest one; one
+// wavefront per 128-posting block of it (+ one for its vint tail / single doc); records and start
+// blocks of the other terms written by k_conj_seek every run
+int build_phrase_work(irs_hip_batch* b) {
+  std::vector<uint32_t> lead_of(b->nq, 0);
+  for (uint32_t u = 0; u < b->nq; ++u) {
+    const DevQuery& dq = b->queries[u];
+    if (!dq.n_terms) continue;
+    const irs_hip_segment* sg = b->segs[dq.seg];
+    uint32_t best = 0xFFFFFFFFu, items = 0;
+    for (uint32_t j = 0; j < dq.n_terms; ++j) {
+      const DevTerm& t = sg->terms[b->qterms[dq.first_term + j].term];
+      if (t.docs_count < best) {
+        best = t.docs_count;
+        items = t.nblk + ((t.docs_count == 1 || t.tail_n) ? 1u : 0u);
+        lead_of[u] = j;
+      }
+    }
+    // (the lists of the pilot pass: same bookkeeping as for conjunctions)
+    b->blocks.units.push_back(u);
+    b->blocks.items.push_back(items);
+  }
+  if (b->blocks.units.empty()) return IRS_HIP_OK;   // (no query has all its terms in its segment)
+  const int rc = stage_lead_items(b, b->blocks.d_lead_of, lead_of);
+  b->blocks.n_phrase_wgs = (b->blocks.n_items + kPhraseWaves - 1) / kPhraseWaves;
+  return rc;
+}
+
+// k_conj work of the batch's block-driven conjunctions (blocks.units): the lead term of a unit is
+// its first one (sorted by cost at create); one wavefront per 128-posting block of it (+ one for
+// its vint tail / single doc), its record and the other terms' start blocks written by
+// k_conj_seek every run.  Rebuilt whenever ensure_scratch deals the conjunctions anew.
+int build_conj_work(irs_hip_batch* b) {
+  int rc = IRS_HIP_OK;
+  b->blocks.items.clear();
+  b->blocks.n_items = 0;
+  b->blocks.n_wgs = 0;
+  b->blocks.n_pilot = 0;
+  b->blocks.pilot_stride = 0;
+  if (b->blocks.units.empty()) return rc;
+  try {
+    // A lead block whose 128 docs fall into many blocks of the other terms — a rare lead against
+    // frequent terms — is one wavefront decoding those blocks one after the other: it is cut into
+    // 2^lg pieces, a wavefront each (ConjItem).  A lead doc falls into at most one block per term,
+    // and a term has df_j / df_lead blocks per lead doc: W = sum_j min(128, df_j / df_lead) blocks
+    // per lead block; pieces of about 16.  (Measured on the reference's AndHighLow class — lead df
+    // ~280 against 720 k: 0.98 -> 0.11 ms per 256 queries.)  Only while the batch cannot fill the
+    // chip anyway: with more lead blocks than wavefront slots every wavefront's chain hides behind
+    // the others', and the pieces' repeated lead decodes and shared border blocks only add work
+    // (config 5's AND batch: 13.4 -> 15.7 ms with the cut applied to every unit).
+    uint64_t lead_items = 0;
+    for (uint32_t u : b->blocks.units) {
+      const DevQuery& dq = b->queries[u];
+      if (dq.n_terms) lead_items += b->segs[dq.seg]->terms[b->qterms[dq.first_term].term].nblk + 1u;
+    }
+    const bool roomy = lead_items < 2ull * 32ull * b->seg->cus;   // (8 wavefronts per SIMD)
+    const int forced_lg = b->knobs.conj_split_log2;   // tuning / test knob
+    std::vector<uint32_t> split_lg;
+    for (uint32_t u : b->blocks.units) {
+      const DevQuery& dq = b->queries[u];
+      uint32_t items = 0, lg = 0;
+      if (dq.n_terms) {
+        const irs_hip_segment* sg = b->segs[dq.seg];
+        const DevTerm& t = sg->terms[b->qterms[dq.first_term].term];
+        items = t.nblk + ((t.docs_count == 1 || t.tail_n) ? 1u : 0u);
+        uint64_t want = 0;
+        for (uint32_t j = 1; j < dq.n_terms; ++j) {
+          const uint64_t df = sg->terms[b->qterms[dq.first_term + j].term].docs_count;
+          want += std::min<uint64_t>(kBlock, df / std::max<uint32_t>(1u, t.docs_count));
+        }
+        while (roomy && lg < kConjSplitMax && (want >> lg) > 16u) ++lg;
+        if (forced_lg >= 0) lg = uint32_t(forced_lg);
+      }
+      split_lg.push_back(lg);
+      b->blocks.items.push_back(items << lg);
+    }
+    if (const int rc = stage_lead_items(b, b->blocks.d_lg, split_lg)) return rc;
+    b->blocks.n_wgs = (b->blocks.n_items + kConjWaves - 1) / kConjWaves;
+  } catch (...) {
+    rc = IRS_HIP_ENOMEM;
+  }
+  return rc;
+}
+
+// The pilot pass's work list of a block-driven batch (And / by_phrase): lead items
+// {phase, phase + P, ...} of every unit in blocks.units.
+bool ensure_pilot_list(irs_hip_batch* b, uint32_t stride, rt::stream_t st) {
+  if (b->blocks.pilot_stride == stride) return true;
+  std::vector<PhraseWg> pl;
+  for (size_t c = 0; c < b->blocks.units.size(); ++c) {
+    const uint32_t u = b->blocks.units[c];
+    for (uint32_t it = (u * 7u) % stride; it < b->blocks.items[c]; it += stride)
+      pl.push_back(PhraseWg{u, it});
+  }
+  // (the list being replaced may still be read by a run in flight: recoveries come here)
+  if ((b->blocks.d_pilot.p && !rt::sync(st)) ||
+      !b->blocks.d_pilot.alloc(std::max<size_t>(1, pl.size()) * sizeof(PhraseWg)) ||
+      !b->up.copy(b->blocks.d_pilot.p, pl.data(), pl.size() * sizeof(PhraseWg)) || !b->up.flush(st))
+    return false;
+  b->blocks.n_pilot = uint32_t(pl.size());
+  b->blocks.pilot_stride = stride;
+  return true;
+}
+
+// What k_conj and k_phrase read of the batch, the same for both (ConjArgs: passed by value)
+ConjArgs block_args(const irs_hip_batch* b, uint32_t pilot_stride) {
+  ConjArgs a{};
+  a.segs = b->d_segs.as<DevSegment>();
+  a.queries = b->d_queries.as<DevQuery>();
+  a.qterms = b->d_qterms.as<DevQTerm>();
+  a.wgs = nullptr;
+  a.n_items = b->blocks.n_items;
+  a.tails = b->d_tails.as<DevTail>();
+  a.bstar = b->d_bstar.as<uint32_t>();
+  a.cands = b->d_cands.as<uint64_t>();
+  a.cand_count = b->d_cand_count.as<uint32_t>();
+  a.hits = b->d_hits.as<unsigned long long>();
+  a.hist = b->blocks.d_hist.as<uint32_t>();
+  a.touched = b->count_touched ? b->d_touched.as<unsigned long long>() : nullptr;
+  a.seek = b->blocks.d_seek.as<uint32_t>();
+  a.recs = b->blocks.d_recs.as<ConjItem>();
+  a.unit_items = b->blocks.d_unit_items.as<uint32_t>();
+  a.item_hits = b->blocks.d_item_hits.as<uint32_t>();
+  a.jt = b->jt;
+  a.cand_cap = b->cand_cap;
+  a.pilot_stride = pilot_stride;
+  return a;
+}
+
+// Conjunctions: [pilot pass over every P-th lead block -> threshold bins] -> full pass.
+template<int LAYOUT>
+bool launch_conj(irs_hip_batch* b, rt::stream_t st) {
+  if (b->blocks.n_wgs == 0) return true;
+  ConjArgs a = block_args(b, b->stride_eff);
+  a.wand = b->wand ? 1u : 0u;
+  a.pruned = b->d_pruned.as<uint32_t>();
+  if (!ensure_pilot_list(b, a.pilot_stride, st)) return false;
+  if (!rt::dmemset(b->blocks.d_hist.p, 0, b->blocks.d_hist.n, st) ||
+      !rt::dmemset(b->blocks.d_item_hits.p, 0, b->blocks.d_item_hits.n, st))
+    return false;
+  RT_LAUNCH(k_conj_seek, (b->blocks.n_items + kThreads - 1) / kThreads, kThreads, 0, st,
+            b->d_segs.as<DevSegment>(), b->d_queries.as<DevQuery>(), b->d_tails.as<DevTail>(),
+            b->jt, b->blocks.d_units.as<uint32_t>(), b->blocks.d_item_base.as<uint32_t>(),
+            uint32_t(b->blocks.units.size()), static_cast<const uint32_t*>(nullptr),
+            b->blocks.d_lg.as<uint32_t>(), b->blocks.d_seek.as<uint32_t>(), b->blocks.d_recs.as<ConjItem>());
+  if (b->blocks.n_pilot) {
+    ConjArgs p = a;
+    p.wgs = b->blocks.d_pilot.as<PhraseWg>();
+    p.n_pilot = b->blocks.n_pilot;
+    RT_LAUNCH((k_conj<LAYOUT>), (b->blocks.n_pilot + kConjWaves - 1) / kConjWaves, kConjWaves * 64, 0,
+              st, p, 1u);
+  }
+  RT_LAUNCH(k_conj_threshold, uint32_t(b->blocks.units.size()), 64, 0, st,
+            b->d_queries.as<DevQuery>(), b->blocks.d_units.as<uint32_t>(),
+            b->blocks.d_items.as<uint32_t>(), b->blocks.d_hist.as<uint32_t>(), a.pilot_stride,
+            b->estimate ? kPilotMargin : 0u, b->d_bstar.as<uint32_t>(), min_bins(b));
+  RT_LAUNCH((k_conj<LAYOUT>), (b->blocks.n_items + kConjWaves - 1) / kConjWaves, kConjWaves * 64,
+            0, st, a, 0u);
+  RT_LAUNCH(k_conj_hits, uint32_t(b->blocks.units.size()), 64, 0, st, b->blocks.d_units.as<uint32_t>(),
+            b->blocks.d_item_base.as<uint32_t>(), b->blocks.d_item_hits.as<uint32_t>(),
+            b->d_hits.as<unsigned long long>());
+  return rt::last_error_ok();
+}
+
+// by_phrase: lead-item records + start blocks -> pilot pass over every P-th lead block ->
+// threshold bins -> full pass.
+template<int LAYOUT, int MT>
+bool launch_phrase(irs_hip_batch* b, rt::stream_t st) {
+  if (b->blocks.n_phrase_wgs == 0) return true;  // no query has all its terms in its segment
+  const uint32_t stride = b->stride_eff;
+  if (!ensure_pilot_list(b, stride, st) || !rt::dmemset(b->blocks.d_hist.p, 0, b->blocks.d_hist.n, st))
+    return false;
+  ConjArgs a = block_args(b, stride);
+  a.lead_of = b->blocks.d_lead_of.as<uint32_t>();
+  if (!rt::dmemset(b->blocks.d_item_hits.p, 0, b->blocks.d_item_hits.n, st)) return false;
+  RT_LAUNCH(k_conj_seek, (b->blocks.n_items + kThreads - 1) / kThreads, kThreads, 0, st,
+            b->d_segs.as<DevSegment>(), b->d_queries.as<DevQuery>(), b->d_tails.as<DevTail>(),
+            b->jt, b->blocks.d_units.as<uint32_t>(), b->blocks.d_item_base.as<uint32_t>(),
+            uint32_t(b->blocks.units.size()), b->blocks.d_lead_of.as<uint32_t>(),
+            static_cast<const uint32_t*>(nullptr), b->blocks.d_seek.as<uint32_t>(),
+            b->blocks.d_recs.as<ConjItem>());
+  if (b->blocks.n_pilot) {
+    ConjArgs p = a;
+    p.wgs = b->blocks.d_pilot.as<PhraseWg>();
+    p.n_pilot = b->blocks.n_pilot;
+    p.touched = nullptr;
+    if (MT == 2) {
+      RT_LAUNCH(k_phrase2<LAYOUT>, (b->blocks.n_pilot + kPhraseWaves - 1) / kPhraseWaves,
+                kPhraseWaves * 64, 0, st, p, 1u);
+    } else {
+      RT_LAUNCH((k_phrase<LAYOUT, MT>), (b->blocks.n_pilot + kPhraseWaves - 1) / kPhraseWaves,
+                kPhraseWaves * 64, 0, st, p, 1u);
+    }
+  }
+  RT_LAUNCH(k_conj_threshold, uint32_t(b->blocks.units.size()), 64, 0, st,
+            b->d_queries.as<DevQuery>(), b->blocks.d_units.as<uint32_t>(),
+            b->blocks.d_items.as<uint32_t>(), b->blocks.d_hist.as<uint32_t>(), stride,
+            b->estimate ? kPilotMargin : 0u, b->d_bstar.as<uint32_t>(), min_bins(b));
+  if (MT == 2) {
+    RT_LAUNCH(k_phrase2<LAYOUT>, b->blocks.n_phrase_wgs, kPhraseWaves * 64, 0, st, a, 0u);
+  } else {
+    RT_LAUNCH((k_phrase<LAYOUT, MT>), b->blocks.n_phrase_wgs, kPhraseWaves * 64, 0, st, a, 0u);
+  }
+  RT_LAUNCH(k_conj_hits, uint32_t(b->blocks.units.size()), 64, 0, st, b->blocks.d_units.as<uint32_t>(),
+            b->blocks.d_item_base.as<uint32_t>(), b->blocks.d_item_hits.as<uint32_t>(),
+            b->d_hits.as<unsigned long long>());
+  return rt::last_error_ok();
+}
+template<int LAYOUT>
+bool launch_phrase_terms(irs_hip_batch* b, rt::stream_t st) {
+  if (b->jt <= 2) return launch_phrase<LAYOUT, 2>(b, st);
+  if (b->jt <= 4) return launch_phrase<LAYOUT, 4>(b, st);
+  return launch_phrase<LAYOUT, int(kPhraseMaxTerms)>(b, st);
+}
+
+}  // namespace

@@ -1,0 +1,532 @@
+// plan_join.h — host half of the units on joined posting streams (join.h): which units join, the
+// batch's distinct streams and k_join's work list, the shared-threshold groups, the k_join /
+// k_join_pilot / k_join_score launches.  Included by irs_hip.hip (one translation unit).
+#pragma once
+
+namespace {
+
+// Can the batch's doc-tile units run as joined streams?  (Anything else keeps score.h's work
+// items: per-doc match counters, Max / Min merged scores, scorers outside the table family,
+// 64-bit accumulators, a frequency that does not fit an entry.)
+bool join_allowed(const irs_hip_batch* b) {   // batch level
+  if (b->path_pref == IRS_HIP_PATH_ITEMS) return false;
+  if (b->knobs.join_off && b->path_pref != IRS_HIP_PATH_JOINED) return false;   // tuning / test knob
+  // (a unit on joined streams runs exhaustively under ExecutionContext::wand: the top k is the
+  // exhaustive one by construction; pruning stays with the block-driven / work-item kernels)
+  return !b->phrase && b->acc32;
+}
+// Conjunction as joined streams or block driven?  Measured on 10 M docs (tools/sweep.py --op and,
+// GPU time summed over the chip, picoseconds): joined = 4200 per doc tile of the unit (barriers,
+// epilogue: the part that does not depend on the postings) + 1.5 per posting of its terms
+// (k_join_score 0.3 + a share of k_join's decode); block driven = 2300 + 400 x terms per
+// 128-posting block of the rarest term: its decode plus a seek and a block decode in every other
+// term.  The conjunctions of two frequent terms are the ones that join.
+// Returns the picoseconds saved by joining (<= 0: block driven is cheaper).
+int64_t join_and_saving(const irs_hip_batch* b, const DevQuery& dq) {
+  const irs_hip_segment* sg = b->segs[dq.seg];
+  uint64_t sum = 0, lead = ~0ull;
+  for (uint32_t j = 0; j < dq.n_terms; ++j) {
+    const uint64_t df = sg->terms[b->qterms[dq.first_term + j].term].docs_count;
+    sum += df;
+    lead = std::min(lead, df);
+  }
+  const uint64_t tiles = sg->dev.num_docs / kJoinTile + 1;
+  const uint64_t lead_blocks = lead / kBlock + 1;
+  return int64_t(lead_blocks * (2300ull + 400ull * dq.n_terms)) -
+         int64_t(4200ull * tiles + (3ull * sum) / 2);
+}
+// ... and the launches of the joined kernels themselves (k_join, the pilot, one more score
+// kernel) only pay when the conjunctions that would join save more than that together
+constexpr int64_t kJoinAndLaunchCost = 500000000;   // 0.5 ms
+int join_and_forced(const irs_hip_batch* b) {   // -1: decide by cost
+  if (b->path_pref == IRS_HIP_PATH_JOINED) return 1;   // (forced: wherever it is possible)
+  return b->knobs.join_and;   // tuning / test knob (-1: not set)
+}
+// Plain disjunctions as joined streams or as work items?  Measured on one MI355X, BM25, 10 M docs
+// (tools/cost_sweep.py, profiles/r04_sweeps.txt; picoseconds of step time):
+//   joined:     2.9 per posting of every DISTINCT stream (k_join: decode + 4 B written)
+//             + 0.47 per posting a query references + 3800 per (unit, doc tile)
+//   work items: 1.14 per referenced posting + 6200 per (unit, doc tile)
+// A stream pays for itself when it is shared (the headline batch: 5.7 G referenced postings on
+// 0.31 G distinct ones) or when there are many units (the per-tile cost is lower): joining wins
+// iff  2.9 D < 0.67 R + 2400 T.  128 queries x 8 terms without one shared term: 1.51 ms as work
+// items against 1.60 joined; on a corpus of 1000-word docs 0.75 against 1.35.
+bool join_or_pays(const irs_hip_batch* b, const std::vector<uint32_t>& units) {
+  if (units.empty()) return false;
+  uint64_t refs = 0, distinct = 0, tiles = 0;
+  std::vector<std::vector<uint8_t>> seen(b->segs.size());
+  for (uint32_t u : units) {
+    const DevQuery& dq = b->queries[u];
+    const irs_hip_segment* sg = b->segs[dq.seg];
+    tiles += sg->dev.num_docs / kJoinTile + 1;
+    if (seen[dq.seg].empty()) seen[dq.seg].assign(sg->dev.num_terms, 0);
+    for (uint32_t j = 0; j < dq.n_terms; ++j) {
+      const uint32_t term = b->qterms[dq.first_term + j].term;
+      const uint64_t df = sg->terms[term].docs_count;
+      refs += df;
+      if (!seen[dq.seg][term]) {
+        seen[dq.seg][term] = 1;
+        distinct += df;
+      }
+    }
+  }
+  return 29ull * distinct < (67ull * refs) / 10ull + 24000ull * tiles;
+}
+int join_or_forced(const irs_hip_batch* b) {   // -1: decide by cost
+  if (b->path_pref == IRS_HIP_PATH_JOINED) return 1;
+  return b->knobs.join_or;   // tuning / test knob (-1: not set)
+}
+bool unit_counts_matches(const DevQuery& dq) {   // min-match / the kMin disjunction of two
+  return (dq.op & 0xFF) == 1 || query_min_both(dq.op);
+}
+bool unit_joinable(const irs_hip_batch* b, uint32_t u) {
+  const DevQuery& dq = b->queries[u];
+  if (query_min_both(dq.op) || query_merge(dq.op) != kScoreSum) return false;
+  if ((dq.op & 0xFF) != 0) {
+    // min-match / conjunction: the match count rides in the accumulator's low bits (join.h
+    // COUNT) where that costs no precision that matters
+    if (!dq.n_terms || !b->count_precise[u] || !b->knobs.join_counts) return false;
+  }
+  const irs_hip_segment* sg = b->segs[dq.seg];
+  for (uint32_t j = 0; j < dq.n_terms; ++j) {
+    const DevQTerm& qt = b->qterms[dq.first_term + j];
+    if (!table_kind(qt.kind) || qt.cache_id >= kMaxCaches) return false;
+    if (sg->terms[qt.term].tf_bound > kJoinTfMax) return false;
+  }
+  return true;
+}
+
+// The batch's distinct (segment, term) streams, k_join's work list and the per-(unit, term)
+// records of k_join_score.  Static per batch: built once, the kernels refill the entries and
+// boundaries in every run.
+bool build_streams(irs_hip_batch* b) {
+  struct WgRef { uint32_t stream, first; };   // a k_join workgroup before its record is made
+  std::unique_ptr<HostTrace> tr(new HostTrace("  streams: distinct terms"));
+  auto lap = [&](const char* what) { tr.reset(); tr.reset(new HostTrace(what)); };
+  std::vector<StreamRec> streams;
+  std::vector<WgRef> wgs;
+  std::vector<JoinTerm> jterms(b->qterms.size());
+  // A stream = a distinct (segment, term, scorer signature) of the joined units: the signature
+  // — (kind, norm_const, norm_length) — is normally ONE per batch.  stream_of[unit term] by an
+  // open-addressing table: the streams come out in first-use order.
+  struct Sig { int32_t kind; float nc, nl; };
+  std::vector<Sig> sigs;
+  std::vector<uint32_t> stream_of(b->qterms.size(), 0xFFFFFFFFu);
+  std::vector<uint8_t> stream_sig;
+  {
+    size_t slots = 64;
+    size_t n_keys = 0;
+    for (uint32_t u : b->join.units) n_keys += b->queries[u].n_terms;
+    while (slots < 2 * n_keys + 2) slots <<= 1;
+    std::vector<uint64_t> hkey(slots, ~0ull);
+    std::vector<uint32_t> hval(slots, 0);
+    for (uint32_t u : b->join.units) {
+      const DevQuery& dq = b->queries[u];
+      for (uint32_t j = 0; j < dq.n_terms; ++j) {
+        const DevQTerm& qt = b->qterms[dq.first_term + j];
+        uint32_t sg_id = 0;
+        for (; sg_id < sigs.size(); ++sg_id)
+          if (sigs[sg_id].kind == qt.kind && sigs[sg_id].nc == qt.norm_const && sigs[sg_id].nl == qt.norm_length) break;
+        if (sg_id == sigs.size()) {
+          if (sigs.size() >= 255) return false;
+          sigs.push_back(Sig{qt.kind, qt.norm_const, qt.norm_length});
+        }
+        if (dq.seg >= (1u << 24)) return false;
+        const uint64_t key = (uint64_t(sg_id) << 56) | (uint64_t(dq.seg) << 32) | qt.term;
+        size_t h = size_t((key * 0x9E3779B97F4A7C15ull) >> 32) & (slots - 1);
+        while (hkey[h] != ~0ull && hkey[h] != key) h = (h + 1) & (slots - 1);
+        if (hkey[h] == ~0ull) {
+          hkey[h] = key;
+          hval[h] = uint32_t(streams.size());
+          StreamRec r{};
+          r.seg = dq.seg;
+          r.term = qt.term;
+          r.n = b->segs[dq.seg]->terms[qt.term].docs_count;
+          streams.push_back(r);
+          stream_sig.push_back(uint8_t(sg_id));
+        }
+        stream_of[dq.first_term + j] = hval[h];
+      }
+    }
+  }
+  uint64_t entries = 0, bounds = 0;
+  std::vector<uint64_t> ent_off, bnd_off;
+  for (size_t si = 0; si < streams.size(); ++si) {
+    const irs_hip_segment* sg = b->segs[streams[si].seg];
+    const DevTerm& t = sg->terms[streams[si].term];
+    ent_off.push_back(entries);
+    bnd_off.push_back(bounds);
+    const uint32_t n_tiles = (sg->dev.num_docs + kJoinTile - 1) / kJoinTile;
+    const uint32_t nb = t.nblk + ((t.docs_count == 1 || t.tail_n) ? 1u : 0u);
+    for (uint32_t first = 0; first < nb; first += kJoinBlocks)
+      wgs.push_back(WgRef{uint32_t(si), first});
+    entries += t.docs_count;
+    bounds += uint64_t(n_tiles) + 1;
+  }
+  if (wgs.size() > 0x7FFFFFFFull) return false;
+  lap("  streams: work list order");
+  // k_join reads a norm byte per posting: launched term after term, the workgroups in flight
+  // would touch the whole norm column at once (10 MB at 10 M docs against 4 MB of L2 per XCD).
+  // Ordered by where in the doc space a workgroup's blocks lie — estimated as its position
+  // inside its list — the ones in flight share a doc range, i.e. norm cache lines.
+  {
+    // (a counting sort over 1024 positions per segment: this runs once per batch on the host,
+    // in front of the batch's first kernel)
+    constexpr uint32_t kPos = 1024;
+    std::vector<uint32_t> key(wgs.size()), start(b->segs.size() * kPos + 1, 0);
+    for (size_t i = 0; i < wgs.size(); ++i) {
+      const StreamRec& sr = streams[wgs[i].stream];
+      const DevTerm& t = b->segs[sr.seg]->terms[sr.term];
+      const uint32_t nb = t.nblk + ((t.docs_count == 1 || t.tail_n) ? 1u : 0u);
+      const uint64_t at = (uint64_t(2u * wgs[i].first + kJoinBlocks) * kPos) / (2ull * (nb + kJoinBlocks));
+      key[i] = sr.seg * kPos + uint32_t(std::min<uint64_t>(at, kPos - 1));
+      ++start[key[i] + 1];
+    }
+    for (size_t k = 1; k < start.size(); ++k) start[k] += start[k - 1];
+    std::vector<WgRef> sorted(wgs.size());
+    for (size_t i = 0; i < wgs.size(); ++i) sorted[start[key[i]]++] = wgs[i];
+    wgs.swap(sorted);
+  }
+  lap("  streams: buffers");
+  if (!b->join.d_entries.alloc((entries + kJoinSlack) * 4) || !b->join.d_bounds.alloc((bounds + 1) * 4) ||
+      !b->join.d_streams.alloc(std::max<size_t>(1, streams.size()) * sizeof(StreamRec)) ||
+      !b->join.d_wgs.alloc(std::max<size_t>(1, wgs.size()) * sizeof(JoinWg)) ||
+      !b->join.d_jterms.alloc(jterms.size() * sizeof(JoinTerm)) ||
+      !b->join.d_args.alloc(2 * sizeof(JoinArgs)) ||
+      !b->join.d_units.alloc(b->join.units.size() * 4) ||
+      !b->join.d_order.alloc(b->join.units.size() * 4))
+    return false;
+  // k_join_score's queues (JoinArgs): per launch — the plain disjunctions, then the units with
+  // match counts — the units sorted by (segment, heaviest term) and cut into kJoinQueues runs of
+  // about equal work, one queue per XCD: the workgroups that share an L2 work on units that share
+  // their longest stream (and the same doc range: chunk-major within a queue).
+  lap("  streams: queue order");
+  std::vector<uint32_t> order;
+  {
+    struct Item { uint64_t work; uint64_t key; uint32_t unit; };
+    b->join.n_plain = 0;
+    for (uint32_t part = 0; part < 2; ++part) {
+      std::vector<Item> items;
+      for (uint32_t u : b->join.units) {
+        const DevQuery& dq = b->queries[u];
+        if ((query_need(dq.op) > 1u) != (part == 1u)) continue;
+        uint64_t w = 0, top = 0, top_term = 0;
+        for (uint32_t j = 0; j < dq.n_terms; ++j) {
+          const uint32_t term = b->qterms[dq.first_term + j].term;
+          const uint64_t df = b->segs[dq.seg]->terms[term].docs_count;
+          w += df;
+          if (df > top) { top = df; top_term = term; }
+        }
+        items.push_back({w, (uint64_t(dq.seg) << 32) | top_term, u});
+      }
+      if (part == 0) b->join.n_plain = uint32_t(items.size());
+      std::stable_sort(items.begin(), items.end(),
+                       [](const Item& x, const Item& y) { return x.key < y.key; });
+      uint64_t total = 0;
+      for (const Item& it : items) total += it.work + 1;
+      uint32_t (&first)[kJoinQueues + 1] = b->join.first[part];
+      size_t at = 0;
+      uint64_t done = 0;
+      for (uint32_t g = 0; g < kJoinQueues; ++g) {
+        first[g] = uint32_t(order.size());
+        const uint64_t goal = total * (g + 1) / kJoinQueues;
+        const size_t from = at;
+        while (at < items.size() && (done < goal || g + 1 == kJoinQueues)) done += items[at++].work + 1;
+        // (round 6: the units of a queue by decreasing work instead — longest processing time first
+        // within every chunk round — changes nothing: 0.956 ms either way for a 1.25 M-doc share)
+        for (size_t i = from; i < at; ++i) order.push_back(items[i].unit);
+      }
+      first[kJoinQueues] = uint32_t(order.size());
+    }
+  }
+  for (size_t i = 0; i < streams.size(); ++i) {
+    streams[i].entries = reinterpret_cast<uint64_t>(b->join.d_entries.as<uint32_t>() + ent_off[i]);
+    streams[i].bounds = reinterpret_cast<uint64_t>(b->join.d_bounds.as<uint32_t>() + bnd_off[i]);
+    streams[i].n_tiles = (b->segs[streams[i].seg]->dev.num_docs + kJoinTile - 1) / kJoinTile;
+    const Sig& sig = sigs[stream_sig[i]];
+    streams[i].kind = sig.kind;
+    streams[i].nc = sig.nc;
+    streams[i].nl = sig.nl;
+  }
+  for (irs_hip_segment* sg : b->segs)
+    if (prepare_posting_norms(sg) != IRS_HIP_OK) return false;
+  lap("  streams: k_join records");
+  // the workgroups' records (JoinWg: everything k_join reads before its first payload byte)
+  JoinWg* wg_recs = static_cast<JoinWg*>(b->up.put(b->join.d_wgs.p, wgs.size() * sizeof(JoinWg)));
+  if (!wg_recs && !wgs.empty()) return false;
+  for (size_t i = 0; i < wgs.size(); ++i) {
+    const StreamRec& sr = streams[wgs[i].stream];
+    const irs_hip_segment* sg = b->segs[sr.seg];
+    const DevSegment& ds = sg->dev;
+    const DevTerm& t = sg->terms[sr.term];
+    JoinWg& w = wg_recs[i];
+    w.entries = sr.entries;
+    w.bounds = sr.bounds;
+    w.doc = reinterpret_cast<uint64_t>(ds.doc) + t.doc_start;
+    w.dir = reinterpret_cast<uint64_t>(ds.blk_dir + t.dir_off);
+    const bool tiny = sg->d_pnorm.p != nullptr;
+    w.pnorm = tiny ? reinterpret_cast<uint64_t>(sg->d_pnorm.as<uint8_t>() + t.dir_off * kBlock) : 0ull;
+    w.tail_norms = tiny ? reinterpret_cast<uint64_t>(sg->d_tail_norms.as<uint8_t>() + t.tail_row) : 0ull;
+    w.tail_docs = reinterpret_cast<uint64_t>(ds.tail_docs + t.tail_row);
+    w.tail_freqs = reinterpret_cast<uint64_t>(ds.tail_freqs + t.tail_row);
+    w.first = wgs[i].first;
+    w.nblk = t.nblk;
+    w.tail_n = t.docs_count == 1u ? 1u : t.tail_n;
+    w.tail_base = t.nblk ? t.tail_base : 0u;
+    w.last_doc = t.last_doc;
+    w.n_tiles = (ds.num_docs + kJoinTile - 1) / kJoinTile;
+    w.n = sr.n;
+    w.dead_lo = uint32_t(reinterpret_cast<uint64_t>(ds.dead));
+    w.dead_hi = uint32_t(reinterpret_cast<uint64_t>(ds.dead) >> 32);
+    w.pad = 0;
+    w.pk = reinterpret_cast<uint64_t>(ds.pk);
+    w.pad2 = 0;
+  }
+  lap("  streams: per-term records");
+  for (uint32_t u : b->join.units) {
+    DevQuery& dq = b->queries[u];
+    const uint32_t rows = table_rows(dq.n_caches);
+    for (uint32_t j = 0; j < dq.n_terms; ++j) {
+      const DevQTerm& qt = b->qterms[dq.first_term + j];
+      const size_t sid = stream_of[dq.first_term + j];
+      JoinTerm& jt = jterms[dq.first_term + j];
+      jt.pad[0] = jt.pad[1] = 0;
+      jt.entries = streams[sid].entries;
+      jt.bounds = streams[sid].bounds;
+      jt.cs = qt.c0 * dq.fx_mul;
+      // (the form only matters for a term with frequencies beyond the table's rows: a TF-IDF
+      // batch whose terms all fit the tables runs the table-only loop like a BM25 one)
+      const bool general = qt.pad1 >= rows;
+      jt.mode = (qt.cache_id * rows * 1024u) |
+                (general ? kJoinGeneral | (sqrt_kind(qt.kind) ? kJoinSqrt : 0u) : 0u);
+    }
+  }
+  // (the slack behind the last stream is only ever read by masked-off look-ahead: zero it once)
+  b->join.slack_zeroed = false;   // (run_impl zeroes it on the run's stream)
+  if (!b->up.copy(b->join.d_streams.p, streams.data(), streams.size() * sizeof(StreamRec)) ||
+      !b->up.copy(b->join.d_jterms.p, jterms.data(), jterms.size() * sizeof(JoinTerm)) ||
+      !b->up.copy(b->join.d_units.p, b->join.units.data(), b->join.units.size() * 4) ||
+      !b->up.copy(b->join.d_order.p, order.data(), order.size() * 4))
+    return false;
+  b->join.n_streams = uint32_t(streams.size());
+  b->join.n_wgs = uint32_t(wgs.size());
+  b->join.entries = entries;
+  return true;
+}
+
+bool launch_join(irs_hip_batch* b, rt::stream_t st) {
+  if (!b->join.n_wgs) return true;
+  with_layout(b->seg->dev.layout, [&](auto L) {
+    RT_LAUNCH((k_join<decltype(L)::value>), b->join.n_wgs, kThreads, 0, st, b->join.d_wgs.as<JoinWg>());
+  });
+  return rt::last_error_ok();
+}
+
+// Groups of a batch over several segments (irs_hip_batch_set_shared_threshold): the units of one
+// query — where every one of them runs on joined streams and they bin scores alike (the bins
+// span [0, upper bound of the query's score]: equal for scorers whose bound does not depend on the
+// segment's frequencies).  Anything else keeps a threshold per unit.
+bool build_groups(irs_hip_batch* b) {
+  b->groups.n = 0;
+  const uint32_t n_segs = uint32_t(b->segs.size());
+  const bool across = b->comm != nullptr && !b->phrase;
+  if (!across && (!b->groups.shared || n_segs < 2 || n_segs > 64 || b->join.units.empty())) return true;
+  const uint32_t nq_user = b->nq_user;
+  std::vector<uint8_t> is_join(b->nq, 0);
+  for (uint32_t u : b->join.units) is_join[u] = 1;
+  std::vector<uint32_t> group_of(b->nq, 0), members(size_t(nq_user) * n_segs, 0xFFFFFFFFu);
+  uint32_t grouped = 0;
+  for (uint32_t g = 0; g < nq_user && n_segs <= 64; ++g) {
+    bool ok = true;
+    uint32_t live = 0;
+    for (uint32_t sgi = 0; sgi < n_segs && ok; ++sgi) {
+      const uint32_t u = sgi * nq_user + g;
+      const DevQuery& dq = b->queries[u];
+      if (!dq.n_terms) continue;   // (nothing of the query in this segment)
+      ok = is_join[u] != 0;
+      if (across) {
+        // the other ranks' units cannot be asked: only a bound that every segment of the index
+        // arrives at by itself qualifies (the boosts of ALL the query's terms, present or not)
+        ok = ok && b->groups.upper[u] > 0.0;
+      } else {
+        for (uint32_t s2 = 0; s2 < sgi && ok; ++s2) {
+          const DevQuery& other = b->queries[s2 * nq_user + g];
+          if (other.n_terms) ok = other.bin_scale == dq.bin_scale && other.k == dq.k;
+        }
+      }
+      ++live;
+    }
+    if (!ok || live < (across ? 1u : 2u)) continue;
+    for (uint32_t sgi = 0; sgi < n_segs; ++sgi) {
+      const uint32_t u = sgi * nq_user + g;
+      if (!b->queries[u].n_terms) continue;
+      if (across) b->queries[u].bin_scale = float(double(kBins) / b->groups.upper[u]);
+      group_of[u] = g + 1;
+      members[size_t(g) * n_segs + sgi] = u;
+    }
+    ++grouped;
+  }
+  // (across ranks the collectives run whatever this rank's own units look like)
+  if (!grouped && !across) return true;
+  if (!b->groups.d_of.alloc(group_of.size() * 4) || !b->groups.d_members.alloc(members.size() * 4) ||
+      !b->groups.d_hist.alloc(uint64_t(nq_user) * (kBins + 2) * 4) ||
+      !b->groups.d_sums.alloc((uint64_t(nq_user) * kGroupSumWords + 2) * 4) ||
+      !b->up.copy(b->groups.d_of.p, group_of.data(), group_of.size() * 4) ||
+      !b->up.copy(b->groups.d_members.p, members.data(), members.size() * 4))
+    return false;
+  b->groups.n = nq_user;
+  return true;
+}
+
+bool launch_join_pilot(irs_hip_batch* b, rt::stream_t st) {
+  const size_t smem = JoinOff::end + kBins * sizeof(uint32_t);
+  if (!big_smem(k_join_pilot, smem)) return false;
+  RT_LAUNCH(k_join_pilot, uint32_t(b->join.units.size()), b->join.threads, smem, st,
+            b->join.d_units.as<uint32_t>(), b->d_queries.as<DevQuery>(),
+            b->d_qterms.as<DevQTerm>(), b->join.d_jterms.as<JoinTerm>(), b->stride_eff,
+            b->join.nw_log2, b->d_bstar.as<uint32_t>(), b->estimate ? kPilotMargin : 0u,
+            min_bins(b), b->groups.n ? b->groups.d_of.as<uint32_t>() : nullptr,
+            b->groups.d_hist.as<uint32_t>());
+  return rt::last_error_ok();
+}
+
+// One threshold per group from the summed pilot histograms — summed over the ranks first when the
+// batch has a communicator: the units of a query on ALL segments of the index then admit together
+// what one heap over all segments would (index-search.cpp:719-779).
+bool launch_group_threshold(irs_hip_batch* b, rt::stream_t st) {
+  if (!b->groups.n) return true;
+  if (b->comm && !b->phrase &&
+      !rt::comm::all_reduce_u32(b->comm->h, b->groups.d_hist.p, size_t(b->groups.n) * (kBins + 2), st))
+    return false;
+  RT_LAUNCH(k_group_threshold, b->groups.n, 64, 0, st, b->d_queries.as<DevQuery>(),
+            b->groups.d_members.as<uint32_t>(), uint32_t(b->segs.size()),
+            b->groups.d_hist.as<uint32_t>(), b->estimate ? kPilotMargin : 0u, min_bins(b),
+            b->d_bstar.as<uint32_t>());
+  return rt::last_error_ok();
+}
+
+// Paired tiles (join.h join_pairs) for the launch of the plain disjunctions: no segment of theirs
+// has deleted docs (their entries leave the doc order k_join_rescore searches in).
+// IRS_HIP_JOIN_HALF=0 / irs_hip_batch_set_paired_tiles(0) keeps the 32-bit tiles (A/B runs, tests:
+// the two must agree bit for bit).
+bool join_half_ok(const irs_hip_batch* b) {
+  if (b->knobs.join_half == 0) return false;
+  if (!b->join.pairs_allowed || !b->acc32 || !b->join.n_plain) return false;
+  // Where it pays (measured on one MI355X, GPU time summed over the chip): a (unit, doc tile)
+  // visited in a pair saves ~1.4 ns — half of that when the batch is too small to keep the chip
+  // busy through the tail of the work queue (fewer than ~400 k visits) —, a look-up of
+  // k_join_rescore costs ~40 ps, and a unit looks up about min(3 k / G, k) docs in each of its
+  // terms (G: the units that share its threshold — the segments of a batch with a shared
+  // threshold times the ranks of its communicator; 3 = kPilotMargin).  10 M docs in one segment,
+  // k = 1000: 1.14 us saved against 0.35 per unit (5.65 -> 4.74 ms per 1000 units); a 1.25 M-doc
+  // share of it alone: 0.07 against 0.2 (stays on 32-bit tiles: 0.97 against 1.10 ms); the
+  // same as 8 segments of one batch: 0.14 against 0.08 (5.79 -> 5.27 ms).
+  // IRS_HIP_JOIN_HALF=1 / set_paired_tiles(2) pair whatever the size (tests on small segments).
+  const bool forced = b->join.pairs_forced || b->knobs.join_half == 1;
+  uint64_t visits = 0, lookups = 0;
+  for (uint32_t u : b->join.units) {
+    const DevQuery& dq = b->queries[u];
+    if (query_need(dq.op) > 1u) continue;
+    if (b->segs[dq.seg]->dev.dead) return false;
+    const uint64_t group = uint64_t((b->groups.shared || b->comm) ? b->segs.size() : 1) *
+                           uint64_t(b->comm ? std::max(1, b->comm->n_ranks) : 1);
+    visits += b->segs[dq.seg]->dev.num_docs / kJoinTile + 1;
+    lookups += std::min<uint64_t>((uint64_t(kPilotMargin) * dq.k + group - 1) / group, uint64_t(dq.k) + 64) *
+               dq.n_terms;
+  }
+  if (!forced && (visits >= 400000 ? 1400ull : 700ull) * visits <= 40ull * lookups) return false;
+  return true;
+}
+
+bool launch_join_score(irs_hip_batch* b, rt::stream_t st) {
+  const size_t smem = JoinOff::end;
+  if (!big_smem(k_join_score<kJKPlain>, smem) || !big_smem(k_join_score<kJKCount>, smem) ||
+      !big_smem(k_join_score<kJKHalf>, smem))
+    return false;
+  const bool half = join_half_ok(b);
+  b->join.pairs_used = half;
+  const uint32_t waves = b->join.threads / 64;
+  uint32_t per_cu = uint32_t((160u * 1024u) / smem);
+  per_cu = std::max<uint32_t>(1, std::min<uint32_t>(per_cu, 32u / waves));
+  // chunks of up to kJoinChunkTiles tiles, the unit's tiles cut evenly (102 tiles: 4 x 26, not
+  // 3 x 32 + 6 — a short last chunk pays the whole per-chunk prologue for a few tiles).  A small
+  // batch takes shorter chunks: with fewer than ~20 chunks per resident workgroup the last round
+  // of the work queue leaves CUs idle (1000 units x 102 tiles: 8 chunks per workgroup at 26 tiles,
+  // 1.12 ms; 21 at 10 tiles, 0.95 ms — profiles/r05_chunks.txt), while a large batch loses to the
+  // per-chunk prologue below 26 (10 M docs: 5.61 ms at 32, 5.88 at 16, 6.50 at 8).
+  // (paired tiles: up to kJoinChunkTiles = 64 tiles = 32 visits per chunk, 4.98 -> 4.91 ms)
+  auto chunking = [&](uint32_t cap, uint32_t& cpq, uint32_t& chunk_tiles) {
+    const uint64_t tiles = uint64_t(b->join.units.size()) * b->join.n_max;
+    const uint64_t wgs = uint64_t(b->seg->cus) * per_cu;
+    uint32_t max_chunk = uint32_t(std::min<uint64_t>(cap, std::max<uint64_t>(8, tiles / (20 * wgs))));
+    const uint32_t v = b->knobs.join_chunk;   // tuning knob: tiles per chunk at most
+    if (v >= 1 && v <= cap) max_chunk = v;
+    cpq = std::max<uint32_t>(1, (b->join.n_max + max_chunk - 1) / max_chunk);
+    chunk_tiles = std::max<uint32_t>(1, (b->join.n_max + cpq - 1) / cpq);
+  };
+  const uint32_t n_all = uint32_t(b->join.units.size());
+  // [0]: the live counters, [1]: their start values (copied over [0] on the device every run)
+  if (!b->join.d_ctr.p && !b->join.d_ctr.alloc(2 * sizeof b->join.ctr_init)) return false;
+  // two launches: the plain disjunctions, then the units whose accumulators count matches
+  for (uint32_t part = 0; part < 2; ++part) {
+    const uint32_t n_units = part ? n_all - b->join.n_plain : b->join.n_plain;
+    if (!n_units) continue;
+    uint32_t cpq = 1, chunk_tiles = 1;
+    chunking((!part && half) ? kJoinChunkTiles : kJoinChunkPlain, cpq, chunk_tiles);
+    const uint64_t chunks = uint64_t(n_units) * cpq;
+    if (chunks > 0xFFFF0000ull) return false;
+    const uint32_t grid = uint32_t(std::min<uint64_t>(chunks, uint64_t(b->seg->cus) * per_cu));
+    JoinArgs& a = b->join.args[part];   // read by the kernel from device memory
+    a.queries = b->d_queries.as<DevQuery>();
+    a.qterms = b->d_qterms.as<DevQTerm>();
+    a.jterms = b->join.d_jterms.as<JoinTerm>();
+    a.bstar = b->d_bstar.as<uint32_t>();
+    a.cands = b->d_cands.as<uint64_t>();
+    a.cand_count = b->d_cand_count.as<uint32_t>();
+    a.hits = b->d_hits.as<unsigned long long>();
+    a.order = b->join.d_order.as<uint32_t>();
+    a.work_counter = b->join.d_ctr.as<uint32_t>() + part * kJoinQueues;
+    uint32_t base = 0;
+    for (uint32_t g = 0; g <= kJoinQueues; ++g) {
+      a.first[g] = b->join.first[part][g];
+      a.base[g] = base;
+      if (g < kJoinQueues) {
+        b->join.ctr_init[part][g] = base;
+        base += (b->join.first[part][g + 1] - b->join.first[part][g]) * cpq;
+      }
+    }
+    a.cpq = cpq;
+    a.n_units = n_units;
+    a.nw_log2 = b->join.nw_log2;
+    const uint32_t v = b->knobs.join_split_log2;   // tuning knob: a tile's entries among the first
+    if (v < a.nw_log2) a.nw_log2 = v;                // 2^v wavefronts only
+    a.cand_cap = b->cand_cap;
+    a.chunk_tiles = chunk_tiles;
+    JoinArgs* d_args = b->join.d_args.as<JoinArgs>() + part;
+    uint32_t* d_init = a.work_counter + 2 * kJoinQueues;
+    if (!b->join.args_valid[part] || std::memcmp(&a, &b->join.args_sent[part], sizeof a) != 0) {
+      if (!b->up.copy(d_args, &a, sizeof a) ||
+          !b->up.copy(d_init, b->join.ctr_init[part], sizeof b->join.ctr_init[part]) ||
+          !b->up.flush(st))
+        return false;
+      std::memcpy(&b->join.args_sent[part], &a, sizeof a);
+      b->join.args_valid[part] = true;
+    }
+    if (!rt::d2d(a.work_counter, d_init, sizeof b->join.ctr_init[part], st)) return false;
+    if (part) {
+      RT_LAUNCH(k_join_score<kJKCount>, grid, b->join.threads, smem, st, d_args);
+    } else if (half) {
+      // (join.d_order: the plain units first — one k_join_rescore workgroup each)
+      RT_LAUNCH(k_join_score<kJKHalf>, grid, b->join.threads, smem, st, d_args);
+      RT_LAUNCH(k_join_rescore, n_units, kRescoreThreads, 0, st, b->join.d_order.as<uint32_t>(),
+                b->d_queries.as<DevQuery>(), b->d_qterms.as<DevQTerm>(), b->join.d_jterms.as<JoinTerm>(),
+                b->d_bstar.as<uint32_t>(), b->d_cands.as<uint64_t>(), b->d_cand_count.as<uint32_t>(),
+                b->cand_cap);
+    } else {
+      RT_LAUNCH(k_join_score<kJKPlain>, grid, b->join.threads, smem, st, d_args);
+    }
+  }
+  return rt::last_error_ok();
+}
+
+}  // namespace

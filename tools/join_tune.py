@@ -54,17 +54,17 @@ def main():
             L = _lib.bind(ctypes.CDLL(path))
             libs[name] = (L, search.SegmentReader.from_synth(seg, L=L))
         L, sr = libs[name]
-        b = sr.batch(prep, args.k).profile(True)
         # settings: items | exact[threads] | [threads]  (the joined path at 256 / 512 / 1024 threads)
         # (a trailing "-np": the joined plain disjunctions on 32-bit tiles, not on paired tiles)
-        if setting.endswith("-np"):
+        paired = not setting.endswith("-np")
+        if not paired:
             setting = setting[:-3]
-            b.set_paired_tiles(False)
-        if setting == "items":
-            b.set_path(_lib.PATH_ITEMS)
-        else:
+        if setting != "items":   # (a batch reads the knob when it is created)
             os.environ["IRS_HIP_JOIN_THREADS"] = (setting[5:] if setting.startswith("exact") else setting) or "1024"
-            b.set_path(_lib.PATH_JOINED)
+        b = sr.batch(prep, args.k).profile(True)
+        if not paired:
+            b.set_paired_tiles(False)
+        b.set_path(_lib.PATH_ITEMS if setting == "items" else _lib.PATH_JOINED)
         b.run()
         try:
             hits, counts, totals = b.results()

@@ -24,6 +24,7 @@ extern "C" {
 #define IRS_HIP_MAX_TERMS 16u    /* terms per boolean query               */
 #define IRS_HIP_MAX_K 4096u      /* largest top-k                         */
 #define IRS_HIP_MAX_PHRASE_TERMS 8u /* terms of one by_phrase query       */
+#define IRS_HIP_MAX_EXCLUDED 16u /* IRS_HIP_EXCLUDE entries of one query   */
 #define IRS_HIP_NO_TERM 0xFFFFFFFFu
 #define IRS_HIP_POS_OFFSETS 1u
 #define IRS_HIP_POS_PAYLOADS 2u
@@ -224,6 +225,19 @@ typedef enum irs_hip_scorer_kind {
   IRS_HIP_SCORE_TFIDF = 3,     /* tfidf.cpp:185-187, 251                                */
   IRS_HIP_SCORE_TFIDF_NORM = 4 /* tfidf.cpp:253, normalize() == true                   */
 } irs_hip_scorer_kind;
+/* Not a scorer: the `kind` of an EXCLUDED term — a by_term under irs::Not in an And
+ * (boolean_filter.cpp:92-135, boolean_query.cpp:121-141: the included part wrapped in
+ * exclusion(incl, disjunction(excluded)), exclusion.hpp).  Docs that contain the term are removed
+ * from the query's matches; the term scores nothing and changes no statistic.  Such entries follow
+ * the included ones in [first_term, first_term + n_terms), at most IRS_HIP_MAX_EXCLUDED of them,
+ * and at least one included entry precedes them.  c0, norm_* and phrase_offset are ignored;
+ * IRS_HIP_NO_TERM means absent in this segment (no effect, boolean_query.cpp:131-134); a batch
+ * over several segments carries each segment's own ordinal, as for included terms.  The op,
+ * min_match and merge apply to the included entries only.  For every op (OR, AND, MINMATCH,
+ * PHRASE) the matches are the included part's, minus deleted docs, minus every doc of an
+ * excluded term: scores and order are unchanged, total_hits counts what remains and the top k
+ * is drawn from it.  Which path such a unit takes: irs_hip_batch_set_path. */
+#define IRS_HIP_EXCLUDE 0x100
 
 /* One query term = the (term cookie, stats blob, boost) triple TermQuery::execute
  * hands to postings()/CompileScore (term_query.cpp:35-74), flattened. */
@@ -252,7 +266,8 @@ typedef enum irs_hip_merge {
 
 typedef struct irs_hip_query {
   int32_t op;          /* irs_hip_op                                   */
-  uint32_t n_terms;    /* 1..IRS_HIP_MAX_TERMS (PHRASE: ..IRS_HIP_MAX_PHRASE_TERMS) */
+  uint32_t n_terms;    /* included entries: 1..IRS_HIP_MAX_TERMS (PHRASE: ..IRS_HIP_MAX_PHRASE_TERMS),
+                          then 0..IRS_HIP_MAX_EXCLUDED IRS_HIP_EXCLUDE entries */
   uint32_t first_term; /* index of the first entry in the `terms` array */
   uint32_t k;          /* top-k, 1..IRS_HIP_MAX_K (index-search --topN) */
   uint32_t min_match;  /* IRS_HIP_OP_MINMATCH: Or::min_match_count(); else ignored */
@@ -384,7 +399,11 @@ int irs_hip_batch_configure(irs_hip_batch* batch, uint32_t tile_docs,
  *                        scorers (BM25 / BM15 / TF-IDF over 1-byte norms or none), frequencies
  *                        < 256 — plain disjunctions, and conjunctions / min-match disjunctions of
  *                        at most 15 terms whose counting accumulators stay within the parity
- *                        tolerance; units that do not qualify run as ITEMS whatever was asked;
+ *                        tolerance; units that do not qualify run as ITEMS whatever was asked —
+ *                        so does every unit with excluded terms (IRS_HIP_EXCLUDE): its own
+ *                        mask of docs cannot ride on streams shared with other units (an
+ *                        Or / min-match unit runs as work items, an And block driven, a
+ *                        phrase on its phrase kernel);
  *   IRS_HIP_PATH_AUTO    (default) by measured cost: plain disjunctions join when the batch's
  *                        streams are shared enough or its units many enough to pay for decoding
  *                        every distinct stream once (2.9 ps per distinct posting against 0.67 ps
@@ -407,7 +426,8 @@ int irs_hip_batch_path(irs_hip_batch* batch, int* path);
  * the look-ups added (about min(3 k / units sharing the threshold, k) docs per term): a 10 M-doc
  * segment at k = 1000 pairs, a lone 1.25 M-doc segment does not — unless a segment of the batch's
  * plain joined units has deleted documents; enable = 2: whatever the size (tests); enable = 0:
- * never — the units run on 32-bit tiles.
+ * never — the units run on 32-bit tiles.  Units with excluded terms (IRS_HIP_EXCLUDE) never join
+ * and so never take paired tiles; the other units of their batch decide as without them.
  * irs_hip_batch_paired_tiles: whether the last run took them. */
 int irs_hip_batch_set_paired_tiles(irs_hip_batch* batch, int enable);
 int irs_hip_batch_paired_tiles(irs_hip_batch* batch, int* used);
@@ -470,7 +490,8 @@ int irs_hip_segment_wand_source(irs_hip_segment* seg, uint64_t* from_index, uint
  * timings() waits for the stream and returns the durations (ms) of the last run. */
 enum {
   IRS_HIP_K_PLAN = 0,   /* block-range planning per (query, term) + work items; joined path:
-                           the decode + norm join of the batch's distinct terms (k_join) */
+                           the decode + norm join of the batch's distinct terms (k_join);
+                           the masks of units with excluded terms (k_excl_mask) */
   IRS_HIP_K_PILOT = 1,  /* pilot tiles -> per-query score threshold */
   IRS_HIP_K_SCORE = 2,  /* decode + score + accumulate + candidates (phrase batches: k_phrase) */
   IRS_HIP_K_SELECT = 3, /* exact top-k of the candidates            */
@@ -481,8 +502,9 @@ enum {
 int irs_hip_batch_profile(irs_hip_batch* batch, int enable);
 int irs_hip_batch_timings(irs_hip_batch* batch, float ms[IRS_HIP_K_COUNT]);
 /* Work accounting for the roofline: algorithmic bytes A(q)
- * summed over the batch = posting bytes of every query term + 1 norm byte per
- * posting (norm_width) + 8*k result bytes; and the number of postings. */
+ * summed over the batch = posting bytes of every query term (excluded terms included: their
+ * doc blocks are read) + 1 norm byte per scored posting (norm_width) + 8*k result bytes; and the
+ * number of scored postings. */
 int irs_hip_batch_work(irs_hip_batch* batch, uint64_t* algorithmic_bytes,
                        uint64_t* postings);
 /* What the last run of a conjunction / phrase batch really read, next to the algorithmic
@@ -496,6 +518,13 @@ int irs_hip_batch_touched(irs_hip_batch* batch, uint64_t* doc_bytes, uint64_t* p
  * provable threshold), or the candidate buffer overflowed (exact re-run, then a
  * larger buffer).  Results are exact either way; this only tells what it cost. */
 int irs_hip_batch_reruns(irs_hip_batch* batch, uint32_t* count);
+
+/* The doc mask unit `unit` (= segment * n_queries + query) ran with in the batch's last run, for
+ * inspection/tests, in irs_hip_bit_union's layout (bit `doc` of 64-bit little-endian words,
+ * n_words of them, docs beyond dropped): the segment's deleted docs plus every doc of the unit's
+ * excluded terms — or just the deleted docs for a unit without excluded terms (an empty set when
+ * the segment has none).  Waits for the run. */
+int irs_hip_batch_unit_mask(irs_hip_batch* batch, uint32_t unit, uint64_t* set, uint64_t n_words);
 
 /* Multi-segment / multi-GPU merge: merges `n_lists` per-query
  * top-k lists (device pointers, each [n_queries][k] hits + [n_queries] counts,

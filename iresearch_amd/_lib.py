@@ -18,10 +18,11 @@ OK, EINVAL, ECORRUPT, ENOMEM, EHIP, EOVERFLOW, EUNSUPPORTED, EPEER = 0, -1, -2, 
 LAYOUT_SCALAR, LAYOUT_SIMD4 = 0, 1
 OP_OR, OP_AND, OP_MINMATCH, OP_PHRASE = 0, 1, 2, 3
 SCORE_BM25, SCORE_BM15, SCORE_BM1, SCORE_TFIDF, SCORE_TFIDF_NORM = 0, 1, 2, 3, 4
+EXCLUDE = 0x100   # irs_hip_term_scorer.kind of an excluded term (irs::Not)
 NO_TERM = 0xFFFFFFFF
 PATH_AUTO, PATH_ITEMS, PATH_JOINED = 0, 1, 2
 WAND_NONE, WAND_DIV_NORM, WAND_MAX_FREQ, WAND_MIN_NORM = 0, 1, 2, 3   # Scorer::WandType
-MAX_TERMS, MAX_K, MAX_PHRASE_TERMS = 16, 4096, 8
+MAX_TERMS, MAX_K, MAX_PHRASE_TERMS, MAX_EXCLUDED = 16, 4096, 8, 16
 K_PLAN, K_PILOT, K_SCORE, K_SELECT, K_COUNT = 0, 1, 2, 3, 4
 KERNEL_NAMES = ("k_plan", "k_pilot", "k_score", "k_select")
 KERNEL_NAMES_JOINED = ("k_join", "k_join_pilot", "k_join_score", "k_select")
@@ -75,7 +76,7 @@ SYMBOLS = (
     "irs_hip_batch_set_comm",
     "irs_hip_term_blockmax",
     "irs_hip_segment_wand_source",
-    "irs_hip_batch_touched",
+    "irs_hip_batch_touched", "irs_hip_batch_unit_mask",
     "irs_hip_comm_unique_id", "irs_hip_comm_init_rank", "irs_hip_comm_destroy",
     "irs_hip_comm_library",
     "irs_hip_topk_allgather", "irs_hip_device_alloc", "irs_hip_device_free",
@@ -153,6 +154,8 @@ def bind(L: C.CDLL) -> C.CDLL:
     L.irs_hip_term_blockmax.argtypes = [vp, u32, vp, vp, u32, P(u32)]
     L.irs_hip_term_blockmax.restype = C.c_int
     L.irs_hip_batch_touched.argtypes, L.irs_hip_batch_touched.restype = [vp, P(u64), P(u64)], C.c_int
+    L.irs_hip_batch_unit_mask.argtypes = [vp, u32, vp, u64]
+    L.irs_hip_batch_unit_mask.restype = C.c_int
     L.irs_hip_comm_unique_id.argtypes, L.irs_hip_comm_unique_id.restype = [vp], C.c_int
     L.irs_hip_comm_init_rank.argtypes = [i32, vp, i32, i32, P(vp)]
     L.irs_hip_comm_init_rank.restype = C.c_int

@@ -152,7 +152,17 @@ struct by_phrase {
     return *this;
   }
 };
-using filter = std::variant<by_term, Or, And, by_phrase>;
+// irs::And of ONE included filter and Not(by_term) children (boolean_filter.cpp:92-135,
+// boolean_query.cpp:121-141): the included filter's matches minus every doc of an excluded term —
+// scores, order and statistics are the included filter's (the excluded part is prepared without
+// scorers).  An And of several terms with Not children is Exclusion{And{...}, ...}; Not(Or of
+// terms) is several excluded terms.  Or with Not children and filters of only Nots match all
+// docs but some (a zero-score fill) and are not offered.
+struct Exclusion {
+  std::variant<by_term, Or, And, by_phrase> incl;
+  std::vector<by_term> excl;   // at most IRS_HIP_MAX_EXCLUDED
+};
+using filter = std::variant<by_term, Or, And, by_phrase, Exclusion>;
 
 // What by_term::prepare reads from one segment without touching postings.
 struct SegmentStats {
@@ -200,8 +210,8 @@ std::vector<PreparedQuery> prepare(const std::vector<filter>& filters, const Sco
   };
   std::vector<PreparedQuery> out;
   out.reserve(filters.size());
-  for (const filter& f : filters) {
-    PreparedQuery q;
+  // the included filter (either variant: a filter or an Exclusion's included part)
+  auto fill = [&](PreparedQuery& q, const auto& f) {
     if (const auto* t = std::get_if<by_term>(&f)) {
       q.op = IRS_HIP_OP_OR;
       q.terms.push_back(one(*t));
@@ -229,6 +239,21 @@ std::vector<PreparedQuery> prepare(const std::vector<filter>& filters, const Sco
       }
     }
     if (q.terms.empty()) throw illegal_argument(IRS_HIP_EINVAL, "empty filter");
+  };
+  for (const filter& f : filters) {
+    PreparedQuery q;
+    if (const auto* x = std::get_if<Exclusion>(&f)) {
+      fill(q, x->incl);
+      // behind the included entries: one IRS_HIP_EXCLUDE entry per excluded term, no scorer
+      for (const by_term& t : x->excl) {
+        irs_hip_term_scorer e{};
+        e.term = t.term;
+        e.kind = IRS_HIP_EXCLUDE;
+        q.terms.push_back(e);
+      }
+    } else {
+      fill(q, f);
+    }
     out.push_back(std::move(q));
   }
   return out;

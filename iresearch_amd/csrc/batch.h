@@ -26,6 +26,7 @@ struct Knobs {
   uint32_t wg_threads = kDefaultWgThreads;   // IRS_HIP_WG_THREADS: threads per k_pilot / k_score workgroup
   uint32_t join_threads = 1024;   // IRS_HIP_JOIN_THREADS: ... per k_join_pilot / k_join_score workgroup
   bool acc64 = false;        // IRS_HIP_ACC=64: 64-bit accumulators whatever the queries
+  uint32_t excl_slice = kExclSliceWords;   // IRS_HIP_EXCL_SLICE: mask words per k_excl_mask workgroup (64..8192, a power of two)
   static Knobs from_env() {
     Knobs k;
     int v = 0;
@@ -45,6 +46,8 @@ struct Knobs {
     if (set("IRS_HIP_WG_THREADS") && (v == 256 || v == 512 || v == 1024)) k.wg_threads = uint32_t(v);
     if (set("IRS_HIP_JOIN_THREADS") && (v == 256 || v == 512 || v == 1024)) k.join_threads = uint32_t(v);
     if (set("IRS_HIP_ACC")) k.acc64 = v == 64;
+    if (set("IRS_HIP_EXCL_SLICE") && v >= 64 && uint32_t(v) <= kExclSliceWords && (v & (v - 1)) == 0)
+      k.excl_slice = uint32_t(v);
     return k;
   }
 };
@@ -119,6 +122,16 @@ struct BlockWork {
   DevBuf d_lead_of;   // by_phrase: slot of every unit's lead term
   DevBuf d_pilot;             // the lead items the pilot pass samples, {unit, item} each
   uint32_t n_pilot = 0, pilot_stride = 0;
+};
+
+// Units with excluded terms (IRS_HIP_EXCLUDE, excl.h): one doc mask per distinct (segment, present
+// excluded terms), built by k_excl_mask in every run's plan stage; DevQuery::dead points at it
+struct ExclWork {
+  std::vector<ExclMask> masks;   // (the `out` pointers lie in d_words)
+  std::vector<uint32_t> terms;   // the masks' term ordinals, ExclMask::first / n
+  DevBuf d_words, d_masks, d_terms;
+  uint32_t slices = 0;           // k_excl_mask workgroups per mask (of the largest segment's)
+  bool on() const { return !masks.empty(); }
 };
 
 // One threshold per query for its units on the batch's segments (irs_hip_batch_set_shared_threshold)
@@ -226,6 +239,7 @@ struct irs_hip_batch {
   TileWork tiles;
   JoinWork join;
   BlockWork blocks;
+  ExclWork excl;
   Groups groups;
   RunSync sync;
 };

@@ -436,7 +436,7 @@ k_conj(ConjArgs A, uint32_t pilot) {
       score[ld_e[h]] = 0.f;
       // a deleted doc (SegmentReaderImpl::mask) keeps its place among the lead docs — the doc range
       // and the ranks of the others do not change — but is never alive: no term can reach it
-      live[h] = on && !(seg.dead && doc_dead(seg.dead, ld_d[h]));
+      live[h] = on && !(qd.dead && doc_dead(qd.dead, ld_d[h]));
       cnt[ld_e[h]] = live[h] ? 1u : 0u;
     }
     // (words 2*lane, 2*lane+1 of the three bitmaps; the 4 slack words stay zero from here)
@@ -485,7 +485,7 @@ k_conj(ConjArgs A, uint32_t pilot) {
   const uint32_t span = dhi - dlo;
   const uint32_t s = span < kConjBuckets ? 0u
                      : 32u - uint32_t(__builtin_clz(span)) - (5u + uint32_t(__builtin_ctz(kConjWords)));
-  const bool masked = seg.dead != nullptr;   // (wave-uniform)
+  const bool masked = qd.dead != nullptr;   // (wave-uniform)
 #pragma unroll
   for (int h = 0; h < 2; ++h) {
     if (ld_e[h] < n) {

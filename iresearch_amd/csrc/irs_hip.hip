@@ -26,6 +26,7 @@
 #include "score.h"
 #include "conj.h"
 #include "join.h"
+#include "excl.h"
 
 using namespace irs_hip;
 
@@ -438,20 +439,41 @@ static int batch_create_multi_impl(irs_hip_segment* const* segs, uint32_t n_segs
     exps.reserve(nq);
     std::vector<DevQTerm> row;
     std::vector<double> smins;
+    std::vector<uint32_t> excl;   // a unit's present excluded terms
+    std::map<std::pair<uint32_t, std::vector<uint32_t>>, uint32_t> mask_ids;   // (segment, terms) -> mask
+    std::vector<uint32_t> mask_of(nq, 0);   // [unit] mask + 1, 0: none
     for (uint32_t q = 0; q < nq && rc == IRS_HIP_OK; ++q) {
       // unit q = (segment q / nq_user, query q % nq_user); the segment's own term entries
       irs_hip_segment* seg = segs[q / nq_user];
       const irs_hip_term_scorer* terms = all_terms + size_t(q / nq_user) * n_entries;
       const irs_hip_query& in = queries[q % nq_user];
-      if ((in.op != IRS_HIP_OP_OR && in.op != IRS_HIP_OP_AND && in.op != IRS_HIP_OP_MINMATCH &&
-           in.op != IRS_HIP_OP_PHRASE) ||
-          in.n_terms == 0 || in.merge > IRS_HIP_MERGE_MIN ||
-          (in.op == IRS_HIP_OP_PHRASE && in.merge != IRS_HIP_MERGE_SUM) ||
-          in.n_terms > IRS_HIP_MAX_TERMS || in.k == 0 || in.k > IRS_HIP_MAX_K ||
-          uint64_t(in.first_term) + in.n_terms > n_entries) {
+      if (uint64_t(in.first_term) + in.n_terms > n_entries) {
         rc = IRS_HIP_EINVAL;
         break;
       }
+      // the included entries, then the excluded ones (IRS_HIP_EXCLUDE): n_incl of the n_terms
+      uint32_t n_incl = 0;
+      while (n_incl < in.n_terms && terms[in.first_term + n_incl].kind != IRS_HIP_EXCLUDE) ++n_incl;
+      const uint32_t n_excl = in.n_terms - n_incl;
+      if ((in.op != IRS_HIP_OP_OR && in.op != IRS_HIP_OP_AND && in.op != IRS_HIP_OP_MINMATCH &&
+           in.op != IRS_HIP_OP_PHRASE) ||
+          n_incl == 0 || in.merge > IRS_HIP_MERGE_MIN ||
+          (in.op == IRS_HIP_OP_PHRASE && in.merge != IRS_HIP_MERGE_SUM) ||
+          n_incl > IRS_HIP_MAX_TERMS || n_excl > IRS_HIP_MAX_EXCLUDED || in.k == 0 || in.k > IRS_HIP_MAX_K) {
+        rc = IRS_HIP_EINVAL;
+        break;
+      }
+      // excluded terms: the docs of those present here leave the unit's matches (exclusion.hpp); an
+      // absent one has no effect (boolean_query.cpp:131-134)
+      excl.clear();
+      for (uint32_t j = n_incl; j < in.n_terms && rc == IRS_HIP_OK; ++j) {
+        const irs_hip_term_scorer& ts = terms[in.first_term + j];
+        if (ts.kind != IRS_HIP_EXCLUDE || (ts.term != IRS_HIP_NO_TERM && ts.term >= seg->dev.num_terms))
+          rc = IRS_HIP_EINVAL;
+        else if (ts.term != IRS_HIP_NO_TERM && seg->terms[ts.term].docs_count)
+          excl.push_back(ts.term);
+      }
+      if (rc != IRS_HIP_OK) break;
       const bool is_phrase = in.op == IRS_HIP_OP_PHRASE;
       if (q == 0) b->phrase = is_phrase;
       if (is_phrase != b->phrase) {  // a batch holds phrase queries only, or none
@@ -459,7 +481,7 @@ static int batch_create_multi_impl(irs_hip_segment* const* segs, uint32_t n_segs
         break;
       }
       if (is_phrase) {
-        if (in.n_terms > IRS_HIP_MAX_PHRASE_TERMS || terms[in.first_term].phrase_offset != 0) {
+        if (n_incl > IRS_HIP_MAX_PHRASE_TERMS || terms[in.first_term].phrase_offset != 0) {
           rc = IRS_HIP_EINVAL;
           break;
         }
@@ -472,7 +494,7 @@ static int batch_create_multi_impl(irs_hip_segment* const* segs, uint32_t n_segs
       smins.clear();   // per present term: the smallest score of one posting
       bool absent = false, same_bound = true;
       double upper = 0.0, min_score = 1e300, upper_all = 0.0;
-      for (uint32_t j = 0; j < in.n_terms; ++j) {
+      for (uint32_t j = 0; j < n_incl; ++j) {
         const irs_hip_term_scorer& ts = terms[in.first_term + j];
         DevQTerm qt{};
         qt.term = ts.term;
@@ -569,7 +591,7 @@ static int batch_create_multi_impl(irs_hip_segment* const* segs, uint32_t n_segs
           break;
         }
         const uint32_t m = in.min_match;
-        need = (m > in.n_terms || m > row.size()) ? 0xFFu : m;
+        need = (m > n_incl || m > row.size()) ? 0xFFu : m;
       }
       if (is_phrase) {
         // no phrase state for a segment lacking one of the terms (phrase_filter.cpp:254-258)
@@ -582,6 +604,27 @@ static int batch_create_multi_impl(irs_hip_segment* const* segs, uint32_t n_segs
         if (rc != IRS_HIP_OK) break;
       }
       if (need == 0xFFu) row.clear();
+      // the unit's masked docs: its segment's deleted ones, and for a unit with present excluded
+      // terms a mask of its own (dead | their docs), shared by the units with the same terms
+      dq.dead = seg->dev.dead;
+      if (!row.empty() && !excl.empty()) {
+        std::sort(excl.begin(), excl.end());
+        excl.erase(std::unique(excl.begin(), excl.end()), excl.end());
+        auto ins = mask_ids.emplace(std::make_pair(q / nq_user, excl), uint32_t(b->excl.masks.size()));
+        if (ins.second) {
+          ExclMask m{};
+          m.seg = q / nq_user;
+          m.first = uint32_t(b->excl.terms.size());
+          m.n = uint32_t(excl.size());
+          m.words = dead_words(seg->dev.num_docs);
+          m.dead = seg->dev.dead;
+          b->excl.masks.push_back(m);
+          b->excl.terms.insert(b->excl.terms.end(), excl.begin(), excl.end());
+        }
+        mask_of[q] = ins.first->second + 1u;
+        // (what k_excl_mask reads for the unit: the excluded terms' doc blocks)
+        for (uint32_t t : excl) b->alg_bytes += uint64_t(seg->terms[t].blocks_bytes) + seg->terms[t].tail_bytes;
+      }
       // A doc that exists matches at least `need` terms: c matched postings score at least
       // c times the mean of the `need` smallest per-term minima — the score below which no
       // posting of a matching doc falls ON AVERAGE, which is what bounds the relative error of
@@ -685,6 +728,31 @@ static int batch_create_multi_impl(irs_hip_segment* const* segs, uint32_t n_segs
       b->k_max = std::max(b->k_max, in.k);
     }
     if (b->knobs.acc64) b->acc32 = false;   // tuning / test knob
+    if (rc == IRS_HIP_OK && b->excl.on()) {
+      // the masks' words, one pool block; every unit with a mask points at its own
+      uint64_t words = 0, most = 0;
+      for (const ExclMask& m : b->excl.masks) {
+        words += m.words;
+        most = std::max(most, m.words);
+      }
+      if (!b->excl.d_words.alloc(words * 4) || !b->excl.d_masks.alloc(b->excl.masks.size() * sizeof(ExclMask)) ||
+          !b->excl.d_terms.alloc(b->excl.terms.size() * 4)) {
+        rc = IRS_HIP_ENOMEM;
+      } else {
+        words = 0;
+        for (ExclMask& m : b->excl.masks) {
+          m.out = b->excl.d_words.as<uint32_t>() + words;
+          words += m.words;
+        }
+        for (uint32_t q = 0; q < nq; ++q)
+          if (mask_of[q]) b->queries[q].dead = b->excl.masks[mask_of[q] - 1u].out;
+        b->excl.slices = uint32_t((most + b->knobs.excl_slice - 1) / b->knobs.excl_slice);
+        if (uint64_t(b->excl.slices) * b->excl.masks.size() > 0x7FFFFFFFull) rc = IRS_HIP_EUNSUPPORTED;
+        else if (!b->up.copy(b->excl.d_masks.p, b->excl.masks.data(), b->excl.masks.size() * sizeof(ExclMask)) ||
+                 !b->up.copy(b->excl.d_terms.p, b->excl.terms.data(), b->excl.terms.size() * 4))
+          rc = IRS_HIP_ENOMEM;
+      }
+    }
     for (uint32_t q = 0; q < nq && rc == IRS_HIP_OK && q < exps.size(); ++q) {
       const int e = exps[q];
       b->queries[q].fx_mul = std::ldexp(1.f, (b->acc32 ? 30 : 29) - e);
@@ -923,6 +991,18 @@ static int batch_profile_impl(irs_hip_batch* b, int enable) {
 static bool plan_stage(irs_hip_batch* b, rt::stream_t st) {
   auto mark = [&](int i) { return !b->profile || b->sync.prof[i].record(st); };
   bool ok = mark(2 * IRS_HIP_K_PLAN);
+  // the doc masks of the units with excluded terms (excl.h), before anything reads them
+  if (ok && b->excl.on()) {
+    const size_t smem = size_t(b->knobs.excl_slice) * 4;
+    const uint32_t grid = b->excl.slices * uint32_t(b->excl.masks.size());
+    ok = with_layout(b->seg->dev.layout, [&](auto L) {
+      if (!big_smem(k_excl_mask<decltype(L)::value>, smem)) return false;
+      RT_LAUNCH((k_excl_mask<decltype(L)::value>), grid, kThreads, smem, st, b->d_segs.as<DevSegment>(),
+                b->excl.d_masks.as<ExclMask>(), b->excl.d_terms.as<uint32_t>(), b->excl.slices,
+                b->knobs.excl_slice);
+      return rt::last_error_ok();
+    });
+  }
   // (a joined batch without conjunctions needs none of k_plan's tables)
   if (ok && (b->phrase || !b->tiles.units.empty() || !b->blocks.units.empty())) {
     RT_LAUNCH(k_plan, b->nq * b->jt, kThreads, 0, st, b->d_segs.as<DevSegment>(),
@@ -933,6 +1013,24 @@ static bool plan_stage(irs_hip_batch* b, rt::stream_t st) {
   if (ok && b->join.on()) ok = launch_join(b, st);
   if (ok && !b->phrase && !b->tiles.units.empty()) ok = launch_items(b, st);
   return ok && mark(2 * IRS_HIP_K_PLAN + 1);
+}
+
+// irs_hip_batch_unit_mask: the mask the unit's last run tested, in irs_hip_bit_union's layout
+static int batch_unit_mask_impl(irs_hip_batch* b, uint32_t unit, uint64_t* set, uint64_t n_words) {
+  if (!b || !set || unit >= b->nq || !b->ran) return IRS_HIP_EINVAL;
+  if (!rt::set_device(b->seg->device)) return IRS_HIP_EHIP;
+  if (!b->sync.done.sync()) return IRS_HIP_EHIP;
+  const DevQuery& dq = b->queries[unit];
+  const uint32_t num_docs = b->segs[dq.seg]->dev.num_docs;
+  std::fill(set, set + n_words, uint64_t(0));
+  if (!dq.dead) return IRS_HIP_OK;
+  std::vector<uint32_t> w(dead_words(num_docs));
+  if (!rt::d2h(w.data(), dq.dead, w.size() * 4, nullptr) || !rt::sync(nullptr)) return IRS_HIP_EHIP;
+  for (uint64_t j = 0; j < uint64_t(num_docs); ++j) {   // bit j = doc j + kDocMin
+    const uint64_t doc = j + kDocMin;
+    if ((w[j >> 5] >> (j & 31u)) & 1u && doc < 64 * n_words) set[doc >> 6] |= uint64_t(1) << (doc & 63u);
+  }
+  return IRS_HIP_OK;
 }
 
 static int batch_plan_impl(irs_hip_batch* b, void* stream) {
@@ -1512,6 +1610,9 @@ int irs_hip_topk_allgather(irs_hip_comm* c, const void* d_send, void* d_recv,
 }
 int irs_hip_batch_touched(irs_hip_batch* b, uint64_t* doc_bytes, uint64_t* positions) {
   return settled(b, [&] { return batch_touched_impl(b, doc_bytes, positions); });
+}
+int irs_hip_batch_unit_mask(irs_hip_batch* b, uint32_t unit, uint64_t* set, uint64_t n_words) {
+  return settled(b, [&] { return batch_unit_mask_impl(b, unit, set, n_words); });
 }
 int irs_hip_batch_plan(irs_hip_batch* b, void* stream) {
   return settled(b, [&] { return batch_plan_impl(b, stream); });

@@ -557,7 +557,7 @@ __device__ __forceinline__ void phrase_item(const ConjArgs& A, uint32_t pilot /*
       docs[idx] = idx < n ? ld_d[h] : 0xFFFFFFFFu;
       // a deleted doc (SegmentReaderImpl::mask) keeps its place among the lead docs but counts as
       // not reached by the lead: it can never be a match
-      live[h] = idx < n && !(seg.dead && doc_dead(seg.dead, ld_d[h]));
+      live[h] = idx < n && !(qd.dead && doc_dead(qd.dead, ld_d[h]));
       for (uint32_t i = 0; i < m; ++i) {
         W.pidx[i][idx] = i == lead ? p[h] : 0u;
         W.tf[i][idx] = (i == lead && live[h]) ? f[h] : 0u;
@@ -579,7 +579,7 @@ __device__ __forceinline__ void phrase_item(const ConjArgs& A, uint32_t pilot /*
   const uint32_t span = dhi - dlo;
   const uint32_t s = span < kConjBuckets ? 0u
                      : 32u - uint32_t(__builtin_clz(span)) - (5u + uint32_t(__builtin_ctz(kConjWords)));
-  const bool masked = seg.dead != nullptr;   // (wave-uniform)
+  const bool masked = qd.dead != nullptr;   // (wave-uniform)
 #pragma unroll
   for (int h = 0; h < 2; ++h) {
     if (ld_e[h] < n) {

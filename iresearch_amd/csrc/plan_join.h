@@ -82,6 +82,9 @@ bool unit_counts_matches(const DevQuery& dq) {   // min-match / the kMin disjunc
 bool unit_joinable(const irs_hip_batch* b, uint32_t u) {
   const DevQuery& dq = b->queries[u];
   if (query_min_both(dq.op) || query_merge(dq.op) != kScoreSum) return false;
+  // a unit with excluded terms: k_join applies the SEGMENT's deleted docs while it decodes the
+  // streams every unit shares, the unit's own mask (excl.h) cannot ride there
+  if (dq.dead != b->segs[dq.seg]->dev.dead) return false;
   if ((dq.op & 0xFF) != 0) {
     // min-match / conjunction: the match count rides in the accumulator's low bits (join.h
     // COUNT) where that costs no precision that matters

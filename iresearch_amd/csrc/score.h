@@ -1040,7 +1040,7 @@ k_pilot(const uint32_t* units, const DevSegment* segs, const DevQuery* queries,
   const uint64_t norms1 = tiny ? reinterpret_cast<uint64_t>(seg.norms) + (kDocMin - seg.norm_min_doc) : 0;
   const uint64_t norm_count = tiny ? seg.norm_count - (kDocMin - seg.norm_min_doc) : 0;
   const uint32_t n_tiles = qd.n_tiles;
-  const uint32_t* dead = seg.dead;
+  const uint32_t* dead = qd.dead;   // the unit's masked docs (null: none)
   for (uint32_t i = tid; i < kBins; i += blockDim.x) hist[i] = 0u;
   for (uint32_t i = tid; i < uint32_t(TILE) + 64u; i += blockDim.x) sm.acc[i] = ACC(0);
   if (AND) {
@@ -1238,7 +1238,7 @@ k_score(uint64_t args /*address of a ScoreArgs*/) {
     const uint64_t norms1 = tiny ? reinterpret_cast<uint64_t>(seg.norms) + (kDocMin - seg.norm_min_doc) : 0;
     const uint64_t norm_count = tiny ? seg.norm_count - (kDocMin - seg.norm_min_doc) : 0;
     const uint32_t n_tiles = qd.n_tiles;
-    const uint32_t* dead = seg.dead;   // the segment's deleted docs (null: none)
+    const uint32_t* dead = qd.dead;   // the unit's deleted / excluded docs (null: none)
     const uint32_t ntile = tile0 >= n_tiles ? 0u
                            : ((n_tiles - tile0) < kChunkTiles ? (n_tiles - tile0) : kChunkTiles);
     const uint32_t bs = IRS_ARG(bstar)[q];

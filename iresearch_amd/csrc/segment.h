@@ -401,9 +401,8 @@ static int segment_open_impl(const irs_hip_segment_desc* d, irs_hip_segment** ou
     v.wand_count = d->wand_count;
     s->live_docs = d->num_docs;
     if (d->doc_mask_count) {
-      // DocumentMask -> bitmap, bit (doc - kDocMin); a whole doc tile behind the last doc stays
-      // readable (the tile kernels test their accumulators' docs group by group)
-      const uint64_t words = (uint64_t(d->num_docs) + 12288u + 31u) / 32u + 16u;
+      // DocumentMask -> bitmap, bit (doc - kDocMin) (dead_words, excl.h)
+      const uint64_t words = dead_words(d->num_docs);
       std::vector<uint32_t> bits;
       try {
         bits.assign(words, 0u);

@@ -157,8 +157,13 @@ struct DevQuery {
   uint32_t run_unit;
   uint32_t tile_base;   // index of the unit's first doc tile in the batch-wide per-tile tables
                         // (DevQuery n_tiles summed over the units in front of it)
-  uint32_t pad_q[2];
+  // the docs this unit never matches (null: none): its segment's `dead` bitmap, or — for a unit
+  // with excluded terms (IRS_HIP_EXCLUDE, excl.h) — its own mask, dead | every excluded term's docs,
+  // laid out like DevSegment::dead.  What the work-item, block-driven and phrase kernels test; the
+  // joined streams (join.h) apply the segment's bitmap at decode time and take no masked unit
+  const uint32_t* dead;
 };
+static_assert(sizeof(DevQuery) == 64, "DevQuery: 64 bytes");
 
 struct DevQTerm {
   uint32_t term;        // ordinal in the term table, 0xFFFFFFFF = absent

@@ -25,7 +25,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import _lib
-from ._lib import (HIT, NO_TERM, OP_AND, OP_MINMATCH, OP_OR, OP_PHRASE, QUERY, SCORE_BM1, SCORE_BM15, SCORE_BM25,
+from ._lib import (EXCLUDE, HIT, NO_TERM, OP_AND, OP_MINMATCH, OP_OR, OP_PHRASE, QUERY, SCORE_BM1, SCORE_BM15, SCORE_BM25,
                    SCORE_TFIDF, SCORE_TFIDF_NORM, TERM_META, TERM_SCORER, SegmentDesc)
 
 f32 = np.float32
@@ -138,7 +138,74 @@ class by_phrase:
             raise ValueError("offsets are relative to the first term")
 
 
+@dataclass
+class Not:
+    """irs::Not (boolean_filter.hpp): as a child of an And, the docs its filter matches leave the
+    And's matches (boolean_query.cpp:121-141: exclusion(included, disjunction(excluded)),
+    exclusion.hpp) — scoring nothing and changing no statistic.  `filter`: a by_term, an Or of
+    by_term (several excluded terms) or another Not (Not(Not(f)) is f, optimize_not,
+    boolean_filter.cpp:35-48)."""
+    filter: object
+
+
+def _unwrap_not(flt):
+    """optimize_not (boolean_filter.cpp:35-48): (filter, negated) with double negations removed."""
+    neg = False
+    while isinstance(flt, Not):
+        flt, neg = flt.filter, not neg
+    return flt, neg
+
+
+def _excluded_terms(flt):
+    """Term ordinals of the filter under a Not: a by_term, or a plain Or of by_term."""
+    if isinstance(flt, by_term):
+        return [flt.term]
+    if type(flt) is Or and flt.min_match <= 1 and flt.subs and all(type(s) is by_term for s in flt.subs):
+        return [s.term for s in flt.subs]
+    raise ValueError("Not of %s is not on the GPU path: only Not(by_term) and Not(Or([by_term...])) "
+                     "exclude docs" % type(flt).__name__)
+
+
+def split_exclusions(flt):
+    """(included filter, excluded term ordinals) of a filter: And([..., Not(...), ...]) is the And
+    of its other children minus the docs of the negated terms; a single included Or / And /
+    by_phrase child keeps its own op, min_match and merge (boolean_filter.cpp:200-208,
+    boolean_query.cpp:104-109).  Filters without Not come back as they are.  Refused (ValueError):
+    what the reference gives other semantics — an Or with a Not child (all docs but ..., with a
+    zero-score fill, boolean_filter.cpp:120-127), a filter of only Nots, Not of a phrase or an And."""
+    flt, neg = _unwrap_not(flt)
+    if neg:
+        raise ValueError("a filter of only Not matches all docs but some (zero-score fill): "
+                         "not on the GPU path")
+    if isinstance(flt, (Or, And)) and any(isinstance(s, Not) for s in flt.subs):
+        if type(flt) is not And:
+            raise ValueError("an Or with a Not child matches all docs but some (zero-score fill, "
+                             "boolean_filter.cpp:120-127): not on the GPU path")
+        incl, excl = [], []
+        for s in flt.subs:
+            f, n = _unwrap_not(s)
+            if n:
+                excl += _excluded_terms(f)
+            else:
+                incl.append(f)
+        if not incl:
+            raise ValueError("an And of only Not children matches all docs but some "
+                             "(zero-score fill): not on the GPU path")
+        if len(incl) == 1 and not isinstance(incl[0], by_term):
+            inner = incl[0]
+            if isinstance(inner, (Or, And)) and any(isinstance(s, Not) for s in inner.subs):
+                raise ValueError("Not is taken in the outermost And only")
+            return inner, excl
+        if any(type(s) is not by_term for s in incl):
+            raise ValueError("an And with Not children takes by_term children or ONE Or / And / "
+                             "by_phrase child")
+        return And(incl, merge=flt.merge), excl
+    return flt, []
+
+
 def _terms_of(flt):
+    if isinstance(flt, Not):
+        raise ValueError("Not is taken by prepare() only (as a child of an And), not here")
     if isinstance(flt, by_term):
         return OP_OR, [flt]
     if not flt.subs or any(not isinstance(s, by_term) for s in flt.subs):
@@ -155,6 +222,7 @@ class PreparedQuery:
     min_match: int = 0
     offsets: list | None = None   # OP_PHRASE: position of every term in the phrase
     merge: int = MERGE_SUM
+    excluded: list = field(default_factory=list)   # term ordinals under Not (IRS_HIP_EXCLUDE)
 
 
 # ------------------------------------------------------------------ segment --
@@ -308,17 +376,22 @@ class QueryArrays:
 
     @classmethod
     def from_prepared(cls, segs, prepared, k):
-        n_entries = sum(len(p.terms) for p in prepared)
+        n_entries = sum(len(p.terms) + len(p.excluded) for p in prepared)
         queries = np.zeros(len(prepared), QUERY)
         terms = np.zeros((len(segs), max(n_entries, 1)), TERM_SCORER)
         at = 0
         for q, p in enumerate(prepared):
-            queries[q] = (p.op, len(p.terms), at, int(k), p.min_match, p.merge)
+            queries[q] = (p.op, len(p.terms) + len(p.excluded), at, int(k), p.min_match, p.merge)
             offs = p.offsets if p.offsets is not None else [0] * len(p.terms)
             for t, (kind, c0, nc, nl), off in zip(p.terms, p.scorers, offs):
                 for s, sr in enumerate(segs):       # same scorer, the segment's own ordinal
                     present = t is not None and 0 <= t < len(sr.metas)
                     terms[s, at] = (t if present else NO_TERM, kind, c0, nc, nl, off)
+                at += 1
+            for t in p.excluded:                     # behind the included entries
+                for s, sr in enumerate(segs):
+                    present = t is not None and 0 <= t < len(sr.metas)
+                    terms[s, at] = (t if present else NO_TERM, EXCLUDE, 0.0, 0.0, 0.0, 0)
                 at += 1
         return cls(len(segs), queries, terms, k)
 
@@ -405,6 +478,9 @@ def prepare_filters(filters, scorer, segment_stats, segs, k):
                 terms_q = None
             if not subs or terms_q is None or (set(map(type, subs)) != {by_term} and
                                                any(not isinstance(s, by_term) for s in subs)):
+                if any(isinstance(s, Not) for s in subs):
+                    raise ValueError("Not is taken by prepare() (IRS_HIP_EXCLUDE), not by the "
+                                     "array path prepare_filters")
                 raise ValueError("only flat Or/And of by_term are on the GPU path")
             op = flt.op
         else:
@@ -595,6 +671,14 @@ class QueryBatch:
                    "irs_hip_batch_reruns")
         return n.value
 
+    def unit_mask(self, unit: int, n_words: int):
+        """The docs unit `unit` (segment * n_queries + query) did not match whatever it scored in
+        the last run — deleted plus excluded — as a bit_union-style bitset (bit = doc id)."""
+        out = np.zeros(n_words, np.uint64)
+        _lib.check(self.L, self.L.irs_hip_batch_unit_mask(self.handle, unit, out.ctypes.data, n_words),
+                   "irs_hip_batch_unit_mask")
+        return out
+
     def touched(self):
         """(`.doc` + norm bytes decoded, positions read) by the last run (And / by_phrase)."""
         a, p = C.c_uint64(), C.c_uint64()
@@ -686,6 +770,13 @@ def prepare(filters, scorer, segment_stats):
     ttf = sum(s.total_term_freq for s in segment_stats)
     out = []
     for flt in filters:
+        flt, excluded = split_exclusions(flt)
+        if excluded:
+            # (the excluded part is prepared without scorers: no score, no statistic)
+            p = prepare([flt], scorer, segment_stats)[0]
+            p.excluded = [int(t) for t in excluded]
+            out.append(p)
+            continue
         if isinstance(flt, by_phrase):
             # FixedPrepareCollect (phrase_filter.cpp:212-293): term_stats.finish() of every
             # phrase term lands in ONE stats blob — BM25::collect / TFIDF::collect do

@@ -6,7 +6,8 @@ the segment's DocumentMask, which the oracle applies as SegmentReaderImpl::mask 
 random Or / And / min-match / by_term
 filters with random boosts and merge types (or by_phrase filters), a random scorer and k, and
 checks the results as the parity tests do; the same batch is then re-run with block-max pruning
-(top-k must not change) and with the k-th score pushed down as irs::score::Min.
+(top-k must not change) and with the k-th score pushed down as irs::score::Min.  Every third
+boolean round also runs the filters with 0-2 excluded terms each (And(filter, Not(by_term))).
 
   python tools/fuzz_parity.py --seconds 120            # on the GPU (libirs_hip.so)
   python tools/fuzz_parity.py --sim --seconds 60       # on the CPU emulator
@@ -22,6 +23,36 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+
+def excl_round(sr, seg, filters, scorer, k, st, rng, max_rank):
+    """And(filter, Not(by_term)...) on a path picked at random: each query against the oracle's
+    run of its included part on the segment with the excluded terms' docs deleted as well."""
+    import copy
+
+    import oracle
+    import parity
+    from iresearch_amd import _lib, search
+    from iresearch_amd.search import And, Not, by_term
+    trip = []
+    for f in filters:
+        ex = [int(rng.integers(0, max_rank + 2)) for _ in range(int(rng.integers(0, 3)))]
+        trip.append((And([f] + [Not(by_term(x)) for x in ex]) if ex else f, f, ex))
+    path = int(rng.choice([_lib.PATH_AUTO, _lib.PATH_ITEMS, _lib.PATH_JOINED]))
+    b = sr.batch(search.prepare([t[0] for t in trip], scorer, st), k).set_path(path)
+    h, c, t = b.run().results()
+    gone0 = np.zeros(0, np.int64) if getattr(seg, "doc_mask", None) is None else \
+        np.asarray(seg.doc_mask, np.int64)
+    for q, (_, incl, ex) in enumerate(trip):
+        parts = [gone0[(gone0 >= 1) & (gone0 <= seg.num_docs)]]
+        for x in ex:
+            if x < len(seg.metas) and int(seg.metas[x]["docs_count"]):
+                parts.append(oracle.decode_term(seg.doc_file, seg.metas[x], seg.layout,
+                                                wand_count=int(getattr(seg, "wand_count", 0)))[0].astype(np.int64))
+        ms = copy.copy(seg)
+        ms.doc_mask = np.unique(np.concatenate(parts)).astype(np.uint32)
+        parity.check_single_segment(ms, [incl], scorer, k, h[q:q + 1], c[q:q + 1], t[q:q + 1])
+    b.close()
 
 
 def main():
@@ -104,6 +135,8 @@ def main():
             b = sr.batch(prep, k)
             hits, counts, totals = (x.copy() for x in b.run().results())
             parity.check_single_segment(seg, filters, scorer, k, hits, counts, totals)
+            if rounds % 3 == 1:   # irs::Not: some queries lose the docs of 1-2 excluded terms
+                excl_round(sr, seg, filters, scorer, k, st, rng, max_rank)
             if rounds % 3 == 0:   # the same results through page-locked host memory, a run later
                 hh, hc, ht = b.run().results_to_host().host_results()
                 assert np.array_equal(hc, counts) and np.array_equal(ht, totals), "host results: counts"

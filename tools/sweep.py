@@ -38,11 +38,15 @@ def main():
                          "wherever a unit can take them")
     ap.add_argument("--touched", action="store_true",
                     help="And / by_phrase: one more run that counts the bytes actually decoded")
+    ap.add_argument("--exclude", type=int, default=0,
+                    help="And(query, Not(term)...): N excluded terms per query (IRS_HIP_EXCLUDE), drawn "
+                         "from --lo-rank..--hi-rank; also times the plan stage without them (the "
+                         "difference is k_excl_mask)")
     args = ap.parse_args()
     import torch
 
     from iresearch_amd import _lib, search, synth
-    from iresearch_amd.search import BM25, TFIDF, And, Or, by_phrase, by_term
+    from iresearch_amd.search import BM25, TFIDF, And, Not, Or, by_phrase, by_term
     L = _lib.bind(ctypes.CDLL(args.lib)) if args.lib else _lib.lib()
     t0 = time.perf_counter()
     kw = dict(topic_docs=4096, topic_percent=85, topic_terms=12) if args.clustered else {}
@@ -67,6 +71,13 @@ def main():
     scorer = {"bm25": BM25(), "tfidf": TFIDF(True), "bm15": BM25(1.2, 0.0)}[args.scorer]
     st = search.SegmentStats(seg.docs_with_field, seg.total_term_freq,
                              np.asarray(seg.metas["docs_count"]))
+    plain_prep = None
+    if args.exclude:
+        rng = np.random.default_rng(synth.SEED + 3)
+        plain_prep = search.prepare(filters, scorer, [st])
+        filters = [And([f] + [Not(by_term(int(r) - 1))
+                              for r in rng.integers(args.lo_rank, args.hi_rank + 1, args.exclude)])
+                   for f in filters]
     prep = search.prepare(filters, scorer, [st])
     ref = None
     for cfg in args.configs.split(","):
@@ -93,6 +104,19 @@ def main():
                                                               b.reruns()), flush=True)
         print("   hits/query: mean %.0f max %d" % (float(np.mean(totals)), int(np.max(totals))),
               flush=True)
+        if plain_prep is not None:
+            pb = sr.batch(plain_prep, args.k).configure(tile, stride, 0).set_path(path).profile(True)
+            pb.run()
+            pb.results()
+            pms = []
+            for _ in range(args.steps):
+                pb.run()
+                pms.append(pb.timings())
+            pavg = np.mean(pms, axis=0)
+            print("   without the exclusions: plan %.3f ms (path %s)  ->  mask build ~%.3f ms for %d "
+                  "masks" % (pavg[0], "joined" if pb.path() == _lib.PATH_JOINED else "items",
+                             avg[0] - pavg[0], args.queries), flush=True)
+            pb.close()
         if args.touched:
             b.profile(3).run()
             td, tp = b.touched()

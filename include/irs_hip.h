@@ -23,7 +23,9 @@ extern "C" {
 #define IRS_HIP_BLOCK_SIZE 128u  /* postings per block, formats_10.cpp:90 */
 #define IRS_HIP_MAX_TERMS 16u    /* terms per boolean query               */
 #define IRS_HIP_MAX_K 4096u      /* largest top-k                         */
-#define IRS_HIP_MAX_PHRASE_TERMS 8u /* terms of one by_phrase query       */
+#define IRS_HIP_MAX_PHRASE_TERMS 8u /* terms (parts) of one by_phrase query */
+#define IRS_HIP_MAX_PHRASE_ENTRIES 16u /* included entries of one variadic by_phrase,
+                                           every member of every part counted        */
 #define IRS_HIP_MAX_EXCLUDED 16u /* IRS_HIP_EXCLUDE entries of one query   */
 #define IRS_HIP_NO_TERM 0xFFFFFFFFu
 #define IRS_HIP_POS_OFFSETS 1u
@@ -212,7 +214,9 @@ typedef enum irs_hip_op {
                              were finished (phrase_filter.cpp:281-287: idf sums), times
                              the filter boost.  score = that scorer at tf = phrase
                              frequency.  An absent term empties the query in that segment.
-                             A batch holds phrase queries only, or none.               */
+                             A batch holds phrase queries only, or none.
+                             Variadic phrases (a part standing for a set of terms,
+                             VariadicPhraseQuery): IRS_HIP_PHRASE_ALT below.           */
 } irs_hip_op;
 
 /* Which ScoreFunction Scorer::prepare_scorer would have built. */
@@ -238,6 +242,24 @@ typedef enum irs_hip_scorer_kind {
  * excluded term: scores and order are unchanged, total_hits counts what remains and the top k
  * is drawn from it.  Which path such a unit takes: irs_hip_batch_set_path. */
 #define IRS_HIP_EXCLUDE 0x100
+
+/* OR-ed into the `kind` of an IRS_HIP_OP_PHRASE entry: one more member of the phrase part opened by
+ * the nearest preceding entry without the flag — a by_phrase_options part of by_terms / by_prefix /
+ * by_wildcard / by_range (phrase_filter.hpp:41-47), whose visitor yields a set of terms in
+ * dictionary order (VariadicPrepareCollect, phrase_filter.cpp:295-432).  The entry's
+ * phrase_offset equals its part's; the first included entry never carries the flag; the same term
+ * twice in one part is IRS_HIP_EINVAL; every entry carries the phrase's one scorer, as for plain
+ * phrases.  At most IRS_HIP_MAX_PHRASE_TERMS parts and IRS_HIP_MAX_PHRASE_ENTRIES included entries
+ * (more: IRS_HIP_EUNSUPPORTED); IRS_HIP_EXCLUDE entries may follow.  Per segment an absent member
+ * (IRS_HIP_NO_TERM or no docs) is dropped, and a part without a present member empties the query.
+ * Phrase frequency (VariadicPhraseFrequency, phrase_iterator.hpp:197-364), parts P_0..P_n-1 at
+ * offsets off_i (off_0 = 0):
+ *   freq(d) = sum over t in P_0 of #{p in pos(t, d) : for every i >= 1 some u in P_i has
+ *             p + off_i in pos(u, d)}
+ * — members of the first part add up, a later part needs one member at the position.  Score: the
+ * scorer at tf = freq(d), as for plain phrases.  A compatible addition to ABI 12: without the flag
+ * an entry means what it always did, and a kind with the flag was IRS_HIP_EINVAL before. */
+#define IRS_HIP_PHRASE_ALT 0x200
 
 /* One query term = the (term cookie, stats blob, boost) triple TermQuery::execute
  * hands to postings()/CompileScore (term_query.cpp:35-74), flattened. */
@@ -266,7 +288,8 @@ typedef enum irs_hip_merge {
 
 typedef struct irs_hip_query {
   int32_t op;          /* irs_hip_op                                   */
-  uint32_t n_terms;    /* included entries: 1..IRS_HIP_MAX_TERMS (PHRASE: ..IRS_HIP_MAX_PHRASE_TERMS),
+  uint32_t n_terms;    /* included entries: 1..IRS_HIP_MAX_TERMS (PHRASE: ..IRS_HIP_MAX_PHRASE_TERMS;
+                          with IRS_HIP_PHRASE_ALT members ..IRS_HIP_MAX_PHRASE_ENTRIES),
                           then 0..IRS_HIP_MAX_EXCLUDED IRS_HIP_EXCLUDE entries */
   uint32_t first_term; /* index of the first entry in the `terms` array */
   uint32_t k;          /* top-k, 1..IRS_HIP_MAX_K (index-search --topN) */

@@ -19,10 +19,12 @@ LAYOUT_SCALAR, LAYOUT_SIMD4 = 0, 1
 OP_OR, OP_AND, OP_MINMATCH, OP_PHRASE = 0, 1, 2, 3
 SCORE_BM25, SCORE_BM15, SCORE_BM1, SCORE_TFIDF, SCORE_TFIDF_NORM = 0, 1, 2, 3, 4
 EXCLUDE = 0x100   # irs_hip_term_scorer.kind of an excluded term (irs::Not)
+PHRASE_ALT = 0x200   # OR-ed into a phrase entry's kind: one more member of the part before it
 NO_TERM = 0xFFFFFFFF
 PATH_AUTO, PATH_ITEMS, PATH_JOINED = 0, 1, 2
 WAND_NONE, WAND_DIV_NORM, WAND_MAX_FREQ, WAND_MIN_NORM = 0, 1, 2, 3   # Scorer::WandType
 MAX_TERMS, MAX_K, MAX_PHRASE_TERMS, MAX_EXCLUDED = 16, 4096, 8, 16
+MAX_PHRASE_ENTRIES = 16   # included entries of a variadic phrase, members counted
 K_PLAN, K_PILOT, K_SCORE, K_SELECT, K_COUNT = 0, 1, 2, 3, 4
 KERNEL_NAMES = ("k_plan", "k_pilot", "k_score", "k_select")
 KERNEL_NAMES_JOINED = ("k_join", "k_join_pilot", "k_join_score", "k_select")

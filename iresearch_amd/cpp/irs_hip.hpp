@@ -144,10 +144,26 @@ struct by_phrase {
   std::vector<uint32_t> terms;
   std::vector<uint32_t> offsets;  // relative to the first term; empty = consecutive words
   float boost = 1.f;
+  // variadic phrase (VariadicPrepareCollect): members[i] = part i's terms, what its by_terms /
+  // by_prefix / by_wildcard / by_range visitor yields, in dictionary order; empty: plain terms only
+  std::vector<std::vector<uint32_t>> members;
   // by_phrase_options::push_back<by_term_options>(offs): `offs` positions after the end
   by_phrase& push_back(uint32_t term, uint32_t offs = 0) {
     const uint32_t next = offsets.empty() ? 0u : offsets.back() + 1u;
     terms.push_back(term);
+    offsets.push_back(next + offs);
+    if (!members.empty()) members.push_back({term});
+    return *this;
+  }
+  // a part that stands for a set of terms (by_phrase_options::push_back<by_terms_options> etc.)
+  by_phrase& push_back(std::vector<uint32_t> part, uint32_t offs = 0) {
+    if (part.empty()) throw illegal_argument(IRS_HIP_EINVAL, "by_phrase: a part without terms");
+    if (members.empty())
+      for (uint32_t t : terms) members.push_back({t});
+    const uint32_t first = part[0];
+    members.push_back(std::move(part));
+    const uint32_t next = offsets.empty() ? 0u : offsets.back() + 1u;
+    terms.push_back(first);
     offsets.push_back(next + offs);
     return *this;
   }
@@ -210,6 +226,67 @@ std::vector<PreparedQuery> prepare(const std::vector<filter>& filters, const Sco
   };
   std::vector<PreparedQuery> out;
   out.reserve(filters.size());
+  // A variadic phrase (VariadicPrepareCollect, phrase_filter.cpp:295-432): in every segment the
+  // present members of each part (docs_count > 0) go to collector slots 0, 1, ... of the part —
+  // of the `found`-th part, the count of parts that had members there before it
+  // (phrase_part_stats[found_parts]) — and ONE blob gets the idf of every slot of every collector,
+  // each slot's docs_with_term summed over the segments.  Entries: the members part after part,
+  // all but a part's first flagged IRS_HIP_PHRASE_ALT.
+  auto variadic = [&](PreparedQuery& q, const by_phrase& p) {
+    const size_t np = p.members.size();
+    if (np != p.terms.size() || (!p.offsets.empty() && (p.offsets.size() != np || p.offsets[0] != 0)))
+      throw illegal_argument(IRS_HIP_EINVAL, "by_phrase: offsets are relative to the first term");
+    if (np < 2)
+      throw illegal_argument(IRS_HIP_EINVAL, "by_phrase: a phrase of one part is that part's own "
+                             "filter (by_phrase::Prepare): use Or of by_term / prepare_expansion");
+    if (np > IRS_HIP_MAX_PHRASE_TERMS)
+      throw illegal_argument(IRS_HIP_EINVAL, "by_phrase: more than IRS_HIP_MAX_PHRASE_TERMS parts");
+    size_t total = 0;
+    for (const auto& part : p.members) {
+      if (part.empty()) throw illegal_argument(IRS_HIP_EINVAL, "by_phrase: a part without terms");
+      for (size_t i = 0; i < part.size(); ++i)
+        for (size_t k = 0; k < i; ++k)
+          if (part[k] == part[i]) throw illegal_argument(IRS_HIP_EINVAL, "by_phrase: a term twice in one part");
+      total += part.size();
+    }
+    if (total > IRS_HIP_MAX_PHRASE_ENTRIES)
+      throw not_supported(IRS_HIP_EUNSUPPORTED, "by_phrase: more than IRS_HIP_MAX_PHRASE_ENTRIES members");
+    std::vector<std::vector<uint64_t>> slots(np);
+    for (const auto& seg : index) {
+      size_t found = 0;
+      for (const auto& part : p.members) {
+        size_t off = 0;
+        for (uint32_t t : part) {
+          const uint64_t df = seg.docs_count(t);
+          if (!df) continue;
+          if (slots[found].size() <= off) slots[found].push_back(0);
+          slots[found][off++] += df;
+        }
+        if (off) ++found;
+      }
+    }
+    TermStats st;
+    bool any = false;
+    for (const auto& col : slots)
+      for (uint64_t dwt : col) {
+        scorer.collect(st, dwf, dwt, ttf);
+        any = true;
+      }
+    if (!any) {   // no segment holds a member: nothing matches; the norm constants all the same
+      scorer.collect(st, dwf, 0, ttf);
+      st.idf = 0.f;
+    }
+    irs_hip_term_scorer e = scorer.term_scorer(st, p.boost);
+    q.op = IRS_HIP_OP_PHRASE;
+    const int32_t kind = e.kind;
+    for (size_t i = 0; i < np; ++i)
+      for (size_t k = 0; k < p.members[i].size(); ++k) {
+        e.term = p.members[i][k];
+        e.kind = k ? (kind | IRS_HIP_PHRASE_ALT) : kind;
+        e.phrase_offset = p.offsets.empty() ? uint32_t(i) : p.offsets[i];
+        q.terms.push_back(e);
+      }
+  };
   // the included filter (either variant: a filter or an Exclusion's included part)
   auto fill = [&](PreparedQuery& q, const auto& f) {
     if (const auto* t = std::get_if<by_term>(&f)) {
@@ -224,6 +301,8 @@ std::vector<PreparedQuery> prepare(const std::vector<filter>& filters, const Sco
       q.op = IRS_HIP_OP_AND;
       q.merge = a->merge_type;
       for (const auto& t : a->subs) q.terms.push_back(one(t));
+    } else if (!std::get<by_phrase>(f).members.empty()) {
+      variadic(q, std::get<by_phrase>(f));
     } else {
       const auto& p = std::get<by_phrase>(f);
       if (!p.offsets.empty() && (p.offsets.size() != p.terms.size() || p.offsets[0] != 0))

@@ -120,6 +120,11 @@ struct BlockWork {
   DevBuf d_lg;   // [unit] log2 of the pieces a lead block is cut into (ConjItem)
   DevBuf d_item_hits;   // [lead item] matches (ConjArgs::item_hits, k_conj_hits)
   DevBuf d_lead_of;   // by_phrase: slot of every unit's lead term
+  // variadic by_phrase (IRS_HIP_PHRASE_ALT in any unit: every phrase unit of the batch runs on
+  // k_vphrase): per unit, bit r of `opens` set = row r opens a part; the iteration lead part's rows
+  bool variadic = false;
+  std::vector<uint32_t> opens;
+  DevBuf d_opens, d_lead_rows;   // [unit] opens; lead part's rows lo | hi << 8
   DevBuf d_pilot;             // the lead items the pilot pass samples, {unit, item} each
   uint32_t n_pilot = 0, pilot_stride = 0;
 };

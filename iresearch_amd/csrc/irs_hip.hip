@@ -23,6 +23,7 @@
 #include "gpu_rt.h"
 #include "kernels.h"
 #include "phrase.h"
+#include "vphrase.h"
 #include "score.h"
 #include "conj.h"
 #include "join.h"
@@ -434,6 +435,7 @@ static int batch_create_multi_impl(irs_hip_segment* const* segs, uint32_t n_segs
     b->queries.resize(nq);
     b->count_precise.assign(nq, 0);
     b->groups.upper.assign(nq, 0.0);
+    b->blocks.opens.assign(nq, 0);
     b->qterms.reserve(size_t(n_entries) * n_segs);
     std::vector<int> exps;
     exps.reserve(nq);
@@ -455,6 +457,14 @@ static int batch_create_multi_impl(irs_hip_segment* const* segs, uint32_t n_segs
       uint32_t n_incl = 0;
       while (n_incl < in.n_terms && terms[in.first_term + n_incl].kind != IRS_HIP_EXCLUDE) ++n_incl;
       const uint32_t n_excl = in.n_terms - n_incl;
+      // a variadic phrase (IRS_HIP_PHRASE_ALT members): up to IRS_HIP_MAX_PHRASE_ENTRIES entries
+      bool alt = false;
+      for (uint32_t j = 0; j < n_incl && in.op == IRS_HIP_OP_PHRASE; ++j)
+        alt = alt || (terms[in.first_term + j].kind & IRS_HIP_PHRASE_ALT) != 0;
+      if (alt && n_incl > IRS_HIP_MAX_PHRASE_ENTRIES) {
+        rc = IRS_HIP_EUNSUPPORTED;
+        break;
+      }
       if ((in.op != IRS_HIP_OP_OR && in.op != IRS_HIP_OP_AND && in.op != IRS_HIP_OP_MINMATCH &&
            in.op != IRS_HIP_OP_PHRASE) ||
           n_incl == 0 || in.merge > IRS_HIP_MERGE_MIN ||
@@ -481,7 +491,11 @@ static int batch_create_multi_impl(irs_hip_segment* const* segs, uint32_t n_segs
         break;
       }
       if (is_phrase) {
-        if (n_incl > IRS_HIP_MAX_PHRASE_TERMS || terms[in.first_term].phrase_offset != 0) {
+        uint32_t n_parts = 0;
+        for (uint32_t j = 0; j < n_incl; ++j)
+          n_parts += (terms[in.first_term + j].kind & IRS_HIP_PHRASE_ALT) ? 0u : 1u;
+        if (n_parts > IRS_HIP_MAX_PHRASE_TERMS || (terms[in.first_term].kind & IRS_HIP_PHRASE_ALT) ||
+            terms[in.first_term].phrase_offset != 0) {
           rc = IRS_HIP_EINVAL;
           break;
         }
@@ -494,8 +508,26 @@ static int batch_create_multi_impl(irs_hip_segment* const* segs, uint32_t n_segs
       smins.clear();   // per present term: the smallest score of one posting
       bool absent = false, same_bound = true;
       double upper = 0.0, min_score = 1e300, upper_all = 0.0;
+      // phrase parts: entries [part_first, j) so far form the current one; bit r of `opens` = row r
+      // is the first present member of its part; `found` = the parts with a present member
+      uint32_t n_parts = 0, part_first = 0, opens = 0, found = 0;
+      bool part_open = false;
       for (uint32_t j = 0; j < n_incl; ++j) {
         const irs_hip_term_scorer& ts = terms[in.first_term + j];
+        const bool member = is_phrase && (ts.kind & IRS_HIP_PHRASE_ALT) != 0;
+        const int32_t kind = is_phrase ? (ts.kind & ~IRS_HIP_PHRASE_ALT) : ts.kind;
+        if (is_phrase && !member) {
+          ++n_parts;
+          part_first = j;
+          part_open = false;
+        } else if (member) {
+          // one more member of the part: at the part's offset, a term not yet in it
+          const irs_hip_term_scorer& head = terms[in.first_term + part_first];
+          if (ts.phrase_offset != head.phrase_offset) rc = IRS_HIP_EINVAL;
+          for (uint32_t x = part_first; x < j && ts.term != IRS_HIP_NO_TERM; ++x)
+            if (terms[in.first_term + x].term == ts.term) rc = IRS_HIP_EINVAL;
+          if (rc != IRS_HIP_OK) break;
+        }
         DevQTerm qt{};
         qt.term = ts.term;
         qt.c0 = ts.c0;
@@ -510,7 +542,7 @@ static int batch_create_multi_impl(irs_hip_segment* const* segs, uint32_t n_segs
         // still mark the doc as matched, and sums below kMaxTerms units come back as 0)
         const bool norms = seg->dev.norms != nullptr;
         const bool legacy = norms && seg->dev.norm_legacy;
-        switch (ts.kind) {
+        switch (kind) {
           case IRS_HIP_SCORE_BM25:
             qt.kind = !norms ? kBM25One
                       : legacy ? kBM25Legacy
@@ -533,14 +565,20 @@ static int batch_create_multi_impl(irs_hip_segment* const* segs, uint32_t n_segs
         if (rc != IRS_HIP_OK) break;
         // (BM25 family: a posting scores below its boost c0 whatever the segment holds; the
         // TF-IDF bound grows with the segment's largest frequency)
-        same_bound = same_bound && (ts.kind == IRS_HIP_SCORE_BM25 || ts.kind == IRS_HIP_SCORE_BM15 ||
-                                    ts.kind == IRS_HIP_SCORE_BM1);
+        same_bound = same_bound && (kind == IRS_HIP_SCORE_BM25 || kind == IRS_HIP_SCORE_BM15 ||
+                                    kind == IRS_HIP_SCORE_BM1);
         upper_all += double(ts.c0);
         // TermQuery::execute: no term state in this segment -> empty iterator
         // (term_query.cpp:41-43)
         if (qt.term == IRS_HIP_NO_TERM || seg->terms[qt.term].docs_count == 0) {
-          absent = true;
+          // (a phrase: an absent member is dropped; a part without a present one is `absent`)
+          if (!is_phrase) absent = true;
           continue;
+        }
+        if (is_phrase) {
+          if (!part_open) opens |= 1u << row.size();
+          part_open = true;
+          found |= 1u << (n_parts - 1u);
         }
         const DevTerm& t = seg->terms[qt.term];
         qt.pad1 = t.tf_bound;
@@ -562,6 +600,8 @@ static int batch_create_multi_impl(irs_hip_segment* const* segs, uint32_t n_segs
         }
         const bool tfidf = qt.kind == kTfidf || qt.kind == kTfidfTiny || qt.kind == kTfidfWide ||
                            qt.kind == kTfidfLegacy;
+        // (a phrase's frequency is at most the sum of the tf_bound of its first part's members; the
+        // sum over every row of sqrt(tf_bound) bounds the square root of that, sqrt being subadditive)
         upper += tfidf ? double(qt.c0) * std::sqrt(double(t.tf_bound)) : double(qt.c0);
         b->postings += t.docs_count;
         b->alg_bytes += uint64_t(t.blocks_bytes) + t.tail_bytes;
@@ -594,8 +634,11 @@ static int batch_create_multi_impl(irs_hip_segment* const* segs, uint32_t n_segs
         need = (m > n_incl || m > row.size()) ? 0xFFu : m;
       }
       if (is_phrase) {
-        // no phrase state for a segment lacking one of the terms (phrase_filter.cpp:254-258)
+        // no phrase state for a segment lacking one of the terms (phrase_filter.cpp:254-258), or
+        // a part with none of its members (:370-379)
+        absent = found != (1u << n_parts) - 1u;
         need = absent ? 0xFFu : 1u;
+        b->blocks.variadic = b->blocks.variadic || alt;
         // the phrase's scorer is one stats blob: every entry must carry the same values
         for (const DevQTerm& qt : row)
           if (qt.kind != row[0].kind || qt.c0 != row[0].c0 ||
@@ -698,6 +741,7 @@ static int batch_create_multi_impl(irs_hip_segment* const* segs, uint32_t n_segs
       dq.n_caches = n_caches;
       dq.n_terms = uint32_t(row.size());
       dq.first_term = uint32_t(b->qterms.size());
+      if (is_phrase && !row.empty()) b->blocks.opens[q] = opens;
       upper *= 1.0 + 1e-6;
       if (!row.empty() && upper == 0.0) upper = 1.0;   // every boost is 0: all scores are 0
       if (!row.empty() && !(upper > 0.0 && std::isfinite(upper))) {

@@ -39,10 +39,53 @@ int stage_lead_items(irs_hip_batch* b, DevBuf& d_per_unit, const std::vector<uin
   return IRS_HIP_OK;
 }
 
+// k_vphrase work (vphrase.h) of a batch with variadic phrases: the iteration lead of a unit is the
+// part with the smallest sum of its members' docs_count (a disjunction costs the sum of its
+// members, Conjunction sorts by cost; the first such part on ties); one wavefront per block (+ tail)
+// of every member of it.  The pilot pass samples those items like any others.
+int build_vphrase_work(irs_hip_batch* b) {
+  std::vector<uint32_t> lead_rows(b->nq, 0);
+  for (uint32_t u = 0; u < b->nq; ++u) {
+    const DevQuery& dq = b->queries[u];
+    if (!dq.n_terms) continue;
+    const irs_hip_segment* sg = b->segs[dq.seg];
+    const uint32_t opens = b->blocks.opens[u] | 1u;
+    uint64_t best = ~uint64_t(0);
+    uint32_t items = 0;
+    for (uint32_t lo = 0; lo < dq.n_terms;) {
+      uint32_t end = lo + 1;
+      while (end < dq.n_terms && !((opens >> end) & 1u)) ++end;
+      uint64_t cost = 0;
+      uint32_t k = 0;
+      for (uint32_t r = lo; r < end; ++r) {
+        const DevTerm& t = sg->terms[b->qterms[dq.first_term + r].term];
+        cost += t.docs_count;
+        k += t.nblk + ((t.docs_count == 1 || t.tail_n) ? 1u : 0u);
+      }
+      if (cost < best) {
+        best = cost;
+        items = k;
+        lead_rows[u] = lo | (end << 8);
+      }
+      lo = end;
+    }
+    b->blocks.units.push_back(u);
+    b->blocks.items.push_back(items);
+  }
+  if (b->blocks.units.empty()) return IRS_HIP_OK;
+  if (!b->blocks.d_opens.alloc(uint64_t(b->nq) * 4) ||
+      !b->up.copy(b->blocks.d_opens.p, b->blocks.opens.data(), uint64_t(b->nq) * 4))
+    return IRS_HIP_ENOMEM;
+  const int rc = stage_lead_items(b, b->blocks.d_lead_rows, lead_rows);
+  b->blocks.n_phrase_wgs = (b->blocks.n_items + kPhraseWaves - 1) / kPhraseWaves;
+  return rc;
+}
+
 // k_phrase work of a phrase batch, built at create: the lead term of a unit is its rarest one; one
 // wavefront per 128-posting block of it (+ one for its vint tail / single doc); records and start
 // blocks of the other terms written by k_conj_seek every run
 int build_phrase_work(irs_hip_batch* b) {
+  if (b->blocks.variadic) return build_vphrase_work(b);
   std::vector<uint32_t> lead_of(b->nq, 0);
   for (uint32_t u = 0; u < b->nq; ++u) {
     const DevQuery& dq = b->queries[u];
@@ -247,8 +290,42 @@ bool launch_phrase(irs_hip_batch* b, rt::stream_t st) {
             b->d_hits.as<unsigned long long>());
   return rt::last_error_ok();
 }
+// Variadic phrases (k_vphrase): the same stages, with the items of every lead member.
+template<int LAYOUT>
+bool launch_vphrase(irs_hip_batch* b, rt::stream_t st) {
+  if (b->blocks.n_phrase_wgs == 0) return true;
+  const uint32_t stride = b->stride_eff;
+  if (!ensure_pilot_list(b, stride, st) || !rt::dmemset(b->blocks.d_hist.p, 0, b->blocks.d_hist.n, st) ||
+      !rt::dmemset(b->blocks.d_item_hits.p, 0, b->blocks.d_item_hits.n, st))
+    return false;
+  ConjArgs a = block_args(b, stride);
+  const uint32_t* opens = b->blocks.d_opens.as<uint32_t>();
+  RT_LAUNCH(k_vphrase_seek, (b->blocks.n_items + kThreads - 1) / kThreads, kThreads, 0, st,
+            b->d_segs.as<DevSegment>(), b->d_queries.as<DevQuery>(), b->d_tails.as<DevTail>(),
+            b->jt, b->blocks.d_units.as<uint32_t>(), b->blocks.d_item_base.as<uint32_t>(),
+            uint32_t(b->blocks.units.size()), b->blocks.d_lead_rows.as<uint32_t>(),
+            b->blocks.d_seek.as<uint32_t>(), b->blocks.d_recs.as<ConjItem>());
+  if (b->blocks.n_pilot) {
+    ConjArgs p = a;
+    p.wgs = b->blocks.d_pilot.as<PhraseWg>();
+    p.n_pilot = b->blocks.n_pilot;
+    p.touched = nullptr;
+    RT_LAUNCH(k_vphrase<LAYOUT>, (b->blocks.n_pilot + kPhraseWaves - 1) / kPhraseWaves,
+              kPhraseWaves * 64, 0, st, p, opens, 1u);
+  }
+  RT_LAUNCH(k_conj_threshold, uint32_t(b->blocks.units.size()), 64, 0, st,
+            b->d_queries.as<DevQuery>(), b->blocks.d_units.as<uint32_t>(),
+            b->blocks.d_items.as<uint32_t>(), b->blocks.d_hist.as<uint32_t>(), stride,
+            b->estimate ? kPilotMargin : 0u, b->d_bstar.as<uint32_t>(), min_bins(b));
+  RT_LAUNCH(k_vphrase<LAYOUT>, b->blocks.n_phrase_wgs, kPhraseWaves * 64, 0, st, a, opens, 0u);
+  RT_LAUNCH(k_conj_hits, uint32_t(b->blocks.units.size()), 64, 0, st, b->blocks.d_units.as<uint32_t>(),
+            b->blocks.d_item_base.as<uint32_t>(), b->blocks.d_item_hits.as<uint32_t>(),
+            b->d_hits.as<unsigned long long>());
+  return rt::last_error_ok();
+}
 template<int LAYOUT>
 bool launch_phrase_terms(irs_hip_batch* b, rt::stream_t st) {
+  if (b->blocks.variadic) return launch_vphrase<LAYOUT>(b, st);
   if (b->jt <= 2) return launch_phrase<LAYOUT, 2>(b, st);
   if (b->jt <= 4) return launch_phrase<LAYOUT, 4>(b, st);
   return launch_phrase<LAYOUT, int(kPhraseMaxTerms)>(b, st);

@@ -1,0 +1,447 @@
+// vphrase.h — by_phrase with parts that stand for a set of terms (IRS_HIP_PHRASE_ALT).
+//
+// Reference: VariadicPrepareCollect (core/search/phrase_filter.cpp:295-432), VariadicPhraseQuery::
+// execute (phrase_query.cpp:197-294) -> PhraseIterator<Conjunction of one disjunction per part,
+// VariadicPhraseFrequency> (phrase_iterator.hpp:197-364).  Parts P_0..P_n-1 at offsets off_i
+// (off_0 = 0); per doc
+//   freq(d) = sum over t in P_0 of #{p in pos(t, d) : for every i >= 1 some u in P_i has
+//             p + off_i in pos(u, d)}
+// (VisitLead adds the counts of the first part's members, VisitFollower is satisfied by one member).
+//
+// The rows of a unit (DevQuery::n_terms <= kVarRows) are the present members, part after part;
+// bit r of the unit's `opens` word is set when row r opens a part.  The block-driven scheme of
+// k_phrase (phrase.h) with these changes:
+//   - the ITERATION LEAD is the part with the smallest sum of docs_count (a disjunction costs the sum
+//     of its members, Conjunction sorts by cost); its lead items are the blocks (and tails) of EVERY
+//     one of its members, a wavefront each (k_vphrase_seek writes the records and start blocks);
+//   - an item of lead member j owns doc d only if no lead member j' < j holds d: those are decoded
+//     first and their hits leave the alive set, so every doc is scored by exactly one item;
+//   - every other part's members are decoded for the alive docs (the same "blocks that can hold an
+//     alive doc" step as k_phrase), each into its own row; after the part, alive = docs one of its
+//     members reached.  The lead's members after j are decoded last, for the surviving docs;
+//   - per surviving doc, one lane merges the position lists with one cursor per row (registers,
+//     compile-time indexed: the loops over rows are unrolled).
+// Alive sets are kept per doc in the lanes (two lead entries each); the bucket bitmap that steers
+// the block selection is rebuilt from them after every step.
+//
+// The fixed kernels (k_phrase2 / k_phrase) are left as they are, instruction for instruction: the
+// follower decode below repeats theirs rather than sharing it (sharing changed their register
+// allocation).  A batch with any variadic unit runs all of its phrase units here.
+#pragma once
+#include "phrase.h"
+
+namespace irs_hip {
+
+constexpr uint32_t kVarRows = 16;   // IRS_HIP_MAX_PHRASE_ENTRIES
+
+// As k_conj_seek, for the lead items of the variadic kernel: item t of unit `unit` is block / tail
+// `item` of the lead part's member in row `row` (ConjItem::item = item | row << 24); seek row: the
+// start block in every other row, in row order.  lead_rows[unit] = first | end << 8 of the lead part.
+__global__ void __launch_bounds__(kThreads)
+k_vphrase_seek(const DevSegment* segs, const DevQuery* queries, const DevTail* tails, uint32_t jt,
+               const uint32_t* units, const uint32_t* item_base /*[n_units + 1]*/, uint32_t n_units,
+               const uint32_t* lead_rows, uint32_t* seek, ConjItem* recs) {
+  const uint32_t t = blockIdx.x * kThreads + threadIdx.x;
+  if (t >= item_base[n_units]) return;
+  uint32_t lo = 0, hi = n_units;   // the unit whose items hold t: last c with item_base[c] <= t
+  while (hi - lo > 1) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (item_base[mid] <= t) lo = mid; else hi = mid;
+  }
+  const uint32_t unit = units[lo];
+  const DevQuery qd = queries[unit];
+  const DevSegment& seg = segs[qd.seg];
+  const DevTail* tl = tails + uint64_t(unit) * jt;
+  const uint32_t lr = lead_rows[unit];
+  uint32_t item = t - item_base[lo], row = lr & 0xFFu;
+  for (; row + 1u < (lr >> 8); ++row) {   // the member whose items hold t: blocks, then its tail
+    const uint32_t k = tl[row].nblk + (tl[row].n ? 1u : 0u);
+    if (item < k) break;
+    item -= k;
+  }
+  const DevTail ld = tl[row];
+  ConjItem r{};
+  r.unit = unit;
+  r.item = item | (row << 24);
+  if (item < ld.nblk) {
+    const uint64_t e = ld.dir_off + item;
+    r.base = item ? seg.blk_last[e - 1] : kDocMin;
+    r.r_lo = item ? r.base + 1u : kDocMin;
+    r.r_hi = seg.blk_last[e];
+    r.aoff = seg.blk_aoff[e];
+    r.bits = seg.blk_bits[e];
+    r.off = seg.blk_off[e];
+  } else {
+    r.r_lo = ld.first_doc;
+    r.r_hi = ld.last_doc;
+  }
+  recs[t] = r;
+  for (uint32_t i = 0; i < qd.n_terms; ++i) {
+    if (i == row) continue;
+    const uint32_t* last = seg.blk_last + tl[i].dir_off;
+    uint32_t a = 0, b = tl[i].nblk;  // lower_bound(last, r_lo)
+    while (a < b) {
+      const uint32_t mid = (a + b) >> 1;
+      if (last[mid] < r.r_lo) a = mid + 1; else b = mid;
+    }
+    seek[uint64_t(t) * (jt - 1u) + (i < row ? i : i - 1u)] = a;
+  }
+}
+
+struct VPhraseWave {
+  uint32_t docs[kBlock];
+  uint32_t pidx[kVarRows][kBlock];    // first position number of the doc in row r's list
+  uint32_t tf[kVarRows][kBlock];      // its frequency there (0: the member does not hold the doc)
+  alignas(16) uint8_t first[kConjBuckets];   // bucket -> 1 + entry index of its first lead doc
+  uint32_t bm[kConjWords + 4];        // alive docs' buckets over [dlo, dhi]
+  uint8_t apre[kConjWords + 4];       // bits of bm in the words before word w
+  DevPosTerm pt[kVarRows];
+  uint32_t off[kVarRows];
+};
+
+template<int LAYOUT>
+__device__ __forceinline__ void vphrase_item(const ConjArgs& A, const uint32_t* opens_of,
+                                             uint32_t pilot, VPhraseWave* s_wave) {
+  const uint32_t tid = threadIdx.x;
+  const unsigned lane = tid & 63u;
+  const uint32_t wv = wave::uniform(tid >> 6);
+  uint32_t e = blockIdx.x * kPhraseWaves + wv;
+  if (pilot) {
+    if (e >= A.n_pilot) return;
+    const PhraseWg w = A.wgs[e];
+    e = wave::uniform(A.unit_items[w.unit] + w.first_item);
+  } else if (e >= A.n_items) {
+    return;
+  }
+  const ConjItem R = wave::sload<ConjItem>(reinterpret_cast<uint64_t>(A.recs) + uint64_t(e) * sizeof(ConjItem));
+  const uint32_t unit = R.unit, item = R.item & kConjItemBlock, j = (R.item >> 24) & 0xFu;
+  const DevQuery qd = wave::sload<DevQuery>(reinterpret_cast<uint64_t>(A.queries) + uint64_t(unit) * sizeof(DevQuery));
+  const uint32_t m = qd.n_terms;
+  if (m == 0 || m > kVarRows || j >= m) return;
+  const DevSegment& seg = A.segs[qd.seg];
+  const uint64_t tl_at = reinterpret_cast<uint64_t>(A.tails) + uint64_t(unit) * A.jt * sizeof(DevTail);
+  auto term_tail = [&](uint32_t i) { return wave::sload<DevTail>(tl_at + i * sizeof(DevTail)); };
+  const uint32_t opens = wave::uniform(opens_of[unit]) | 1u;
+  const uint32_t n_parts = uint32_t(__builtin_popcount(opens));
+  // rows [part_lo(r), part_end(r)) form the part of row r
+  auto part_lo = [&](uint32_t r) { return 31u - uint32_t(__builtin_clz(opens & ((2u << r) - 1u))); };
+  auto part_end = [&](uint32_t r) {
+    const uint32_t above = opens & ~((2u << r) - 1u) & ((1u << m) - 1u);
+    return above ? uint32_t(__builtin_ctz(above)) : m;
+  };
+  const uint32_t lead_lo = part_lo(j), lead_end = part_end(j);
+  const uint32_t first_end = part_end(0);   // rows of P_0, whose positions are counted
+  const DevTail ld = term_tail(j);
+  const DevQTerm qt = A.qterms[qd.first_term];  // the phrase's scorer rides on every entry
+  const uint32_t bs = pilot ? 0u : A.bstar[unit];
+  VPhraseWave& W = s_wave[wv];
+  uint32_t* docs = W.docs;
+  const uint32_t* seek = A.seek + uint64_t(e) * (A.jt - 1u);
+  if (lane < m) {
+    const DevTail t = A.tails[uint64_t(unit) * A.jt + lane];
+    W.pt[lane] = seg.pterms[t.term];
+    W.off[lane] = A.qterms[qd.first_term + lane].pad0;
+  }
+
+  // ---- 1. the lead item: entry index 2*lane + h (block) or lane + 64*h (tail)
+  uint32_t n = kBlock;
+  uint32_t bytes = 0;
+  const bool counting = !pilot && A.touched != nullptr;
+  auto block_bytes = [](uint32_t bits) {
+    const uint32_t db = bits & 0xFFu, fb = bits >> 8;
+    return 2u + (db ? 16u * db : 1u) + (fb ? 16u * fb : 1u);
+  };
+  uint32_t ld_d[2], ld_e[2];
+  bool alive[2];   // the lane's lead entries still in the running (docs of the segment, not masked)
+  {
+    uint32_t f[2], p[2], estep;
+    if (item < ld.nblk) {
+      const uint64_t eb = ld.dir_off + item;
+      if (counting) bytes += block_bytes(R.bits);
+      uint32_t before;
+      if (pk_both(R.bits & 0xFFu, R.bits >> 8)) {
+        decode_packed_pos<LAYOUT>(seg.pk + (uint64_t(R.aoff) << 4), R.bits & 0xFFu, R.bits >> 8,
+                                  R.base, lane, ld_d[0], ld_d[1], f[0], f[1], before);
+      } else {
+        decode_block_pos<LAYOUT>(seg.doc + ld.doc_start + R.off, R.bits & 0xFFu, R.bits >> 8,
+                                 R.base, lane, ld_d[0], ld_d[1], f[0], f[1], before);
+      }
+      p[0] = seg.blk_pos[eb] - seg.blk_pos[ld.dir_off] + before;
+      p[1] = p[0] + f[0];
+      ld_e[0] = 2u * lane;
+      estep = 1u;
+    } else {
+      n = ld.n;
+      const uint32_t base = seg.blk_pos[ld.dir_off + ld.nblk] - seg.blk_pos[ld.dir_off];
+      tail_pidx(seg, ld.tail_row, n, base, lane, ld_d, f, p);
+      ld_e[0] = lane;
+      estep = 64u;
+    }
+    ld_e[1] = ld_e[0] + estep;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const uint32_t idx = ld_e[h];
+      docs[idx] = idx < n ? ld_d[h] : 0xFFFFFFFFu;
+      alive[h] = idx < n && !(qd.dead && doc_dead(qd.dead, ld_d[h]));
+      for (uint32_t i = 0; i < m; ++i) {
+        W.pidx[i][idx] = i == j ? p[h] : 0u;
+        W.tf[i][idx] = (i == j && alive[h]) ? f[h] : 0u;
+      }
+    }
+    static_assert(kConjBuckets == 64u * 16u, "one 16-byte store per lane clears `first`");
+    reinterpret_cast<ConjQuad*>(W.first)[lane] = ConjQuad{0u, 0u, 0u, 0u};
+  }
+  wave::sync();
+  const uint32_t dlo = wave::uniform(docs[0]), dhi = wave::uniform(docs[n - 1]);
+  const uint32_t span = dhi - dlo;
+  const uint32_t s = span < kConjBuckets ? 0u
+                     : 32u - uint32_t(__builtin_clz(span)) - (5u + uint32_t(__builtin_ctz(kConjWords)));
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    if (ld_e[h] < n) {
+      const uint32_t bk = (ld_d[h] - dlo) >> s;
+      if (ld_e[h] == 0u || ((docs[ld_e[h] - 1u] - dlo) >> s) != bk) W.first[bk] = uint8_t(ld_e[h] + 1u);
+    }
+  }
+  // the alive bitmap from the lanes' alive entries, and its prefix counts: number of alive buckets
+  auto rebuild = [&]() {
+    if (lane < (kConjWords + 4u) / 2u) {
+      W.bm[2u * lane] = 0u;
+      W.bm[2u * lane + 1u] = 0u;
+    }
+    wave::sync();
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      if (alive[h]) {
+        const uint32_t bk = (ld_d[h] - dlo) >> s;
+        atomicOr(&W.bm[bk >> 5], 1u << (bk & 31u));
+      }
+    }
+    wave::sync();
+    uint32_t p0 = 0, p1 = 0;
+    if (lane < kConjWords / 2u) {
+      p0 = uint32_t(__builtin_popcount(W.bm[2u * lane]));
+      p1 = uint32_t(__builtin_popcount(W.bm[2u * lane + 1u]));
+    }
+    const uint32_t incl = wave::inclusive_scan(p0 + p1);
+    if (lane < kConjWords / 2u) {
+      W.apre[2u * lane] = uint8_t(incl - p0 - p1);
+      W.apre[2u * lane + 1u] = uint8_t(incl - p1);
+    }
+    if (lane == kConjWords / 2u - 1u) W.apre[kConjWords] = uint8_t(incl);
+    wave::sync();
+    return wave::read_lane(incl, 63);
+  };
+  auto alive_below = [&](uint32_t x) {
+    return uint32_t(W.apre[x >> 5]) + uint32_t(__builtin_popcount(W.bm[x >> 5] & ((1u << (x & 31u)) - 1u)));
+  };
+
+  // ---- 2. one row: the blocks of its list that can hold an alive doc (k_phrase step 2), decoded;
+  // a posting on a lead doc leaves (P, tf) in the row at the doc's entry
+  auto decode_row = [&](uint32_t i) {
+    const DevTail tl = term_tail(i);
+    auto put = [&](uint32_t doc, uint32_t f, uint32_t p) {
+      const uint32_t x = doc - dlo;
+      if (f == 0 || x > span) return;
+      const uint32_t t = lead_index(W.first, docs, n, x >> s, s, doc);
+      if (t == n) return;
+      W.pidx[i][t] = p;
+      W.tf[i][t] = f;
+    };
+    if (tl.nblk) {
+      const uint64_t last_at = reinterpret_cast<uint64_t>(seg.blk_last + tl.dir_off);
+      const uint64_t dir_at = reinterpret_cast<uint64_t>(seg.blk_dir + tl.dir_off);
+      const uint64_t pos_at = reinterpret_cast<uint64_t>(seg.blk_pos + tl.dir_off);
+      const uint32_t pos0 = seg.blk_pos[tl.dir_off];
+      const uint32_t b_first = seek[i < j ? i : i - 1u];
+      for (uint32_t b0 = b_first; b0 < tl.nblk; b0 += 64) {
+        const uint32_t bl = b0 + lane;
+        const bool valid = bl < tl.nblk;
+        const uint32_t lst = valid ? wave::gload_u32(last_at, bl * 4u) : 0xFFFFFFFFu;
+        BlkDir d{};
+        uint32_t pos_l = 0;
+        if (valid) {
+          uint32_t w[4];
+          wave::gload_u32x4(dir_at, bl * uint32_t(sizeof(BlkDir)), w);
+          d = BlkDir{w[0], w[1], w[2], w[3]};
+          pos_l = wave::gload_u32(pos_at, bl * 4u);
+        }
+        const uint32_t prv = bl ? d.prev_last : 0u;   // the block holds docs in (prv, lst]
+        const bool reach = valid && prv < dhi && lst >= dlo;
+        bool want = false;
+        if (reach) {
+          const uint32_t x0 = prv + 1u > dlo ? prv + 1u - dlo : 0u;
+          const uint32_t x1 = (lst < dhi ? lst : dhi) - dlo;
+          want = alive_below((x1 >> s) + 1u) > alive_below(x0 >> s);
+        }
+        uint64_t mask = wave::ballot(want);
+        const bool more = wave::ballot(valid && prv >= dhi) == 0;
+        while (mask) {
+          const uint32_t k = uint32_t(__builtin_ctzll(mask));
+          mask &= mask - 1;
+          const uint32_t bits = wave::read_lane(d.bits, k);
+          if (counting) bytes += block_bytes(bits);
+          const uint32_t base = wave::read_lane(d.prev_last, k);
+          uint32_t d0, d1, f0, f1, before;
+          const uint32_t dbits = bits & 0xFFu, fbits = bits >> 8;
+          if (pk_both(dbits, fbits)) {
+            decode_packed_pos<LAYOUT>(seg.pk + (uint64_t(wave::read_lane(d.aoff, k)) << 4), dbits,
+                                      fbits, base, lane, d0, d1, f0, f1, before);
+          } else {
+            decode_block_pos<LAYOUT>(seg.doc + tl.doc_start + wave::read_lane(d.off, k), dbits,
+                                     fbits, base, lane, d0, d1, f0, f1, before);
+          }
+          const uint32_t p0 = wave::read_lane(pos_l, k) - pos0 + before;
+          put(d0, f0, p0);
+          put(d1, f1, p0 + f0);
+        }
+        if (!more) break;
+      }
+    }
+    if (tl.n && tl.first_doc <= dhi && tl.last_doc >= dlo) {  // vint tail / single doc
+      const uint32_t base = seg.blk_pos[tl.dir_off + tl.nblk] - seg.blk_pos[tl.dir_off];
+      uint32_t d[2], f[2], p[2];
+      tail_pidx(seg, tl.tail_row, tl.n, base, lane, d, f, p);
+      put(d[0], f[0], p[0]);
+      put(d[1], f[1], p[1]);
+    }
+  };
+  auto quit = [&]() {   // no doc left: what was decoded is counted
+    if (counting && lane == 0) atomicAdd(&A.touched[2u * unit], static_cast<unsigned long long>(bytes));
+  };
+  auto held = [&](uint32_t h, uint32_t lo, uint32_t end) {   // does a row of [lo, end) hold entry h?
+    const uint32_t idx = ld_e[h] < n ? ld_e[h] : 0u;
+    bool any = false;
+    for (uint32_t r = lo; r < end; ++r) any = any || W.tf[r][idx] != 0u;
+    return any;
+  };
+  // a. ownership: the lead members in front of j take the docs they hold
+  if (j > lead_lo) {
+    if (rebuild() == 0u) return quit();
+    for (uint32_t r = lead_lo; r < j; ++r) decode_row(r);
+    wave::sync();
+#pragma unroll
+    for (int h = 0; h < 2; ++h) alive[h] = alive[h] && !held(h, lead_lo, j);
+  }
+  // b. every other part: alive = docs one of its members holds
+  for (uint32_t lo = 0; lo < m;) {
+    const uint32_t end = part_end(lo);
+    if (lo != lead_lo) {
+      if (rebuild() == 0u) return quit();
+      for (uint32_t r = lo; r < end; ++r) decode_row(r);
+      wave::sync();
+#pragma unroll
+      for (int h = 0; h < 2; ++h) alive[h] = alive[h] && held(h, lo, end);
+    }
+    lo = end;
+  }
+  // c. the lead members behind j: their positions on the surviving docs
+  if (rebuild() == 0u) return quit();
+  for (uint32_t r = j + 1u; r < lead_end; ++r) decode_row(r);
+  wave::sync();
+
+  // ---- 3./4. surviving docs, compacted: merge the position lists, score, emit
+  const uint64_t below = (1ull << lane) - 1ull;
+  const uint64_t m0 = wave::ballot(alive[0]), m1 = wave::ballot(alive[1]);
+  const uint32_t c0 = uint32_t(__builtin_popcountll(m0));
+  const uint32_t total = c0 + uint32_t(__builtin_popcountll(m1));
+  uint8_t* list = W.first;   // (the bucket table has served)
+  wave::sync();
+  if (alive[0]) list[__builtin_popcountll(m0 & below)] = uint8_t(ld_e[0]);
+  if (alive[1]) list[c0 + uint32_t(__builtin_popcountll(m1 & below))] = uint8_t(ld_e[1]);
+  wave::sync();
+  uint32_t my_hits = 0, my_pos = 0;
+  DevSegment ps{};
+  ps.pos = seg.pos;
+  ps.pblk_off = seg.pblk_off;
+  ps.pblk_bits = seg.pblk_bits;
+  ps.ptail = seg.ptail;
+  ps.pos_base = seg.pos_base;
+  const uint32_t need = ((1u << n_parts) - 1u) & ~1u;   // every part but P_0
+  for (uint32_t q0 = 0; q0 < total; q0 += 64) {
+    bool cand = false;
+    float score = 0.f;
+    uint32_t doc = 0;
+    if (q0 + lane < total) {
+      const uint32_t sl = list[q0 + lane];
+      uint32_t P[kVarRows], T[kVarRows], K[kVarRows], V[kVarRows];
+#pragma unroll
+      for (int u = 0; u < int(kVarRows); ++u) {
+        const bool on = uint32_t(u) < m;
+        P[u] = on ? W.pidx[u][sl] : 0u;
+        T[u] = on ? W.tf[u][sl] : 0u;
+      }
+      uint32_t pf = 0;
+      for (uint32_t a = 0; a < first_end; ++a) {   // VisitLead: the members of P_0 add up
+        const uint32_t ta = W.tf[a][sl], pa = W.pidx[a][sl];
+#pragma unroll
+        for (int u = 0; u < int(kVarRows); ++u) {
+          K[u] = 0u;
+          V[u] = ps.pos_base;
+        }
+        uint32_t head = ps.pos_base;
+        for (uint32_t k = 0; k < ta; ++k) {
+          head += pos_delta<LAYOUT>(ps, W.pt[a], 0u, pa + k);
+          ++my_pos;
+          uint32_t hit = 0, open = 0;   // parts with a member at p + off / one that may still have
+#pragma unroll
+          for (int u = 1; u < int(kVarRows); ++u) {
+            if (uint32_t(u) < first_end || uint32_t(u) >= m) continue;
+            const uint32_t pb = 1u << (uint32_t(__builtin_popcount(opens & ((2u << u) - 1u))) - 1u);
+            if (hit & pb) continue;     // VisitFollower: one member at the position suffices
+            const uint32_t target = head + W.off[u];
+            // position::seek(target) :1578-1604 (value_ invalid until the first position: K == 0)
+            while ((K[u] == 0u || V[u] < target) && K[u] < T[u]) {
+              V[u] += pos_delta<LAYOUT>(ps, W.pt[u], 0u, P[u] + K[u]);
+              ++K[u];
+              ++my_pos;
+            }
+            if (K[u] != 0u && V[u] == target) hit |= pb;
+            else if (K[u] < T[u] || V[u] > target) open |= pb;
+          }
+          if (hit == need) ++pf;
+          else if (((hit | open) & need) != need) break;   // a part exhausted: no later p matches
+        }
+      }
+      if (pf) {
+        doc = docs[sl];
+        const uint32_t nv = !seg.pnorm ? norm_value(seg, doc)
+                            : (item < ld.nblk ? seg.pnorm[(ld.dir_off + item) * kBlock + sl]
+                                              : seg.tail_norms[ld.tail_row + sl]);
+        score = score_value(qt, pf, nv);
+        const uint32_t bin = score_bin(score, qd.bin_scale);
+        if (pilot) atomicAdd(&A.hist[uint64_t(unit) * kBins + bin], 1u);
+        else cand = bin >= bs;
+        ++my_hits;
+      }
+    }
+    const uint64_t cm = wave::ballot(cand);
+    if (cm) {
+      uint32_t base = 0;
+      if (lane == 0) base = atomicAdd(&A.cand_count[unit], uint32_t(__builtin_popcountll(cm)));
+      base = wave::read_lane(base, 0);
+      const uint32_t slot = base + uint32_t(__builtin_popcountll(cm & below));
+      if (cand && slot < A.cand_cap) A.cands[uint64_t(unit) * A.cand_cap + slot] = make_key(score, doc);
+    }
+  }
+  if (pilot) return;
+  my_hits = wave::reduce_add(my_hits);
+  if (lane == 0 && my_hits) A.item_hits[e] = my_hits;
+  if (A.touched) {
+    my_pos = wave::reduce_add(my_pos);
+    if (lane == 0) {
+      atomicAdd(&A.touched[2u * unit], static_cast<unsigned long long>(bytes));
+      if (my_pos) atomicAdd(&A.touched[2u * unit + 1u], static_cast<unsigned long long>(my_pos));
+    }
+  }
+}
+
+// 4 wavefronts x ~18.6 KB of rows: two workgroups per CU (LDS bound)
+template<int LAYOUT>
+__global__ void __launch_bounds__(kPhraseWaves * 64)
+k_vphrase(ConjArgs A, const uint32_t* opens, uint32_t pilot) {
+  __shared__ VPhraseWave s_wave[kPhraseWaves];
+  vphrase_item<LAYOUT>(A, opens, pilot, s_wave);
+}
+
+}  // namespace irs_hip

@@ -25,7 +25,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import _lib
-from ._lib import (EXCLUDE, HIT, NO_TERM, OP_AND, OP_MINMATCH, OP_OR, OP_PHRASE, QUERY, SCORE_BM1, SCORE_BM15, SCORE_BM25,
+from ._lib import (EXCLUDE, HIT, NO_TERM, OP_AND, OP_MINMATCH, OP_OR, OP_PHRASE, PHRASE_ALT, QUERY, SCORE_BM1, SCORE_BM15, SCORE_BM25,
                    SCORE_TFIDF, SCORE_TFIDF_NORM, TERM_META, TERM_SCORER, SegmentDesc)
 
 f32 = np.float32
@@ -124,8 +124,10 @@ class And:
 
 @dataclass
 class by_phrase:
-    """irs::by_phrase of plain terms (by_phrase_options::push_back<by_term_options>):
-    `terms` are term ordinals; `offsets[i]` = position of term i relative to the first
+    """irs::by_phrase (by_phrase_options): `terms[i]` is part i — a term ordinal
+    (push_back<by_term_options>) or a list of them: a part that stands for a set of terms, what a
+    by_terms / by_prefix / by_wildcard / by_range visitor yields, in dictionary order (a variadic
+    phrase, VariadicPrepareCollect); `offsets[i]` = position of part i relative to the first
     (default: consecutive words)."""
     terms: list
     offsets: list | None = None
@@ -136,6 +138,32 @@ class by_phrase:
             self.offsets = list(range(len(self.terms)))
         if len(self.offsets) != len(self.terms) or (self.offsets and self.offsets[0] != 0):
             raise ValueError("offsets are relative to the first term")
+
+    @property
+    def variadic(self):
+        return any(isinstance(t, (list, tuple)) for t in self.terms)
+
+    def parts(self):
+        """The member lists of the parts, checked: what the GPU path takes of a variadic phrase."""
+        parts = [list(t) if isinstance(t, (list, tuple)) else [t] for t in self.terms]
+        if len(parts) < 2:
+            raise ValueError("a by_phrase of one part is that part's own filter (by_phrase::Prepare, "
+                             "phrase_filter.cpp:442-449): send it as an Or of by_term, or through "
+                             "prepare_expansions")
+        if len(parts) > _lib.MAX_PHRASE_TERMS:
+            raise ValueError("a by_phrase has at most %d parts" % _lib.MAX_PHRASE_TERMS)
+        for part in parts:
+            if not part:
+                raise ValueError("a by_phrase part without terms")
+            if any(isinstance(t, (bool, float)) or not isinstance(t, (int, np.integer)) for t in part):
+                raise ValueError("per-member boosts (the reference's VolatileBoost path) are not on "
+                                 "the GPU path: a part's members are plain term ordinals")
+            if len(set(int(t) for t in part)) != len(part):
+                raise ValueError("a term twice in one by_phrase part")
+        if sum(len(p) for p in parts) > _lib.MAX_PHRASE_ENTRIES:
+            raise ValueError("a variadic by_phrase has at most %d members in all"
+                             % _lib.MAX_PHRASE_ENTRIES)
+        return [[int(t) for t in part] for part in parts]
 
 
 @dataclass
@@ -223,6 +251,8 @@ class PreparedQuery:
     offsets: list | None = None   # OP_PHRASE: position of every term in the phrase
     merge: int = MERGE_SUM
     excluded: list = field(default_factory=list)   # term ordinals under Not (IRS_HIP_EXCLUDE)
+    alts: list | None = None   # OP_PHRASE: True for an entry that is one more member of the part
+                               # before it (IRS_HIP_PHRASE_ALT)
 
 
 # ------------------------------------------------------------------ segment --
@@ -383,7 +413,9 @@ class QueryArrays:
         for q, p in enumerate(prepared):
             queries[q] = (p.op, len(p.terms) + len(p.excluded), at, int(k), p.min_match, p.merge)
             offs = p.offsets if p.offsets is not None else [0] * len(p.terms)
-            for t, (kind, c0, nc, nl), off in zip(p.terms, p.scorers, offs):
+            alts = p.alts if p.alts is not None else [False] * len(p.terms)
+            for t, (kind, c0, nc, nl), off, alt in zip(p.terms, p.scorers, offs, alts):
+                kind = kind | PHRASE_ALT if alt else kind
                 for s, sr in enumerate(segs):       # same scorer, the segment's own ordinal
                     present = t is not None and 0 <= t < len(sr.metas)
                     terms[s, at] = (t if present else NO_TERM, kind, c0, nc, nl, off)
@@ -460,6 +492,9 @@ def prepare_filters(filters, scorer, segment_stats, segs, k):
             bl.append(flt.boost)
             continue
         if isinstance(flt, by_phrase):
+            if flt.variadic:
+                raise ValueError("variadic by_phrase (a part of several terms) is taken by "
+                                 "prepare(), not by the array path prepare_filters")
             n = len(flt.terms)
             ops[q], nts[q] = OP_PHRASE, n
             if not ol_any:
@@ -777,6 +812,9 @@ def prepare(filters, scorer, segment_stats):
             p.excluded = [int(t) for t in excluded]
             out.append(p)
             continue
+        if isinstance(flt, by_phrase) and flt.variadic:
+            out.append(_prepare_variadic(flt, scorer, segment_stats, dwf, ttf))
+            continue
         if isinstance(flt, by_phrase):
             # FixedPrepareCollect (phrase_filter.cpp:212-293): term_stats.finish() of every
             # phrase term lands in ONE stats blob — BM25::collect / TFIDF::collect do
@@ -806,6 +844,46 @@ def prepare(filters, scorer, segment_stats):
                                  int(getattr(flt, "min_match", 0)),
                                  merge=int(getattr(flt, "merge", MERGE_SUM))))
     return out
+
+
+def variadic_slots(parts, segment_stats):
+    """VariadicPrepareCollect's statistics (phrase_filter.cpp:295-432) — docs_with_term of every
+    collector slot, collector after collector.  In each segment a part's visitor yields its members
+    present there (docs_count > 0) in dictionary order, and the i-th of them is collected into slot
+    i (term_offset_ restarts per segment, :159-186) of collector phrase_part_stats[found_parts]:
+    the count of parts that had members in that segment before this one."""
+    slots = [[] for _ in parts]
+    for st in segment_stats:
+        found = 0
+        for part in parts:
+            present = [t for t in part if 0 <= t < len(st.docs_count) and int(st.docs_count[t]) > 0]
+            col = slots[found]
+            for i, t in enumerate(present):
+                if i == len(col):
+                    col.append(0)
+                col[i] += int(st.docs_count[t])
+            found += 1 if present else 0
+    return [dwt for col in slots for dwt in col]
+
+
+def _prepare_variadic(flt, scorer, segment_stats, dwf, ttf):
+    """prepare() of a variadic by_phrase: ONE stats blob into which every slot was finished in
+    collector order (`idf +=`), entries part after part, every member after a part's first flagged
+    IRS_HIP_PHRASE_ALT."""
+    parts = flt.parts()
+    idf = f32(0)
+    stats = scorer.collect(dwf, 0, ttf)   # (no slot at all: nothing matches; same norm constants)
+    for dwt in variadic_slots(parts, segment_stats):
+        stats = scorer.collect(dwf, dwt, ttf)
+        idf = f32(idf + stats.idf)
+    one = scorer.term_scorer(TermStats(idf, stats.norm_const, stats.norm_length), flt.boost)
+    terms, offs, alts = [], [], []
+    for part, off in zip(parts, flt.offsets):
+        for i, t in enumerate(part):
+            terms.append(t)
+            offs.append(int(off))
+            alts.append(i > 0)
+    return PreparedQuery(OP_PHRASE, terms, [one] * len(terms), 0, offs, alts=alts)
 
 
 def merge_topk_host(per_segment, k: int):

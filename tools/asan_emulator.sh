@@ -52,6 +52,13 @@ cases.case_shared_threshold(L, sizes=(30_000, 13_000, 40_000), max_rank=128)
 cases.case_shared_threshold_misled(L)
 cases.case_doc_mask(L, 1, num_docs=30_000, max_rank=128)
 cases.case_conj_sparse_lead(L, 1, n_docs=120_000)
+import test_variadic_phrase as tv   # variadic phrases (k_vphrase)
+from iresearch_amd.search import BM25
+tv.case_abi(L)
+for layout in (1, 0):
+    tv.case_lists(L, layout)
+tv.case_parity(L, 6_000, 48, 1, (BM25(),), (10, 1000), 6)
+tv.case_multi(L, (3_000, 1_500, 4_000))
 print("asan emulator run: clean")
 PY
 # ... and the C++ host readers (header only: instrumented with the test binary) over a segment of

@@ -7,7 +7,8 @@ random Or / And / min-match / by_term
 filters with random boosts and merge types (or by_phrase filters), a random scorer and k, and
 checks the results as the parity tests do; the same batch is then re-run with block-max pruning
 (top-k must not change) and with the k-th score pushed down as irs::score::Min.  Every third
-boolean round also runs the filters with 0-2 excluded terms each (And(filter, Not(by_term))).
+boolean round also runs the filters with 0-2 excluded terms each (And(filter, Not(by_term))), and
+every phrase round also runs variadic phrases (parts of several terms).
 
   python tools/fuzz_parity.py --seconds 120            # on the GPU (libirs_hip.so)
   python tools/fuzz_parity.py --sim --seconds 60       # on the CPU emulator
@@ -114,6 +115,19 @@ def main():
             b = sr.batch(prep, k)
             hits, counts, totals = (x.copy() for x in b.run().results())
             parity.check_phrase_segment(seg, filters, scorer, k, hits, counts, totals)
+            # variadic phrases (IRS_HIP_PHRASE_ALT): 2-4 parts of 1-4 members near each other's
+            # frequency, against the restatement of tests/test_variadic_phrase.py
+            import test_variadic_phrase as tv
+            vf = tv.random_phrases(min(max_rank, 48), 8, int(rng.integers(1, 1 << 30)))
+            vprep = search.prepare(vf, scorer, st)
+            vb = sr.batch(vprep, k)
+            vh, vc, vt = (x.copy() for x in vb.run().results())
+            pos = tv._Pos(seg)
+            gone = () if getattr(seg, "doc_mask", None) is None else seg.doc_mask
+            for q, f in enumerate(vf):
+                tv.check(seg, pos, f, vprep[q], k, vh[q], vc[q], vt[q], gone)
+            vb.close()
+            queries += len(vf)
         else:
             filters = []
             for _ in range(16):

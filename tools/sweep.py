@@ -42,6 +42,10 @@ def main():
                     help="And(query, Not(term)...): N excluded terms per query (IRS_HIP_EXCLUDE), drawn "
                          "from --lo-rank..--hi-rank; also times the plan stage without them (the "
                          "difference is k_excl_mask)")
+    ap.add_argument("--alts", default="",
+                    help="--op phrase: comma list N,...: every part but the first gets N members (the "
+                         "word and N-1 ranks near it: a variadic phrase, IRS_HIP_PHRASE_ALT); 1 = the "
+                         "plain phrase of the same words.  Times each and exits")
     args = ap.parse_args()
     import torch
 
@@ -78,6 +82,34 @@ def main():
         filters = [And([f] + [Not(by_term(int(r) - 1))
                               for r in rng.integers(args.lo_rank, args.hi_rank + 1, args.exclude)])
                    for f in filters]
+    if args.alts and args.op == "phrase":
+        for n_alt in (int(x) for x in args.alts.split(",")):
+            rng = np.random.default_rng(synth.SEED + 4)
+            vf = []
+            for row in ranks:
+                words = [int(r) - 1 for r in row]
+                parts = [words[0]]
+                for w in words[1:]:
+                    near = [w]
+                    while len(near) < n_alt:
+                        x = int(np.clip(w + rng.integers(-8, 9), 0, 4095))
+                        if x not in near:
+                            near.append(x)
+                    parts.append(sorted(near) if n_alt > 1 else w)
+                vf.append(by_phrase(parts))
+            b = sr.batch(search.prepare(vf, scorer, [st]), args.k).profile(True)
+            b.run()
+            _, _, totals = b.results()
+            t0 = time.perf_counter()
+            for _ in range(args.steps):
+                b.run()
+                b.results()
+            dt = (time.perf_counter() - t0) / args.steps
+            print("alts=%d  %s  step %.2f ms  = %.2f ms per 1000 phrases  hits/query mean %.0f  reruns=%d"
+                  % (n_alt, "variadic" if n_alt > 1 else "plain", dt * 1e3, dt * 1e3 * 1000 / len(vf),
+                     float(np.mean(totals)), b.reruns()), flush=True)
+            b.close()
+        sys.exit(0)
     prep = search.prepare(filters, scorer, [st])
     ref = None
     for cfg in args.configs.split(","):

@@ -526,12 +526,26 @@ class QueryBatch {
       if (part.h) check(irs_hip_batch_set_async(part.h, enable ? 1 : 0), "irs_hip_batch_set_async");
     return *this;
   }
+  // how the disjunctions of the batch run (irs_hip_batch_set_path): by measured cost (default),
+  // every query decoding its own blocks, or every distinct term decoded once (joined streams)
+  enum class Path : int { Auto = IRS_HIP_PATH_AUTO, Items = IRS_HIP_PATH_ITEMS, Joined = IRS_HIP_PATH_JOINED };
+  QueryBatch& set_path(Path path) {
+    for (Part& part : part_)
+      if (part.h) check(irs_hip_batch_set_path(part.h, static_cast<int>(path)), "irs_hip_batch_set_path");
+    return *this;
+  }
   // joined plain disjunctions on paired doc tiles (default) or on 32-bit tiles
   // (irs_hip_batch_set_paired_tiles: the results are bit-identical, a tuning / test knob)
   QueryBatch& set_paired_tiles(bool enable) {
+    return set_paired_tiles(enable ? PairedTiles::WherePays : PairedTiles::Never);
+  }
+  // ... or by its three values: never / where the cost rule says they pay (default) / whatever
+  // the segments' size (small segments in tests)
+  enum class PairedTiles : int { Never = 0, WherePays = 1, Always = 2 };
+  QueryBatch& set_paired_tiles(PairedTiles mode) {
     for (Part& part : part_)
       if (part.h)
-        check(irs_hip_batch_set_paired_tiles(part.h, enable ? 1 : 0), "irs_hip_batch_set_paired_tiles");
+        check(irs_hip_batch_set_paired_tiles(part.h, static_cast<int>(mode)), "irs_hip_batch_set_paired_tiles");
     return *this;
   }
   bool paired_tiles() {   // whether the last run took them (any part)

@@ -1435,10 +1435,16 @@ k_join_score(const JoinArgs* __restrict__ args) {
 // so with S_k the k-th largest S of the unit, the k docs at or above it all have
 // f > (S_k - 2 m - 1) 2^15 while a doc with S <= S_k - 2 m - 3 has f < (S_k - 2 m - 3) 2^15: it
 // is not among the k best and k_select would drop it.  Only the docs with S >= S_k - 2 m - 2 are
-// looked up (about k of the ~3 k an estimated threshold stages); if fewer than k of them pass the
-// exact test — the k-th score sits within 2 m units of the threshold — the rest is looked up
-// too, and the list is exactly the 32-bit kernel's.  Either way k_select sees >= k candidates
-// exactly when that list has >= k, and the k best of both are the same docs with the same sums.
+// looked up (about k of the ~3 k an estimated threshold stages), and at least k of them pass the
+// exact test whenever some staged doc is left out: that doc has S <= S_k - 2 m - 3 and was staged,
+// S >= max(thr >> 15, 1), so each of the k docs with S >= S_k has
+//     f > (S_k - 2 m - 1) 2^15 >= (max(thr >> 15, 1) + 2) 2^15 >= thr + 2^15,
+// and 2^15 units are more than the 1e-6 relative bin_threshold lowers the bin edge by (sums stay
+// below 2^31): they pass the bin test too.  Every staged doc is looked up (kRescoreMax at a time)
+// only when the window holds more than kRescoreMax docs, or when no more than k were staged.  The
+// test "fewer than k passed, docs were left out" below cannot come true; it stays as a safety
+// net.  Either way k_select sees >= k candidates exactly when the 32-bit kernel's list has >= k,
+// and the k best of both are the same docs with the same sums.
 //
 // The look-up: the docs of a term are spread evenly, so the posting of doc offset o among the n
 // entries of a tile sits near n o / 12288: sixteen entries around that guess (four independent
@@ -1646,8 +1652,8 @@ k_join_rescore(const uint32_t* units, const DevQuery* queries, const DevQTerm* q
       for (uint32_t c = tid; c < sel; c += blockDim.x) mine += passes(fsum[c]) ? 1u : 0u;
       if (mine) atomicAdd(&vars[kPass], mine);
       __syncthreads();
-      // k of them pass (or nothing was left out): they are the list; else — the k-th score sits
-      // within 2 m units of the threshold, rare — every staged doc is looked up below
+      // k of them pass (or nothing was left out): they are the list.  (Fewer than k passing with
+      // docs left out cannot happen — the bound above; should it, every staged doc is looked up.)
       if (vars[kPass] >= qd.k || sel == n) {
         for (uint32_t c = tid; c < sel; c += blockDim.x)
           if (passes(fsum[c])) list[atomicAdd(&vars[kOut], 1u)] = key_of(c);

@@ -289,7 +289,10 @@ def case_decode_synth(L, layout, num_docs, max_rank, step=1):
 
 # ----------------------------------------------------------------- queries --
 
-def run_and_check(L, seg, filters, scorer, k, tile=0, stride=0, cap=0, sr=None, path=None):
+def run_and_check(L, seg, filters, scorer, k, tile=0, stride=0, cap=0, sr=None, path=None,
+                  expect_path=None, expect_paired=None):
+    """`expect_path` / `expect_paired`: what b.path() / b.paired_tiles() must say after the run
+    (pins the cost rules' choice for the batch: a change of rule fails here, not silently)."""
     own = sr is None
     sr = sr or search.SegmentReader.from_synth(seg, L=L)
     prep = search.prepare(filters, scorer, [parity.segment_stats(seg)])
@@ -299,6 +302,10 @@ def run_and_check(L, seg, filters, scorer, k, tile=0, stride=0, cap=0, sr=None, 
     if path is not None:
         b.set_path(path)
     hits, counts, totals = b.run().results()
+    if expect_path is not None:
+        assert b.path() == expect_path, (b.path(), expect_path)
+    if expect_paired is not None:
+        assert b.paired_tiles() == expect_paired, (b.paired_tiles(), expect_paired)
     parity.check_single_segment(seg, filters, scorer, k, hits, counts, totals)
     b.close()
     if own:
@@ -633,6 +640,363 @@ def case_paths_agree(L, num_docs=70_000, max_rank=256, layout=synth.LAYOUT_SIMD4
                     assert np.array_equal(hi[qi], hj[qi]), qi
                     assert np.array_equal(got[_lib.PATH_AUTO][0][qi], hj[qi]), qi
     sr.close()
+
+
+# ----------------------------------------------------- paired tiles: edges --
+# k_join_score<kJKHalf> stages docs by 16-bit sums, k_join_rescore looks their postings up and
+# forms the exact 32-bit sums (join.h).  Every case below runs the SAME prepared batch paired
+# (set_paired_tiles(2)), on 32-bit tiles (set_paired_tiles(0)) and on work items (k_score): the
+# three agree bit for bit and each agrees with the oracle.
+
+def _paired_runs(L, readers, prep, k, check, *, paired=True, reruns=0, cap=0, shared=False, joined=True):
+    """`readers`: one SegmentReader or a list (one batch over several segments).  `check(h, c, t)`
+    compares one run with the oracle.  `paired` / `joined`: whether the forced run pairs / whether
+    PATH_JOINED stays joined (64-bit accumulators: work items); `reruns` of the forced run (< 0:
+    at least one).  Returns the paired run's (hits, counts, totals)."""
+    got = []
+    for mode, path in ((2, _lib.PATH_JOINED), (0, _lib.PATH_JOINED), (2, _lib.PATH_ITEMS)):
+        if isinstance(readers, list):
+            b = search.QueryBatch(readers, prep).set_shared_threshold(shared)
+        else:
+            b = readers.batch(prep, k)
+        if cap:
+            b.configure(0, 0, cap)
+        b.set_path(path).set_paired_tiles(mode)
+        h, c, t = b.run().results()
+        assert b.path() == (path if joined else _lib.PATH_ITEMS), (mode, path, b.path())
+        assert b.paired_tiles() == (paired and mode == 2 and path == _lib.PATH_JOINED), (mode, path)
+        if mode == 2 and path == _lib.PATH_JOINED:   # (reruns < 0: at least one)
+            assert (b.reruns() >= 1) if reruns < 0 else (b.reruns() == reruns), b.reruns()
+        check(h, c, t)
+        got.append((h.copy(), c.copy(), t.copy()))
+        b.close()
+    for other in got[1:2] if shared else got[1:]:
+        for x, y in zip(got[0], other):
+            assert np.array_equal(x, y)
+    if shared:   # (work items share no threshold: every segment lists its own k — merged, the same)
+        merged = [search.merge_topk_host([(h[i], c[i]) for i in range(len(readers))], k)
+                  for h, c, _ in (got[0], got[2])]
+        assert merged[0] == merged[1] and np.array_equal(got[0][2], got[2][2])
+    return got[0]
+
+
+def _exact_ties(seg, filters, scorer, k, hits, counts):
+    """The docs and their order are exactly the first k of the oracle's exhaustive scores sorted
+    by (score desc, doc asc): where scores tie across the k-th position the smallest doc ids stay.
+    (Only where tied docs tie in float too — here every tie is one of equal postings.)"""
+    view = parity.oracle_view(seg)
+    for q, flt in enumerate(filters):
+        op, subs = search._terms_of(flt)
+        terms = [s.term for s in subs]
+        scores, matched = oracle.score_all(view, parity.metas_for(seg, terms), op, parity.oracle_scorer(scorer),
+                                           seg.docs_with_field, [int(seg.metas[t]["docs_count"]) for t in terms],
+                                           seg.total_term_freq, [s.boost for s in subs])
+        docs = np.nonzero(matched)[0]
+        want = docs[np.lexsort((docs, -scores[docs].astype(np.float64)))][:k]
+        n = int(counts[q])
+        assert n == want.size and np.array_equal(hits[q, :n]["doc"], want), q
+
+
+def _in_tile_docs(tiles, offsets):   # doc ids at these offsets of these 12288-doc tiles
+    return np.sort(np.concatenate([1 + t * 12288 + np.asarray(offsets, np.int64) for t in tiles]))
+
+
+def case_paired_ties(L, layout=synth.LAYOUT_SIMD4):
+    """Docs that share one score (constant tf, constant norm): single terms and OR-2 / OR-8 at
+    k = 1, 1000 and hits - 1 / hits / hits + 1.  k_join_rescore's window around the k-th 16-bit
+    sum then holds every staged doc: 5 000 tied docs at k = 1000 take the full look-up over three
+    chunks of kRescoreMax (sel > 2048); 3 000 at k = 2 999 over two; k >= 3 000 = hits (n <= k)
+    the full path directly.  Ties across the k-th position come back as the oracle's: the
+    smallest doc ids, ascending."""
+    n_docs = 5 * 12288 - 1000
+    rng = np.random.default_rng(41)
+    def term(n, tf):
+        d = np.sort(rng.choice(n_docs, n, replace=False)).astype(np.uint32) + 1
+        return d, np.full(n, tf, np.uint32)
+    lists = [term(5000, 3), term(3000, 3), term(2000, 2), term(2000, 2)]
+    lists += [term(1500, 1) for _ in range(8)]
+    seg, sr = open_lists(L, lists, n_docs, layout, norms=np.full(n_docs, 9, np.uint8))
+    filters = [by_term(0), by_term(1), Or([by_term(2), by_term(3)]),
+               Or([by_term(j) for j in range(4, 12)])]
+    for scorer in (BM25(), TFIDF(True)):
+        prep = search.prepare(filters, scorer, [parity.segment_stats(seg)])
+        for k in (1, 1000, 2999, 3000, 3001):
+            def check(h, c, t):
+                parity.check_single_segment(seg, filters, scorer, k, h, c, t)
+                _exact_ties(seg, filters, scorer, k, h, c)
+            _, c, t = _paired_runs(L, sr, prep, k, check)
+            assert int(t[0]) == 5000 and int(t[1]) == 3000
+    sr.close()
+
+
+
+def case_paired_window(L, layout=synth.LAYOUT_SIMD4, k=40):
+    """k_join_rescore looks up the docs within 2 m + 2 units of the k-th 16-bit sum S_k, because the
+    16-bit sums round every contribution up by one to two units: k docs hold 8 terms each (S about
+    12 units above their exact sum), one doc Y holds a single term boosted to score 2e-4 more —
+    Y's exact sum is the best, its S about 8 units below theirs.  A narrower window leaves Y out."""
+    n_docs = 3 * 12288
+    rng = np.random.default_rng(61)
+    pool = rng.permutation(n_docs).astype(np.uint32) + 1
+    xs, y = np.sort(pool[:k]), int(pool[k])
+    lists = []
+    for j in range(8):   # X docs + 300 docs of their own: the same docs_count, the same idf
+        d = np.sort(np.concatenate([xs, pool[k + 1 + 300 * j:k + 1 + 300 * (j + 1)]]))
+        lists.append((d, np.ones(d.size, np.uint32)))
+    d = np.sort(np.concatenate([[y], pool[k + 1 + 2400:k + 1 + 2400 + k + 299]]))
+    f = np.ones(d.size, np.uint32)
+    f[np.searchsorted(d, y)] = 4                        # sqrt(4) x 4.0008 = 8.0016
+    lists.append((d, f))
+    seg, sr = open_lists(L, lists, n_docs, layout, norms=False)
+    filters = [Or([by_term(j) for j in range(8)] + [by_term(8, 4.0008)])]
+    prep = search.prepare(filters, TFIDF(False), [parity.segment_stats(seg)])
+    h, c, t = _paired_runs(L, sr, prep, k, lambda h, c, t: parity.check_single_segment(
+        seg, filters, TFIDF(False), k, h, c, t))
+    assert int(h[0, 0]["doc"]) == y and set(h[0, 1:k]["doc"].tolist()) <= set(xs.tolist())
+    sr.close()
+
+def case_paired_ceiling(L, layout=synth.LAYOUT_SIMD4):
+    """16-term queries (IRS_HIP_MAX_TERMS) on docs that hold all 16 terms at the term's largest
+    frequency and the shortest norm — the sums closest to the query's upper bound, where a 16-bit
+    half comes closest to 2^16 — at the same offset in both tiles of a pair, at offsets 0 and
+    12287, and in the last pair, which has one tile.  Frequencies up to 15 (table form) and up to
+    255 (general form); TF-IDF without norms, BM25, BM15, TF-IDF with norms.  Then boosts that
+    put upper / min_score just inside the 32-bit accumulators' 1000 (pairs) and just outside
+    (64-bit accumulators: no pairs)."""
+    n_docs = 5 * 12288                       # tiles 0+1, 2+3, 4 (a pair of one tile)
+    rng = np.random.default_rng(43)
+    top = _in_tile_docs(range(5), [0, 1, 4097, 12286, 12287]).astype(np.uint32)
+    norms = rng.integers(2, 200, n_docs).astype(np.uint8)
+    norms[top - 1] = 1
+    lists = []
+    for tf_max in (15, 255):
+        for j in range(16):
+            rest = np.setdiff1d(rng.choice(n_docs, 700 + 37 * j, replace=False).astype(np.uint32) + 1, top)
+            d = np.concatenate([top, rest])
+            f = np.concatenate([np.full(top.size, tf_max, np.uint32),
+                                rng.integers(1, tf_max, rest.size).astype(np.uint32)])
+            o = np.argsort(d)
+            lists.append((d[o], f[o]))
+    # two terms of tf 1 for the boost-ratio queries
+    for j in range(2):
+        d = np.sort(rng.choice(n_docs, 900, replace=False)).astype(np.uint32) + 1
+        lists.append((d, np.ones(d.size, np.uint32)))
+    seg, sr = open_lists(L, lists, n_docs, layout, norms=norms)
+    filters = [Or([by_term(j) for j in range(16)]), Or([by_term(16 + j) for j in range(16)])]
+    st = [parity.segment_stats(seg)]
+    # (TF-IDF with norms: 16 x sqrt(255) x sqrt(255) over 1000 — 64-bit accumulators, no pairs)
+    for scorer in (TFIDF(False), BM25(), BM25(1.2, 0.0)):
+        prep = search.prepare(filters, scorer, st)
+        for k in (1, 10):
+            h, c, t = _paired_runs(L, sr, prep, k, lambda h, c, t: parity.check_single_segment(
+                seg, filters, scorer, k, h, c, t))
+            for q in range(2):        # the ceiling docs lead, in doc order (all tie)
+                assert set(h[q, :int(c[q])]["doc"].tolist()) <= set(top.tolist()), (scorer, q)
+    # upper / min_score of a TF-IDF (no norms) OR of two tf-1 terms: (c0a + c0b)(1 + 1e-6) / c0b
+    # for boost a >> b — the host's rule (irs_hip.hip: 32-bit accumulators while <= 1000)
+    scorer = TFIDF(False)
+    a, b = 32, 33
+    ia, ib = (float(search.prepare([by_term(t)], scorer, st)[0].scorers[0][1]) for t in (a, b))
+    for ratio, paired in ((999.9, True), (1000.1, False)):
+        boost = (ratio / (1.0 + 1e-6) - 1.0) * ib / ia
+        p = search.prepare([Or([by_term(a, boost), by_term(b)])], scorer, st)[0]
+        c0a, c0b = float(p.scorers[0][1]), float(p.scorers[1][1])
+        r = (c0a + c0b) * (1.0 + 1e-6) / min(c0a, c0b)
+        assert (r <= 1000.0) == paired and abs(r - 1000.0) < 0.2, r
+        fl = [Or([by_term(a, boost), by_term(b)]), Or([by_term(b), by_term(a)])]
+        prep = search.prepare(fl, scorer, st)
+        # (outside: 64-bit accumulators — the batch leaves the joined streams, which sum in 32 bits)
+        _paired_runs(L, sr, prep, 50, lambda h, c, t: parity.check_single_segment(
+            seg, fl, scorer, 50, h, c, t), paired=paired, joined=paired)
+    sr.close()
+
+
+def case_paired_lookups(L, layout=synth.LAYOUT_SIMD4):
+    """Terms whose postings in a tile are far from evenly spread — all in the tile's last eighth
+    plus one at offset 0; bursts at both ends — with n below 16, around 256 and in the thousands
+    per tile, in queries with evenly spread terms: k_join_rescore's look-ups (join_find) take the
+    density-corrected probe, both gallops, the binary search and the in-window misses.  The last
+    query's last term is the batch's last stream (the over-read behind it: kJoinSlack)."""
+    n_docs = 5 * 12288 - 17
+    rng = np.random.default_rng(47)
+    tiles = range(5)
+    def last_eighth(n):
+        return np.concatenate([[0], np.sort(rng.choice(np.arange(12288 - 1536, 12288), n - 1, replace=False))])
+    def both_ends(n):
+        return np.concatenate([np.arange(n // 2), np.arange(12288 - (n - n // 2), 12288)])
+    def lst(offs_of, n, tf_hi=8):
+        d = np.concatenate([1 + t * 12288 + offs_of(n) for t in tiles])
+        d = np.unique(d[d <= n_docs]).astype(np.uint32)
+        return d, rng.integers(1, tf_hi, d.size).astype(np.uint32)
+    def even(n):
+        d = np.sort(rng.choice(n_docs, n, replace=False)).astype(np.uint32) + 1
+        return d, rng.integers(1, 12, d.size).astype(np.uint32)
+    lists = [lst(last_eighth, 12), lst(last_eighth, 300), lst(last_eighth, 1500),
+             lst(both_ends, 10), lst(both_ends, 260), lst(both_ends, 3000),
+             even(9000), even(20000), even(4000),
+             even(2500)]                        # 9: only in the last query, as its last term
+    seg, sr = open_lists(L, lists, n_docs, layout, norms=rng.integers(1, 60, n_docs).astype(np.uint8))
+    filters = [Or([by_term(6), by_term(0), by_term(1), by_term(2)]),
+               Or([by_term(7), by_term(3), by_term(4), by_term(5)]),
+               Or([by_term(j) for j in range(9)]),
+               Or([by_term(2, 3.0), by_term(5, 3.0), by_term(8)]),
+               by_term(1), by_term(5),
+               Or([by_term(7), by_term(0), by_term(3), by_term(9)])]
+    st = [parity.segment_stats(seg)]
+    # (TF-IDF with norms: the rare terms' idf puts upper / min_score over 1000 — no pairs)
+    for scorer in (BM25(), TFIDF(False)):
+        prep = search.prepare(filters, scorer, st)
+        for k in (10, 1000, 4096):
+            _paired_runs(L, sr, prep, k, lambda h, c, t: parity.check_single_segment(
+                seg, filters, scorer, k, h, c, t))
+    sr.close()
+
+
+def _check_term_sums(seg, prep, k, hits, counts, totals):
+    """The oracle per term — each with the scorer constants of its own row — summed in double
+    (for queries whose terms do not share one scorer)."""
+    view = parity.oracle_view(seg)
+    for q, p in enumerate(prep):
+        total = np.zeros(seg.num_docs + 2, np.float64)
+        matched = np.zeros(seg.num_docs + 2, bool)
+        for t, sc in zip(p.terms, p.scorers):
+            osc, boost = sc[4], sc[5]
+            s, m = oracle.score_all(view, parity.metas_for(seg, [t]), oracle.OP_OR, parity.oracle_scorer(osc),
+                                    seg.docs_with_field, [int(seg.metas[t]["docs_count"])],
+                                    seg.total_term_freq, [boost])
+            total[:s.size] += s
+            matched[:m.size] |= m.astype(bool)
+        n_match = int(matched.sum())
+        assert int(totals[q]) == n_match, q
+        n = int(counts[q])
+        assert n == min(k, n_match), q
+        docs = hits[q, :n]["doc"].astype(np.int64)
+        assert len(set(docs.tolist())) == n and matched[docs].all(), q
+        ref = total[docs]
+        assert (np.abs(hits[q, :n]["score"] - ref) <= parity.REL_TOL * ref).all(), q
+        s, d = hits[q, :n]["score"], hits[q, :n]["doc"]
+        assert ((s[:-1] > s[1:]) | ((s[:-1] == s[1:]) & (d[:-1] < d[1:]))).all(), q
+        kth = np.sort(total[matched])[::-1][n - 1]
+        must = np.nonzero(matched & (total > kth * (1 + 2 * parity.REL_TOL)))[0]
+        assert np.isin(must, docs).all(), q
+
+
+def case_paired_forms(L, layout=synth.LAYOUT_SIMD4):
+    """A term's form in k_join_score and k_join_rescore (join_fx): table rows for every frequency
+    (tf_bound < rows) or row 0 + the general expression.  rows = 16 / 8 / 4 for 1 / 2 / 3 table
+    slots (distinct (kind, norm_const, norm_length) of a query), so terms of tf_bound 3, 4, 7, 8,
+    15, 16, 63, 64, 255 (kJoinTfMax) fall on either side; a term of tf_bound 256 leaves the joined
+    path for its unit (work items), the batch's other units still pair.  Two and three slots:
+    the prepared per-term rows are rewritten with the constants of other BM25 scorers and the
+    result is checked against per-term oracle scores summed in double."""
+    n_docs = 5 * 12288 - 300
+    rng = np.random.default_rng(53)
+    bounds = (3, 4, 7, 8, 15, 16, 63, 64, 255, 256)
+    lists = []
+    for tfb in bounds:
+        d = np.sort(rng.choice(n_docs, 1800, replace=False)).astype(np.uint32) + 1
+        f = rng.integers(1, tfb + 1, d.size).astype(np.uint32)
+        f[rng.integers(0, d.size)] = tfb
+        lists.append((d, f))
+    seg, sr = open_lists(L, lists, n_docs, layout, norms=rng.integers(1, 90, n_docs).astype(np.uint8))
+    st = [parity.segment_stats(seg)]
+    T = {tfb: i for i, tfb in enumerate(bounds)}
+    joinable = [T[b] for b in bounds[:-1]]
+    filters = [Or([by_term(T[15]), by_term(T[16])]), Or([by_term(T[63]), by_term(T[64]), by_term(T[255])]),
+               Or([by_term(j) for j in joinable]), Or([by_term(T[256]), by_term(T[3])]),
+               by_term(T[16]), by_term(T[255])]
+    for scorer in (BM25(), TFIDF(False), TFIDF(True)):
+        prep = search.prepare(filters, scorer, st)
+        for k in (10, 1000):
+            _paired_runs(L, sr, prep, k, lambda h, c, t: parity.check_single_segment(
+                seg, filters, scorer, k, h, c, t))
+    # two / three table slots: rows 8 / 4
+    others = (BM25(), BM25(2.0, 1.0), BM25(1.2, 0.0))
+    mixed = [[T[7], T[8], T[3]], [T[3], T[4], T[8]], joinable, [T[15], T[16], T[4], T[7]]]
+    for n_slots in (2, 3):
+        prep = []
+        for q, terms in enumerate(mixed):
+            rows = []
+            for j, t in enumerate(terms):
+                sc = others[(j + q) % n_slots]
+                dwt = int(seg.metas[t]["docs_count"])
+                kind, c0, nc, nl = sc.term_scorer(sc.collect(seg.docs_with_field, dwt, seg.total_term_freq),
+                                                  1.0 + 0.25 * j)
+                rows.append((kind, c0, nc, nl, sc, 1.0 + 0.25 * j))
+            prep.append(search.PreparedQuery(_lib.OP_OR, list(terms), rows))
+        run = [search.PreparedQuery(p.op, p.terms, [r[:4] for r in p.scorers]) for p in prep]
+        for k in (10, 1000):
+            _paired_runs(L, sr, run, k, lambda h, c, t: _check_term_sums(seg, prep, k, h, c, t))
+    sr.close()
+
+
+def case_paired_overflow(L, k=100):
+    """More staged docs than candidate slots on a paired run (configure(cand_cap = k)):
+    k_join_rescore leaves the unit alone (n > cap), k_select raises the overflow, the batch grows
+    its buffer and runs again (recover_overflow) — the same results as unpaired and the oracle.
+    A second run of the batch keeps the grown buffer: no further re-run."""
+    seg = synth.build_segment(5 * 12288, 256)
+    sr = search.SegmentReader.from_synth(seg, L=L)
+    ranks = synth.make_queries(6, 8, 4, 256, synth.SEED + 21)
+    filters = [Or([by_term(int(r) - 1) for r in row]) for row in ranks] + [by_term(0)]
+    prep = search.prepare(filters, BM25(), [parity.segment_stats(seg)])
+    check = lambda h, c, t: parity.check_single_segment(seg, filters, BM25(), k, h, c, t)  # noqa: E731
+    h, c, t = _paired_runs(L, sr, prep, k, check, cap=k, reruns=-1)
+    b = sr.batch(prep, k).configure(0, 0, k).set_path(_lib.PATH_JOINED).set_paired_tiles(2)
+    assert b.reruns() == 0
+    b.run().results()
+    n = b.reruns()
+    assert n >= 1 and b.paired_tiles()
+    h2, c2, t2 = b.run().results()
+    assert b.reruns() == n
+    assert np.array_equal(h, h2) and np.array_equal(c, c2) and np.array_equal(t, t2)
+    b.close()
+    sr.close()
+
+
+def case_paired_groups(L, sizes=(40_000, 12_000, 90_000), max_rank=256):
+    """Paired tiles across segments: three segments of uneven size, one of a single tile, one
+    threshold per query (set_shared_threshold) — the merged top k equals the unpaired batch's and
+    the oracle's.  And the guard that keeps k_join_rescore's search in doc order: a segment
+    opened with a doc mask never pairs, even forced, alone or in a batch with an unmasked one."""
+    first = np.concatenate([[0], np.cumsum(sizes)[:-1]])
+    segs = [synth.build_segment(int(n), max_rank, first_doc=int(f)) for n, f in zip(sizes, first)]
+    readers = [search.SegmentReader.from_synth(s, L=L) for s in segs]
+    ranks = synth.make_queries(8, 8, 4, max_rank, synth.SEED + 23)
+    filters = [Or([by_term(int(r) - 1) for r in row]) for row in ranks] + [by_term(3)]
+    for scorer in (BM25(), BM25(1.2, 0.0)):
+        prep = search.prepare(filters, scorer, [parity.segment_stats(s) for s in segs])
+        for k in (10, 500):
+            ref = parity.oracle_topk(segs, filters, scorer, k)
+            def check(h, c, t):
+                merged = search.merge_topk_host([(h[i], c[i]) for i in range(len(segs))], k)
+                for q, (rows, (ohits, total)) in enumerate(zip(merged, ref)):
+                    assert len(rows) == len(ohits) and int(t[:, q].sum()) == total, q
+                    a = np.array([r[0] for r in rows], np.float32)
+                    assert np.allclose(a, np.sort(ohits["score"])[::-1], rtol=parity.REL_TOL, atol=0), q
+            arrays = search.QueryArrays.from_prepared(readers, prep, k)
+            _paired_runs(L, readers, arrays, k, check, shared=True)
+    for r in readers:
+        r.close()
+    # a doc mask: no pairs, whatever set_paired_tiles says
+    seg = synth.build_segment(5 * 12288, max_rank)
+    rng = np.random.default_rng(59)
+    seg.doc_mask = np.sort(rng.choice(seg.num_docs, 3000, replace=False)).astype(np.uint32) + 1
+    masked = search.SegmentReader.from_synth(seg, L=L)
+    prep = search.prepare(filters, BM25(), [parity.segment_stats(seg)])
+    _paired_runs(L, masked, prep, 100, lambda h, c, t: parity.check_single_segment(
+        seg, filters, BM25(), 100, h, c, t), paired=False)
+    other = synth.build_segment(3 * 12288, max_rank, first_doc=seg.num_docs)
+    plain = search.SegmentReader.from_synth(other, L=L)
+    both = [seg, other]
+    prep = search.prepare(filters, BM25(), [parity.segment_stats(s) for s in both])
+    def check2(h, c, t):
+        for i, s in enumerate(both):
+            parity.check_single_segment(s, filters, BM25(), 100, h[i], c[i], t[i], both)
+    _paired_runs(L, [masked, plain], search.QueryArrays.from_prepared([masked, plain], prep, 100), 100,
+                 check2, paired=False)
+    masked.close()
+    plain.close()
 
 
 def case_join_counts(L, num_docs=70_000, max_rank=256):

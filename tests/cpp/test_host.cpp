@@ -130,7 +130,13 @@ int main() {
   const BM25 scorer;  // k = 1.2, b = 0.75
   const auto prepared = prepare(filters, scorer, {a.stats(), b.stats()});
   QueryBatch batch({a.reader.get(), b.reader.get()}, prepared, kTop);
-  const auto res = batch.run().results();
+  // joined streams and paired tiles whatever the size (by the cost rules a batch this small would
+  // run on work items): compared with the 32-bit tiles below
+  const auto res = batch.set_path(QueryBatch::Path::Joined)
+                       .set_paired_tiles(QueryBatch::PairedTiles::Always)
+                       .run()
+                       .results();
+  REQUIRE(batch.paired_tiles());
   REQUIRE(res.n_segments == 2 && res.n_queries == filters.size());
   {  // the serving-loop form: the copy queued behind the run, read later — the same arrays
     const auto again = batch.results_to_host().host_results();
@@ -206,25 +212,30 @@ int main() {
     batch.set_min_scores({});
     // the joined plain disjunctions on 32-bit tiles instead of paired tiles
     // (irs_hip_batch_set_paired_tiles): the same lists, bit for bit
-    const auto unpaired = merge(batch.set_paired_tiles(false).run().results());
+    const auto unpaired = merge(batch.set_paired_tiles(QueryBatch::PairedTiles::Never).run().results());
     REQUIRE(!batch.paired_tiles());
-    batch.set_paired_tiles(true);
+    batch.set_paired_tiles(QueryBatch::PairedTiles::Always);
     for (size_t q = 0; q < top.size(); ++q) {
       REQUIRE(unpaired[q].size() == top[q].size());
       for (size_t i = 0; i < top[q].size(); ++i)
         REQUIRE(unpaired[q][i].score == top[q][i].score && unpaired[q][i].doc == top[q][i].doc);
     }
   }
-  // the one-call form gives the same lists
+  // the one-call form gives the same lists as the batch on its default paths (the joined path
+  // rounds the contributions of conjunctions / min-match, which count matches in their sums)
   {
+    const auto dflt = merge(batch.set_path(QueryBatch::Path::Auto)
+                                .set_paired_tiles(QueryBatch::PairedTiles::WherePays)
+                                .run()
+                                .results());
     const auto again = search({a.reader.get(), b.reader.get()}, {a.stats(), b.stats()}, filters,
                               scorer, kTop);
-    REQUIRE(again.size() == top.size());
-    for (size_t q = 0; q < top.size(); ++q) {
-      REQUIRE(again[q].size() == top[q].size());
-      for (size_t i = 0; i < top[q].size(); ++i)
-        REQUIRE(again[q][i].score == top[q][i].score && again[q][i].doc == top[q][i].doc &&
-                again[q][i].segment == top[q][i].segment);
+    REQUIRE(again.size() == dflt.size());
+    for (size_t q = 0; q < dflt.size(); ++q) {
+      REQUIRE(again[q].size() == dflt[q].size());
+      for (size_t i = 0; i < dflt[q].size(); ++i)
+        REQUIRE(again[q][i].score == dflt[q][i].score && again[q][i].doc == dflt[q][i].doc &&
+                again[q][i].segment == dflt[q][i].segment);
     }
   }
 

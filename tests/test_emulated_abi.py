@@ -122,6 +122,37 @@ def test_paired_tiles(simlib, layout):
     cases.case_paired_tiles(simlib, layout=layout)
 
 
+
+@pytest.mark.parametrize("layout", [0, 1])
+def test_paired_ties(simlib, layout):
+    cases.case_paired_ties(simlib, layout=layout)
+
+
+@pytest.mark.parametrize("layout", [0, 1])
+def test_paired_window(simlib, layout):
+    cases.case_paired_window(simlib, layout=layout)
+
+
+def test_paired_ceiling(simlib):
+    cases.case_paired_ceiling(simlib)
+
+
+@pytest.mark.parametrize("layout", [0, 1])
+def test_paired_lookups(simlib, layout):
+    cases.case_paired_lookups(simlib, layout=layout)
+
+
+def test_paired_forms(simlib):
+    cases.case_paired_forms(simlib)
+
+
+def test_paired_overflow(simlib):
+    cases.case_paired_overflow(simlib)
+
+
+def test_paired_groups(simlib):
+    cases.case_paired_groups(simlib)
+
 def test_scored_multiterm_expansion(simlib):
     cases.case_scored_expansion(simlib, sizes=(30_000, 12_000), max_rank=384)
 

@@ -52,6 +52,13 @@ cases.case_shared_threshold(L, sizes=(30_000, 13_000, 40_000), max_rank=128)
 cases.case_shared_threshold_misled(L)
 cases.case_doc_mask(L, 1, num_docs=30_000, max_rank=128)
 cases.case_conj_sparse_lead(L, 1, n_docs=120_000)
+cases.case_paired_ties(L)        # paired tiles: k_join_score<kJKHalf> + k_join_rescore at their edges
+cases.case_paired_window(L)
+cases.case_paired_ceiling(L)
+cases.case_paired_lookups(L)     # (its last query's last term: the batch's last stream, kJoinSlack)
+cases.case_paired_forms(L)
+cases.case_paired_overflow(L)
+cases.case_paired_groups(L)
 import test_variadic_phrase as tv   # variadic phrases (k_vphrase)
 from iresearch_amd.search import BM25
 tv.case_abi(L)

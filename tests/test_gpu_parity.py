@@ -541,6 +541,92 @@ def test_config3_headline_batch(gpulib, monkeypatch):
     for r in readers:
         r.close()
 
+def test_config5_headline_batch(gpulib, monkeypatch, capfd):
+    """BASELINE config 5 as bench.py --config 5 runs its set 0: 8 consecutive 6.25 M-doc segments
+    with positions and MaxFreq wand data, 1000 AND-of-2..4 (WAND) and 1000 2-word phrases,
+    TF-IDF without norms, k = 100, one QueryBatch over the 8 segments per class.  Prints the
+    re-runs and the recovery IRS_HIP_TRACE names.  32 spread queries of each class against the
+    oracle per segment and merged; WAND == exhaustive on all 1000 ANDs; a second fresh batch ==
+    the first; term_blockmax of the longest list of a segment == its skip entries (tens of
+    thousands: k_wand_skip0 re-stages its LDS window many times).  About 40 s on one MI355X."""
+    import time
+
+    import test_block_driven as bd
+    from iresearch_amd import _lib
+    t0 = time.perf_counter()
+    n_segs, docs, nq, k = 8, 50_000_000, 1000, 100
+    per = docs // n_segs
+    # (the builder's output does not depend on its thread count)
+    segs = [synth.build_segment(per if s < n_segs - 1 else docs - per * (n_segs - 1), 4096,
+                                first_doc=s * per, with_positions=True, wand_count=1,
+                                wand_kind=synth.WAND_MAX_FREQ, threads=16) for s in range(n_segs)]
+    t_build = time.perf_counter() - t0
+    readers = [search.SegmentReader.from_synth(s, L=gpulib) for s in segs]
+    for sr in readers:
+        assert sr.wand_source()[0] > 0
+    stats = [parity.segment_stats(s) for s in segs]
+    ands, phrases = bd.config5_queries(nq, nq, 16, 4096)
+    assert len(ands) == nq and len(phrases) == nq
+    sc = TFIDF(False)
+    arrays = {name: search.QueryArrays.from_prepared(readers, search.prepare(fl, sc, stats), k)
+              for name, fl in (("and", ands), ("phrase", phrases))}
+
+    def run(name, wand):
+        b = search.QueryBatch(readers, arrays[name])
+        if wand:
+            b.set_wand(True)
+        b.profile(True)
+        res = tuple(x.copy() for x in b.run().results())
+        info = (b.reruns(), b.path())
+        b.close()
+        return res, info
+
+    monkeypatch.setenv("IRS_HIP_TRACE", "1")
+    capfd.readouterr()
+    first = {name: run(name, name == "and") for name in ("and", "phrase")}
+    trace = [ln for ln in capfd.readouterr().err.splitlines() if "[irs_hip] re-run:" in ln]
+    monkeypatch.delenv("IRS_HIP_TRACE")
+    second = {name: run(name, name == "and") for name in ("and", "phrase")}
+    exh, exh_info = run("and", False)
+    # (the cost rule joins the conjunctions of two frequent terms at this size: join_and_saving)
+    assert first["and"][1][1] == _lib.PATH_JOINED and first["phrase"][1][1] == _lib.PATH_ITEMS
+    # On fresh segments the AND batch overflows the default candidate cap (more than 16384 tied
+    # candidates in some units) and re-runs once with a grown buffer; the second batch starts with
+    # that size (cand_cap_hint).  The phrase batch needs no re-run.
+    assert first["and"][1][0] == 1 and first["phrase"][1][0] == 0, (first["and"][1], first["phrase"][1])
+    assert second["and"][1][0] == 0 and second["phrase"][1][0] == 0 and exh_info[0] == 0
+    assert len(trace) == 1 and "re-run: status 2," in trace[0], trace
+    for name in ("and", "phrase"):
+        for x, y in zip(first[name][0], second[name][0]):
+            assert np.array_equal(x, y), ("second fresh batch", name)
+    h, c, t = first["and"][0]
+    assert np.array_equal(h, exh[0]) and np.array_equal(c, exh[1]), "WAND != exhaustive"
+    assert (t <= exh[2]).all()
+    pick = np.linspace(0, nq - 1, 32).astype(int)
+    for name, fl, res in (("and", ands, exh), ("phrase", phrases, first["phrase"][0])):
+        hh, cc, tt = res
+        sel = [fl[q] for q in pick]
+        for s, seg in enumerate(segs):
+            check = parity.check_single_segment if name == "and" else parity.check_phrase_segment
+            check(seg, sel, sc, k, hh[s][pick], cc[s][pick], tt[s][pick], all_segs=segs)
+        merged = search.merge_topk_host([(hh[s][pick], cc[s][pick]) for s in range(n_segs)], k)
+        ref = (parity.oracle_topk(segs, sel, sc, k) if name == "and" else bd._phrase_topk(segs, sel, sc, k))
+        bd._check_merged(merged, ref, name)
+    longest = int(np.argmax(segs[0].metas["docs_count"]))
+    entries = bd.check_skip_entries(readers[0], segs[0], longest)
+    for r in readers:
+        r.close()
+    with capfd.disabled():
+        print("\nconfig 5 headline: built in %.1f s, test %.1f s; AND (WAND) reruns %d path %d, phrase "
+              "reruns %d path %d; second batches reruns %d / %d; exhaustive AND reruns %d; WAND left "
+              "%d of %d hits unevaluated; longest list %d: %d skip entries"
+              % (t_build, time.perf_counter() - t0, first["and"][1][0], first["and"][1][1],
+                 first["phrase"][1][0], first["phrase"][1][1], second["and"][1][0], second["phrase"][1][0],
+                 exh_info[0], int(exh[2].sum() - t.sum()), int(exh[2].sum()), longest, entries))
+        for ln in trace:
+            print(ln)
+
+
 def test_rccl_behind_the_c_abi(gpulib):
     """irs_hip_comm_* / irs_hip_topk_allgather on the real GPU: librccl is bound at first use,
     a one-rank communicator is created from a fresh id and the all-gather moves the send

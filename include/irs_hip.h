@@ -261,6 +261,25 @@ typedef enum irs_hip_scorer_kind {
  * an entry means what it always did, and a kind with the flag was IRS_HIP_EINVAL before. */
 #define IRS_HIP_PHRASE_ALT 0x200
 
+/* The same bit OR-ed into the `kind` of an included IRS_HIP_OP_AND entry: one more member of the
+ * group opened by the nearest preceding included entry without the flag — an And whose children
+ * are Ors of by_term (And::prepare -> make_conjunction over the children, an Or child being its
+ * own make_disjunction; boolean_filter.cpp:150-210, boolean_query.cpp:60-145).  A group is an Or
+ * of its members (a plain by_term child is a group of one).  Per doc:
+ *   d matches iff every group has a member holding d (minus deleted docs and IRS_HIP_EXCLUDE terms);
+ *   group score s_g(d) = the sum of the scores of its members holding d (the inner Or merges
+ *   with SUM); doc score = the query's `merge` (SUM / MAX / MIN) over the s_g(d), groups in cost
+ *   order (the sum of their members' docs_count, as Conjunction sorts its children).
+ * Boosts are the callers': each entry's c0 carries its term boost x Or boost x And boost.  At most
+ * IRS_HIP_MAX_TERMS included entries in all; IRS_HIP_EXCLUDE entries may follow.  The flag on the
+ * first included entry, on an IRS_HIP_EXCLUDE entry or on an OR / MINMATCH entry is IRS_HIP_EINVAL.
+ * A term may appear in several groups; a term twice in one group scores once per appearance (an Or
+ * of the same by_term twice).  Per segment an absent member (IRS_HIP_NO_TERM or no docs) is
+ * dropped, and a group without a present member empties the query.  Such a query runs block driven
+ * on k_conj_any (see irs_hip_batch_set_path for what the batch controls do with it).  A compatible
+ * addition to ABI 12: a non-phrase kind with the flag was IRS_HIP_EINVAL before. */
+#define IRS_HIP_GROUP_ALT IRS_HIP_PHRASE_ALT
+
 /* One query term = the (term cookie, stats blob, boost) triple TermQuery::execute
  * hands to postings()/CompileScore (term_query.cpp:35-74), flattened. */
 typedef struct irs_hip_term_scorer {
@@ -434,6 +453,13 @@ int irs_hip_batch_configure(irs_hip_batch* batch, uint32_t tile_docs,
  *                        tools/cost_sweep.py); a conjunction joins when walking every entry of
  *                        its terms beats decoding only the blocks its rarest term's docs fall
  *                        into.
+ * Grouped conjunctions (IRS_HIP_GROUP_ALT) never join posting streams: like units with excluded
+ * terms they run block driven (k_conj_any) whatever the path, and the other units of the batch
+ * choose their paths as they would without them.  irs_hip_batch_set_wand leaves them exhaustive (no
+ * block-max pruning: the top k is exact and total_hits the full count);
+ * irs_hip_batch_set_min_scores applies to them; under irs_hip_batch_set_shared_threshold /
+ * irs_hip_batch_set_comm they keep thresholds of their own; irs_hip_batch_work / _touched
+ * account for them as for block-driven conjunctions.
  * Call before the batch's first run (or after a configure). */
 enum { IRS_HIP_PATH_AUTO = 0, IRS_HIP_PATH_ITEMS = 1, IRS_HIP_PATH_JOINED = 2 };
 int irs_hip_batch_set_path(irs_hip_batch* batch, int path);

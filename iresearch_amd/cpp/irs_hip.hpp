@@ -135,10 +135,18 @@ struct Or {
   std::vector<by_term> subs;
   uint32_t min_match_count = 1;  // irs::Or::min_match_count()
   irs_hip_merge merge_type = IRS_HIP_MERGE_SUM;  // boolean_filter::merge_type()
+  float boost = 1.f;   // multiplies into its terms' boosts (boolean_filter.cpp:153-154, 204)
 };
+// irs::And of by_term children (`subs`) and Or-of-by_term children (`groups`: an And of Ors,
+// IRS_HIP_GROUP_ALT).  Children in that order: subs, then groups.  A group of one term is that term
+// (the single node case, boolean_filter.cpp:152-155); a group merges with SUM and min_match_count
+// <= 1 (anything else: not_supported).  Each term's boost is multiplied by its Or's and the And's
+// boosts, from the top down.  At most IRS_HIP_MAX_TERMS terms in all.
 struct And {
   std::vector<by_term> subs;
   irs_hip_merge merge_type = IRS_HIP_MERGE_SUM;
+  std::vector<Or> groups;
+  float boost = 1.f;
 };
 struct by_phrase {
   std::vector<uint32_t> terms;
@@ -296,11 +304,37 @@ std::vector<PreparedQuery> prepare(const std::vector<filter>& filters, const Sco
       q.op = o->min_match_count > 1 ? IRS_HIP_OP_MINMATCH : IRS_HIP_OP_OR;
       q.min_match = o->min_match_count > 1 ? o->min_match_count : 0;
       q.merge = o->merge_type;
-      for (const auto& t : o->subs) q.terms.push_back(one(t));
+      for (const auto& t : o->subs) q.terms.push_back(one(by_term{t.term, o->boost * t.boost}));
     } else if (const auto* a = std::get_if<And>(&f)) {
       q.op = IRS_HIP_OP_AND;
       q.merge = a->merge_type;
-      for (const auto& t : a->subs) q.terms.push_back(one(t));
+      // the groups, normalised: a by_term child is a group of one, so is a one-term Or; a group's
+      // members after its first are flagged IRS_HIP_GROUP_ALT — unless no group has two members:
+      // then the query is today's flat And
+      std::vector<std::vector<by_term>> groups;
+      for (const auto& t : a->subs) groups.push_back({by_term{t.term, a->boost * t.boost}});
+      bool grouped = false;
+      for (const Or& g : a->groups) {
+        if (g.subs.empty()) throw illegal_argument(IRS_HIP_EINVAL, "And: an Or group without terms");
+        if (g.min_match_count > 1)
+          throw not_supported(IRS_HIP_EUNSUPPORTED, "And: an Or group with min_match_count > 1");
+        if (g.subs.size() > 1 && g.merge_type != IRS_HIP_MERGE_SUM)
+          throw not_supported(IRS_HIP_EUNSUPPORTED, "And: an Or group merges with SUM on the GPU path");
+        const float mult = a->boost * g.boost;
+        groups.emplace_back();
+        for (const auto& t : g.subs) groups.back().push_back(by_term{t.term, mult * t.boost});
+        grouped = grouped || g.subs.size() > 1;
+      }
+      size_t total = 0;
+      for (const auto& g : groups) total += g.size();
+      if (grouped && total > IRS_HIP_MAX_TERMS)
+        throw not_supported(IRS_HIP_EUNSUPPORTED, "And: more than IRS_HIP_MAX_TERMS terms in its groups");
+      for (const auto& g : groups)
+        for (size_t i = 0; i < g.size(); ++i) {
+          irs_hip_term_scorer e = one(g[i]);
+          if (i) e.kind |= IRS_HIP_GROUP_ALT;
+          q.terms.push_back(e);
+        }
     } else if (!std::get<by_phrase>(f).members.empty()) {
       variadic(q, std::get<by_phrase>(f));
     } else {

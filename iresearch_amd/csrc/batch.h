@@ -129,6 +129,15 @@ struct BlockWork {
   uint32_t n_pilot = 0, pilot_stride = 0;
 };
 
+// Grouped conjunctions (an And of Ors of by_term, IRS_HIP_GROUP_ALT; conj_any.h): the tables of
+// BlockWork, a list of their own — built at create (they never join streams, never change path),
+// next to a batch's block-driven or joined flat conjunctions.  `opens` and the lead group's rows as
+// for variadic phrases; n_wgs: k_conj_any workgroups.  Of BlockWork the grouped path uses units,
+// items, n_items, n_wgs, the lead-item tables (d_units, d_items, d_hist, d_item_base, d_unit_items,
+// d_seek, d_recs, d_item_hits), opens / d_opens / d_lead_rows and the pilot list (d_pilot,
+// n_pilot, pilot_stride); d_lg, d_lead_of, n_phrase_wgs and `variadic` stay unused.
+struct AnyWork : BlockWork {};
+
 // Units with excluded terms (IRS_HIP_EXCLUDE, excl.h): one doc mask per distinct (segment, present
 // excluded terms), built by k_excl_mask in every run's plan stage; DevQuery::dead points at it
 struct ExclWork {
@@ -244,6 +253,7 @@ struct irs_hip_batch {
   TileWork tiles;
   JoinWork join;
   BlockWork blocks;
+  AnyWork any;
   ExclWork excl;
   Groups groups;
   RunSync sync;
@@ -265,7 +275,7 @@ static const uint32_t* min_bins(const irs_hip_batch* b) {
 static uint32_t default_cand_cap(const irs_hip_batch* b) {
   const uint64_t per_k = b->estimate ? 16ull : 4ull * b->stride_eff;
   uint64_t learned = 0;   // (block-driven units only: tile units cut ties by their per-tile staging)
-  if (b->phrase || !b->all_conj_units.empty())
+  if (b->phrase || !b->all_conj_units.empty() || !b->any.units.empty())
     for (const irs_hip_segment* sg : b->segs) learned = std::max<uint64_t>(learned, sg->cand_cap_hint.load());
   return uint32_t(std::min<uint64_t>(std::max<uint64_t>({per_k * b->k_max, 16384, learned}), 262144));
 }

@@ -26,6 +26,7 @@
 #include "vphrase.h"
 #include "score.h"
 #include "conj.h"
+#include "conj_any.h"
 #include "join.h"
 #include "excl.h"
 
@@ -36,6 +37,7 @@ using namespace irs_hip;
 #include "batch.h"
 #include "plan_tiles.h"
 #include "plan_blocks.h"
+#include "plan_any.h"
 #include "plan_join.h"
 
 namespace {
@@ -430,12 +432,14 @@ static int batch_create_multi_impl(irs_hip_segment* const* segs, uint32_t n_segs
   b->nq = nq;
   b->nq_user = nq_user;
   int rc = IRS_HIP_OK;
+  std::vector<uint32_t> grouped_units;   // units of grouped conjunctions (IRS_HIP_GROUP_ALT)
   try {
     b->segs.assign(segs, segs + n_segs);
     b->queries.resize(nq);
     b->count_precise.assign(nq, 0);
     b->groups.upper.assign(nq, 0.0);
     b->blocks.opens.assign(nq, 0);
+    b->any.opens.assign(nq, 0);
     b->qterms.reserve(size_t(n_entries) * n_segs);
     std::vector<int> exps;
     exps.reserve(nq);
@@ -444,6 +448,7 @@ static int batch_create_multi_impl(irs_hip_segment* const* segs, uint32_t n_segs
     std::vector<uint32_t> excl;   // a unit's present excluded terms
     std::map<std::pair<uint32_t, std::vector<uint32_t>>, uint32_t> mask_ids;   // (segment, terms) -> mask
     std::vector<uint32_t> mask_of(nq, 0);   // [unit] mask + 1, 0: none
+    std::vector<uint32_t> row_group;        // per present row of a grouped unit: its group
     for (uint32_t q = 0; q < nq && rc == IRS_HIP_OK; ++q) {
       // unit q = (segment q / nq_user, query q % nq_user); the segment's own term entries
       irs_hip_segment* seg = segs[q / nq_user];
@@ -470,6 +475,15 @@ static int batch_create_multi_impl(irs_hip_segment* const* segs, uint32_t n_segs
           n_incl == 0 || in.merge > IRS_HIP_MERGE_MIN ||
           (in.op == IRS_HIP_OP_PHRASE && in.merge != IRS_HIP_MERGE_SUM) ||
           n_incl > IRS_HIP_MAX_TERMS || n_excl > IRS_HIP_MAX_EXCLUDED || in.k == 0 || in.k > IRS_HIP_MAX_K) {
+        rc = IRS_HIP_EINVAL;
+        break;
+      }
+      // a grouped conjunction: an And whose entries with IRS_HIP_GROUP_ALT are more members of the
+      // group (an Or of by_term) opened by the nearest entry before them without it
+      bool grouped = false;
+      for (uint32_t j = 0; j < n_incl && in.op == IRS_HIP_OP_AND; ++j)
+        grouped = grouped || (terms[in.first_term + j].kind & IRS_HIP_GROUP_ALT) != 0;
+      if (grouped && (terms[in.first_term].kind & IRS_HIP_GROUP_ALT)) {
         rc = IRS_HIP_EINVAL;
         break;
       }
@@ -510,12 +524,15 @@ static int batch_create_multi_impl(irs_hip_segment* const* segs, uint32_t n_segs
       double upper = 0.0, min_score = 1e300, upper_all = 0.0;
       // phrase parts: entries [part_first, j) so far form the current one; bit r of `opens` = row r
       // is the first present member of its part; `found` = the parts with a present member
-      uint32_t n_parts = 0, part_first = 0, opens = 0, found = 0;
+      // (a grouped conjunction: n_groups so far, `found` = the groups with a present member)
+      uint32_t n_parts = 0, part_first = 0, opens = 0, found = 0, n_groups = 0;
       bool part_open = false;
+      row_group.clear();
       for (uint32_t j = 0; j < n_incl; ++j) {
         const irs_hip_term_scorer& ts = terms[in.first_term + j];
         const bool member = is_phrase && (ts.kind & IRS_HIP_PHRASE_ALT) != 0;
-        const int32_t kind = is_phrase ? (ts.kind & ~IRS_HIP_PHRASE_ALT) : ts.kind;
+        const int32_t kind = (is_phrase || grouped) ? (ts.kind & ~IRS_HIP_PHRASE_ALT) : ts.kind;
+        if (grouped && !(ts.kind & IRS_HIP_GROUP_ALT)) ++n_groups;
         if (is_phrase && !member) {
           ++n_parts;
           part_first = j;
@@ -571,9 +588,14 @@ static int batch_create_multi_impl(irs_hip_segment* const* segs, uint32_t n_segs
         // TermQuery::execute: no term state in this segment -> empty iterator
         // (term_query.cpp:41-43)
         if (qt.term == IRS_HIP_NO_TERM || seg->terms[qt.term].docs_count == 0) {
-          // (a phrase: an absent member is dropped; a part without a present one is `absent`)
-          if (!is_phrase) absent = true;
+          // (a phrase / grouped conjunction: an absent member is dropped; a part / group without
+          // a present one is `absent`)
+          if (!is_phrase && !grouped) absent = true;
           continue;
+        }
+        if (grouped) {
+          found |= 1u << (n_groups - 1u);
+          row_group.push_back(n_groups - 1u);
         }
         if (is_phrase) {
           if (!part_open) opens |= 1u << row.size();
@@ -622,6 +644,8 @@ static int batch_create_multi_impl(irs_hip_segment* const* segs, uint32_t n_segs
       // min-match block disjunction: every matching term scores, docs with < m matches drop.
       uint32_t need = 1;
       if (in.op == IRS_HIP_OP_AND) {
+        // (a grouped one: a group without a present member empties it)
+        if (grouped) absent = found != (1u << n_groups) - 1u;
         need = absent ? 0xFFu : uint32_t(row.size());
       } else if (in.op == IRS_HIP_OP_MINMATCH) {
         // Or::prepare turns min_match_count == 0 into the all-docs filter
@@ -681,7 +705,33 @@ static int batch_create_multi_impl(irs_hip_segment* const* segs, uint32_t n_segs
       // low byte of op: 0 = disjunction in doc tiles, 1 = doc tiles with per-doc match
       // counters (min-match), 2 = conjunction, block by block of its rarest term (conj.h)
       dq.op = 0;
-      if (need > 1 && !row.empty() && !is_phrase) {
+      if (grouped) {
+        // MakeConjunction sorts its children by cost (conjunction.hpp:450-453): the groups, by the
+        // sum of their members' docs_count (the cheapest leads; the members keep their order);
+        // always block driven (conj_any.h), whatever the number of rows
+        if (!row.empty()) {
+          std::vector<uint64_t> cost(n_groups, 0);
+          for (size_t r = 0; r < row.size(); ++r) cost[row_group[r]] += seg->terms[row[r].term].docs_count;
+          std::vector<uint32_t> order(n_groups);
+          for (uint32_t g = 0; g < n_groups; ++g) order[g] = g;
+          std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return cost[x] < cost[y]; });
+          std::vector<DevQTerm> sorted;
+          opens = 0;
+          for (uint32_t g : order) {
+            bool first = true;
+            for (size_t r = 0; r < row.size(); ++r) {
+              if (row_group[r] != g) continue;
+              if (first) opens |= 1u << sorted.size();
+              first = false;
+              sorted.push_back(row[r]);
+            }
+          }
+          row.swap(sorted);
+          b->any.opens[q] = opens;
+          grouped_units.push_back(q);
+        }
+        dq.op = int32_t(2u | (uint32_t(row.size()) << 8));
+      } else if (need > 1 && !row.empty() && !is_phrase) {
         if (need == row.size()) {
           // MakeConjunction sorts by cost (conjunction.hpp:450-453): the cheapest leads, and
           // the scores are summed in that order
@@ -713,7 +763,7 @@ static int batch_create_multi_impl(irs_hip_segment* const* segs, uint32_t n_segs
         }
       }
       dq.op |= int32_t(merge << 16);
-      if (!is_phrase) ((dq.op & 0xFF) == 2 ? b->all_conj_units : b->all_tile_units).push_back(q);
+      if (!is_phrase && !grouped) ((dq.op & 0xFF) == 2 ? b->all_conj_units : b->all_tile_units).push_back(q);
       // match counts in the low bits of a 32-bit accumulator (join.h COUNT) round every posting
       // to 16 fixed-point units (+-8): relative to any doc's score that is at most
       // 8 * upper / (2^29 * min_score) — allowed while it stays below 2e-6
@@ -764,7 +814,8 @@ static int batch_create_multi_impl(irs_hip_segment* const* segs, uint32_t n_segs
           rc = IRS_HIP_EUNSUPPORTED;
           break;
         }
-        if (!(min_score > 0.0) || upper / min_score > 1000.0) b->acc32 = false;
+        // (grouped units score in floats, block driven: the flat units' accumulators are theirs)
+        if (!grouped && (!(min_score > 0.0) || upper / min_score > 1000.0)) b->acc32 = false;
       }
       exps.push_back(e);
       b->qterms.insert(b->qterms.end(), row.begin(), row.end());
@@ -812,10 +863,17 @@ static int batch_create_multi_impl(irs_hip_segment* const* segs, uint32_t n_segs
       rc = IRS_HIP_ENOMEM;
     }
   }
+  if (rc == IRS_HIP_OK && !grouped_units.empty()) {
+    try {
+      rc = build_any_work(b, grouped_units);
+    } catch (...) {
+      rc = IRS_HIP_ENOMEM;
+    }
+  }
   // (the block-driven kernels read the norms of a lead block's docs from the posting-order copy)
   // — a permanent copy per segment, one byte per posting (irs_hip_segment_device_bytes counts
   // it): built the first time a conjunction / phrase whose scorer reads norms arrives
-  if (rc == IRS_HIP_OK && (b->phrase || !b->all_conj_units.empty())) {
+  if (rc == IRS_HIP_OK && (b->phrase || !b->all_conj_units.empty() || !b->any.units.empty())) {
     bool wanted = false;
     for (const DevQTerm& qt : b->qterms) wanted = wanted || needs_norm(qt.kind);
     for (irs_hip_segment* sg : b->segs)
@@ -1048,7 +1106,7 @@ static bool plan_stage(irs_hip_batch* b, rt::stream_t st) {
     });
   }
   // (a joined batch without conjunctions needs none of k_plan's tables)
-  if (ok && (b->phrase || !b->tiles.units.empty() || !b->blocks.units.empty())) {
+  if (ok && (b->phrase || !b->tiles.units.empty() || !b->blocks.units.empty() || !b->any.units.empty())) {
     RT_LAUNCH(k_plan, b->nq * b->jt, kThreads, 0, st, b->d_segs.as<DevSegment>(),
               b->d_queries.as<DevQuery>(), b->d_qterms.as<DevQTerm>(), b->jt, b->tiles.docs,
               b->d_first.as<uint32_t>(), b->d_tails.as<DevTail>());
@@ -1152,6 +1210,7 @@ static int run_impl(irs_hip_batch* b, rt::stream_t st) {
     ok = ok && with_tile_kernel(b, [&](auto k) { return launch_score(b, st, k); });
   if (b->join.on()) ok = ok && launch_join_score(b, st);
   if (!b->phrase) ok = ok && (simd ? launch_conj<kSimd4>(b, st) : launch_conj<kScalar>(b, st));
+  if (!b->phrase) ok = ok && (simd ? launch_any<kSimd4>(b, st) : launch_any<kScalar>(b, st));
   ok = ok && mark(2 * IRS_HIP_K_SCORE + 1);
   // 4. exact top-k
   ok = ok && mark(2 * IRS_HIP_K_SELECT);

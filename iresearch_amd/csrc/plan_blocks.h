@@ -5,51 +5,54 @@
 
 namespace {
 
-// The rows of the seek table — the lead items of blocks.units, unit after unit — and the tables of
+// The rows of the seek table — the lead items of w.units, unit after unit — and the tables of
 // the block-driven kernels; `per_unit` goes to `d_per_unit` (a conjunction's lead-block cut /
-// a phrase's lead term)
-int stage_lead_items(irs_hip_batch* b, DevBuf& d_per_unit, const std::vector<uint32_t>& per_unit) {
+// a phrase's lead term / a variadic phrase's or grouped conjunction's lead rows).  w: b->blocks,
+// or b->any (grouped conjunctions, plan_any.h)
+int stage_lead_items(irs_hip_batch* b, BlockWork& w, DevBuf& d_per_unit, const std::vector<uint32_t>& per_unit) {
   const uint32_t nq = b->nq;
-  std::vector<uint32_t> item_base(b->blocks.units.size() + 1, 0), unit_items(nq, 0);
+  std::vector<uint32_t> item_base(w.units.size() + 1, 0), unit_items(nq, 0);
   uint64_t total = 0;
-  for (size_t c = 0; c < b->blocks.units.size(); ++c) {
+  for (size_t c = 0; c < w.units.size(); ++c) {
     item_base[c] = uint32_t(total);
-    unit_items[b->blocks.units[c]] = uint32_t(total);
-    total += b->blocks.items[c];
+    unit_items[w.units[c]] = uint32_t(total);
+    total += w.items[c];
   }
   if (total > 0x7FFFFFFFull) return IRS_HIP_EUNSUPPORTED;
-  item_base[b->blocks.units.size()] = uint32_t(total);
-  b->blocks.n_items = uint32_t(total);
-  if (!b->blocks.d_item_base.alloc(item_base.size() * 4) ||
-      !b->blocks.d_unit_items.alloc(unit_items.size() * 4) ||
-      !b->blocks.d_seek.alloc((total + 2) * uint64_t(kMaxTerms) * 4) ||
-      !b->blocks.d_recs.alloc((total + 1) * sizeof(ConjItem)) ||
-      !b->blocks.d_item_hits.alloc((total + 1) * 4) ||
-      !b->blocks.d_units.alloc(b->blocks.units.size() * 4) ||
-      !b->blocks.d_items.alloc(b->blocks.items.size() * 4) ||
+  item_base[w.units.size()] = uint32_t(total);
+  w.n_items = uint32_t(total);
+  if (!w.d_item_base.alloc(item_base.size() * 4) ||
+      !w.d_unit_items.alloc(unit_items.size() * 4) ||
+      !w.d_seek.alloc((total + 2) * uint64_t(kMaxTerms) * 4) ||
+      !w.d_recs.alloc((total + 1) * sizeof(ConjItem)) ||
+      !w.d_item_hits.alloc((total + 1) * 4) ||
+      !w.d_units.alloc(w.units.size() * 4) ||
+      !w.d_items.alloc(w.items.size() * 4) ||
       !d_per_unit.alloc(per_unit.size() * 4) ||
-      !b->blocks.d_hist.alloc(uint64_t(nq) * kBins * 4))
+      !w.d_hist.alloc(uint64_t(nq) * kBins * 4))
     return IRS_HIP_ENOMEM;
-  if (!b->up.copy(b->blocks.d_item_base.p, item_base.data(), item_base.size() * 4) ||
-      !b->up.copy(b->blocks.d_unit_items.p, unit_items.data(), unit_items.size() * 4) ||
-      !b->up.copy(b->blocks.d_units.p, b->blocks.units.data(), b->blocks.units.size() * 4) ||
-      !b->up.copy(b->blocks.d_items.p, b->blocks.items.data(), b->blocks.items.size() * 4) ||
+  if (!b->up.copy(w.d_item_base.p, item_base.data(), item_base.size() * 4) ||
+      !b->up.copy(w.d_unit_items.p, unit_items.data(), unit_items.size() * 4) ||
+      !b->up.copy(w.d_units.p, w.units.data(), w.units.size() * 4) ||
+      !b->up.copy(w.d_items.p, w.items.data(), w.items.size() * 4) ||
       !b->up.copy(d_per_unit.p, per_unit.data(), per_unit.size() * 4))
     return IRS_HIP_ENOMEM;
   return IRS_HIP_OK;
 }
 
-// k_vphrase work (vphrase.h) of a batch with variadic phrases: the iteration lead of a unit is the
-// part with the smallest sum of its members' docs_count (a disjunction costs the sum of its
-// members, Conjunction sorts by cost; the first such part on ties); one wavefront per block (+ tail)
-// of every member of it.  The pilot pass samples those items like any others.
-int build_vphrase_work(irs_hip_batch* b) {
+// The lead-group planning of k_vphrase (variadic phrases) and k_conj_any (grouped conjunctions,
+// conj_any.h) over the units `cand` (those without rows are skipped): the iteration lead of a unit
+// is the part / group with the smallest sum of its members' docs_count (a disjunction costs the sum
+// of its members, Conjunction sorts by cost; the first such one on ties); one wavefront per block
+// (+ tail) of every member of it.  The pilot pass samples those items like any others.  w.opens
+// holds every unit's `opens` word; w.d_lead_rows gets lead rows lo | end << 8.
+int build_lead_groups(irs_hip_batch* b, BlockWork& w, const std::vector<uint32_t>& cand) {
   std::vector<uint32_t> lead_rows(b->nq, 0);
-  for (uint32_t u = 0; u < b->nq; ++u) {
+  for (uint32_t u : cand) {
     const DevQuery& dq = b->queries[u];
     if (!dq.n_terms) continue;
     const irs_hip_segment* sg = b->segs[dq.seg];
-    const uint32_t opens = b->blocks.opens[u] | 1u;
+    const uint32_t opens = w.opens[u] | 1u;
     uint64_t best = ~uint64_t(0);
     uint32_t items = 0;
     for (uint32_t lo = 0; lo < dq.n_terms;) {
@@ -69,14 +72,22 @@ int build_vphrase_work(irs_hip_batch* b) {
       }
       lo = end;
     }
-    b->blocks.units.push_back(u);
-    b->blocks.items.push_back(items);
+    w.units.push_back(u);
+    w.items.push_back(items);
   }
-  if (b->blocks.units.empty()) return IRS_HIP_OK;
-  if (!b->blocks.d_opens.alloc(uint64_t(b->nq) * 4) ||
-      !b->up.copy(b->blocks.d_opens.p, b->blocks.opens.data(), uint64_t(b->nq) * 4))
+  if (w.units.empty()) return IRS_HIP_OK;
+  if (!w.d_opens.alloc(uint64_t(b->nq) * 4) ||
+      !b->up.copy(w.d_opens.p, w.opens.data(), uint64_t(b->nq) * 4))
     return IRS_HIP_ENOMEM;
-  const int rc = stage_lead_items(b, b->blocks.d_lead_rows, lead_rows);
+  return stage_lead_items(b, w, w.d_lead_rows, lead_rows);
+}
+
+// k_vphrase work (vphrase.h) of a batch with variadic phrases: every unit of it
+int build_vphrase_work(irs_hip_batch* b) {
+  std::vector<uint32_t> all(b->nq);
+  for (uint32_t u = 0; u < b->nq; ++u) all[u] = u;
+  const int rc = build_lead_groups(b, b->blocks, all);
+  if (b->blocks.units.empty()) return rc;
   b->blocks.n_phrase_wgs = (b->blocks.n_items + kPhraseWaves - 1) / kPhraseWaves;
   return rc;
 }
@@ -105,7 +116,7 @@ int build_phrase_work(irs_hip_batch* b) {
     b->blocks.items.push_back(items);
   }
   if (b->blocks.units.empty()) return IRS_HIP_OK;   // (no query has all its terms in its segment)
-  const int rc = stage_lead_items(b, b->blocks.d_lead_of, lead_of);
+  const int rc = stage_lead_items(b, b->blocks, b->blocks.d_lead_of, lead_of);
   b->blocks.n_phrase_wgs = (b->blocks.n_items + kPhraseWaves - 1) / kPhraseWaves;
   return rc;
 }
@@ -158,7 +169,7 @@ int build_conj_work(irs_hip_batch* b) {
       split_lg.push_back(lg);
       b->blocks.items.push_back(items << lg);
     }
-    if (const int rc = stage_lead_items(b, b->blocks.d_lg, split_lg)) return rc;
+    if (const int rc = stage_lead_items(b, b->blocks, b->blocks.d_lg, split_lg)) return rc;
     b->blocks.n_wgs = (b->blocks.n_items + kConjWaves - 1) / kConjWaves;
   } catch (...) {
     rc = IRS_HIP_ENOMEM;
@@ -166,45 +177,46 @@ int build_conj_work(irs_hip_batch* b) {
   return rc;
 }
 
-// The pilot pass's work list of a block-driven batch (And / by_phrase): lead items
-// {phase, phase + P, ...} of every unit in blocks.units.
-bool ensure_pilot_list(irs_hip_batch* b, uint32_t stride, rt::stream_t st) {
-  if (b->blocks.pilot_stride == stride) return true;
+// The pilot pass's work list of a block-driven batch (And / by_phrase / grouped And): lead items
+// {phase, phase + P, ...} of every unit in w.units.
+bool ensure_pilot_list(irs_hip_batch* b, BlockWork& w, uint32_t stride, rt::stream_t st) {
+  if (w.pilot_stride == stride) return true;
   std::vector<PhraseWg> pl;
-  for (size_t c = 0; c < b->blocks.units.size(); ++c) {
-    const uint32_t u = b->blocks.units[c];
-    for (uint32_t it = (u * 7u) % stride; it < b->blocks.items[c]; it += stride)
+  for (size_t c = 0; c < w.units.size(); ++c) {
+    const uint32_t u = w.units[c];
+    for (uint32_t it = (u * 7u) % stride; it < w.items[c]; it += stride)
       pl.push_back(PhraseWg{u, it});
   }
   // (the list being replaced may still be read by a run in flight: recoveries come here)
-  if ((b->blocks.d_pilot.p && !rt::sync(st)) ||
-      !b->blocks.d_pilot.alloc(std::max<size_t>(1, pl.size()) * sizeof(PhraseWg)) ||
-      !b->up.copy(b->blocks.d_pilot.p, pl.data(), pl.size() * sizeof(PhraseWg)) || !b->up.flush(st))
+  if ((w.d_pilot.p && !rt::sync(st)) ||
+      !w.d_pilot.alloc(std::max<size_t>(1, pl.size()) * sizeof(PhraseWg)) ||
+      !b->up.copy(w.d_pilot.p, pl.data(), pl.size() * sizeof(PhraseWg)) || !b->up.flush(st))
     return false;
-  b->blocks.n_pilot = uint32_t(pl.size());
-  b->blocks.pilot_stride = stride;
+  w.n_pilot = uint32_t(pl.size());
+  w.pilot_stride = stride;
   return true;
 }
 
-// What k_conj and k_phrase read of the batch, the same for both (ConjArgs: passed by value)
-ConjArgs block_args(const irs_hip_batch* b, uint32_t pilot_stride) {
+// What k_conj, k_phrase and k_conj_any read of the batch, the same for all (ConjArgs: passed by
+// value); w: the tables of their units
+ConjArgs block_args(const irs_hip_batch* b, const BlockWork& w, uint32_t pilot_stride) {
   ConjArgs a{};
   a.segs = b->d_segs.as<DevSegment>();
   a.queries = b->d_queries.as<DevQuery>();
   a.qterms = b->d_qterms.as<DevQTerm>();
   a.wgs = nullptr;
-  a.n_items = b->blocks.n_items;
+  a.n_items = w.n_items;
   a.tails = b->d_tails.as<DevTail>();
   a.bstar = b->d_bstar.as<uint32_t>();
   a.cands = b->d_cands.as<uint64_t>();
   a.cand_count = b->d_cand_count.as<uint32_t>();
   a.hits = b->d_hits.as<unsigned long long>();
-  a.hist = b->blocks.d_hist.as<uint32_t>();
+  a.hist = w.d_hist.as<uint32_t>();
   a.touched = b->count_touched ? b->d_touched.as<unsigned long long>() : nullptr;
-  a.seek = b->blocks.d_seek.as<uint32_t>();
-  a.recs = b->blocks.d_recs.as<ConjItem>();
-  a.unit_items = b->blocks.d_unit_items.as<uint32_t>();
-  a.item_hits = b->blocks.d_item_hits.as<uint32_t>();
+  a.seek = w.d_seek.as<uint32_t>();
+  a.recs = w.d_recs.as<ConjItem>();
+  a.unit_items = w.d_unit_items.as<uint32_t>();
+  a.item_hits = w.d_item_hits.as<uint32_t>();
   a.jt = b->jt;
   a.cand_cap = b->cand_cap;
   a.pilot_stride = pilot_stride;
@@ -215,10 +227,10 @@ ConjArgs block_args(const irs_hip_batch* b, uint32_t pilot_stride) {
 template<int LAYOUT>
 bool launch_conj(irs_hip_batch* b, rt::stream_t st) {
   if (b->blocks.n_wgs == 0) return true;
-  ConjArgs a = block_args(b, b->stride_eff);
+  ConjArgs a = block_args(b, b->blocks, b->stride_eff);
   a.wand = b->wand ? 1u : 0u;
   a.pruned = b->d_pruned.as<uint32_t>();
-  if (!ensure_pilot_list(b, a.pilot_stride, st)) return false;
+  if (!ensure_pilot_list(b, b->blocks, a.pilot_stride, st)) return false;
   if (!rt::dmemset(b->blocks.d_hist.p, 0, b->blocks.d_hist.n, st) ||
       !rt::dmemset(b->blocks.d_item_hits.p, 0, b->blocks.d_item_hits.n, st))
     return false;
@@ -252,9 +264,9 @@ template<int LAYOUT, int MT>
 bool launch_phrase(irs_hip_batch* b, rt::stream_t st) {
   if (b->blocks.n_phrase_wgs == 0) return true;  // no query has all its terms in its segment
   const uint32_t stride = b->stride_eff;
-  if (!ensure_pilot_list(b, stride, st) || !rt::dmemset(b->blocks.d_hist.p, 0, b->blocks.d_hist.n, st))
+  if (!ensure_pilot_list(b, b->blocks, stride, st) || !rt::dmemset(b->blocks.d_hist.p, 0, b->blocks.d_hist.n, st))
     return false;
-  ConjArgs a = block_args(b, stride);
+  ConjArgs a = block_args(b, b->blocks, stride);
   a.lead_of = b->blocks.d_lead_of.as<uint32_t>();
   if (!rt::dmemset(b->blocks.d_item_hits.p, 0, b->blocks.d_item_hits.n, st)) return false;
   RT_LAUNCH(k_conj_seek, (b->blocks.n_items + kThreads - 1) / kThreads, kThreads, 0, st,
@@ -295,10 +307,10 @@ template<int LAYOUT>
 bool launch_vphrase(irs_hip_batch* b, rt::stream_t st) {
   if (b->blocks.n_phrase_wgs == 0) return true;
   const uint32_t stride = b->stride_eff;
-  if (!ensure_pilot_list(b, stride, st) || !rt::dmemset(b->blocks.d_hist.p, 0, b->blocks.d_hist.n, st) ||
+  if (!ensure_pilot_list(b, b->blocks, stride, st) || !rt::dmemset(b->blocks.d_hist.p, 0, b->blocks.d_hist.n, st) ||
       !rt::dmemset(b->blocks.d_item_hits.p, 0, b->blocks.d_item_hits.n, st))
     return false;
-  ConjArgs a = block_args(b, stride);
+  ConjArgs a = block_args(b, b->blocks, stride);
   const uint32_t* opens = b->blocks.d_opens.as<uint32_t>();
   RT_LAUNCH(k_vphrase_seek, (b->blocks.n_items + kThreads - 1) / kThreads, kThreads, 0, st,
             b->d_segs.as<DevSegment>(), b->d_queries.as<DevQuery>(), b->d_tails.as<DevTail>(),

@@ -20,7 +20,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-from dataclasses import dataclass, field
+from dataclasses import dataclass, field, replace
 
 import numpy as np
 
@@ -104,10 +104,11 @@ MERGE_SUM, MERGE_MAX, MERGE_MIN = 0, 1, 2
 @dataclass
 class Or:
     """irs::Or; min_match > 1 is Or::min_match_count() (boolean_filter.hpp); `merge` its
-    merge_type()."""
+    merge_type(); `boost` multiplies into the boosts of its terms (boolean_filter.cpp:153-154, 204)."""
     subs: list
     min_match: int = 1
     merge: int = MERGE_SUM
+    boost: float = 1.0
 
     @property
     def op(self):
@@ -116,10 +117,13 @@ class Or:
 
 @dataclass
 class And:
+    """irs::And of by_term and Or-of-by_term children (the Ors are groups: IRS_HIP_GROUP_ALT);
+    `boost` multiplies into the boosts of its terms."""
     subs: list
     op: int = OP_AND
     min_match: int = 0
     merge: int = MERGE_SUM
+    boost: float = 1.0
 
 
 @dataclass
@@ -223,12 +227,77 @@ def split_exclusions(flt):
             inner = incl[0]
             if isinstance(inner, (Or, And)) and any(isinstance(s, Not) for s in inner.subs):
                 raise ValueError("Not is taken in the outermost And only")
+            if flt.boost != 1.0:   # (the And's boost multiplies into its one child's)
+                inner = replace(inner, boost=float(f32(f32(flt.boost) * f32(inner.boost))))
             return inner, excl
         if any(type(s) is not by_term for s in incl):
             raise ValueError("an And with Not children takes by_term children or ONE Or / And / "
-                             "by_phrase child")
-        return And(incl, merge=flt.merge), excl
+                             "by_phrase child (groups minus some terms: And([And([...]), Not(...)]))")
+        return And(incl, merge=flt.merge, boost=flt.boost), excl
     return flt, []
+
+
+def _or_members(flt, mult):
+    """(term, boost product) of every by_term under a SUM Or (nested SUM Ors flattened)."""
+    out = []
+    for s in flt.subs:
+        if type(s) is by_term:
+            out.append((s.term, f32(f32(mult) * f32(s.boost))))
+        elif type(s) is Or and s.min_match <= 1 and (s.merge == MERGE_SUM or len(s.subs) == 1):
+            out += _or_members(s, f32(f32(mult) * f32(s.boost)))
+        elif isinstance(s, And):
+            raise ValueError("an Or with And children (a OR (b AND c)) is not on the GPU path")
+        elif isinstance(s, Not):
+            raise ValueError("an Or with a Not child matches all docs but some (zero-score fill, "
+                             "boolean_filter.cpp:120-127): not on the GPU path")
+        elif isinstance(s, by_phrase):
+            raise ValueError("phrases inside boolean trees are not on the GPU path")
+        elif type(s) is Or:
+            raise ValueError("an Or group takes by_term children and SUM Ors of them: min_match > 1 "
+                             "and non-SUM merges are not on the GPU path")
+        else:
+            raise ValueError("%s inside an Or is not on the GPU path" % type(s).__name__)
+    return out
+
+
+def and_groups(flt, mult=1.0):
+    """The groups of an And of by_term / Or-of-by_term children, normalised: a by_term child is a
+    group of one, so is a one-term Or (the single node case, boolean_filter.cpp:152-155); an And
+    child with the same merge is flattened into it; a SUM Or inside a group is flattened into the
+    group.  Each member is (term, boost): term boost x Or boosts x And boosts, multiplied from the
+    top in float32 as prepare() hands ctx.boost down (boolean_filter.cpp:153-154, 204).  Anything
+    else raises ValueError."""
+    mult = f32(f32(mult) * f32(flt.boost))
+    if flt.op != OP_AND:
+        raise ValueError("an And child with op %d is not on the GPU path" % flt.op)
+    if not flt.subs:
+        raise ValueError("an And without children")
+    groups = []
+    for s in flt.subs:
+        if type(s) is by_term:
+            groups.append([(s.term, f32(mult * f32(s.boost)))])
+        elif type(s) is And:
+            if s.merge != flt.merge:
+                raise ValueError("an And child with another merge type is not on the GPU path")
+            groups += and_groups(s, mult)
+        elif type(s) is Or:
+            if s.min_match > 1:
+                raise ValueError("an Or group with min_match > 1 is not on the GPU path")
+            if len(s.subs) != 1 and s.merge != MERGE_SUM:
+                raise ValueError("an Or group merges with SUM on the GPU path")
+            members = _or_members(s, f32(mult * f32(s.boost)))
+            if not members:
+                raise ValueError("an Or group without terms")
+            groups.append(members)
+        elif isinstance(s, Not):
+            raise ValueError("Not is taken by prepare() only (as a child of the outermost And)")
+        elif isinstance(s, by_phrase):
+            raise ValueError("phrases inside boolean trees are not on the GPU path")
+        else:
+            raise ValueError("%s inside an And is not on the GPU path" % type(s).__name__)
+    if sum(len(g) for g in groups) > _lib.MAX_TERMS:
+        raise ValueError("an And has at most %d terms in all its groups" % _lib.MAX_TERMS)
+    return groups
 
 
 def _terms_of(flt):
@@ -252,7 +321,8 @@ class PreparedQuery:
     merge: int = MERGE_SUM
     excluded: list = field(default_factory=list)   # term ordinals under Not (IRS_HIP_EXCLUDE)
     alts: list | None = None   # OP_PHRASE: True for an entry that is one more member of the part
-                               # before it (IRS_HIP_PHRASE_ALT)
+                               # before it (IRS_HIP_PHRASE_ALT); OP_AND: ... of the group before it
+                               # (IRS_HIP_GROUP_ALT, the same bit)
 
 
 # ------------------------------------------------------------------ segment --
@@ -415,7 +485,7 @@ class QueryArrays:
             offs = p.offsets if p.offsets is not None else [0] * len(p.terms)
             alts = p.alts if p.alts is not None else [False] * len(p.terms)
             for t, (kind, c0, nc, nl), off, alt in zip(p.terms, p.scorers, offs, alts):
-                kind = kind | PHRASE_ALT if alt else kind
+                kind = kind | PHRASE_ALT if alt else kind   # (GROUP_ALT for an And: the same bit)
                 for s, sr in enumerate(segs):       # same scorer, the segment's own ordinal
                     present = t is not None and 0 <= t < len(sr.metas)
                     terms[s, at] = (t if present else NO_TERM, kind, c0, nc, nl, off)
@@ -516,8 +586,11 @@ def prepare_filters(filters, scorer, segment_stats, segs, k):
                 if any(isinstance(s, Not) for s in subs):
                     raise ValueError("Not is taken by prepare() (IRS_HIP_EXCLUDE), not by the "
                                      "array path prepare_filters")
-                raise ValueError("only flat Or/And of by_term are on the GPU path")
+                raise ValueError("only flat Or/And of by_term are on the array path: an And with "
+                                 "Or children is taken by prepare()")
             op = flt.op
+            if flt.boost != 1.0:   # (boost_filter::boost() of the Or / And times each term's)
+                boosts_q = [f32(f32(flt.boost) * f32(b)) for b in boosts_q]
         else:
             op, subs = _terms_of(flt)
             terms_q = [s.term for s in subs]
@@ -831,7 +904,11 @@ def prepare(filters, scorer, segment_stats):
             out.append(PreparedQuery(OP_PHRASE, list(flt.terms), [one] * len(flt.terms), 0,
                                      [int(o) for o in flt.offsets]))
             continue
+        if type(flt) is And and (flt.boost != 1.0 or any(type(s) is not by_term for s in flt.subs)):
+            out.append(_prepare_groups(flt, scorer, segment_stats, dwf, ttf))
+            continue
         op, subs = _terms_of(flt)
+        mult = float(getattr(flt, "boost", 1.0)) if type(flt) is not by_term else 1.0
         scorers = []
         for s in subs:
             dwt = 0
@@ -839,11 +916,27 @@ def prepare(filters, scorer, segment_stats):
                 if 0 <= s.term < len(st.docs_count):
                     dwt += int(st.docs_count[s.term])
             stats = scorer.collect(dwf, dwt, ttf)
-            scorers.append(scorer.term_scorer(stats, s.boost))
+            scorers.append(scorer.term_scorer(stats, s.boost if mult == 1.0 else f32(f32(mult) * f32(s.boost))))
         out.append(PreparedQuery(op, [s.term for s in subs], scorers,
                                  int(getattr(flt, "min_match", 0)),
                                  merge=int(getattr(flt, "merge", MERGE_SUM))))
     return out
+
+
+def _prepare_groups(flt, scorer, segment_stats, dwf, ttf):
+    """prepare() of an And with Or children: per-term statistics as for any by_term, the boost
+    product per member; every member after a group's first flagged IRS_HIP_GROUP_ALT.  A tree
+    whose groups all have one member is a flat And, sent as one."""
+    groups = and_groups(flt)
+    terms, scorers, alts = [], [], []
+    for g in groups:
+        for i, (t, boost) in enumerate(g):
+            dwt = sum(int(st.docs_count[t]) for st in segment_stats if 0 <= t < len(st.docs_count))
+            terms.append(t)
+            scorers.append(scorer.term_scorer(scorer.collect(dwf, dwt, ttf), boost))
+            alts.append(i > 0)
+    return PreparedQuery(OP_AND, terms, scorers, int(flt.min_match), merge=int(flt.merge),
+                         alts=alts if any(alts) else None)
 
 
 def variadic_slots(parts, segment_stats):

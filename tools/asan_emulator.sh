@@ -66,6 +66,12 @@ for layout in (1, 0):
     tv.case_lists(L, layout)
 tv.case_parity(L, 6_000, 48, 1, (BM25(),), (10, 1000), 6)
 tv.case_multi(L, (3_000, 1_500, 4_000))
+import test_nested_boolean as tn   # And of Or groups (k_conj_any)
+tn.case_abi(L)
+tn.case_shapes(L, 8_000, 64, 1, (BM25(),), (10, 1000), merges=(0, 2))
+tn.case_shapes(L, 6_000, 48, 0, (BM25(),), (100,), merges=(1,))
+tn.case_deletions(L, 8_000, 64, 1)
+tn.case_multi(L, (3_000, 1_500, 4_000), (64, 48, 56), k=50)
 print("asan emulator run: clean")
 PY
 # ... and the C++ host readers (header only: instrumented with the test binary) over a segment of

@@ -8,7 +8,8 @@ filters with random boosts and merge types (or by_phrase filters), a random scor
 checks the results as the parity tests do; the same batch is then re-run with block-max pruning
 (top-k must not change) and with the k-th score pushed down as irs::score::Min.  Every third
 boolean round also runs the filters with 0-2 excluded terms each (And(filter, Not(by_term))), and
-every phrase round also runs variadic phrases (parts of several terms).
+every phrase round also runs variadic phrases (parts of several terms); every boolean round runs
+Ands of Or groups (with exclusions, wand on and off; every third over two segments in one batch).
 
   python tools/fuzz_parity.py --seconds 120            # on the GPU (libirs_hip.so)
   python tools/fuzz_parity.py --sim --seconds 60       # on the CPU emulator
@@ -54,6 +55,55 @@ def excl_round(sr, seg, filters, scorer, k, st, rng, max_rank):
         ms.doc_mask = np.unique(np.concatenate(parts)).astype(np.uint32)
         parity.check_single_segment(ms, [incl], scorer, k, h[q:q + 1], c[q:q + 1], t[q:q + 1])
     b.close()
+
+
+def grouped_round(sr, seg, scorer, k, st, rng, max_rank, term, merge, multi, L):
+    """And of Or groups (IRS_HIP_GROUP_ALT, k_conj_any): 2-3 groups of 1-4 members with random
+    boosts and merges, some with 1-2 excluded terms (And([And(groups), Not(...)])), wand off and
+    on, against the composed oracle of tests/test_nested_boolean.py; with `multi` the same over
+    ONE batch of this segment and another one."""
+    import parity
+    import test_nested_boolean as tn
+    from iresearch_amd import search, synth
+    from iresearch_amd.search import And, Not, Or, by_term
+    incl, excl, filters = [], [], []
+    for _ in range(8):
+        groups = []
+        for _ in range(int(rng.integers(2, 4))):
+            n = int(rng.integers(1, 5))
+            subs = [term() for _ in range(n)]
+            groups.append(subs[0] if n == 1 else Or(subs, boost=float(rng.choice([1.0, 1.0, 0.5, 2.0]))))
+        if not any(type(g) is Or for g in groups):
+            groups[0] = Or([groups[0], term()])
+        f = And(groups, merge=merge(), boost=float(rng.choice([1.0, 1.0, 1.5])))
+        ex = [int(rng.integers(0, max_rank)) for _ in range(int(rng.integers(0, 3)))] if rng.integers(0, 2) else []
+        incl.append(f)
+        excl.append(ex)
+        filters.append(And([f] + [Not(by_term(x)) for x in ex]) if ex else f)
+    prep = search.prepare(filters, scorer, st)
+    runs = []
+    for wand in (False, True):
+        b = sr.batch(prep, k).set_wand(wand)
+        runs.append(tuple(x.copy() for x in b.run().results()))
+        b.close()
+    (h, c, t), (wh, wc, wt) = runs
+    assert np.array_equal(h, wh) and np.array_equal(c, wc) and np.array_equal(t, wt), "grouped: wand"
+    for q, f in enumerate(incl):
+        tn.check(seg, f, scorer, k, h[q], c[q], t[q], excluded=excl[q])
+    if multi:
+        other = synth.build_segment(int(rng.integers(1_000, 20_000)), max_rank, layout=seg.layout,
+                                    first_doc=seg.num_docs + 1, seed=int(rng.integers(1, 1 << 30)))
+        segs = [seg, other]
+        readers = [sr, search.SegmentReader.from_synth(other, L=L)]
+        mprep = search.prepare(filters, scorer, [parity.segment_stats(x) for x in segs])
+        mb = search.QueryBatch(readers, mprep, k)
+        mh, mc, mt = (x.copy() for x in mb.run().results())
+        for i, x in enumerate(segs):
+            for q, f in enumerate(incl):
+                tn.check(x, f, scorer, k, mh[i, q], mc[i, q], mt[i, q], segs, excluded=excl[q])
+        mb.close()
+        readers[1].close()
+    return len(filters)
 
 
 def main():
@@ -151,6 +201,8 @@ def main():
             parity.check_single_segment(seg, filters, scorer, k, hits, counts, totals)
             if rounds % 3 == 1:   # irs::Not: some queries lose the docs of 1-2 excluded terms
                 excl_round(sr, seg, filters, scorer, k, st, rng, max_rank)
+            # And of Or groups (k_conj_any), every round; over two segments every third
+            queries += grouped_round(sr, seg, scorer, k, st, rng, max_rank, term, merge, rounds % 3 == 2, L)
             if rounds % 3 == 0:   # the same results through page-locked host memory, a run later
                 hh, hc, ht = b.run().results_to_host().host_results()
                 assert np.array_equal(hc, counts) and np.array_equal(ht, totals), "host results: counts"

@@ -45,7 +45,9 @@ def main():
     ap.add_argument("--alts", default="",
                     help="--op phrase: comma list N,...: every part but the first gets N members (the "
                          "word and N-1 ranks near it: a variadic phrase, IRS_HIP_PHRASE_ALT); 1 = the "
-                         "plain phrase of the same words.  Times each and exits")
+                         "plain phrase of the same words.  --op and: every term becomes an Or group of N "
+                         "members from the same rank range (IRS_HIP_GROUP_ALT); 1 = the plain And.  "
+                         "Times each and exits")
     args = ap.parse_args()
     import torch
 
@@ -82,6 +84,33 @@ def main():
         filters = [And([f] + [Not(by_term(int(r) - 1))
                               for r in rng.integers(args.lo_rank, args.hi_rank + 1, args.exclude)])
                    for f in filters]
+    if args.alts and args.op == "and":
+        for n_alt in (int(x) for x in args.alts.split(",")):
+            rng = np.random.default_rng(synth.SEED + 4)
+            gf = []
+            for row in ranks:
+                groups = []
+                for r in row:
+                    near = [int(r) - 1]
+                    while len(near) < n_alt:
+                        x = int(rng.integers(args.lo_rank, args.hi_rank + 1)) - 1
+                        if x not in near:
+                            near.append(x)
+                    groups.append(Or([by_term(x) for x in near]) if n_alt > 1 else by_term(near[0]))
+                gf.append(And(groups))
+            b = sr.batch(search.prepare(gf, scorer, [st]), args.k).profile(True)
+            b.run()
+            _, _, totals = b.results()
+            t0 = time.perf_counter()
+            for _ in range(args.steps):
+                b.run()
+                b.results()
+            dt = (time.perf_counter() - t0) / args.steps
+            print("alts=%d  %s  step %.2f ms  = %.2f ms per 1000 queries  hits/query mean %.0f  reruns=%d"
+                  % (n_alt, "grouped" if n_alt > 1 else "plain", dt * 1e3, dt * 1e3 * 1000 / len(gf),
+                     float(np.mean(totals)), b.reruns()), flush=True)
+            b.close()
+        sys.exit(0)
     if args.alts and args.op == "phrase":
         for n_alt in (int(x) for x in args.alts.split(",")):
             rng = np.random.default_rng(synth.SEED + 4)

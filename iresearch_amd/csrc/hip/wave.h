@@ -21,6 +21,9 @@ __device__ __forceinline__ uint32_t dpp_zero(uint32_t v) {
 // Inclusive prefix sum across the 64 lanes of a wavefront, entirely in the
 // VALU cross-lane network (no LDS traffic): row_shr 1/2/4/8 inside each row of
 // 16 lanes, then row_bcast:15 (rows 1,3) and row_bcast:31 (rows 2,3).
+// Domain (this and every cross-lane operation below): ALL 64 lanes of the wavefront active —
+// under a partial exec mask the DPP steps do not see every lane's value and the result is not
+// the prefix sum of the active lanes.  Sums wrap at 2^32.
 __device__ __forceinline__ uint32_t inclusive_scan(uint32_t v) {
   v += dpp_zero<0x111, 0xF>(v);  // row_shr:1
   v += dpp_zero<0x112, 0xF>(v);  // row_shr:2
@@ -85,7 +88,8 @@ __device__ __forceinline__ float uniform_f(float v) {
   return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v)));
 }
 
-// Lane `k` (wave-uniform index) of a per-lane value -> SGPR (v_readlane_b32).
+// Lane `k` (wave-uniform index, 0..63) of a per-lane value -> SGPR (v_readlane_b32); the 32
+// bits as they are (read_lane_f: a NaN keeps its payload).
 __device__ __forceinline__ uint32_t read_lane(uint32_t v, uint32_t k) {
   return uint32_t(__builtin_amdgcn_readlane(int(v), int(k)));
 }
@@ -101,6 +105,7 @@ __device__ __forceinline__ float read_lane_f(float v, uint32_t k) {
 }
 
 // Cheap integer helpers that map to single full-rate instructions.
+// mul24: the low 32 bits of a * b for a, b < 2^24 (v_mul_u32_u24)
 __device__ __forceinline__ uint32_t mul24(uint32_t a, uint32_t b) { return __umul24(a, b); }
 // ({hi, lo} >> s) & 0xffffffff, s in 0..31 (v_alignbit_b32)
 __device__ __forceinline__ uint32_t funnel(uint32_t hi, uint32_t lo, uint32_t s) {

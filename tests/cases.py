@@ -1891,10 +1891,12 @@ def case_shared_threshold_misled(L, k=400):
         r.close()
 
 
-def case_merge_ties(L, n_lists=5, nq=7, k=64, seed=11):
+def case_merge_ties(L, n_lists=5, nq=7, k=64, seed=11, single=None):
     """irs_hip_merge_topk alone: few distinct scores (heavy ties across segments), ragged
     counts including empty lists, segment ids not in list order.  Expected order:
-    (score desc, segment asc, doc asc) — tests/search/wand_test.cpp:72-86."""
+    (score desc, segment asc, doc asc) — tests/search/wand_test.cpp:72-86.
+    `single`: that list holds ONE element for every query and all the others are full — the
+    short list voids k_merge_topk's score floor while nearly n_lists * k elements are staged."""
     import ctypes
     import torch
     from iresearch_amd import _lib, distributed
@@ -1910,6 +1912,8 @@ def case_merge_ties(L, n_lists=5, nq=7, k=64, seed=11):
         c = np.zeros(nq, np.uint32)
         for q in range(nq):
             n = int(rng.integers(0, k + 1)) if (q + l) % 4 else (0 if q % 2 else k)
+            if single is not None:
+                n = 1 if l == single else k
             sc = np.sort(rng.choice(levels, n))[::-1]
             docs = np.zeros(n, np.uint32)
             # doc ascending inside a run of equal scores (what k_select emits)
@@ -1938,6 +1942,27 @@ def case_merge_ties(L, n_lists=5, nq=7, k=64, seed=11):
         got = [(float(gh[q, i]["score"]), int(gs[q, i]), int(gh[q, i]["doc"]))
                for i in range(len(want))]
         assert got == want, q
+
+
+def case_merge_limits(L):
+    """irs_hip_merge_topk at its documented limits: 16 lists and kMergeMax = 32768 staged scores
+    (kernels.h).  One step beyond either is refused before anything is launched."""
+    import ctypes
+    import torch
+    from iresearch_amd import _lib
+    arch = ctypes.create_string_buffer(64)
+    L.irs_hip_device_arch(0, arch, 64)
+    dev = "cpu" if arch.value.endswith(b"-sim") else "cuda"
+    for n_lists, k, want in ((16, 2049, _lib.EUNSUPPORTED), (17, 64, _lib.EINVAL), (17, 2049, _lib.EINVAL)):
+        h = torch.zeros((1, k), dtype=torch.int64, device=dev)
+        c = torch.zeros((1,), dtype=torch.int32, device=dev)
+        out_h, out_s, out_c = torch.zeros_like(h), torch.zeros((1, k), dtype=torch.int32, device=dev), torch.zeros_like(c)
+        lists = (ctypes.c_void_p * n_lists)(*[h.data_ptr()] * n_lists)
+        counts = (ctypes.c_void_p * n_lists)(*[c.data_ptr()] * n_lists)
+        seg_ids = np.arange(n_lists, dtype=np.uint32)
+        rc = L.irs_hip_merge_topk(0, lists, counts, seg_ids.ctypes.data, n_lists, 1, k, out_h.data_ptr(),
+                                  out_s.data_ptr(), out_c.data_ptr(), None)
+        assert rc == want, (n_lists, k, rc)
 
 
 # ------------------------------------------------------------------ errors --

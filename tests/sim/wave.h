@@ -12,7 +12,13 @@ namespace wave {
 
 __device__ __forceinline__ unsigned lane_id() { return threadIdx.x & 63u; }
 
-// Inclusive prefix sum across the 64 lanes of a wavefront.
+// The domains are those of hip/wave.h, and tests/test_wave_primitives.py holds both files to one
+// statement per primitive inside them: cross-lane operations with all 64 lanes active, lane
+// indices 0..63, mul24 operands < 2^24, funnel s in 0..31, bfe 1 <= bits <= 31 (1u << 32 below is
+// undefined, v_bfe_u32 gives 0), 16-byte LDS operations at multiples of 16, gload offsets
+// unsigned and 4-byte aligned.  Outside them the two files may differ.  A primitive added here
+// or there gets a statement and a case in the same change.
+// Inclusive prefix sum across the 64 lanes of a wavefront (sums wrap at 2^32).
 __device__ __forceinline__ uint32_t inclusive_scan(uint32_t v) {
 #pragma unroll
   for (int d = 1; d < 64; d <<= 1) {

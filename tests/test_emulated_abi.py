@@ -190,6 +190,10 @@ def test_multi_segment_batch(simlib):
 
 def test_merge_ties(simlib):
     cases.case_merge_ties(simlib)
+    cases.case_merge_ties(simlib, n_lists=5, nq=7, k=63, seed=3)       # odd n_lists * k: `hp` moves a word
+    cases.case_merge_ties(simlib, n_lists=5, nq=4, k=63, seed=4, single=0)
+    cases.case_merge_ties(simlib, n_lists=16, nq=1, k=2048, seed=17, single=9)   # kMergeMax, a floor voided
+    cases.case_merge_limits(simlib)
 
 
 @pytest.mark.parametrize("layout", LAYOUTS)

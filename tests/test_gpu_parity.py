@@ -269,6 +269,13 @@ def test_multi_segment_batch(gpulib):
 def test_merge_ties(gpulib):
     cases.case_merge_ties(gpulib)
     cases.case_merge_ties(gpulib, n_lists=8, nq=5, k=1000, seed=5)
+    # the documented limits: 16 lists x 2048 = kMergeMax staged scores (131 KB of dynamic LDS)
+    cases.case_merge_ties(gpulib, n_lists=16, nq=3, k=2048, seed=16)
+    cases.case_merge_ties(gpulib, n_lists=16, nq=2, k=2048, seed=17, single=9)
+    cases.case_merge_ties(gpulib, n_lists=5, nq=7, k=63, seed=3)       # odd n_lists * k: `hp` moves a word
+    cases.case_merge_ties(gpulib, n_lists=5, nq=4, k=63, seed=4, single=0)
+    cases.case_merge_ties(gpulib, n_lists=8, nq=3, k=1000, seed=6, single=7)
+    cases.case_merge_limits(gpulib)
 
 
 def test_full_vocabulary_million_terms(gpulib):

@@ -74,6 +74,23 @@ tn.case_deletions(L, 8_000, 64, 1)
 tn.case_multi(L, (3_000, 1_500, 4_000), (64, 48, 56), k=50)
 print("asan emulator run: clean")
 PY
+# ... the probe of the wave:: primitives (tests/probe), same flags: every index of its kernels and
+# of its host code stays inside its buffer
+PROBE=${TMPDIR:-/tmp}/libwave_probe_asan.so
+g++ -O1 -g -std=c++17 -fPIC -shared -pthread -ffp-contract=off -fsanitize=address \
+  -fno-omit-frame-pointer -I include -I iresearch_amd/csrc -I tests/sim -I iresearch_amd/csrc/hip \
+  -Wno-unknown-pragmas -o "$PROBE" -x c++ tests/probe/wave_probe.hip -x assembler tests/sim/sim_switch.S
+LD_PRELOAD=$(gcc -print-file-name=libasan.so) \
+ASAN_OPTIONS=detect_leaks=0:detect_stack_use_after_return=0 python - "$PROBE" <<'PY'
+import sys
+from pathlib import Path
+sys.path.insert(0, "."); sys.path.insert(0, "tests")
+import test_wave_primitives as tw
+P = tw.bind(Path(sys.argv[1]))
+tw.check_crosslane(P); tw.check_integer(P); tw.check_float(P, "asan"); tw.check_lds(P, "asan")
+tw.check_sync(P); tw.check_loads(P)
+print("asan probe run: clean")
+PY
 # ... and the C++ host readers (header only: instrumented with the test binary) over a segment of
 # three fields incl. damaged `.ti` / `.sm` / `.tm` files whose checksums were recomputed
 python - <<'PY'

@@ -575,6 +575,33 @@ int irs_hip_batch_reruns(irs_hip_batch* batch, uint32_t* count);
  * the segment has none).  Waits for the run. */
 int irs_hip_batch_unit_mask(irs_hip_batch* batch, uint32_t unit, uint64_t* set, uint64_t n_words);
 
+/* filter::prepared::execute with Scorers::kUnordered (core/search/filter.hpp:52-78): the docs every
+ * unit of the batch matches, all of them, unscored — what a search without a sort, a count and
+ * proxy_filter's cached bitsets (proxy_filter.hpp, bitset_doc_iterator.hpp) run.
+ * Unit u = segment * n_queries + query, as for irs_hip_batch_unit_mask.  `sets` is
+ * [n_units][n_words] in irs_hip_bit_union's layout (64-bit little-endian words, bit index = doc
+ * id): every word of every row is written, nothing is OR-ed into old content.  `counts` is
+ * [n_units], the population of each row — the total_hits a scored run of the batch reports.
+ * n_words must cover the largest segment of the batch, 64 * n_words > num_docs, else
+ * IRS_HIP_EINVAL.  Either output may be NULL (sets == NULL: only 8 bytes per unit leave the
+ * device); both NULL is IRS_HIP_EINVAL.
+ * A doc matches as in a scored run — Or: an entry holds it; And: every group has a member that
+ * holds it; min-match: at least min_match entries hold it — and is neither deleted nor a doc of an
+ * excluded term (IRS_HIP_EXCLUDE).  Scorer values, k, merge and every setter of the batch
+ * (set_wand, set_min_scores, set_path, set_paired_tiles, shared thresholds, set_comm) play no part;
+ * the sets are this rank's, nothing is gathered.  The call may come before, after or without
+ * irs_hip_batch_run and leaves the batch's results, irs_hip_batch_reruns and later runs as they
+ * would have been.  A phrase matches where its phrase frequency is > 0.  (A segment without
+ * frequencies has no batch: irs_hip_batch_create refuses it, IRS_HIP_EUNSUPPORTED.)
+ * Synchronous, like irs_hip_bit_union_counts; the staging memory comes from the pool
+ * (IRS_HIP_ENOMEM when it cannot be had). */
+int irs_hip_batch_match_sets(irs_hip_batch* batch, uint64_t* sets, uint64_t n_words, uint64_t* counts);
+/* The same into device memory (d_sets [n_units][n_words] u64, d_counts [n_units] u64; either may
+ * be NULL), queued on `stream` as irs_hip_batch_results_to_device queues its copies: the
+ * disjunction's doc set handed to a consumer on the device (bitset_doc_iterator.hpp). */
+int irs_hip_batch_match_sets_to_device(irs_hip_batch* batch, void* d_sets, uint64_t n_words,
+                                       void* d_counts, void* stream);
+
 /* Multi-segment / multi-GPU merge: merges `n_lists` per-query
  * top-k lists (device pointers, each [n_queries][k] hits + [n_queries] counts,
  * list i belonging to segment ordinal seg_ids[i]) into the global top-k ordered

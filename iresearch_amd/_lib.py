@@ -80,6 +80,7 @@ SYMBOLS = (
     "irs_hip_term_blockmax",
     "irs_hip_segment_wand_source",
     "irs_hip_batch_touched", "irs_hip_batch_unit_mask",
+    "irs_hip_batch_match_sets", "irs_hip_batch_match_sets_to_device",
     "irs_hip_comm_unique_id", "irs_hip_comm_init_rank", "irs_hip_comm_destroy",
     "irs_hip_comm_library",
     "irs_hip_topk_allgather", "irs_hip_device_alloc", "irs_hip_device_free",
@@ -159,6 +160,10 @@ def bind(L: C.CDLL) -> C.CDLL:
     L.irs_hip_batch_touched.argtypes, L.irs_hip_batch_touched.restype = [vp, P(u64), P(u64)], C.c_int
     L.irs_hip_batch_unit_mask.argtypes = [vp, u32, vp, u64]
     L.irs_hip_batch_unit_mask.restype = C.c_int
+    L.irs_hip_batch_match_sets.argtypes = [vp, vp, u64, vp]
+    L.irs_hip_batch_match_sets.restype = C.c_int
+    L.irs_hip_batch_match_sets_to_device.argtypes = [vp, vp, u64, vp, vp]
+    L.irs_hip_batch_match_sets_to_device.restype = C.c_int
     L.irs_hip_comm_unique_id.argtypes, L.irs_hip_comm_unique_id.restype = [vp], C.c_int
     L.irs_hip_comm_init_rank.argtypes = [i32, vp, i32, i32, P(vp)]
     L.irs_hip_comm_init_rank.restype = C.c_int

@@ -660,6 +660,55 @@ class QueryBatch {
     }
     return r;
   }
+  // filter::prepared::execute with Scorers::kUnordered (filter.hpp:52-78): every doc each query
+  // matches on each segment, unscored, as bitsets in irs_hip_bit_union's layout (bit = doc id),
+  // and their populations (irs_hip_batch_match_sets).  Independent of run(): before, after or
+  // without one.
+  struct MatchSets {
+    uint32_t n_segments = 0, n_queries = 0;
+    uint64_t n_words = 0;                 // 64-bit words per row (0: counts only)
+    std::vector<uint64_t> words;          // [segment][query][n_words]
+    std::vector<uint64_t> counts;         // [segment][query]
+    const uint64_t* of(uint32_t seg, uint32_t q) const {
+      return words.data() + (size_t(seg) * n_queries + q) * n_words;
+    }
+    uint64_t count(uint32_t seg, uint32_t q) const { return counts[size_t(seg) * n_queries + q]; }
+    bool contains(uint32_t seg, uint32_t q, uint32_t doc) const {
+      return doc / 64 < n_words && ((of(seg, q)[doc / 64] >> (doc % 64)) & 1u);
+    }
+  };
+  // n_words: 64 * n_words > num_docs of the largest segment; sets = false: the counts alone
+  MatchSets match_sets(uint64_t n_words, bool sets = true) {
+    MatchSets r;
+    r.n_segments = n_segments_;
+    r.n_queries = n_queries_;
+    r.n_words = sets ? n_words : 0;
+    const size_t units = size_t(n_segments_) * n_queries_;
+    r.counts.resize(units);
+    if (sets) r.words.resize(units * n_words);
+    for (Part& part : part_) {
+      if (!part.h) continue;
+      const size_t nq = part.index.size(), pu = size_t(n_segments_) * nq;
+      std::vector<uint64_t> words(sets ? pu * n_words : 0), counts(pu);
+      check(irs_hip_batch_match_sets(part.h, sets ? words.data() : nullptr, n_words, counts.data()),
+            "irs_hip_batch_match_sets");
+      for (uint32_t s = 0; s < n_segments_; ++s)
+        for (size_t i = 0; i < nq; ++i) {
+          const size_t from = s * nq + i, to = size_t(s) * n_queries_ + part.index[i];
+          if (sets) std::copy_n(words.begin() + from * n_words, n_words, r.words.begin() + to * n_words);
+          r.counts[to] = counts[from];
+        }
+    }
+    return r;
+  }
+  // ... into device memory, queued on `stream` (irs_hip_batch_match_sets_to_device): d_sets
+  // [segment][query][n_words] u64, d_counts [segment][query] u64, either may be null.  Queries that
+  // are all boolean or all by_phrase (one device batch: the rows are in the caller's order).
+  QueryBatch& match_sets_to_device(void* d_sets, uint64_t n_words, void* d_counts, void* stream = nullptr) {
+    check(irs_hip_batch_match_sets_to_device(single_part(), d_sets, n_words, d_counts, stream),
+          "irs_hip_batch_match_sets_to_device");
+    return *this;
+  }
   // the one device batch of a list of queries that are all boolean or all by_phrase
   // (what search_sharded hands to irs_hip_batch_results_to_device)
   irs_hip_batch* single_part() const {
@@ -1606,6 +1655,38 @@ DocSet execute_unscored(const SegmentReader& segment, const std::vector<std::str
   const std::vector<uint32_t> ordinals = visit(field_terms, flt);
   if (!ordinals.empty()) out.postings = segment.bit_union(ordinals, out.words);
   return out;
+}
+
+// The same for the filters a QueryBatch takes — by_term / Or / And / by_phrase / Exclusion without
+// scorers (filter::prepared::execute with Scorers::kUnordered, filter.hpp:52-78: what proxy_filter
+// caches, proxy_filter.hpp): one DocSet per segment, `postings` = the number of docs in it.
+// num_docs[s]: docs_count of segment s.  The statistics of `index` only make the entries valid;
+// no score is computed.
+inline std::vector<DocSet> execute_unscored(const std::vector<const SegmentReader*>& segments,
+                                            const std::vector<SegmentStats>& index,
+                                            const std::vector<uint32_t>& num_docs, const filter& flt) {
+  if (segments.empty() || num_docs.size() != segments.size())
+    throw illegal_argument(IRS_HIP_EINVAL, "execute_unscored: num_docs per segment");
+  const uint64_t n_words = (uint64_t(*std::max_element(num_docs.begin(), num_docs.end())) + 1 + 63) / 64;
+  QueryBatch batch(segments, prepare({flt}, BM25{}, index), 1);
+  const QueryBatch::MatchSets m = batch.match_sets(n_words);
+  std::vector<DocSet> out(segments.size());
+  for (uint32_t s = 0; s < segments.size(); ++s) {
+    out[s].words.assign(m.of(s, 0), m.of(s, 0) + (uint64_t(num_docs[s]) + 1 + 63) / 64);
+    out[s].postings = m.count(s, 0);
+  }
+  return out;
+}
+inline DocSet execute_unscored(const SegmentReader& segment, const SegmentStats& stats, uint32_t num_docs,
+                               const filter& flt) {
+  return execute_unscored({&segment}, {stats}, {num_docs}, flt)[0];
+}
+template<typename F, typename = std::enable_if_t<std::is_same_v<F, by_term> || std::is_same_v<F, Or> ||
+                                                 std::is_same_v<F, And> || std::is_same_v<F, by_phrase> ||
+                                                 std::is_same_v<F, Exclusion>>>
+DocSet execute_unscored(const SegmentReader& segment, const SegmentStats& stats, uint32_t num_docs,
+                        const F& flt) {
+  return execute_unscored(segment, stats, num_docs, filter{flt});
 }
 
 // ---- scored multi-term filters: by_prefix / by_wildcard / by_range with scored_terms_limit ----

@@ -27,6 +27,7 @@ struct Knobs {
   uint32_t join_threads = 1024;   // IRS_HIP_JOIN_THREADS: ... per k_join_pilot / k_join_score workgroup
   bool acc64 = false;        // IRS_HIP_ACC=64: 64-bit accumulators whatever the queries
   uint32_t excl_slice = kExclSliceWords;   // IRS_HIP_EXCL_SLICE: mask words per k_excl_mask workgroup (64..8192, a power of two)
+  uint32_t match_slice = kMatchSliceWords;   // IRS_HIP_MATCH_SLICE: bitmap words per k_match_slice workgroup (64..8192, a power of two)
   static Knobs from_env() {
     Knobs k;
     int v = 0;
@@ -48,6 +49,8 @@ struct Knobs {
     if (set("IRS_HIP_ACC")) k.acc64 = v == 64;
     if (set("IRS_HIP_EXCL_SLICE") && v >= 64 && uint32_t(v) <= kExclSliceWords && (v & (v - 1)) == 0)
       k.excl_slice = uint32_t(v);
+    if (set("IRS_HIP_MATCH_SLICE") && v >= 64 && uint32_t(v) <= kMatchSliceMax && (v & (v - 1)) == 0)
+      k.match_slice = uint32_t(v);
     return k;
   }
 };
@@ -148,6 +151,18 @@ struct ExclWork {
   bool on() const { return !masks.empty(); }
 };
 
+// Unscored execution (match.h, plan_match.h): the units as k_match_slice reads them, built with the
+// first irs_hip_batch_match_sets call; the host form's staging of the sets and counts
+struct MatchWork {
+  bool built = false, sent = false;
+  std::vector<MatchUnit> units;
+  std::vector<uint32_t> rows;    // the units' term ordinals, MatchUnit::first / n_rows
+  DevBuf d_units, d_rows, d_sets, d_counts;
+  uint32_t maps = 1;             // LDS bitmaps per workgroup: of the widest op among the units
+  uint32_t slice_words = 0;      // 32-bit words of one bitmap (Knobs::match_slice, halved to fit)
+  uint32_t max_docs = 0;         // num_docs of the batch's largest segment
+};
+
 // One threshold per query for its units on the batch's segments (irs_hip_batch_set_shared_threshold)
 // ... across ranks (irs_hip_batch_set_comm): the group histograms and the group sums are summed
 // over the communicator's ranks inside every run
@@ -179,6 +194,10 @@ struct RunSync {
   // waits for it and for `done` — never for the stream, which may hold other batches' work)
   Event used;
   bool used_pending = false;
+  // the last irs_hip_batch_match_sets_to_device queued on some stream: it reads the exclusion masks
+  // and the match tables (a run, a setter's re-deal and destroy get behind it)
+  Event matched;
+  bool match_pending = false;
   Event uploaded;   // the first run's table uploads (the device's copy stream)
   Event prof[2 * IRS_HIP_K_COUNT];   // irs_hip_batch_profile: around every stage of a run
   PinBuf h_pin;                // page-locked staging for irs_hip_batch_results
@@ -255,6 +274,7 @@ struct irs_hip_batch {
   BlockWork blocks;
   AnyWork any;
   ExclWork excl;
+  MatchWork match;
   Groups groups;
   RunSync sync;
 };

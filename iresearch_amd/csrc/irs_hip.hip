@@ -29,6 +29,7 @@
 #include "conj_any.h"
 #include "join.h"
 #include "excl.h"
+#include "match.h"
 
 using namespace irs_hip;
 
@@ -39,6 +40,7 @@ using namespace irs_hip;
 #include "plan_blocks.h"
 #include "plan_any.h"
 #include "plan_join.h"
+#include "plan_match.h"
 
 namespace {
 
@@ -226,6 +228,20 @@ bool alloc_scratch(irs_hip_batch* b, uint64_t first_words, uint64_t item_bound) 
   }
   // (the unit records last: dealing the units and building the streams filled fields in)
   return b->up.copy(b->d_queries.p, b->queries.data(), b->queries.size() * sizeof(DevQuery));
+}
+
+// The doc masks of the units with excluded terms (excl.h): every distinct mask in one launch — in the
+// plan stage of every run, and ahead of a batch's match sets (plan_match.h)
+bool launch_excl_masks(irs_hip_batch* b, rt::stream_t st) {
+  const size_t smem = size_t(b->knobs.excl_slice) * 4;
+  const uint32_t grid = b->excl.slices * uint32_t(b->excl.masks.size());
+  return with_layout(b->seg->dev.layout, [&](auto L) {
+    if (!big_smem(k_excl_mask<decltype(L)::value>, smem)) return false;
+    RT_LAUNCH((k_excl_mask<decltype(L)::value>), grid, kThreads, smem, st, b->d_segs.as<DevSegment>(),
+              b->excl.d_masks.as<ExclMask>(), b->excl.d_terms.as<uint32_t>(), b->excl.slices,
+              b->knobs.excl_slice);
+    return rt::last_error_ok();
+  });
 }
 
 bool ensure_scratch(irs_hip_batch* b) {
@@ -915,6 +931,10 @@ static bool quiesce(irs_hip_batch* b) {
     b->sync.plan_pending = false;
   }
   if (b->ran) ok = rt::sync(b->stream) && ok;
+  if (b->sync.match_pending) {
+    ok = b->sync.matched.sync() && ok;
+    b->sync.match_pending = false;
+  }
   return ok;
 }
 
@@ -1094,17 +1114,7 @@ static bool plan_stage(irs_hip_batch* b, rt::stream_t st) {
   auto mark = [&](int i) { return !b->profile || b->sync.prof[i].record(st); };
   bool ok = mark(2 * IRS_HIP_K_PLAN);
   // the doc masks of the units with excluded terms (excl.h), before anything reads them
-  if (ok && b->excl.on()) {
-    const size_t smem = size_t(b->knobs.excl_slice) * 4;
-    const uint32_t grid = b->excl.slices * uint32_t(b->excl.masks.size());
-    ok = with_layout(b->seg->dev.layout, [&](auto L) {
-      if (!big_smem(k_excl_mask<decltype(L)::value>, smem)) return false;
-      RT_LAUNCH((k_excl_mask<decltype(L)::value>), grid, kThreads, smem, st, b->d_segs.as<DevSegment>(),
-                b->excl.d_masks.as<ExclMask>(), b->excl.d_terms.as<uint32_t>(), b->excl.slices,
-                b->knobs.excl_slice);
-      return rt::last_error_ok();
-    });
-  }
+  if (ok && b->excl.on()) ok = launch_excl_masks(b, st);
   // (a joined batch without conjunctions needs none of k_plan's tables)
   if (ok && (b->phrase || !b->tiles.units.empty() || !b->blocks.units.empty() || !b->any.units.empty())) {
     RT_LAUNCH(k_plan, b->nq * b->jt, kThreads, 0, st, b->d_segs.as<DevSegment>(),
@@ -1145,6 +1155,8 @@ static int batch_plan_impl(irs_hip_batch* b, void* stream) {
   if (ok && b->sync.done.made && b->ran) ok = b->sync.done.wait(st);
   // (a plan queued earlier and never consumed may still run on ANOTHER stream)
   if (ok && b->sync.plan_pending) ok = b->sync.plan.wait(st);
+  // (match sets queued on another stream read the masks this stage rewrites)
+  if (ok && b->sync.match_pending) ok = b->sync.matched.wait(st);
   ok = ok && b->up.flush(st) && plan_stage(b, st) && b->sync.plan.record(st);
   b->sync.planned = ok;
   b->sync.plan_pending = b->sync.plan_pending || b->sync.plan.made;   // (whatever got queued)
@@ -1174,6 +1186,12 @@ static int run_impl(irs_hip_batch* b, rt::stream_t st) {
   if (after_plan) ok = b->sync.plan.wait(st);
   rt::stream_t up_st = (!b->ran && !b->up.pending.empty()) ? upload_stream(b->seg->device) : nullptr;
   if (up_st && after_plan) ok = ok && b->sync.plan.wait(up_st);
+  // match sets queued on another stream (irs_hip_batch_match_sets_to_device) read the exclusion
+  // masks this run's plan stage rewrites and the tables its uploads replace
+  if (b->sync.match_pending) {
+    ok = ok && b->sync.matched.wait(st) && (!up_st || b->sync.matched.wait(up_st));
+    b->sync.match_pending = !ok;
+  }
   b->sync.plan_pending = false;
   if (up_st) {
     ok = ok && b->up.flush(up_st) && b->sync.uploaded.record(up_st) && b->sync.uploaded.wait(st);
@@ -1531,6 +1549,7 @@ void irs_hip_batch_destroy(irs_hip_batch* b) {
     waited = waited && b->sync.plan.sync();
   if (b->sync.used_pending) waited = waited && b->sync.used.sync();
   if (b->sync.host_pending) waited = waited && b->sync.host.sync();
+  if (b->sync.match_pending) waited = waited && b->sync.matched.sync();
   if (!waited && b->ran) rt::sync(b->stream);
   // (the batch's events go with it)
   delete b;
@@ -1716,6 +1735,16 @@ int irs_hip_batch_touched(irs_hip_batch* b, uint64_t* doc_bytes, uint64_t* posit
 }
 int irs_hip_batch_unit_mask(irs_hip_batch* b, uint32_t unit, uint64_t* set, uint64_t n_words) {
   return settled(b, [&] { return batch_unit_mask_impl(b, unit, set, n_words); });
+}
+int irs_hip_batch_match_sets(irs_hip_batch* b, uint64_t* sets, uint64_t n_words, uint64_t* counts) {
+  return settled(b, [&] { return batch_match_sets_impl(b, sets, nullptr, n_words, counts, nullptr, nullptr, false); });
+}
+int irs_hip_batch_match_sets_to_device(irs_hip_batch* b, void* d_sets, uint64_t n_words, void* d_counts,
+                                       void* stream) {
+  return settled(b, [&] {
+    return batch_match_sets_impl(b, nullptr, d_sets, n_words, nullptr, d_counts,
+                                 static_cast<rt::stream_t>(stream), true);
+  });
 }
 int irs_hip_batch_plan(irs_hip_batch* b, void* stream) {
   return settled(b, [&] { return batch_plan_impl(b, stream); });

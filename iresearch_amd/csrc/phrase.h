@@ -463,6 +463,10 @@ struct ConjArgs {
 //      per wavefront.
 // Wavefronts are independent (no workgroup barrier).  MT = compile-time bound of the phrase
 // length (cursor state stays in registers).
+// MATCH (match.h, unscored execution): steps 1-3 only — a doc with phrase frequency > 0 sets its bit
+// in the unit's row of `sets32` (zeroed by the caller; matches are sparse: a global atomic) and
+// counts for the unit; the position merge stops at the first match; no threshold, norm, score or
+// candidate.  The scored instantiations compile to what they were without the parameter.
 template<int MT>
 struct PhraseWave {
   uint32_t docs[kBlock];
@@ -477,10 +481,11 @@ struct PhraseWave {
   uint32_t off[MT];
 };
 
-template<int LAYOUT, int MT>
+template<int LAYOUT, int MT, bool MATCH = false>
 __device__ __forceinline__ void phrase_item(const ConjArgs& A, uint32_t pilot /*1: histogram the
                                             scores of the sampled lead items, no candidates*/,
-                                            PhraseWave<MT>* s_wave) {
+                                            PhraseWave<MT>* s_wave, uint32_t* sets32 = nullptr,
+                                            uint64_t words32 = 0, unsigned long long* counts = nullptr) {
   const uint32_t tid = threadIdx.x;
   const unsigned lane = tid & 63u;
   const uint32_t wv = wave::uniform(tid >> 6);
@@ -503,7 +508,7 @@ __device__ __forceinline__ void phrase_item(const ConjArgs& A, uint32_t pilot /*
   const uint32_t lead = A.lead_of[unit];   // the term with the fewest postings leads
   const DevTail ld = term_tail(lead);
   const DevQTerm qt = A.qterms[qd.first_term];  // the phrase's scorer rides on its first term
-  const uint32_t bs = pilot ? 0u : A.bstar[unit];
+  const uint32_t bs = (MATCH || pilot) ? 0u : A.bstar[unit];
   PhraseWave<MT>& W = s_wave[wv];
   uint32_t* docs = W.docs;
   const uint32_t* seek = A.seek + uint64_t(e) * (A.jt - 1u);
@@ -821,6 +826,7 @@ __device__ __forceinline__ void phrase_item(const ConjArgs& A, uint32_t pilot /*
           } else {
             pf += vb == va + off ? 1u : 0u;     // reached the target, or sought too far
             adv_a = true;
+            if (MATCH && pf) break;
           }
           if (adv_a ? ka == T[0] : kb == T[1]) break;   // exhausted: no later position can match
           DevPosTerm pt;
@@ -865,8 +871,15 @@ __device__ __forceinline__ void phrase_item(const ConjArgs& A, uint32_t pilot /*
           }
         }
         if (match && !done) ++pf;
+        if (MATCH && pf) break;
       }
-      if (pf) {
+      if constexpr (MATCH) {
+        if (pf) {
+          doc = docs[sl];
+          if (sets32) atomicOr(&sets32[uint64_t(unit) * words32 + (doc >> 5)], 1u << (doc & 31u));
+          ++my_hits;
+        }
+      } else if (pf) {
         doc = docs[sl];
         // (a posting of the lead block: its norm from the posting-order copy of the column)
         const uint32_t nv = !seg.pnorm ? norm_value(seg, doc)
@@ -888,6 +901,11 @@ __device__ __forceinline__ void phrase_item(const ConjArgs& A, uint32_t pilot /*
       const uint32_t slot = base + uint32_t(__builtin_popcountll(cm & below));
       if (cand && slot < A.cand_cap) A.cands[uint64_t(unit) * A.cand_cap + slot] = make_key(score, doc);
     }
+  }
+  if constexpr (MATCH) {
+    my_hits = wave::reduce_add(my_hits);
+    if (lane == 0 && my_hits && counts) atomicAdd(&counts[unit], static_cast<unsigned long long>(my_hits));
+    return;
   }
   if (pilot) return;
   my_hits = wave::reduce_add(my_hits);

@@ -99,9 +99,13 @@ struct VPhraseWave {
   uint32_t off[kVarRows];
 };
 
-template<int LAYOUT>
+// MATCH: as for phrase_item (phrase.h) — the surviving docs with a phrase frequency > 0 set their
+// bits and count, nothing is scored
+template<int LAYOUT, bool MATCH = false>
 __device__ __forceinline__ void vphrase_item(const ConjArgs& A, const uint32_t* opens_of,
-                                             uint32_t pilot, VPhraseWave* s_wave) {
+                                             uint32_t pilot, VPhraseWave* s_wave,
+                                             uint32_t* sets32 = nullptr, uint64_t words32 = 0,
+                                             unsigned long long* counts = nullptr) {
   const uint32_t tid = threadIdx.x;
   const unsigned lane = tid & 63u;
   const uint32_t wv = wave::uniform(tid >> 6);
@@ -133,7 +137,7 @@ __device__ __forceinline__ void vphrase_item(const ConjArgs& A, const uint32_t* 
   const uint32_t first_end = part_end(0);   // rows of P_0, whose positions are counted
   const DevTail ld = term_tail(j);
   const DevQTerm qt = A.qterms[qd.first_term];  // the phrase's scorer rides on every entry
-  const uint32_t bs = pilot ? 0u : A.bstar[unit];
+  const uint32_t bs = (MATCH || pilot) ? 0u : A.bstar[unit];
   VPhraseWave& W = s_wave[wv];
   uint32_t* docs = W.docs;
   const uint32_t* seek = A.seek + uint64_t(e) * (A.jt - 1u);
@@ -373,6 +377,7 @@ __device__ __forceinline__ void vphrase_item(const ConjArgs& A, const uint32_t* 
       }
       uint32_t pf = 0;
       for (uint32_t a = 0; a < first_end; ++a) {   // VisitLead: the members of P_0 add up
+        if (MATCH && pf) break;
         const uint32_t ta = W.tf[a][sl], pa = W.pidx[a][sl];
 #pragma unroll
         for (int u = 0; u < int(kVarRows); ++u) {
@@ -401,9 +406,16 @@ __device__ __forceinline__ void vphrase_item(const ConjArgs& A, const uint32_t* 
           }
           if (hit == need) ++pf;
           else if (((hit | open) & need) != need) break;   // a part exhausted: no later p matches
+          if (MATCH && pf) break;
         }
       }
-      if (pf) {
+      if constexpr (MATCH) {
+        if (pf) {
+          doc = docs[sl];
+          if (sets32) atomicOr(&sets32[uint64_t(unit) * words32 + (doc >> 5)], 1u << (doc & 31u));
+          ++my_hits;
+        }
+      } else if (pf) {
         doc = docs[sl];
         const uint32_t nv = !seg.pnorm ? norm_value(seg, doc)
                             : (item < ld.nblk ? seg.pnorm[(ld.dir_off + item) * kBlock + sl]
@@ -423,6 +435,11 @@ __device__ __forceinline__ void vphrase_item(const ConjArgs& A, const uint32_t* 
       const uint32_t slot = base + uint32_t(__builtin_popcountll(cm & below));
       if (cand && slot < A.cand_cap) A.cands[uint64_t(unit) * A.cand_cap + slot] = make_key(score, doc);
     }
+  }
+  if constexpr (MATCH) {
+    my_hits = wave::reduce_add(my_hits);
+    if (lane == 0 && my_hits && counts) atomicAdd(&counts[unit], static_cast<unsigned long long>(my_hits));
+    return;
   }
   if (pilot) return;
   my_hits = wave::reduce_add(my_hits);

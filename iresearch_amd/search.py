@@ -787,6 +787,30 @@ class QueryBatch:
                    "irs_hip_batch_unit_mask")
         return out
 
+    def match_words(self) -> int:
+        """The fewest 64-bit words a match-set row may have: a bit for every doc id of the batch's
+        largest segment."""
+        return max(int(sr.num_docs) for sr in self.segs) // 64 + 1
+
+    def match_sets(self, n_words=None, sets=True):
+        """Unscored execution (irs_hip_batch_match_sets): (sets u64[units][n_words] or None,
+        counts u64[units]) — every doc each unit (segment * n_queries + query) matches as a
+        bit_union-style bitset (bit = doc id), and how many.  sets=False: the counts alone."""
+        n_words = self.match_words() if n_words is None else int(n_words)
+        out = np.empty((self.nq, n_words), np.uint64) if sets else None
+        counts = np.empty(self.nq, np.uint64)
+        _lib.check(self.L, self.L.irs_hip_batch_match_sets(
+            self.handle, out.ctypes.data if sets else None, n_words, counts.ctypes.data),
+            "irs_hip_batch_match_sets")
+        return out, counts
+
+    def match_sets_to_device(self, d_sets, n_words: int, d_counts, stream=None):
+        """The same into device memory (irs_hip_batch_match_sets_to_device), queued on `stream`:
+        d_sets u64[units][n_words], d_counts u64[units]; either may be None."""
+        _lib.check(self.L, self.L.irs_hip_batch_match_sets_to_device(
+            self.handle, d_sets, int(n_words), d_counts, stream), "irs_hip_batch_match_sets_to_device")
+        return self
+
     def touched(self):
         """(`.doc` + norm bytes decoded, positions read) by the last run (And / by_phrase)."""
         a, p = C.c_uint64(), C.c_uint64()

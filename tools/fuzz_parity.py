@@ -54,6 +54,7 @@ def excl_round(sr, seg, filters, scorer, k, st, rng, max_rank):
         ms = copy.copy(seg)
         ms.doc_mask = np.unique(np.concatenate(parts)).astype(np.uint32)
         parity.check_single_segment(ms, [incl], scorer, k, h[q:q + 1], c[q:q + 1], t[q:q + 1])
+    match_round(b, seg, [x[1] for x in trip], t, [x[2] for x in trip])
     b.close()
 
 
@@ -85,6 +86,7 @@ def grouped_round(sr, seg, scorer, k, st, rng, max_rank, term, merge, multi, L):
     for wand in (False, True):
         b = sr.batch(prep, k).set_wand(wand)
         runs.append(tuple(x.copy() for x in b.run().results()))
+        match_round(b, seg, incl, runs[-1][2], excl)
         b.close()
     (h, c, t), (wh, wc, wt) = runs
     assert np.array_equal(h, wh) and np.array_equal(c, wc) and np.array_equal(t, wt), "grouped: wand"
@@ -101,9 +103,27 @@ def grouped_round(sr, seg, scorer, k, st, rng, max_rank, term, merge, multi, L):
         for i, x in enumerate(segs):
             for q, f in enumerate(incl):
                 tn.check(x, f, scorer, k, mh[i, q], mc[i, q], mt[i, q], segs, excluded=excl[q])
+        match_round(mb, segs, incl, mt, excl)
         mb.close()
         readers[1].close()
     return len(filters)
+
+
+def match_round(b, seg, filters, totals, excl=None):
+    """Unscored execution of the same batch (irs_hip_batch_match_sets): every unit's set bit for bit
+    against the oracle (tests/test_match_sets.py want_set), the counts against the scored totals.
+    filters: the included filters; excl[q]: the query's excluded terms; seg: the batch's segment, or
+    the list of them (units segment by segment)."""
+    import test_match_sets as tm
+    segs = seg if isinstance(seg, (list, tuple)) else [seg]
+    sets, counts = b.match_sets()
+    assert np.array_equal(counts, np.asarray(totals).reshape(-1)), "match sets: counts vs total hits"
+    for i, x in enumerate(segs):
+        for q, f in enumerate(filters):
+            u = i * len(filters) + q
+            want = tm.want_set(x, f, excl[q] if excl else [], segs)
+            assert np.array_equal(tm.bits_of(sets[u], x.num_docs), want), ("match sets", i, q, f)
+            assert int(counts[u]) == int(want.sum()), ("match sets: count", i, q, f)
 
 
 def main():
@@ -165,6 +185,7 @@ def main():
             b = sr.batch(prep, k)
             hits, counts, totals = (x.copy() for x in b.run().results())
             parity.check_phrase_segment(seg, filters, scorer, k, hits, counts, totals)
+            match_round(b, seg, filters, totals)
             # variadic phrases (IRS_HIP_PHRASE_ALT): 2-4 parts of 1-4 members near each other's
             # frequency, against the restatement of tests/test_variadic_phrase.py
             import test_variadic_phrase as tv
@@ -176,6 +197,7 @@ def main():
             gone = () if getattr(seg, "doc_mask", None) is None else seg.doc_mask
             for q, f in enumerate(vf):
                 tv.check(seg, pos, f, vprep[q], k, vh[q], vc[q], vt[q], gone)
+            match_round(vb, seg, vf, vt)
             vb.close()
             queries += len(vf)
         else:
@@ -199,6 +221,7 @@ def main():
             b = sr.batch(prep, k)
             hits, counts, totals = (x.copy() for x in b.run().results())
             parity.check_single_segment(seg, filters, scorer, k, hits, counts, totals)
+            match_round(b, seg, filters, totals)
             if rounds % 3 == 1:   # irs::Not: some queries lose the docs of 1-2 excluded terms
                 excl_round(sr, seg, filters, scorer, k, st, rng, max_rank)
             # And of Or groups (k_conj_any), every round; over two segments every third
@@ -214,6 +237,7 @@ def main():
             ih, ic, it = (x.copy() for x in ib.run().results())
             parity.check_single_segment(seg, filters, scorer, k, ih, ic, it)
             assert np.array_equal(ic, counts) and np.array_equal(it, totals), "paths: counts"
+            match_round(ib, seg, filters, it)
             ib.close()
             # joined streams wherever a unit is eligible (whatever the cost rules would deal) —
             # against the oracle, counts as before
@@ -226,6 +250,8 @@ def main():
             ub = sr.batch(prep, k).set_path(_lib.PATH_JOINED).set_paired_tiles(0)
             uh, uc, ut = ub.run().results()
             assert np.array_equal(uc, jc) and np.array_equal(ut, jt) and np.array_equal(uh, jh), "paired tiles"
+            match_round(jb, seg, filters, jt)
+            match_round(ub, seg, filters, ut)
             ub.close()
             jb.close()
             # block-max pruning (on the work-item / block-driven kernels): the same top-k, bit for bit
@@ -235,6 +261,7 @@ def main():
             for q in range(len(filters)):
                 assert np.array_equal(ih[q, :ic[q]], wh[q, :ic[q]]), ("wand: top-k", q)
             assert (wt <= totals).all()
+            match_round(wb, seg, filters, totals)   # (pruning changes what a run counts, not the sets)
             wb.close()
             # every third round: the same filters over several segments in ONE batch
             # (irs_hip_batch_create_multi; statistics over all of them) — per segment the oracle's
@@ -250,6 +277,7 @@ def main():
                 mh, mc, mt = (x.copy() for x in mb.run().results())
                 for i, x in enumerate(msegs):
                     parity.check_single_segment(x, filters, scorer, k, mh[i], mc[i], mt[i], msegs)
+                match_round(mb, msegs, filters, mt)
                 mb.close()
                 # one threshold per query for all segments: the merged top k must not change
                 sb = search.QueryBatch(readers, mprep, k).set_shared_threshold(True)
@@ -258,6 +286,7 @@ def main():
                 plain = search.merge_topk_host([(mh[i], mc[i]) for i in range(len(msegs))], k)
                 shared = search.merge_topk_host([(sh[i], sc[i]) for i in range(len(msegs))], k)
                 assert plain == shared, "shared threshold: merged top-k"
+                match_round(sb, msegs, filters, stot)
                 sb.close()
                 for r in readers[1:]:
                     r.close()

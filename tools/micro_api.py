@@ -48,6 +48,17 @@ def main():
         dt = timed(lambda: sr.bit_union(terms, words))
         print("bit_union terms [%d, %d): %10d postings  %.2f ms  %.2f G postings/s" %
               (lo, hi, n, dt * 1e3, n / dt / 1e9), flush=True)
+    # the same union as the match set of one unscored Or (irs_hip_batch_match_sets: at most 16 terms)
+    from iresearch_amd.search import BM25, Or, by_term
+    st = search.SegmentStats(seg.docs_with_field, seg.total_term_freq, np.asarray(seg.metas["docs_count"]))
+    for lo, hi in ((15, 31), (0, 16)):
+        n = int(dc[lo:hi].sum())
+        b = sr.batch(search.prepare([Or([by_term(t) for t in range(lo, hi)])], BM25(), [st]), 10)
+        dt = timed(lambda: b.match_sets(words))
+        du = timed(lambda: sr.bit_union(np.arange(lo, hi, dtype=np.uint32), words))
+        print("match_sets Or of terms [%d, %d): %10d postings  %.2f ms  %.2f G postings/s  (bit_union of "
+              "the same terms: %.2f ms)" % (lo, hi, n, dt * 1e3, n / dt / 1e9, du * 1e3), flush=True)
+        b.close()
 
 
 if __name__ == "__main__":

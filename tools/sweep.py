@@ -48,6 +48,11 @@ def main():
                          "plain phrase of the same words.  --op and: every term becomes an Or group of N "
                          "members from the same rank range (IRS_HIP_GROUP_ALT); 1 = the plain And.  "
                          "Times each and exits")
+    ap.add_argument("--unscored", action="store_true",
+                    help="time irs_hip_batch_match_sets_to_device (every unit's full match set as a "
+                         "bitset + its count, and the counts alone) instead of run + results; the scored "
+                         "step of the same batch and, for --op or, irs_hip_bit_union_counts over the "
+                         "same term sets are timed next to it; then exits")
     args = ap.parse_args()
     import torch
 
@@ -140,6 +145,67 @@ def main():
             b.close()
         sys.exit(0)
     prep = search.prepare(filters, scorer, [st])
+    if args.unscored:
+        b = sr.batch(prep, args.k)
+        nq, n_words = len(filters), b.match_words()
+        ds = torch.empty((nq, n_words), dtype=torch.int64, device="cuda")
+        dc = torch.empty((nq,), dtype=torch.int64, device="cuda")
+
+        def timed(fn):
+            fn()
+            torch.cuda.synchronize()
+            out = []
+            for _ in range(max(args.steps, 3)):
+                t0 = time.perf_counter()
+                fn()
+                torch.cuda.synchronize()
+                out.append((time.perf_counter() - t0) * 1e3)
+            return float(np.median(out)), float(np.min(out))
+        alg, post = b.work()
+        # the bytes the match kernels decode: the DOC part of every full block of every entry (one
+        # header byte + 16 bytes per bit of its widest delta, 2 bytes when all deltas are equal —
+        # worked out from the decoded lists), 4 bytes per decoded tail doc; no frequency payload, no
+        # norm.  (Phrases: what the conjunction of their terms would read in full — an upper bound,
+        # the phrase kernels skip blocks without a lead doc.)
+        doc_part = {}
+
+        def doc_bytes(t):
+            if t not in doc_part:
+                d, _ = sr.decode_term(t, want_freq=False)
+                d = d.astype(np.int64)
+                nb = d.size // 128
+                delta = np.diff(np.concatenate([[1], d[:nb * 128]])).reshape(nb, 128) if nb else np.zeros((0, 128), np.int64)
+                if nb:   # (a block's first delta is relative to the last doc of the block before it)
+                    delta[0, 0] = d[0] - 1
+                bits = np.where(delta.max(axis=1) > 0, np.floor(np.log2(np.maximum(delta.max(axis=1), 1))) + 1, 0)
+                same = (delta.max(axis=1) == delta.min(axis=1))
+                doc_part[t] = int(np.where(same, 2, 1 + 16 * bits).sum()) + 4 * (d.size - nb * 128)
+            return doc_part[t]
+        terms_of = [sorted({int(r) - 1 for r in row}) if args.op == "or" else [int(r) - 1 for r in row]
+                    for row in ranks]
+        dbytes = sum(doc_bytes(t) for row in terms_of for t in row)
+        both = timed(lambda: b.match_sets_to_device(ds.data_ptr(), n_words, dc.data_ptr()))
+        only = timed(lambda: b.match_sets_to_device(None, n_words, dc.data_ptr()))
+        counts = dc.cpu().numpy().view(np.uint64)
+        scored = timed(lambda: b.run().results())
+        _, _, totals = b.results()
+        print("unscored %s x %d terms, %d queries, %d docs: sets + counts %.2f ms (min %.2f)  counts only "
+              "%.2f ms (min %.2f)  = %.1f / %.1f GB/s over the %.1f MB of doc-block bytes of the entries (A(q) "
+              "with frequency blocks and norms: %.1f MB)  %.1f MB of sets  counts == scored totals: %s" % (
+                  args.op, args.terms, nq, args.docs, *both, *only, dbytes / both[0] / 1e6,
+                  dbytes / only[0] / 1e6, dbytes / 1e6, alg / 1e6, nq * n_words * 8 / 1e6,
+                  bool(np.array_equal(counts, totals))), flush=True)
+        print("   scored step of the same batch (run + results, k = %d), for context: %.2f ms (min %.2f)  "
+              "hits/query mean %.0f" % (args.k, *scored, float(np.mean(totals))), flush=True)
+        if args.op == "or" and not args.exclude:
+            sets = [np.unique(np.asarray([int(r) - 1 for r in row], np.uint32)) for row in ranks]
+            base = timed(lambda: sr.bit_union_counts(sets))
+            same = bool(np.array_equal(np.asarray(sr.bit_union_counts(sets), np.uint64), counts))
+            print("   irs_hip_bit_union_counts over the same term sets: %.2f ms (min %.2f)  same counts: %s  "
+                  "match sets / bit union: %.2fx (counts only %.2fx)" % (
+                      *base, same, both[0] / base[0], only[0] / base[0]), flush=True)
+        b.close()
+        sys.exit(0)
     ref = None
     for cfg in args.configs.split(","):
         tile, stride = (int(x) for x in cfg.split(":"))

@@ -496,47 +496,25 @@ __device__ __forceinline__ void join_load(uint64_t base, uint32_t count, unsigne
   }
 }
 
-// `count` consecutive entries from address `base` (wave-uniform), 256 per step.
-template<int FORM, bool COUNT, bool HALF = false>
+// `count` consecutive entries from address `base` (wave-uniform), 256 per step.  (The 32-bit
+// kernels; paired tiles stream their shares through join_finish_pairs.)
+template<int FORM, bool COUNT>
 __device__ __forceinline__ void join_run(const unsigned char* lds, uint64_t base, uint32_t count,
-                                         float cs, uint32_t tabofs, unsigned lane, uint32_t sh = 0u) {
+                                         float cs, uint32_t tabofs, unsigned lane) {
   const uint32_t off = lane * 4u;
-  if (HALF) {
-    // paired tiles: a share is several groups long — group g + 1 is requested before group g is
-    // accumulated (the wait for g leaves g + 1 in flight)
-    if (count >= 256u) {
-      uint32_t cur[4];
+  while (count >= 256u) {
+    uint32_t e[4];
 #pragma unroll
-      for (int k = 0; k < 4; ++k) cur[k] = wave::gload_u32(base, off + 256u * uint32_t(k));
-      base += 1024u;
-      count -= 256u;
-      while (count >= 256u) {
-        uint32_t nxt[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) nxt[k] = wave::gload_u32(base, off + 256u * uint32_t(k));
-        join_post<FORM, 4, COUNT, HALF>(lds, cur, cs, tabofs, sh);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) cur[k] = nxt[k];
-        base += 1024u;
-        count -= 256u;
-      }
-      join_post<FORM, 4, COUNT, HALF>(lds, cur, cs, tabofs, sh);
-    }
-  } else {
-    while (count >= 256u) {
-      uint32_t e[4];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) e[k] = wave::gload_u32(base, off + 256u * uint32_t(k));
-      wave::keep_all(e);
-      join_post<FORM, 4, COUNT, HALF>(lds, e, cs, tabofs, sh);
-      base += 1024u;
-      count -= 256u;
-    }
+    for (int k = 0; k < 4; ++k) e[k] = wave::gload_u32(base, off + 256u * uint32_t(k));
+    wave::keep_all(e);
+    join_post<FORM, 4, COUNT>(lds, e, cs, tabofs);
+    base += 1024u;
+    count -= 256u;
   }
   if (count) {
     uint32_t e[4];
     join_load(base, count, lane, e);
-    join_post_n<FORM, COUNT, HALF>(lds, e, (count + 63u) >> 6, cs, tabofs, sh);
+    join_post_n<FORM, COUNT>(lds, e, (count + 63u) >> 6, cs, tabofs);
   }
 }
 
@@ -612,19 +590,9 @@ __device__ __forceinline__ void join_begin(JoinRun& r, const JoinLane& T, uint32
 template<int M>
 __device__ __forceinline__ void join_some(const unsigned char* lds, uint64_t base, uint32_t cnt,
                                           float cs, uint32_t mode, unsigned lane) {
+  static_assert((M & kJHalf) == 0, "paired tiles: join_finish_pairs");
   constexpr bool COUNT = (M & kJCount) != 0;
-  if (M & kJHalf) {
-    const uint32_t sh = join_half_shift(mode);
-    if (M & kJSimple) {
-      join_run<kJTable, false, true>(lds, base, cnt, cs, 0u, lane, sh);
-    } else {
-      const uint32_t tabofs = mode & kJoinTabMask;
-      const int form = join_form(mode);
-      if (form == kJTable) join_run<kJTable, false, true>(lds, base, cnt, cs, tabofs, lane, sh);
-      else if (form == kJRcp) join_run<kJRcp, false, true>(lds, base, cnt, cs, tabofs, lane, sh);
-      else join_run<kJSqrt, false, true>(lds, base, cnt, cs, tabofs, lane, sh);
-    }
-  } else if (M & kJSimple) {
+  if (M & kJSimple) {
     join_run<kJTable, COUNT>(lds, base, cnt, cs, 0u, lane);
   } else {
     const uint32_t tabofs = mode & kJoinTabMask;
@@ -645,7 +613,8 @@ __device__ __forceinline__ void join_finish(const unsigned char* lds, JoinRun& r
     if (kAblWait) wave::keep_all(r.e);
     return;
   }
-  constexpr bool SIMPLE = (M & kJSimple) != 0 && (M & kJHalf) == 0;   // (no mode word needed)
+  static_assert((M & kJHalf) == 0, "paired tiles: join_finish_pairs");
+  constexpr bool SIMPLE = (M & kJSimple) != 0;   // (no mode word needed)
   const uint32_t mode0 = SIMPLE ? 0u : wave::uniform(r.mode);
   const float cs0 = wave::uniform_f(r.cs);
   {
@@ -662,11 +631,144 @@ __device__ __forceinline__ void join_finish(const unsigned char* lds, JoinRun& r
     const uint32_t j = uint32_t(__builtin_ctzll(mask));
     mask &= mask - 1ull;
     const uint64_t base = (uint64_t(wave::read_lane(r.a_hi, j)) << 32) | wave::read_lane(r.a_lo, j);
-    const uint32_t mode = SIMPLE ? 0u
-                          : (((M & kJSimple) && (M & kJHalf)) ? (j >= kMaxTerms ? uint32_t(kJoinHiHalf) : 0u)
-                                                              : wave::read_lane(T.mode, j));
+    const uint32_t mode = SIMPLE ? 0u : wave::read_lane(T.mode, j);
     join_some<M>(lds, base, wave::read_lane(r.cnt, j), wave::read_lane_f(T.cs, j), mode, lane);
   }
+}
+
+// PAIRED TILES: a share is ONE sequence of groups.  A group is up to kJoinPre entries of one
+// (term, half) piece; the sequence is what begin() requested, then the rest of that piece, then
+// the pieces still in JoinRun::mask, in order.  A share is three to five groups long and every
+// one of them is a round trip to memory that nothing else of the wavefront covers (all the
+// wavefronts of a workgroup stand behind the same barrier), so group n + 1 is REQUESTED BEFORE
+// THE WAIT for group n — whether n is the prefetched group, the last full group in front of a
+// tail, or the last group of a piece, whose successor opens the next piece.  What makes that
+// possible: every group is exactly four loads per lane (offsets clamped to the group's last entry
+// as in join_begin: re-reading a line costs no traffic; lanes past the count take their dummy
+// once the data is there), so the number of loads between a request and its use is a
+// compile-time constant and the wait is s_waitcnt vmcnt(4), not vmcnt(0); and the groups
+// alternate between two NAMED register sets (the loop is unrolled by two), so no entry is copied
+// from one set to the other — a copy is a use, and would wait for the younger group.
+struct JoinGroup {   // (wave-uniform) the descriptor of a group
+  uint64_t base;     // address of its first entry
+  uint32_t n;        // entries: 1 .. kJoinPre
+  float cs;          // of its piece
+  uint32_t mode;     //   half, and table slot | form where the terms have forms of their own
+};
+struct JoinSeq {     // (wave-uniform) what is left of a share behind the groups handed out so far
+  uint64_t rest;     // the current piece: address,
+  uint32_t left;     //   entries
+  uint64_t mask;     // pieces (lanes of JoinRun::a_lo / a_hi / cnt) still to open
+  float cs;          // of the current piece
+  uint32_t mode;
+};
+// the next group of the sequence; false: the share is through — the descriptor is then one entry
+// at `safe` (join_begin's empty share), for a request that nobody uses
+template<int M>
+__device__ __forceinline__ bool join_next(JoinSeq& s, const JoinRun& r, const JoinLane& T,
+                                          uint64_t safe, JoinGroup& g) {
+  bool more = true;
+  if (!s.left) {
+    if (s.mask) {
+      const uint32_t j = uint32_t(__builtin_ctzll(s.mask));
+      s.mask &= s.mask - 1ull;
+      s.rest = (uint64_t(wave::read_lane(r.a_hi, j)) << 32) | wave::read_lane(r.a_lo, j);
+      s.left = wave::read_lane(r.cnt, j);
+      s.cs = wave::read_lane_f(T.cs, j);
+      // (one table: the mode word is just the half — the piece's index says which)
+      s.mode = (M & kJSimple) ? (j >= kMaxTerms ? uint32_t(kJoinHiHalf) : 0u) : wave::read_lane(T.mode, j);
+    } else {
+      more = false;
+    }
+  }
+  const uint32_t n = s.left < kJoinPre ? s.left : kJoinPre;
+  g.base = more ? s.rest : safe;
+  g.n = more ? n : 1u;
+  g.cs = s.cs;
+  g.mode = s.mode;
+  s.rest += 4ull * n;
+  s.left -= n;
+  return more;
+}
+// four loads, always; RAW like JoinRun::e: lanes past `n` hold the group's last entry
+__device__ __forceinline__ void join_request(const JoinGroup& g, unsigned lane, uint32_t (&x)[4]) {
+  const uint32_t last = (g.n - 1u) * 4u;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const uint32_t off = lane * 4u + 256u * uint32_t(k);
+    x[k] = wave::gload_u32(g.base, off < last ? off : last);
+  }
+}
+template<int FORM>
+__device__ __forceinline__ void join_group_form(const unsigned char* lds, const uint32_t (&x)[4],
+                                                const JoinGroup& g, uint32_t tabofs, uint32_t sh,
+                                                unsigned lane) {
+  if (g.n == kJoinPre) {   // (wave-uniform) a full group: every lane's four entries count
+    join_post<FORM, 4, false, true>(lds, x, g.cs, tabofs, sh);
+    return;
+  }
+  const uint32_t dummy = join_dummy(lane);
+  uint32_t e[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) e[k] = lane + 64u * uint32_t(k) < g.n ? x[k] : dummy;
+  join_post_n<FORM, false, true>(lds, e, (g.n + 63u) >> 6, g.cs, tabofs, sh);
+}
+template<int M>
+__device__ __forceinline__ void join_group_post(const unsigned char* lds, const uint32_t (&x)[4],
+                                                const JoinGroup& g, unsigned lane) {
+  const uint32_t sh = join_half_shift(g.mode);
+  if (M & kJSimple) {
+    join_group_form<kJTable>(lds, x, g, 0u, sh, lane);
+  } else {
+    const uint32_t tabofs = g.mode & kJoinTabMask;
+    const int form = join_form(g.mode);   // (wave-uniform)
+    if (form == kJTable) join_group_form<kJTable>(lds, x, g, tabofs, sh, lane);
+    else if (form == kJRcp) join_group_form<kJRcp>(lds, x, g, tabofs, sh, lane);
+    else join_group_form<kJSqrt>(lds, x, g, tabofs, sh, lane);
+  }
+}
+
+template<int M>
+__device__ __forceinline__ void join_finish_pairs(const unsigned char* lds, JoinRun& r,
+                                                  const JoinLane& T, uint64_t safe, unsigned lane) {
+  static_assert((M & kJHalf) != 0 && (M & kJCount) == 0, "join_finish_pairs: paired tiles");
+  // (the run's scalars crossed a barrier and a loop back edge inside a struct: join_finish)
+  const uint32_t pre = wave::uniform(r.pre);
+  if (!pre) {   // (nothing requested: nothing at all)
+    if (kAblWait) wave::keep_all(r.e);
+    return;
+  }
+  JoinSeq s;
+  s.rest = wave::uniform64(r.rest);
+  s.left = wave::uniform(r.left);
+  s.mask = wave::uniform64(r.mask);
+  s.cs = wave::uniform_f(r.cs);
+  s.mode = wave::uniform(r.mode);
+  // Set A starts as the prefetched group; from then on the sets alternate.  Each half of the
+  // loop body: describe the next group, request it into the other set, only then accumulate
+  // (= wait for) this one.  A share that is through still gets its four loads per half — of one
+  // entry at `safe`, never used: with a request that depends on a branch, the wait in front of
+  // the accumulation could count on no younger load at all.  One way in, one way out and plain
+  // if / else inside: with exits from the middle, the control-flow lowering adds edges (never
+  // taken) along which a set would be requested twice in a row, and the wait-count bookkeeping
+  // answers those with vmcnt(0) in front of every request.
+  JoinGroup ga, gb;
+  ga.base = 0;
+  ga.n = pre;
+  ga.cs = s.cs;
+  ga.mode = s.mode;
+  uint32_t a[4], b[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) a[k] = r.e[k];
+  bool more;
+  do {
+    const bool second = join_next<M>(s, r, T, safe, gb);
+    join_request(gb, lane, b);
+    join_group_post<M>(lds, a, ga, lane);
+    more = join_next<M>(s, r, T, safe, ga);   // (a share that is through stays through)
+    join_request(ga, lane, a);
+    if (second) join_group_post<M>(lds, b, gb, lane);
+  } while (more);
 }
 
 // Chunk / pilot prologue, whole workgroup: the query's term scorers and stream records to
@@ -1178,6 +1280,12 @@ __device__ __forceinline__ void join_pairs(unsigned char* smem, const JoinTileCt
       } else {
         const uint32_t g = atomicAdd(&ctx.args->cand_count[ctx.q], 1u);
         if (g < ctx.cap) ctx.args->cands[uint64_t(ctx.q) * ctx.cap + g] = key;
+        // (These two go through pointers read from memory: FLAT instructions.  While one of them
+        // may still be pending, the compiler's wait-count bookkeeping turns every later wait for
+        // a load into vmcnt(0) — in join_finish_pairs too, which every path out of here reaches.
+        // A load that is used on the spot ends that here, where it costs nothing.)
+        uint32_t drained = wave::gload_u32(safe, 0u);
+        wave::keep(drained);
       }
     };
     auto four = [&](uint32_t i, const uint32_t (&v)[4]) {
@@ -1200,10 +1308,10 @@ __device__ __forceinline__ void join_pairs(unsigned char* smem, const JoinTileCt
     __syncthreads();   // B2: accumulators are clear again
   };
   for (uint32_t p = 0; p < npair; p += 2u) {
-    join_finish<M>(smem, r0, T, lane);
+    join_finish_pairs<M>(smem, r0, T, safe, lane);
     begin(p + 2u, r0);
     end_pair(p);
-    join_finish<M>(smem, r1, T, lane);
+    join_finish_pairs<M>(smem, r1, T, safe, lane);
     begin(p + 3u, r1);
     if (p + 1u < npair) end_pair(p + 1u);
   }

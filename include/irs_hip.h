@@ -216,7 +216,9 @@ typedef enum irs_hip_op {
                              frequency.  An absent term empties the query in that segment.
                              A batch holds phrase queries only, or none.
                              Variadic phrases (a part standing for a set of terms,
-                             VariadicPhraseQuery): IRS_HIP_PHRASE_ALT below.           */
+                             VariadicPhraseQuery): IRS_HIP_PHRASE_ALT below; a phrase
+                             plus required terms (an And of a by_phrase and by_terms):
+                             IRS_HIP_PHRASE_REQUIRED below.                            */
 } irs_hip_op;
 
 /* Which ScoreFunction Scorer::prepare_scorer would have built. */
@@ -260,6 +262,34 @@ typedef enum irs_hip_scorer_kind {
  * scorer at tf = freq(d), as for plain phrases.  A compatible addition to ABI 12: without the flag
  * an entry means what it always did, and a kind with the flag was IRS_HIP_EINVAL before. */
 #define IRS_HIP_PHRASE_ALT 0x200
+
+/* OR-ed into the `kind` of an included IRS_HIP_OP_PHRASE entry: a REQUIRED TERM — a by_term child
+ * of the irs::And that also holds this phrase, `+"new york" +hotel` (And::prepare ->
+ * make_conjunction over {PhraseIterator, term iterators}: boolean_filter.cpp:150-210,
+ * boolean_query.cpp:60-145, conjunction.hpp:436-490; every child is prepared on its own and the
+ * And's merger sums the children's scores).  Entry order in [first_term, first_term + n_terms):
+ * the phrase's entries (at least 2), then 1 or more entries with this flag, then 0 to
+ * IRS_HIP_MAX_EXCLUDED IRS_HIP_EXCLUDE entries.  An entry without the flag behind one with it, or
+ * fewer than 2 phrase entries in front of the first flagged one, is IRS_HIP_EINVAL; so is the flag
+ * on an OR / AND / MINMATCH entry.  A flagged entry carries its OWN scorer values (kind, c0,
+ * norm_const, norm_length — the by_term's statistics and boost x the And's boost), validated like
+ * any by_term entry; its phrase_offset is ignored; it may name a term that is also a phrase word.
+ * Phrase entries + flagged entries <= IRS_HIP_MAX_PHRASE_TERMS (more: IRS_HIP_EUNSUPPORTED); a
+ * query with both IRS_HIP_PHRASE_ALT and flagged entries, and a batch that holds variadic phrases
+ * next to queries with flagged entries, are IRS_HIP_EUNSUPPORTED; merge stays IRS_HIP_MERGE_SUM.
+ * Per segment:
+ *   d matches iff the phrase frequency pf(d) > 0 and every required term holds d (minus deleted
+ *   docs and IRS_HIP_EXCLUDE terms);
+ *   score(d) = s_phrase(tf = pf(d), norm(d)) + sum over the required terms of s_j(tf_j(d), norm(d)),
+ *   in float32, the children in cost order as Conjunction sorts them (conjunction.hpp:450-453): the
+ *   phrase costs the smallest docs_count of its words (the front of its approx_ conjunction,
+ *   phrase_iterator.hpp:545-560), a term its docs_count; ties in entry order.
+ * An absent phrase word or required term (IRS_HIP_NO_TERM or no docs) empties the query in that
+ * segment.  total_hits, the top k and every batch control behave as for any phrase batch; a batch
+ * with such a query runs all its phrases on k_phrase_and, plain phrases giving bit for bit what
+ * they give in a batch of their own.  A compatible addition to ABI 12: without the flag an entry
+ * means what it always did, and a kind with the flag was IRS_HIP_EINVAL before. */
+#define IRS_HIP_PHRASE_REQUIRED 0x400
 
 /* The same bit OR-ed into the `kind` of an included IRS_HIP_OP_AND entry: one more member of the
  * group opened by the nearest preceding included entry without the flag — an And whose children

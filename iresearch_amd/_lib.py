@@ -21,6 +21,7 @@ SCORE_BM25, SCORE_BM15, SCORE_BM1, SCORE_TFIDF, SCORE_TFIDF_NORM = 0, 1, 2, 3, 4
 EXCLUDE = 0x100   # irs_hip_term_scorer.kind of an excluded term (irs::Not)
 PHRASE_ALT = 0x200   # OR-ed into a phrase entry's kind: one more member of the part before it
 GROUP_ALT = PHRASE_ALT   # ... into an And entry's kind: one more member of the group (Or) before it
+PHRASE_REQUIRED = 0x400   # ... into a phrase entry's kind: a by_term child of the And that holds the phrase
 NO_TERM = 0xFFFFFFFF
 PATH_AUTO, PATH_ITEMS, PATH_JOINED = 0, 1, 2
 WAND_NONE, WAND_DIV_NORM, WAND_MAX_FREQ, WAND_MIN_NORM = 0, 1, 2, 3   # Scorer::WandType

@@ -137,17 +137,6 @@ struct Or {
   irs_hip_merge merge_type = IRS_HIP_MERGE_SUM;  // boolean_filter::merge_type()
   float boost = 1.f;   // multiplies into its terms' boosts (boolean_filter.cpp:153-154, 204)
 };
-// irs::And of by_term children (`subs`) and Or-of-by_term children (`groups`: an And of Ors,
-// IRS_HIP_GROUP_ALT).  Children in that order: subs, then groups.  A group of one term is that term
-// (the single node case, boolean_filter.cpp:152-155); a group merges with SUM and min_match_count
-// <= 1 (anything else: not_supported).  Each term's boost is multiplied by its Or's and the And's
-// boosts, from the top down.  At most IRS_HIP_MAX_TERMS terms in all.
-struct And {
-  std::vector<by_term> subs;
-  irs_hip_merge merge_type = IRS_HIP_MERGE_SUM;
-  std::vector<Or> groups;
-  float boost = 1.f;
-};
 struct by_phrase {
   std::vector<uint32_t> terms;
   std::vector<uint32_t> offsets;  // relative to the first term; empty = consecutive words
@@ -175,6 +164,23 @@ struct by_phrase {
     offsets.push_back(next + offs);
     return *this;
   }
+};
+// irs::And of by_term children (`subs`) and Or-of-by_term children (`groups`: an And of Ors,
+// IRS_HIP_GROUP_ALT).  Children in that order: subs, then groups.  A group of one term is that term
+// (the single node case, boolean_filter.cpp:152-155); a group merges with SUM and min_match_count
+// <= 1 (anything else: not_supported).  Each term's boost is multiplied by its Or's and the And's
+// boosts, from the top down.  At most IRS_HIP_MAX_TERMS terms in all.
+// `phrases`: ONE by_phrase of plain terms as a child next to the by_terms of `subs` — a phrase plus
+// required terms, `+"new york" +hotel` (IRS_HIP_PHRASE_REQUIRED: the phrase's entries with its one
+// blob, then every by_term with its own statistics; the And's boost multiplies into each child's).
+// With a phrase: at least one term in `subs`, no `groups`, merge SUM, at most
+// IRS_HIP_MAX_PHRASE_TERMS words and terms in all (anything else: not_supported).
+struct And {
+  std::vector<by_term> subs;
+  irs_hip_merge merge_type = IRS_HIP_MERGE_SUM;
+  std::vector<Or> groups;
+  float boost = 1.f;
+  std::vector<by_phrase> phrases;
 };
 // irs::And of ONE included filter and Not(by_term) children (boolean_filter.cpp:92-135,
 // boolean_query.cpp:121-141): the included filter's matches minus every doc of an excluded term —
@@ -305,6 +311,46 @@ std::vector<PreparedQuery> prepare(const std::vector<filter>& filters, const Sco
       q.min_match = o->min_match_count > 1 ? o->min_match_count : 0;
       q.merge = o->merge_type;
       for (const auto& t : o->subs) q.terms.push_back(one(by_term{t.term, o->boost * t.boost}));
+    } else if (std::get_if<And>(&f) && !std::get_if<And>(&f)->phrases.empty()) {
+      // a phrase plus required terms (And::prepare -> make_conjunction over the children,
+      // boolean_filter.cpp:150-210): the phrase's words with its ONE blob, then every by_term with
+      // its own statistics, flagged IRS_HIP_PHRASE_REQUIRED
+      const And& a = *std::get_if<And>(&f);
+      if (a.phrases.size() > 1)
+        throw not_supported(IRS_HIP_EUNSUPPORTED, "And: two phrases (ONE by_phrase plus by_terms is taken)");
+      const by_phrase& p = a.phrases[0];
+      if (!p.members.empty())
+        throw not_supported(IRS_HIP_EUNSUPPORTED, "And: a variadic by_phrase with required terms "
+                            "(ONE by_phrase of plain terms plus by_terms is taken)");
+      if (!a.groups.empty())
+        throw not_supported(IRS_HIP_EUNSUPPORTED, "And: an Or group next to a by_phrase "
+                            "(ONE by_phrase plus by_terms is taken)");
+      if (a.merge_type != IRS_HIP_MERGE_SUM)
+        throw not_supported(IRS_HIP_EUNSUPPORTED, "And: a by_phrase child merges with SUM on the GPU path");
+      if (a.subs.empty())
+        throw illegal_argument(IRS_HIP_EINVAL, "And: a by_phrase alone is that phrase (send the by_phrase)");
+      if (p.terms.size() < 2)
+        throw illegal_argument(IRS_HIP_EINVAL, "And: a by_phrase of one term is a by_term");
+      if (!p.offsets.empty() && (p.offsets.size() != p.terms.size() || p.offsets[0] != 0))
+        throw illegal_argument(IRS_HIP_EINVAL, "by_phrase: offsets are relative to the first term");
+      if (p.terms.size() + a.subs.size() > IRS_HIP_MAX_PHRASE_TERMS)
+        throw not_supported(IRS_HIP_EUNSUPPORTED, "And: more than IRS_HIP_MAX_PHRASE_TERMS phrase words "
+                            "and required terms");
+      q.op = IRS_HIP_OP_PHRASE;
+      TermStats st;  // ONE blob for the phrase, from its own words (FixedPrepareCollect)
+      for (uint32_t t : p.terms) scorer.collect(st, dwf, docs_with_term(t), ttf);
+      irs_hip_term_scorer e = scorer.term_scorer(st, a.boost * p.boost);
+      for (size_t i = 0; i < p.terms.size(); ++i) {
+        e.term = p.terms[i];
+        e.phrase_offset = p.offsets.empty() ? uint32_t(i) : p.offsets[i];
+        q.terms.push_back(e);
+      }
+      for (const auto& t : a.subs) {
+        irs_hip_term_scorer r = one(by_term{t.term, a.boost * t.boost});
+        r.kind |= IRS_HIP_PHRASE_REQUIRED;
+        r.phrase_offset = 0;
+        q.terms.push_back(r);
+      }
     } else if (const auto* a = std::get_if<And>(&f)) {
       q.op = IRS_HIP_OP_AND;
       q.merge = a->merge_type;

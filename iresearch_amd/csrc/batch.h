@@ -128,6 +128,11 @@ struct BlockWork {
   bool variadic = false;
   std::vector<uint32_t> opens;
   DevBuf d_opens, d_lead_rows;   // [unit] opens; lead part's rows lo | hi << 8
+  // by_phrase with required terms (IRS_HIP_PHRASE_REQUIRED in any unit: every phrase unit of the
+  // batch runs on k_phrase_and): per unit the rows that are phrase words, the required terms' behind
+  bool required = false;
+  std::vector<uint32_t> n_phrase;
+  DevBuf d_n_phrase;
   DevBuf d_pilot;             // the lead items the pilot pass samples, {unit, item} each
   uint32_t n_pilot = 0, pilot_stride = 0;
 };
@@ -138,7 +143,7 @@ struct BlockWork {
 // for variadic phrases; n_wgs: k_conj_any workgroups.  Of BlockWork the grouped path uses units,
 // items, n_items, n_wgs, the lead-item tables (d_units, d_items, d_hist, d_item_base, d_unit_items,
 // d_seek, d_recs, d_item_hits), opens / d_opens / d_lead_rows and the pilot list (d_pilot,
-// n_pilot, pilot_stride); d_lg, d_lead_of, n_phrase_wgs and `variadic` stay unused.
+// n_pilot, pilot_stride); d_lg, d_lead_of, n_phrase_wgs, `variadic` and `required` stay unused.
 struct AnyWork : BlockWork {};
 
 // Units with excluded terms (IRS_HIP_EXCLUDE, excl.h): one doc mask per distinct (segment, present

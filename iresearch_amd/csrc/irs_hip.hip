@@ -455,6 +455,7 @@ static int batch_create_multi_impl(irs_hip_segment* const* segs, uint32_t n_segs
     b->count_precise.assign(nq, 0);
     b->groups.upper.assign(nq, 0.0);
     b->blocks.opens.assign(nq, 0);
+    b->blocks.n_phrase.assign(nq, 0);
     b->any.opens.assign(nq, 0);
     b->qterms.reserve(size_t(n_entries) * n_segs);
     std::vector<int> exps;
@@ -494,6 +495,24 @@ static int batch_create_multi_impl(irs_hip_segment* const* segs, uint32_t n_segs
         rc = IRS_HIP_EINVAL;
         break;
       }
+      // a phrase with required terms (IRS_HIP_PHRASE_REQUIRED): the phrase's words (n_words, at
+      // least 2), then the by_term children of the And that holds it, nothing else behind them
+      uint32_t n_words = n_incl;
+      if (in.op == IRS_HIP_OP_PHRASE) {
+        n_words = 0;
+        while (n_words < n_incl && !(terms[in.first_term + n_words].kind & IRS_HIP_PHRASE_REQUIRED)) ++n_words;
+        for (uint32_t j = n_words; j < n_incl; ++j)
+          if (!(terms[in.first_term + j].kind & IRS_HIP_PHRASE_REQUIRED)) rc = IRS_HIP_EINVAL;
+        if (rc == IRS_HIP_OK && n_words < n_incl) {
+          uint32_t plain = 0;   // (members of a variadic part are no words of their own)
+          for (uint32_t j = 0; j < n_words; ++j)
+            plain += (terms[in.first_term + j].kind & IRS_HIP_PHRASE_ALT) ? 0u : 1u;
+          if (plain < 2) rc = IRS_HIP_EINVAL;
+          else if (alt || n_incl > IRS_HIP_MAX_PHRASE_TERMS) rc = IRS_HIP_EUNSUPPORTED;
+        }
+        if (rc != IRS_HIP_OK) break;
+      }
+      const bool with_req = n_words < n_incl;
       // a grouped conjunction: an And whose entries with IRS_HIP_GROUP_ALT are more members of the
       // group (an Or of by_term) opened by the nearest entry before them without it
       bool grouped = false;
@@ -544,10 +563,13 @@ static int batch_create_multi_impl(irs_hip_segment* const* segs, uint32_t n_segs
       uint32_t n_parts = 0, part_first = 0, opens = 0, found = 0, n_groups = 0;
       bool part_open = false;
       row_group.clear();
+      uint32_t word_rows = 0;   // present rows that are phrase words (the required terms' follow)
       for (uint32_t j = 0; j < n_incl; ++j) {
         const irs_hip_term_scorer& ts = terms[in.first_term + j];
         const bool member = is_phrase && (ts.kind & IRS_HIP_PHRASE_ALT) != 0;
-        const int32_t kind = (is_phrase || grouped) ? (ts.kind & ~IRS_HIP_PHRASE_ALT) : ts.kind;
+        const bool req = is_phrase && j >= n_words;
+        const int32_t kind = is_phrase ? (ts.kind & ~(IRS_HIP_PHRASE_ALT | IRS_HIP_PHRASE_REQUIRED))
+                             : grouped ? (ts.kind & ~IRS_HIP_PHRASE_ALT) : ts.kind;
         if (grouped && !(ts.kind & IRS_HIP_GROUP_ALT)) ++n_groups;
         if (is_phrase && !member) {
           ++n_parts;
@@ -567,7 +589,7 @@ static int batch_create_multi_impl(irs_hip_segment* const* segs, uint32_t n_segs
         qt.norm_const = ts.norm_const;
         qt.norm_length = ts.norm_length;
         qt.cache_id = kMaxCaches;
-        qt.pad0 = is_phrase ? ts.phrase_offset : 0u;
+        qt.pad0 = (is_phrase && !req) ? ts.phrase_offset : 0u;
         if (ts.term != IRS_HIP_NO_TERM && ts.term >= seg->dev.num_terms) rc = IRS_HIP_EINVAL;
         if (!(ts.c0 >= 0.f) || !std::isfinite(ts.c0)) rc = IRS_HIP_EINVAL;
         if (rc != IRS_HIP_OK) break;
@@ -647,6 +669,7 @@ static int batch_create_multi_impl(irs_hip_segment* const* segs, uint32_t n_segs
             qt.kind == kTfidfWide || qt.kind == kBM25Legacy || qt.kind == kTfidfLegacy)
           b->alg_bytes += uint64_t(t.docs_count) * seg->dev.norm_width;
         row.push_back(qt);
+        if (!req) ++word_rows;
       }
       if (rc != IRS_HIP_OK) break;
       b->alg_bytes += 8ull * in.k;
@@ -679,12 +702,22 @@ static int batch_create_multi_impl(irs_hip_segment* const* segs, uint32_t n_segs
         absent = found != (1u << n_parts) - 1u;
         need = absent ? 0xFFu : 1u;
         b->blocks.variadic = b->blocks.variadic || alt;
-        // the phrase's scorer is one stats blob: every entry must carry the same values
-        for (const DevQTerm& qt : row)
+        b->blocks.required = b->blocks.required || with_req;
+        // (k_vphrase takes no required terms, k_phrase_and no variadic parts)
+        if (b->blocks.variadic && b->blocks.required) {
+          rc = IRS_HIP_EUNSUPPORTED;
+          break;
+        }
+        // the phrase's scorer is one stats blob: every word's entry must carry the same values (a
+        // required term carries its own)
+        for (uint32_t r = 0; r < word_rows; ++r) {
+          const DevQTerm& qt = row[r];
           if (qt.kind != row[0].kind || qt.c0 != row[0].c0 ||
               qt.norm_const != row[0].norm_const || qt.norm_length != row[0].norm_length)
             rc = IRS_HIP_EINVAL;
+        }
         if (rc != IRS_HIP_OK) break;
+        b->blocks.n_phrase[q] = word_rows;
       }
       if (need == 0xFFu) row.clear();
       // the unit's masked docs: its segment's deleted ones, and for a unit with present excluded

@@ -8,6 +8,7 @@
 //                   carried from "union of the excluded terms" to the unit's whole filter — and
 //                   writes every output word once
 //   k_phrase_match  by_phrase units: the match-only instantiation of phrase_item (phrase.h) —
+//   k_phrase_and_match ... with required terms (IRS_HIP_PHRASE_REQUIRED: phrase_item's REQ form),
 //   k_vphrase_match ... and of vphrase_item (vphrase.h, variadic phrases): phrase frequency > 0
 //                   sets the doc's bit in the unit's zeroed row
 #pragma once
@@ -229,6 +230,14 @@ __global__ void __launch_bounds__(kPhraseWaves * 64)
 k_phrase_match(ConjArgs A, uint32_t* sets32, uint64_t words32, unsigned long long* counts) {
   __shared__ PhraseWave<MT> s_wave[kPhraseWaves];
   phrase_item<LAYOUT, MT, true>(A, 0u, s_wave, sets32, words32, counts);
+}
+// ... with required terms (k_phrase_and, phrase.h): a doc must also be held by every required row
+template<int LAYOUT, int MT>
+__global__ void __launch_bounds__(kPhraseWaves * 64)
+k_phrase_and_match(ConjArgs A, const uint32_t* n_phrase, uint32_t* sets32, uint64_t words32,
+                   unsigned long long* counts) {
+  __shared__ PhraseWave<MT> s_wave[kPhraseWaves];
+  phrase_item<LAYOUT, MT, true, true>(A, 0u, s_wave, sets32, words32, counts, n_phrase);
 }
 template<int LAYOUT>
 __global__ void __launch_bounds__(kPhraseWaves * 64)

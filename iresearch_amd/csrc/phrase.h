@@ -467,6 +467,8 @@ struct ConjArgs {
 // in the unit's row of `sets32` (zeroed by the caller; matches are sparse: a global atomic) and
 // counts for the unit; the position merge stops at the first match; no threshold, norm, score or
 // candidate.  The scored instantiations compile to what they were without the parameter.
+// REQ (k_phrase_and below): rows [n_phrase[unit], m) of the unit are REQUIRED TERMS — the by_term
+// children of the irs::And that holds the phrase (IRS_HIP_PHRASE_REQUIRED) — see there.
 template<int MT>
 struct PhraseWave {
   uint32_t docs[kBlock];
@@ -481,11 +483,12 @@ struct PhraseWave {
   uint32_t off[MT];
 };
 
-template<int LAYOUT, int MT, bool MATCH = false>
+template<int LAYOUT, int MT, bool MATCH = false, bool REQ = false>
 __device__ __forceinline__ void phrase_item(const ConjArgs& A, uint32_t pilot /*1: histogram the
                                             scores of the sampled lead items, no candidates*/,
                                             PhraseWave<MT>* s_wave, uint32_t* sets32 = nullptr,
-                                            uint64_t words32 = 0, unsigned long long* counts = nullptr) {
+                                            uint64_t words32 = 0, unsigned long long* counts = nullptr,
+                                            const uint32_t* n_phrase = nullptr /*REQ: [unit] phrase rows*/) {
   const uint32_t tid = threadIdx.x;
   const unsigned lane = tid & 63u;
   const uint32_t wv = wave::uniform(tid >> 6);
@@ -502,6 +505,12 @@ __device__ __forceinline__ void phrase_item(const ConjArgs& A, uint32_t pilot /*
   const DevQuery qd = wave::sload<DevQuery>(reinterpret_cast<uint64_t>(A.queries) + uint64_t(unit) * sizeof(DevQuery));
   const uint32_t m = qd.n_terms;
   if (m == 0 || m > uint32_t(MT)) return;
+  // rows [0, mp) are the phrase's words (the lists step 3 merges), rows [mp, m) required terms
+  uint32_t mp = m;
+  if constexpr (REQ) {
+    mp = wave::uniform(n_phrase[unit]);
+    if (mp == 0u || mp > m) return;
+  }
   const DevSegment& seg = A.segs[qd.seg];   // (read field by field)
   const uint64_t tl_at = reinterpret_cast<uint64_t>(A.tails) + uint64_t(unit) * A.jt * sizeof(DevTail);
   auto term_tail = [&](uint32_t i) { return wave::sload<DevTail>(tl_at + i * sizeof(DevTail)); };
@@ -516,7 +525,32 @@ __device__ __forceinline__ void phrase_item(const ConjArgs& A, uint32_t pilot /*
     const DevTail t = A.tails[uint64_t(unit) * A.jt + lane];
     W.pt[lane] = seg.pterms[t.term];
     W.term[lane] = t.term;
-    W.off[lane] = A.qterms[qd.first_term + lane].pad0;  // desired offset in the phrase
+    if (!REQ || lane < mp) W.off[lane] = A.qterms[qd.first_term + lane].pad0;  // desired offset in the phrase
+  }
+  // REQ: the order the And's children are summed in — Conjunction sorts them by cost
+  // (conjunction.hpp:450-453): the phrase costs its rarest word's docs_count (the front of its
+  // approx_ conjunction, phrase_iterator.hpp:545-560), a term its own; ties in entry order.
+  // W.off[mp + r] (no offset lives there) = the r-th cheapest required row, phrase_at = required
+  // rows summed in front of the phrase.
+  uint32_t phrase_at = 0;
+  if constexpr (REQ) {
+    uint32_t cost = 0xFFFFFFFFu;
+    if (lane < m) {
+      const DevTail t = A.tails[uint64_t(unit) * A.jt + lane];
+      cost = t.nblk * kBlock + t.n;
+    }
+    uint32_t pcost = 0xFFFFFFFFu;
+    for (uint32_t j = 0; j < mp; ++j) {
+      const uint32_t cj = wave::read_lane(cost, j);
+      pcost = cj < pcost ? cj : pcost;
+    }
+    uint32_t rank = 0;
+    for (uint32_t j = mp; j < m; ++j) {
+      const uint32_t cj = wave::read_lane(cost, j);
+      rank += (cj < cost || (cj == cost && j < lane)) ? 1u : 0u;
+      phrase_at += cj < pcost ? 1u : 0u;
+    }
+    if (lane >= mp && lane < m) W.off[mp + rank] = lane;
   }
 
   // ---- 1. the lead block: entry index 2*lane + h (block) or lane + 64*h (tail)
@@ -795,7 +829,7 @@ __device__ __forceinline__ void phrase_item(const ConjArgs& A, uint32_t pilot /*
       uint32_t P[MT], T[MT], K[MT], V[MT];
 #pragma unroll
       for (int i = 0; i < MT; ++i) {
-        const bool on = uint32_t(i) < m;
+        const bool on = uint32_t(i) < mp;
         P[i] = on ? W.pidx[i][sl] : 0u;
         T[i] = on ? W.tf[i][sl] : 0u;
         K[i] = 0u;
@@ -805,7 +839,7 @@ __device__ __forceinline__ void phrase_item(const ConjArgs& A, uint32_t pilot /*
       // reference's lead.seek(sought - offset), which only skips positions that cannot match.
       uint32_t pf = 0, head = ps.pos_base;
       bool done = false;
-      if (MT == 2 && m == 2u) {
+      if (REQ ? mp == 2u : (MT == 2 && m == 2u)) {
         // Two terms: ONE loop that reads one position per trip, of whichever list is behind
         // (the term's records selected per lane).  The nested form below costs a wavefront the
         // SUM over lead positions of the LONGEST seek among its 64 docs; this one the longest
@@ -856,7 +890,7 @@ __device__ __forceinline__ void phrase_item(const ConjArgs& A, uint32_t pilot /*
         bool match = true;
 #pragma unroll
         for (int i = 1; i < MT; ++i) {
-          if (uint32_t(i) < m && match && !done) {
+          if (uint32_t(i) < mp && match && !done) {
             const uint32_t target = head + W.off[i];
             if (target < head) { done = true; break; }  // !pos_limits::valid(term_position)
             // position::seek(target) :1578-1604
@@ -886,6 +920,19 @@ __device__ __forceinline__ void phrase_item(const ConjArgs& A, uint32_t pilot /*
                             : (item < ld.nblk ? seg.pnorm[(ld.dir_off + item) * kBlock + sl]
                                               : seg.tail_norms[ld.tail_row + sl]);
         score = score_value(qt, pf, nv);
+        if constexpr (REQ) {
+          // + every required term's own score at its frequency in the doc, in cost order (each
+          // row's scorer read where it is used: up to 6 of them would not stay in registers)
+          const uint32_t nreq = m - mp;
+          float sum = phrase_at == 0u ? score : 0.f;
+          for (uint32_t r = 0; r < nreq; ++r) {
+            const uint32_t row = W.off[mp + r];
+            const float v = score_value(A.qterms[qd.first_term + row], W.tf[row][sl], nv);
+            sum = (r == 0u && phrase_at != 0u) ? v : sum + v;
+            if (r + 1u == phrase_at) sum += score;
+          }
+          score = sum;
+        }
         const uint32_t bin = score_bin(score, qd.bin_scale);
         if (pilot) atomicAdd(&A.hist[uint64_t(unit) * kBins + bin], 1u);
         else cand = bin >= bs;   // below the pilot's threshold bin: cannot be among the top k
@@ -934,6 +981,28 @@ __global__ void __launch_bounds__(kPhraseWaves * 64) RT_WAVES_PER_SIMD(8)
 k_phrase2(ConjArgs A, uint32_t pilot) {
   __shared__ PhraseWave<2> s_wave[kPhraseWaves];
   phrase_item<LAYOUT, 2>(A, pilot, s_wave);
+}
+
+
+// And([by_phrase, by_term...]) — a phrase plus required terms (IRS_HIP_PHRASE_REQUIRED; the
+// reference: And::prepare -> make_conjunction over {PhraseIterator, term iterators},
+// boolean_filter.cpp:150-210, boolean_query.cpp:60-145, conjunction.hpp:436-490).  phrase_item with
+// rows [n_phrase[unit], m) as required terms:
+//   lead  the rarest of ALL rows; when a required term leads, every phrase word gets its (P, tf)
+//         from step 2's `put`; the doc's norm still comes from the lead's posting-order copy;
+//   2.    a required row is intersected like a phrase word (its P is stored and never read: the
+//         LDS row of an MT-wide wavefront is there anyway);
+//   3.    "reached by every row" runs over all rows, the position merge over the phrase rows only
+//         (two words: the single loop); phrase frequency 0 = no match whatever the terms hold;
+//   4.    score = phrase scorer at tf = phrase frequency + every required term's scorer at its own
+//         tf, float32, children in cost order — into the bin, the pilot histogram and the key.
+// A plain phrase of such a batch has no required rows: its score is the phrase's alone, bit for bit
+// what k_phrase gives.  MT in {4, 8}: phrase words + required terms <= 8.
+template<int LAYOUT, int MT>
+__global__ void __launch_bounds__(kPhraseWaves * 64)
+k_phrase_and(ConjArgs A, const uint32_t* n_phrase, uint32_t pilot) {
+  __shared__ PhraseWave<MT> s_wave[kPhraseWaves];
+  phrase_item<LAYOUT, MT, false, true>(A, pilot, s_wave, nullptr, 0, nullptr, n_phrase);
 }
 
 }  // namespace irs_hip

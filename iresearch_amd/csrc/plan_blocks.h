@@ -118,6 +118,11 @@ int build_phrase_work(irs_hip_batch* b) {
   if (b->blocks.units.empty()) return IRS_HIP_OK;   // (no query has all its terms in its segment)
   const int rc = stage_lead_items(b, b->blocks, b->blocks.d_lead_of, lead_of);
   b->blocks.n_phrase_wgs = (b->blocks.n_items + kPhraseWaves - 1) / kPhraseWaves;
+  // (required terms: the lead above is the rarest of the phrase words AND the required terms)
+  if (rc == IRS_HIP_OK && b->blocks.required &&
+      (!b->blocks.d_n_phrase.alloc(uint64_t(b->nq) * 4) ||
+       !b->up.copy(b->blocks.d_n_phrase.p, b->blocks.n_phrase.data(), uint64_t(b->nq) * 4)))
+    return IRS_HIP_ENOMEM;
   return rc;
 }
 
@@ -260,7 +265,8 @@ bool launch_conj(irs_hip_batch* b, rt::stream_t st) {
 
 // by_phrase: lead-item records + start blocks -> pilot pass over every P-th lead block ->
 // threshold bins -> full pass.
-template<int LAYOUT, int MT>
+// REQ: a batch with required terms (IRS_HIP_PHRASE_REQUIRED), every unit on k_phrase_and.
+template<int LAYOUT, int MT, bool REQ = false>
 bool launch_phrase(irs_hip_batch* b, rt::stream_t st) {
   if (b->blocks.n_phrase_wgs == 0) return true;  // no query has all its terms in its segment
   const uint32_t stride = b->stride_eff;
@@ -280,7 +286,10 @@ bool launch_phrase(irs_hip_batch* b, rt::stream_t st) {
     p.wgs = b->blocks.d_pilot.as<PhraseWg>();
     p.n_pilot = b->blocks.n_pilot;
     p.touched = nullptr;
-    if (MT == 2) {
+    if constexpr (REQ) {
+      RT_LAUNCH((k_phrase_and<LAYOUT, MT>), (b->blocks.n_pilot + kPhraseWaves - 1) / kPhraseWaves,
+                kPhraseWaves * 64, 0, st, p, b->blocks.d_n_phrase.as<uint32_t>(), 1u);
+    } else if (MT == 2) {
       RT_LAUNCH(k_phrase2<LAYOUT>, (b->blocks.n_pilot + kPhraseWaves - 1) / kPhraseWaves,
                 kPhraseWaves * 64, 0, st, p, 1u);
     } else {
@@ -292,7 +301,10 @@ bool launch_phrase(irs_hip_batch* b, rt::stream_t st) {
             b->d_queries.as<DevQuery>(), b->blocks.d_units.as<uint32_t>(),
             b->blocks.d_items.as<uint32_t>(), b->blocks.d_hist.as<uint32_t>(), stride,
             b->estimate ? kPilotMargin : 0u, b->d_bstar.as<uint32_t>(), min_bins(b));
-  if (MT == 2) {
+  if constexpr (REQ) {
+    RT_LAUNCH((k_phrase_and<LAYOUT, MT>), b->blocks.n_phrase_wgs, kPhraseWaves * 64, 0, st, a,
+              b->blocks.d_n_phrase.as<uint32_t>(), 0u);
+  } else if (MT == 2) {
     RT_LAUNCH(k_phrase2<LAYOUT>, b->blocks.n_phrase_wgs, kPhraseWaves * 64, 0, st, a, 0u);
   } else {
     RT_LAUNCH((k_phrase<LAYOUT, MT>), b->blocks.n_phrase_wgs, kPhraseWaves * 64, 0, st, a, 0u);
@@ -338,6 +350,9 @@ bool launch_vphrase(irs_hip_batch* b, rt::stream_t st) {
 template<int LAYOUT>
 bool launch_phrase_terms(irs_hip_batch* b, rt::stream_t st) {
   if (b->blocks.variadic) return launch_vphrase<LAYOUT>(b, st);
+  if (b->blocks.required)
+    return b->jt <= 4 ? launch_phrase<LAYOUT, 4, true>(b, st)
+                      : launch_phrase<LAYOUT, int(kPhraseMaxTerms), true>(b, st);
   if (b->jt <= 2) return launch_phrase<LAYOUT, 2>(b, st);
   if (b->jt <= 4) return launch_phrase<LAYOUT, 4>(b, st);
   return launch_phrase<LAYOUT, int(kPhraseMaxTerms)>(b, st);

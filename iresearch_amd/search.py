@@ -25,7 +25,7 @@ from dataclasses import dataclass, field, replace
 import numpy as np
 
 from . import _lib
-from ._lib import (EXCLUDE, HIT, NO_TERM, OP_AND, OP_MINMATCH, OP_OR, OP_PHRASE, PHRASE_ALT, QUERY, SCORE_BM1, SCORE_BM15, SCORE_BM25,
+from ._lib import (EXCLUDE, HIT, NO_TERM, OP_AND, OP_MINMATCH, OP_OR, OP_PHRASE, PHRASE_ALT, PHRASE_REQUIRED, QUERY, SCORE_BM1, SCORE_BM15, SCORE_BM25,
                    SCORE_TFIDF, SCORE_TFIDF_NORM, TERM_META, TERM_SCORER, SegmentDesc)
 
 f32 = np.float32
@@ -117,8 +117,11 @@ class Or:
 
 @dataclass
 class And:
-    """irs::And of by_term and Or-of-by_term children (the Ors are groups: IRS_HIP_GROUP_ALT);
-    `boost` multiplies into the boosts of its terms."""
+    """irs::And of by_term and Or-of-by_term children (the Ors are groups: IRS_HIP_GROUP_ALT), or of
+    ONE by_phrase of plain terms and by_term children — a phrase plus required terms,
+    `+"new york" +hotel` (IRS_HIP_PHRASE_REQUIRED; merge SUM, at most 8 words and terms in all;
+    prepare(..., required_terms=True));
+    Not children exclude docs either way; `boost` multiplies into the boosts of its children."""
     subs: list
     op: int = OP_AND
     min_match: int = 0
@@ -132,7 +135,9 @@ class by_phrase:
     (push_back<by_term_options>) or a list of them: a part that stands for a set of terms, what a
     by_terms / by_prefix / by_wildcard / by_range visitor yields, in dictionary order (a variadic
     phrase, VariadicPrepareCollect); `offsets[i]` = position of part i relative to the first
-    (default: consecutive words)."""
+    (default: consecutive words).  A phrase of plain terms may also be a child of an And, next to
+    by_term children (required terms) and Nots (prepare(..., required_terms=True)); not of an Or,
+    and not next to another phrase."""
     terms: list
     offsets: list | None = None
     boost: float = 1.0
@@ -230,9 +235,13 @@ def split_exclusions(flt):
             if flt.boost != 1.0:   # (the And's boost multiplies into its one child's)
                 inner = replace(inner, boost=float(f32(f32(flt.boost) * f32(inner.boost))))
             return inner, excl
+        if any(isinstance(s, by_phrase) for s in incl):
+            # a phrase plus required terms (checked by prepare(): _prepare_phrase_and)
+            return And(incl, op=flt.op, merge=flt.merge, boost=flt.boost), excl
         if any(type(s) is not by_term for s in incl):
-            raise ValueError("an And with Not children takes by_term children or ONE Or / And / "
-                             "by_phrase child (groups minus some terms: And([And([...]), Not(...)]))")
+            raise ValueError("an And with Not children takes by_term children, ONE by_phrase plus "
+                             "by_term children, or ONE Or / And / by_phrase child (groups minus some "
+                             "terms: And([And([...]), Not(...)]))")
         return And(incl, merge=flt.merge, boost=flt.boost), excl
     return flt, []
 
@@ -251,7 +260,8 @@ def _or_members(flt, mult):
             raise ValueError("an Or with a Not child matches all docs but some (zero-score fill, "
                              "boolean_filter.cpp:120-127): not on the GPU path")
         elif isinstance(s, by_phrase):
-            raise ValueError("phrases inside boolean trees are not on the GPU path")
+            raise ValueError("a by_phrase inside an Or is not on the GPU path: a phrase is taken alone, "
+                             "or as a child of an And next to by_term children")
         elif type(s) is Or:
             raise ValueError("an Or group takes by_term children and SUM Ors of them: min_match > 1 "
                              "and non-SUM merges are not on the GPU path")
@@ -292,7 +302,8 @@ def and_groups(flt, mult=1.0):
         elif isinstance(s, Not):
             raise ValueError("Not is taken by prepare() only (as a child of the outermost And)")
         elif isinstance(s, by_phrase):
-            raise ValueError("phrases inside boolean trees are not on the GPU path")
+            raise ValueError("a by_phrase inside a nested And is not on the GPU path: a phrase is "
+                             "taken as a child of the outermost And, next to by_term children")
         else:
             raise ValueError("%s inside an And is not on the GPU path" % type(s).__name__)
     if sum(len(g) for g in groups) > _lib.MAX_TERMS:
@@ -323,6 +334,9 @@ class PreparedQuery:
     alts: list | None = None   # OP_PHRASE: True for an entry that is one more member of the part
                                # before it (IRS_HIP_PHRASE_ALT); OP_AND: ... of the group before it
                                # (IRS_HIP_GROUP_ALT, the same bit)
+    required: list | None = None   # OP_PHRASE: True for an entry that is a required term — a by_term
+                                   # child of the And that holds the phrase (IRS_HIP_PHRASE_REQUIRED),
+                                   # carrying its own scorer; None: a phrase alone
 
 
 # ------------------------------------------------------------------ segment --
@@ -484,8 +498,10 @@ class QueryArrays:
             queries[q] = (p.op, len(p.terms) + len(p.excluded), at, int(k), p.min_match, p.merge)
             offs = p.offsets if p.offsets is not None else [0] * len(p.terms)
             alts = p.alts if p.alts is not None else [False] * len(p.terms)
-            for t, (kind, c0, nc, nl), off, alt in zip(p.terms, p.scorers, offs, alts):
+            reqs = p.required if p.required is not None else [False] * len(p.terms)
+            for t, (kind, c0, nc, nl), off, alt, req in zip(p.terms, p.scorers, offs, alts, reqs):
                 kind = kind | PHRASE_ALT if alt else kind   # (GROUP_ALT for an And: the same bit)
+                kind = kind | PHRASE_REQUIRED if req else kind
                 for s, sr in enumerate(segs):       # same scorer, the segment's own ordinal
                     present = t is not None and 0 <= t < len(sr.metas)
                     terms[s, at] = (t if present else NO_TERM, kind, c0, nc, nl, off)
@@ -585,6 +601,10 @@ def prepare_filters(filters, scorer, segment_stats, segs, k):
                                                any(not isinstance(s, by_term) for s in subs)):
                 if any(isinstance(s, Not) for s in subs):
                     raise ValueError("Not is taken by prepare() (IRS_HIP_EXCLUDE), not by the "
+                                     "array path prepare_filters")
+                if any(isinstance(s, by_phrase) for s in subs):
+                    raise ValueError("a by_phrase inside an And (a phrase plus required terms, "
+                                     "IRS_HIP_PHRASE_REQUIRED) is taken by prepare(), not by the "
                                      "array path prepare_filters")
                 raise ValueError("only flat Or/And of by_term are on the array path: an And with "
                                  "Or children is taken by prepare()")
@@ -894,10 +914,14 @@ class SegmentStats:
     docs_count: np.ndarray  # per term ordinal: term_meta::docs_count
 
 
-def prepare(filters, scorer, segment_stats):
+def prepare(filters, scorer, segment_stats, required_terms=False):
     """filter::prepare for a list of filters against ALL segments: statistics are
     index-global (term_filter.cpp:102-125): D = sum docs_with_field,
-    d = sum docs_count of the term, avgdl from the summed field frequency."""
+    d = sum docs_count of the term, avgdl from the summed field frequency.
+    required_terms=True: And([by_phrase, by_term..., Not(...)...]) — a phrase plus required terms,
+    IRS_HIP_PHRASE_REQUIRED — is taken.  Off by default: prepare() then refuses the shape as it
+    always did (ValueError), so callers that send what prepare() refuses down their CPU path see no
+    change until they ask for it."""
     dwf = sum(s.docs_with_field for s in segment_stats)
     ttf = sum(s.total_term_freq for s in segment_stats)
     out = []
@@ -905,7 +929,7 @@ def prepare(filters, scorer, segment_stats):
         flt, excluded = split_exclusions(flt)
         if excluded:
             # (the excluded part is prepared without scorers: no score, no statistic)
-            p = prepare([flt], scorer, segment_stats)[0]
+            p = prepare([flt], scorer, segment_stats, required_terms)[0]
             p.excluded = [int(t) for t in excluded]
             out.append(p)
             continue
@@ -913,20 +937,16 @@ def prepare(filters, scorer, segment_stats):
             out.append(_prepare_variadic(flt, scorer, segment_stats, dwf, ttf))
             continue
         if isinstance(flt, by_phrase):
-            # FixedPrepareCollect (phrase_filter.cpp:212-293): term_stats.finish() of every
-            # phrase term lands in ONE stats blob — BM25::collect / TFIDF::collect do
-            # `idf +=` (bm25.cpp:381-383, tfidf.cpp:272-275), the norm constants are equal
-            idf = f32(0)
-            stats = None
-            for t in flt.terms:
-                dwt = sum(int(st.docs_count[t]) for st in segment_stats
-                          if 0 <= t < len(st.docs_count))
-                stats = scorer.collect(dwf, dwt, ttf)
-                idf = f32(idf + stats.idf)
-            one = scorer.term_scorer(TermStats(idf, stats.norm_const, stats.norm_length),
-                                     flt.boost)
+            one = _phrase_scorer(flt, flt.boost, scorer, segment_stats, dwf, ttf)
             out.append(PreparedQuery(OP_PHRASE, list(flt.terms), [one] * len(flt.terms), 0,
                                      [int(o) for o in flt.offsets]))
+            continue
+        if isinstance(flt, (Or, And)) and any(isinstance(s, by_phrase) for s in flt.subs):
+            if type(flt) is And and not required_terms:
+                raise ValueError("a by_phrase next to other children of an And (a phrase plus required "
+                                 "terms, IRS_HIP_PHRASE_REQUIRED) is taken by "
+                                 "prepare(..., required_terms=True)")
+            out.append(_prepare_phrase_and(flt, scorer, segment_stats, dwf, ttf))
             continue
         if type(flt) is And and (flt.boost != 1.0 or any(type(s) is not by_term for s in flt.subs)):
             out.append(_prepare_groups(flt, scorer, segment_stats, dwf, ttf))
@@ -945,6 +965,65 @@ def prepare(filters, scorer, segment_stats):
                                  int(getattr(flt, "min_match", 0)),
                                  merge=int(getattr(flt, "merge", MERGE_SUM))))
     return out
+
+
+def _phrase_scorer(flt, boost, scorer, segment_stats, dwf, ttf):
+    """FixedPrepareCollect (phrase_filter.cpp:212-293): term_stats.finish() of every phrase term
+    lands in ONE stats blob — BM25::collect / TFIDF::collect do `idf +=` (bm25.cpp:381-383,
+    tfidf.cpp:272-275), the norm constants are equal."""
+    idf = f32(0)
+    stats = None
+    for t in flt.terms:
+        dwt = sum(int(st.docs_count[t]) for st in segment_stats
+                  if 0 <= t < len(st.docs_count))
+        stats = scorer.collect(dwf, dwt, ttf)
+        idf = f32(idf + stats.idf)
+    return scorer.term_scorer(TermStats(idf, stats.norm_const, stats.norm_length), boost)
+
+
+def _prepare_phrase_and(flt, scorer, segment_stats, dwf, ttf):
+    """prepare() of And([by_phrase, by_term...]) — a phrase plus required terms (And::prepare ->
+    make_conjunction over the children, boolean_filter.cpp:150-210): the phrase gets its
+    FixedPrepareCollect blob from its own words, every by_term its own statistics; the And's boost
+    multiplies into every child's in float32.  Entries: the phrase's words, then the required terms
+    (IRS_HIP_PHRASE_REQUIRED).  What is taken: ONE by_phrase of plain terms, at least one by_term,
+    merge SUM, at most 8 words and terms in all (Not children were split off before)."""
+    taken = ("an And takes ONE by_phrase of plain terms plus by_term children "
+             "(and Not children), merged with SUM")
+    if type(flt) is not And or flt.op != OP_AND:
+        raise ValueError("a by_phrase inside an Or is not on the GPU path: " + taken)
+    phrases = [s for s in flt.subs if isinstance(s, by_phrase)]
+    others = [s for s in flt.subs if not isinstance(s, by_phrase)]
+    if len(phrases) > 1:
+        raise ValueError("two phrases in one And are not on the GPU path: " + taken)
+    ph = phrases[0]
+    if ph.variadic:
+        raise ValueError("a variadic by_phrase with required terms is not on the GPU path: " + taken)
+    for s in others:
+        if type(s) is Or:
+            raise ValueError("an Or group next to a by_phrase is not on the GPU path: " + taken)
+        if type(s) is not by_term:
+            raise ValueError("%s next to a by_phrase is not on the GPU path: %s" % (type(s).__name__, taken))
+    if not others:
+        raise ValueError("an And of one by_phrase alone is that phrase: send the by_phrase itself "
+                         "(or under And([..., Not(...)]))")
+    if flt.merge != MERGE_SUM:
+        raise ValueError("an And with a by_phrase child merges with SUM on the GPU path "
+                         "(MAX / MIN over a phrase and terms are not built)")
+    if len(ph.terms) < 2:
+        raise ValueError("a by_phrase of one term is a by_term: " + taken)
+    if len(ph.terms) + len(others) > _lib.MAX_PHRASE_TERMS:
+        raise ValueError("a by_phrase plus required terms has at most %d entries in all"
+                         % _lib.MAX_PHRASE_TERMS)
+    mult = f32(flt.boost)
+    one = _phrase_scorer(ph, f32(mult * f32(ph.boost)), scorer, segment_stats, dwf, ttf)
+    terms, scorers = list(ph.terms), [one] * len(ph.terms)
+    for s in others:
+        dwt = sum(int(st.docs_count[s.term]) for st in segment_stats if 0 <= s.term < len(st.docs_count))
+        terms.append(s.term)
+        scorers.append(scorer.term_scorer(scorer.collect(dwf, dwt, ttf), f32(mult * f32(s.boost))))
+    return PreparedQuery(OP_PHRASE, terms, scorers, 0, [int(o) for o in ph.offsets] + [0] * len(others),
+                         required=[False] * len(ph.terms) + [True] * len(others))
 
 
 def _prepare_groups(flt, scorer, segment_stats, dwf, ttf):

@@ -66,6 +66,13 @@ for layout in (1, 0):
     tv.case_lists(L, layout)
 tv.case_parity(L, 6_000, 48, 1, (BM25(),), (10, 1000), 6)
 tv.case_multi(L, (3_000, 1_500, 4_000))
+import test_phrase_and as tpa   # a phrase plus required terms (k_phrase_and)
+tpa.case_abi(L)
+for layout in (1, 0):
+    tpa.case_lists(L, layout)
+tpa.case_parity(L, 6_000, 48, 1)
+tpa.case_match_sets(L, 6_000, 48, 1)
+tpa.case_multi(L, (3_000, 1_500, 4_000))
 import test_nested_boolean as tn   # And of Or groups (k_conj_any)
 tn.case_abi(L)
 tn.case_shapes(L, 8_000, 64, 1, (BM25(),), (10, 1000), merges=(0, 2))

@@ -8,7 +8,8 @@ filters with random boosts and merge types (or by_phrase filters), a random scor
 checks the results as the parity tests do; the same batch is then re-run with block-max pruning
 (top-k must not change) and with the k-th score pushed down as irs::score::Min.  Every third
 boolean round also runs the filters with 0-2 excluded terms each (And(filter, Not(by_term))), and
-every phrase round also runs variadic phrases (parts of several terms); every boolean round runs
+every phrase round also runs variadic phrases (parts of several terms) and phrases with required
+terms (And([by_phrase, by_term...])); every boolean round runs
 Ands of Or groups (with exclusions, wand on and off; every third over two segments in one batch).
 
   python tools/fuzz_parity.py --seconds 120            # on the GPU (libirs_hip.so)
@@ -200,6 +201,21 @@ def main():
             match_round(vb, seg, vf, vt)
             vb.close()
             queries += len(vf)
+            # a phrase plus required terms (IRS_HIP_PHRASE_REQUIRED): And([by_phrase, by_term...]),
+            # some with a Not, against the composition of tests/test_phrase_and.py (the oracle's
+            # phrase run and its conjunction of the required terms)
+            import test_phrase_and as tpa
+            from iresearch_amd.search import Not
+            rf, _ = tpa.random_queries(seg, max(max_rank, 24), 8, int(rng.integers(1, 1 << 30)))
+            rf = [And(f.subs + [Not(by_term(int(rng.integers(0, max_rank))))], boost=f.boost) if i % 3 == 0 else f
+                  for i, f in enumerate(rf)] + filters[:2]
+            rprep = search.prepare(rf, scorer, st, required_terms=True)
+            rb = sr.batch(rprep, k)
+            rh, rc, rt = (x.copy() for x in rb.run().results())
+            for q, f in enumerate(rf):
+                tpa.check(f, k, rh[q], rc[q], rt[q], *tpa.expected(seg, f, scorer))
+            rb.close()
+            queries += len(rf)
         else:
             filters = []
             for _ in range(16):

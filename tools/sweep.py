@@ -48,6 +48,10 @@ def main():
                          "plain phrase of the same words.  --op and: every term becomes an Or group of N "
                          "members from the same rank range (IRS_HIP_GROUP_ALT); 1 = the plain And.  "
                          "Times each and exits")
+    ap.add_argument("--required", default="",
+                    help="--op phrase: comma list N,...: And([phrase, N by_terms]) — the same phrases with "
+                         "N required terms each (IRS_HIP_PHRASE_REQUIRED), drawn from --lo-rank..--hi-rank; "
+                         "0 = the plain phrases.  Times each and exits")
     ap.add_argument("--unscored", action="store_true",
                     help="time irs_hip_batch_match_sets_to_device (every unit's full match set as a "
                          "bitset + its count, and the counts alone) instead of run + results; the scored "
@@ -114,6 +118,35 @@ def main():
             print("alts=%d  %s  step %.2f ms  = %.2f ms per 1000 queries  hits/query mean %.0f  reruns=%d"
                   % (n_alt, "grouped" if n_alt > 1 else "plain", dt * 1e3, dt * 1e3 * 1000 / len(gf),
                      float(np.mean(totals)), b.reruns()), flush=True)
+            b.close()
+        sys.exit(0)
+    if args.required and args.op == "phrase":
+        for n_req in (int(x) for x in args.required.split(",")):
+            rng = np.random.default_rng(synth.SEED + 6)
+            rf = []
+            for row in ranks:
+                ph = by_phrase([int(r) - 1 for r in row])
+                req = []
+                while len(req) < n_req:
+                    x = int(rng.integers(args.lo_rank, args.hi_rank + 1)) - 1
+                    if x not in req:
+                        req.append(x)
+                rf.append(And([ph] + [by_term(x) for x in req]) if n_req else ph)
+            b = sr.batch(search.prepare(rf, scorer, [st], required_terms=True), args.k).profile(True)
+            b.run()
+            _, _, totals = b.results()
+            ms = []
+            t0 = time.perf_counter()
+            for _ in range(args.steps):
+                b.run()
+                b.results()
+                ms.append(b.timings())
+            dt = (time.perf_counter() - t0) / args.steps
+            avg = np.mean(ms, axis=0)
+            print("required=%d  step %.2f ms  = %.2f ms per 1000 phrases  (plan %.2f pilot %.2f score %.2f "
+                  "select %.2f)  hits/query mean %.1f  reruns=%d"
+                  % (n_req, dt * 1e3, dt * 1e3 * 1000 / len(rf), *avg, float(np.mean(totals)), b.reruns()),
+                  flush=True)
             b.close()
         sys.exit(0)
     if args.alts and args.op == "phrase":

@@ -667,6 +667,33 @@ int irs_hip_device_sync(int32_t device, void* stream);
  * counterpart for callers that watch their memory (formats.hpp:190). */
 int irs_hip_device_trim(int32_t device);
 
+/* Decoded posting streams kept across batches.  The joined path (IRS_HIP_PATH_JOINED, k_join)
+ * decodes every distinct (segment, term) of a batch into 4-byte entries; those are a function of
+ * the segment alone — no scorer, no query —, so the device keeps them, and a later batch that
+ * references a stream it already holds decodes nothing for it.  A batch pins the streams it
+ * references until irs_hip_batch_destroy; unpinned ones are evicted least recently used first when
+ * the byte budget is reached, what does not fit is decoded into the batch's own memory as before:
+ * the cache never makes a batch fail and never changes a result.  irs_hip_segment_close drops the
+ * segment's streams, irs_hip_device_trim every unpinned one.
+ * The budget: an eighth of the device's memory, IRS_HIP_STREAM_CACHE_MB (process-wide, read once)
+ * or this call; 0 switches the cache off (what is held and unpinned is dropped).  The memory comes
+ * from and goes back to the library's pool. */
+int irs_hip_device_set_stream_cache(int32_t device, uint64_t bytes);
+typedef struct irs_hip_stream_cache_stats {
+  uint64_t bytes_held; /* device memory of the streams in the cache                       */
+  uint64_t budget;     /* bytes_held stays at or below it                                 */
+  uint64_t streams;    /* (segment, term) streams it can serve                            */
+  uint64_t hits;       /* look-ups of batches (one per distinct stream of a deal) served  */
+  uint64_t misses;     /* ... not served: decoded by the batch                            */
+  uint64_t evictions;  /* streams dropped for room                                        */
+} irs_hip_stream_cache_stats;
+int irs_hip_device_stream_cache_stats(int32_t device, irs_hip_stream_cache_stats* out);
+/* The distinct (segment, term) streams the batch's joined units reference, and how many of them its
+ * last run (or the irs_hip_batch_plan it used) decoded itself: all of them with the cache off,
+ * none when every stream was held, none for a replayed run of a batch whose first run filled the
+ * cache.  A batch without joined units reports 0, 0.  IRS_HIP_EINVAL before the first run. */
+int irs_hip_batch_stream_counts(irs_hip_batch* batch, uint32_t* distinct, uint32_t* decoded);
+
 typedef struct irs_hip_comm irs_hip_comm;
 #define IRS_HIP_COMM_ID_BYTES 128u
 int irs_hip_comm_unique_id(uint8_t id[IRS_HIP_COMM_ID_BYTES]);

@@ -56,6 +56,11 @@ class SegmentDesc(C.Structure):
     ]
 
 
+class StreamCacheStats(C.Structure):
+    _fields_ = [("bytes_held", C.c_uint64), ("budget", C.c_uint64), ("streams", C.c_uint64),
+                ("hits", C.c_uint64), ("misses", C.c_uint64), ("evictions", C.c_uint64)]
+
+
 class IrsHipError(RuntimeError):
     def __init__(self, status: int, what: str, message: str):
         super().__init__("%s: %s (%d)" % (what, message, status))
@@ -87,6 +92,8 @@ SYMBOLS = (
     "irs_hip_topk_allgather", "irs_hip_device_alloc", "irs_hip_device_free",
     "irs_hip_device_upload", "irs_hip_device_download", "irs_hip_device_sync",
     "irs_hip_device_trim",
+    "irs_hip_device_set_stream_cache", "irs_hip_device_stream_cache_stats",
+    "irs_hip_batch_stream_counts",
 )
 
 
@@ -173,6 +180,12 @@ def bind(L: C.CDLL) -> C.CDLL:
     L.irs_hip_topk_allgather.argtypes = [vp, vp, vp, u64, vp]
     L.irs_hip_topk_allgather.restype = C.c_int
     L.irs_hip_device_trim.argtypes, L.irs_hip_device_trim.restype = [i32], C.c_int
+    L.irs_hip_device_set_stream_cache.argtypes = [i32, u64]
+    L.irs_hip_device_set_stream_cache.restype = C.c_int
+    L.irs_hip_device_stream_cache_stats.argtypes = [i32, P(StreamCacheStats)]
+    L.irs_hip_device_stream_cache_stats.restype = C.c_int
+    L.irs_hip_batch_stream_counts.argtypes = [vp, P(u32), P(u32)]
+    L.irs_hip_batch_stream_counts.restype = C.c_int
     return L
 
 

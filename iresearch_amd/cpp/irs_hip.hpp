@@ -770,6 +770,19 @@ class QueryBatch {
     }
     return total;
   }
+  // the distinct (segment, term) streams of the batch's joined units, and how many of them its
+  // last run decoded itself — the rest came out of the device's stream cache
+  struct StreamCounts { uint32_t distinct = 0, decoded = 0; };
+  StreamCounts stream_counts() const {
+    StreamCounts total;
+    for (const Part& part : part_) {
+      uint32_t n = 0, d = 0;
+      if (part.h) check(irs_hip_batch_stream_counts(part.h, &n, &d), "irs_hip_batch_stream_counts");
+      total.distinct += n;
+      total.decoded += d;
+    }
+    return total;
+  }
 
  private:
   struct Part {  // [0] boolean queries, [1] phrase queries
@@ -1879,6 +1892,17 @@ inline QueryBatch::Results execute_expansions(const std::vector<const SegmentRea
     }
   }
   return r;
+}
+
+// ---- the decoded posting streams a device keeps across batches (irs_hip.h) -------------------
+// budget in bytes: 0 switches the cache off
+inline void set_stream_cache(int32_t device, uint64_t bytes) {
+  check(irs_hip_device_set_stream_cache(device, bytes), "irs_hip_device_set_stream_cache");
+}
+inline irs_hip_stream_cache_stats stream_cache_stats(int32_t device) {
+  irs_hip_stream_cache_stats st{};
+  check(irs_hip_device_stream_cache_stats(device, &st), "irs_hip_device_stream_cache_stats");
+  return st;
 }
 
 // ---- several GPUs: one process per GPU, segments sharded, ONE all-gather per batch -----------

@@ -13,7 +13,8 @@ constexpr uint32_t kDefaultWgThreads = 512;  // 8 wavefronts share one tile (mea
 
 // Tuning and test knobs (environment), read once by irs_hip_batch_create on the caller's thread:
 // a batch keeps what was set when it was created.  (IRS_HIP_POOL_MB, IRS_HIP_PINNED_POOL_MB,
-// IRS_HIP_TRACE and IRS_HIP_ASYNC_RUN are process-wide settings, not batch knobs.)
+// IRS_HIP_STREAM_CACHE_MB, IRS_HIP_TRACE and IRS_HIP_ASYNC_RUN are process-wide settings, not
+// batch knobs.)
 struct Knobs {
   bool join_off = false;     // IRS_HIP_JOIN=0: no joined streams unless irs_hip_batch_set_path asks
   bool join_counts = true;   // IRS_HIP_JOIN_COUNTS=0: no match counts in joined accumulators
@@ -55,21 +56,6 @@ struct Knobs {
   }
 };
 
-// A HIP event, created on first use and destroyed with its owner (sync / wait fail on one that
-// was never created)
-struct Event {
-  rt::event_t e{};
-  bool made = false;
-  Event() = default;
-  Event(const Event&) = delete;
-  Event& operator=(const Event&) = delete;
-  ~Event() { if (made) rt::event_destroy(e); }
-  bool create() { return made || (made = rt::event_create(&e)); }
-  bool record(rt::stream_t st) { return create() && rt::event_record(e, st); }
-  bool sync() const { return made && rt::event_sync(e); }
-  bool wait(rt::stream_t st) const { return made && rt::stream_wait(st, e); }   // st waits for it
-};
-
 // Doc-tile units as work items (score.h): k_plan's tables -> work-item lists -> k_pilot -> k_score
 struct TileWork {
   std::vector<uint32_t> units;
@@ -90,12 +76,25 @@ struct TileWork {
 };
 
 // Joined posting streams (join.h): every distinct (segment, term) of the batch decoded once per run
+// — or not at all, where the device's stream cache holds it
 struct JoinWork {
   std::vector<uint32_t> units;
   bool on() const { return !units.empty(); }   // some unit runs on joined streams
   DevBuf d_streams, d_wgs, d_jterms, d_entries, d_bounds, d_args, d_units, d_order;
   uint32_t n_max = 0;   // doc tiles of the unit with the most
   uint32_t n_streams = 0, n_wgs = 0;
+  // Decoded streams kept across batches (stream_cache.h).  A stream of the deal is a HIT — it
+  // lies in a slab an earlier batch filled: no k_join work —, a FILL — in a slab this deal
+  // claimed: decoded by the deal's first plan stage, served to later batches from then on — or
+  // PRIVATE — in d_entries / d_bounds, decoded in every run (no cache, the budget full of pinned
+  // slabs, a slab another batch has claimed and not queued yet).  d_wgs: the private streams'
+  // workgroups (n_wgs), then the fills' (n_wgs_fill), each in doc-position order.
+  std::vector<scache::SlabPtr> pinned;   // every slab a stream of the deal lies in, `fills` included
+  std::vector<scache::SlabPtr> fills;
+  bool fill_pending = false;             // the fills' k_join is not queued yet
+  uint32_t n_wgs_fill = 0;
+  uint32_t n_private = 0, n_fill = 0;    // streams
+  uint32_t decoded_last = 0;             // streams the last plan stage queued k_join work for
   uint32_t threads = 1024, nw_log2 = 4;   // threads per k_join_pilot / k_join_score workgroup
   uint64_t entries = 0;
   bool slack_zeroed = false;   // the readable slack behind d_entries

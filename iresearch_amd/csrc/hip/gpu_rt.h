@@ -44,6 +44,13 @@ inline int device_cus(int dev) {
   hipDeviceProp_t p;
   return ok(hipGetDeviceProperties(&p, dev)) ? p.multiProcessorCount : 0;
 }
+// (the runtime header of the CPU test tier has no device to ask: stream_cache.h sizes its default
+// by the pool's cap where this is not defined)
+#define RT_HAS_DEVICE_TOTAL_MEM 1
+inline size_t device_total_mem(int dev) {
+  size_t n = 0;
+  return ok(hipDeviceTotalMem(&n, dev)) ? n : 0;
+}
 inline void* dmalloc(size_t n) {
   void* p = nullptr;
   return ok(hipMalloc(&p, n ? n : 1)) ? p : nullptr;

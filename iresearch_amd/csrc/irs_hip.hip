@@ -18,6 +18,8 @@
 #include <new>
 #include <thread>
 #include <type_traits>
+#include <unordered_map>
+#include <unordered_set>
 #include <vector>
 
 #include "gpu_rt.h"
@@ -34,6 +36,7 @@
 using namespace irs_hip;
 
 #include "pool.h"
+#include "stream_cache.h"
 #include "segment.h"
 #include "batch.h"
 #include "plan_tiles.h"
@@ -412,6 +415,7 @@ const char* irs_hip_strerror(int status) {
 void irs_hip_segment_close(irs_hip_segment* seg) {
   if (!seg) return;
   rt::set_device(seg->device);
+  scache::drop_unpinned(seg->device, seg->uid);   // (its decoded streams: back to the pool)
   pool::tl_free_now = true;   // (its buffers are freed, not pooled)
   delete seg;
   pool::tl_free_now = false;
@@ -1191,6 +1195,7 @@ static int batch_plan_impl(irs_hip_batch* b, void* stream) {
   // (match sets queued on another stream read the masks this stage rewrites)
   if (ok && b->sync.match_pending) ok = b->sync.matched.wait(st);
   ok = ok && b->up.flush(st) && plan_stage(b, st) && b->sync.plan.record(st);
+  if (!ok) abandon_fills(b);
   b->sync.planned = ok;
   b->sync.plan_pending = b->sync.plan_pending || b->sync.plan.made;   // (whatever got queued)
   return ok ? IRS_HIP_OK : IRS_HIP_EHIP;
@@ -1237,6 +1242,8 @@ static int run_impl(irs_hip_batch* b, rt::stream_t st) {
     b->join.slack_zeroed = ok;
   }
   ok = ok && rt::dmemset(b->d_zeroed.p, 0, b->d_zeroed.n, st);   // (ensure_scratch: six tables)
+  // (streams out of the device's cache that another stream is still filling)
+  if (b->join.on()) ok = ok && wait_for_streams(b, st);
   // 1. plan (already queued by irs_hip_batch_plan: wait for it instead)
   const bool tiles = !b->phrase && !b->tiles.units.empty();
   if (b->sync.planned) {
@@ -1300,6 +1307,7 @@ static int run_impl(irs_hip_batch* b, rt::stream_t st) {
   // the status word follows the kernels into page-locked memory; the event marks this run
   if (ok && !b->sync.h_status.p) ok = b->sync.h_status.alloc(64);
   ok = ok && rt::d2h(b->sync.h_status.p, b->d_status.p, 4, st) && b->sync.done.record(st);
+  if (!ok) abandon_fills(b);
   b->ran = true;
   return ok ? IRS_HIP_OK : IRS_HIP_EHIP;
 }
@@ -1583,7 +1591,8 @@ void irs_hip_batch_destroy(irs_hip_batch* b) {
   if (b->sync.used_pending) waited = waited && b->sync.used.sync();
   if (b->sync.host_pending) waited = waited && b->sync.host.sync();
   if (b->sync.match_pending) waited = waited && b->sync.matched.sync();
-  if (!waited && b->ran) rt::sync(b->stream);
+  if (!waited && b->ran) waited = rt::sync(b->stream);
+  release_streams(b, waited);   // (its pins in the device's stream cache)
   // (the batch's events go with it)
   delete b;
 }
@@ -1726,9 +1735,41 @@ int irs_hip_device_download(int32_t device, void* h_dst, const void* d_src, uint
 int irs_hip_device_trim(int32_t device) {
   return guarded([&] {
     if (device < 0 || device >= rt::device_count() || !rt::set_device(device)) return int(IRS_HIP_EHIP);
+    scache::drop_unpinned(device, 0);   // (the decoded streams no batch alive references)
     pool::release_all(device, false);
     pool::release_all(device, true);
     return int(IRS_HIP_OK);
+  });
+}
+int irs_hip_device_set_stream_cache(int32_t device, uint64_t bytes) {
+  return guarded([&] {
+    if (device < 0 || device >= rt::device_count() || !rt::set_device(device)) return int(IRS_HIP_EHIP);
+    scache::set_budget(device, bytes);
+    return int(IRS_HIP_OK);
+  });
+}
+int irs_hip_device_stream_cache_stats(int32_t device, irs_hip_stream_cache_stats* out) {
+  return guarded([&] {
+    if (!out) return int(IRS_HIP_EINVAL);
+    if (device < 0 || device >= rt::device_count() || !rt::set_device(device)) return int(IRS_HIP_EHIP);
+    const uint64_t budget = scache::budget_bytes(device);
+    scache::Cache& c = scache::of(device);
+    std::lock_guard<std::mutex> lock(c.m);
+    out->bytes_held = c.held;
+    out->budget = budget;
+    out->streams = c.map.size();
+    out->hits = c.hits;
+    out->misses = c.misses;
+    out->evictions = c.evictions;
+    return int(IRS_HIP_OK);
+  });
+}
+int irs_hip_batch_stream_counts(irs_hip_batch* b, uint32_t* distinct, uint32_t* decoded) {
+  return settled(b, [&]() -> int {
+    if (!b || !b->ran) return IRS_HIP_EINVAL;
+    if (distinct) *distinct = b->join.on() ? b->join.n_streams : 0u;
+    if (decoded) *decoded = b->join.on() ? b->join.decoded_last : 0u;
+    return IRS_HIP_OK;
   });
 }
 int irs_hip_device_sync(int32_t device, void* stream) {

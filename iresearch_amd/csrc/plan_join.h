@@ -21,6 +21,11 @@ bool join_allowed(const irs_hip_batch* b) {   // batch level
 // (k_join_score 0.3 + a share of k_join's decode); block driven = 2300 + 400 x terms per
 // 128-posting block of the rarest term: its decode plus a seek and a block decode in every other
 // term.  The conjunctions of two frequent terms are the ones that join.
+// (With the device's stream cache — stream_cache.h — a stream that is already held costs no
+// k_join at all: these coefficients, join_or_pays' 2.9 per distinct posting and join_half_ok's
+// sizes price every batch as a cold one and so UNDER-state the joined path.  They are kept: AUTO
+// joins wherever it did before and nowhere earlier, as §3.13 kept them for paired tiles — what a
+// warm cache would let join in addition has not been measured.)
 // Returns the picoseconds saved by joining (<= 0: block driven is cheaper).
 int64_t join_and_saving(const irs_hip_batch* b, const DevQuery& dq) {
   const irs_hip_segment* sg = b->segs[dq.seg];
@@ -99,11 +104,43 @@ bool unit_joinable(const irs_hip_batch* b, uint32_t u) {
   return true;
 }
 
+// What the deal holds of the device's stream cache goes back: its pins, and the slabs it claimed
+// and never queued a decode for — those leave the cache unfilled, nobody was ever served them.
+// `waited`: the caller has waited for the batch's queued work (irs_hip_batch_destroy).
+void release_streams(irs_hip_batch* b, bool waited) {
+  if (b->join.pinned.empty()) return;
+  scache::Cache& c = scache::of(b->seg->device);
+  std::vector<scache::SlabPtr> gone;
+  {
+    std::lock_guard<std::mutex> lock(c.m);
+    for (const scache::SlabPtr& s : b->join.fills) {
+      if (!s->queued) scache::drop_locked(c, s.get(), gone);
+      else if (waited) s->settled.store(true);
+    }
+    for (const scache::SlabPtr& s : b->join.pinned) --s->pins;
+  }
+  b->join.fills.clear();
+  b->join.pinned.clear();   // (outside the lock: a slab that left the cache is freed here)
+  b->join.fill_pending = false;
+}
+// A run or a plan stage of the batch failed: whatever it was to decode for the cache is not trusted
+// — the slabs leave the cache (the batch keeps them: a later run of it decodes into them again).
+void abandon_fills(irs_hip_batch* b) {
+  if (b->join.fills.empty()) return;
+  scache::Cache& c = scache::of(b->seg->device);
+  std::vector<scache::SlabPtr> gone;
+  std::lock_guard<std::mutex> lock(c.m);
+  for (const scache::SlabPtr& s : b->join.fills) scache::drop_locked(c, s.get(), gone);
+}
+
 // The batch's distinct (segment, term) streams, k_join's work list and the per-(unit, term)
-// records of k_join_score.  Static per batch: built once, the kernels refill the entries and
-// boundaries in every run.
+// records of k_join_score.  Static per batch: built once.  Every stream is looked up in the
+// device's stream cache (stream_cache.h): a hit costs no k_join work, a miss is decoded once into
+// a slab of the cache by the deal's first plan stage; what the cache cannot take is decoded into
+// the batch's own buffers in every run.
 bool build_streams(irs_hip_batch* b) {
   struct WgRef { uint32_t stream, first; };   // a k_join workgroup before its record is made
+  release_streams(b, false);
   std::unique_ptr<HostTrace> tr(new HostTrace("  streams: distinct terms"));
   auto lap = [&](const char* what) { tr.reset(); tr.reset(new HostTrace(what)); };
   std::vector<StreamRec> streams;
@@ -152,19 +189,123 @@ bool build_streams(irs_hip_batch* b) {
       }
     }
   }
-  uint64_t entries = 0, bounds = 0;
-  std::vector<uint64_t> ent_off, bnd_off;
+  // where every stream lies: a slab of the cache (hit / fill) or the batch's own buffers
+  enum : uint8_t { kPrivate = 0, kHit = 1, kFill = 2 };
+  std::vector<uint8_t> where(streams.size(), kPrivate);
+  std::vector<uint64_t> ent_at(streams.size(), 0), bnd_at(streams.size(), 0);   // device addresses
+  for (size_t si = 0; si < streams.size(); ++si)
+    streams[si].n_tiles = (b->segs[streams[si].seg]->dev.num_docs + kJoinTile - 1) / kJoinTile;
+  lap("  streams: cache lookup");
+  const int device = b->seg->device;
+  const uint64_t budget = scache::budget_bytes(device);
+  if (budget) {
+    scache::Cache& c = scache::of(device);
+    std::vector<scache::SlabPtr> gone;   // evicted: freed behind the lock
+    std::vector<uint32_t> missed;
+    {
+      std::unordered_set<scache::Slab*> seen;
+      std::lock_guard<std::mutex> lock(c.m);
+      for (size_t si = 0; si < streams.size(); ++si) {
+        if (!streams[si].n) continue;   // (an empty list: no entries, no k_join work)
+        auto it = c.map.find(scache::key_of(b->segs[streams[si].seg]->uid, streams[si].term));
+        if (it == c.map.end()) {
+          ++c.misses;
+          missed.push_back(uint32_t(si));
+          continue;
+        }
+        scache::Slab* sl = it->second.slab;
+        if (!sl->queued) {   // claimed by a batch that has not queued its decode yet: not waited for
+          ++c.misses;
+          continue;
+        }
+        ++c.hits;
+        where[si] = kHit;
+        ent_at[si] = it->second.entries;
+        bnd_at[si] = it->second.bounds;
+        sl->last_use = ++c.clock;
+        if (seen.insert(sl).second) {
+          ++sl->pins;
+          for (const scache::SlabPtr& sp : c.slabs)
+            if (sp.get() == sl) b->join.pinned.push_back(sp);
+        }
+      }
+    }
+    // the misses, segment by segment, in slabs of at most kSlabEntries entries
+    std::stable_sort(missed.begin(), missed.end(),
+                     [&](uint32_t x, uint32_t y) { return streams[x].seg < streams[y].seg; });
+    for (size_t from = 0; from < missed.size();) {
+      size_t to = from;
+      uint64_t e = 0, bn = 0;
+      std::vector<uint64_t> e_off, b_off;
+      while (to < missed.size() && streams[missed[to]].seg == streams[missed[from]].seg &&
+             (to == from || e + streams[missed[to]].n <= scache::kSlabEntries)) {
+        e_off.push_back(e);
+        b_off.push_back(bn);
+        e += (uint64_t(streams[missed[to]].n) + scache::kAlign - 1) / scache::kAlign * scache::kAlign;
+        bn += uint64_t(streams[missed[to]].n_tiles) + 1;
+        ++to;
+      }
+      const uint64_t bytes = pool::size_class((e + kJoinSlack + bn) * 4);
+      bool room = false;
+      {
+        std::lock_guard<std::mutex> lock(c.m);
+        room = bytes <= budget && scache::make_room_locked(c, bytes, budget, gone);
+        if (room) c.held += bytes;   // (reserved: the allocation itself happens outside the lock)
+      }
+      gone.clear();
+      scache::SlabPtr sl;
+      if (room) {
+        sl = std::make_shared<scache::Slab>();
+        if (!sl->mem.alloc((e + kJoinSlack + bn) * 4)) {
+          std::lock_guard<std::mutex> lock(c.m);
+          c.held -= bytes;
+          sl.reset();
+        }
+      }
+      if (sl) {
+        irs_hip_segment* sg = b->segs[streams[missed[from]].seg];
+        sl->bytes = bytes;
+        sl->entries = e;
+        sl->seg_uid = sg->uid;
+        sl->n_streams = uint32_t(to - from);
+        sl->pins = 1;
+        sl->listed = true;
+        uint32_t* base = sl->mem.as<uint32_t>();
+        std::lock_guard<std::mutex> lock(c.m);
+        sl->last_use = ++c.clock;
+        for (size_t i = from; i < to; ++i) {
+          const uint32_t si = missed[i];
+          where[si] = kFill;
+          ent_at[si] = reinterpret_cast<uint64_t>(base + e_off[i - from]);
+          bnd_at[si] = reinterpret_cast<uint64_t>(base + e + kJoinSlack + b_off[i - from]);
+          // (another batch may have claimed the term since the lookup: its slab keeps the name)
+          if (c.map.emplace(scache::key_of(sg->uid, streams[si].term),
+                            scache::Where{sl.get(), ent_at[si], bnd_at[si]}).second)
+            sl->terms.push_back(streams[si].term);
+        }
+        c.slabs.push_back(sl);
+        b->join.pinned.push_back(sl);
+        b->join.fills.push_back(sl);
+      }
+      from = to;
+    }
+  }
+  b->join.fill_pending = !b->join.fills.empty();
+  uint64_t entries = 0, bounds = 0;   // of the private streams
+  b->join.n_private = b->join.n_fill = 0;
   for (size_t si = 0; si < streams.size(); ++si) {
     const irs_hip_segment* sg = b->segs[streams[si].seg];
     const DevTerm& t = sg->terms[streams[si].term];
-    ent_off.push_back(entries);
-    bnd_off.push_back(bounds);
-    const uint32_t n_tiles = (sg->dev.num_docs + kJoinTile - 1) / kJoinTile;
+    if (where[si] == kHit) continue;
+    ++(where[si] == kFill ? b->join.n_fill : b->join.n_private);
     const uint32_t nb = t.nblk + ((t.docs_count == 1 || t.tail_n) ? 1u : 0u);
     for (uint32_t first = 0; first < nb; first += kJoinBlocks)
       wgs.push_back(WgRef{uint32_t(si), first});
+    if (where[si] == kFill) continue;
+    ent_at[si] = entries;   // (offsets until the buffers are there)
+    bnd_at[si] = bounds;
     entries += t.docs_count;
-    bounds += uint64_t(n_tiles) + 1;
+    bounds += uint64_t(streams[si].n_tiles) + 1;
   }
   if (wgs.size() > 0x7FFFFFFFull) return false;
   lap("  streams: work list order");
@@ -176,13 +317,15 @@ bool build_streams(irs_hip_batch* b) {
     // (a counting sort over 1024 positions per segment: this runs once per batch on the host,
     // in front of the batch's first kernel)
     constexpr uint32_t kPos = 1024;
-    std::vector<uint32_t> key(wgs.size()), start(b->segs.size() * kPos + 1, 0);
+    // (the private streams' workgroups first, then the fills': a later run launches only the first)
+    std::vector<uint32_t> key(wgs.size()), start(2 * b->segs.size() * kPos + 1, 0);
     for (size_t i = 0; i < wgs.size(); ++i) {
       const StreamRec& sr = streams[wgs[i].stream];
       const DevTerm& t = b->segs[sr.seg]->terms[sr.term];
       const uint32_t nb = t.nblk + ((t.docs_count == 1 || t.tail_n) ? 1u : 0u);
       const uint64_t at = (uint64_t(2u * wgs[i].first + kJoinBlocks) * kPos) / (2ull * (nb + kJoinBlocks));
-      key[i] = sr.seg * kPos + uint32_t(std::min<uint64_t>(at, kPos - 1));
+      key[i] = ((where[wgs[i].stream] == kFill ? uint32_t(b->segs.size()) : 0u) + sr.seg) * kPos +
+               uint32_t(std::min<uint64_t>(at, kPos - 1));
       ++start[key[i] + 1];
     }
     for (size_t k = 1; k < start.size(); ++k) start[k] += start[k - 1];
@@ -191,8 +334,14 @@ bool build_streams(irs_hip_batch* b) {
     wgs.swap(sorted);
   }
   lap("  streams: buffers");
-  if (!b->join.d_entries.alloc((entries + kJoinSlack) * 4) || !b->join.d_bounds.alloc((bounds + 1) * 4) ||
-      !b->join.d_streams.alloc(std::max<size_t>(1, streams.size()) * sizeof(StreamRec)) ||
+  if (b->join.n_private) {
+    if (!b->join.d_entries.alloc((entries + kJoinSlack) * 4) || !b->join.d_bounds.alloc((bounds + 1) * 4))
+      return false;
+  } else {   // (every stream lies in the cache)
+    b->join.d_entries.release();
+    b->join.d_bounds.release();
+  }
+  if (!b->join.d_streams.alloc(std::max<size_t>(1, streams.size()) * sizeof(StreamRec)) ||
       !b->join.d_wgs.alloc(std::max<size_t>(1, wgs.size()) * sizeof(JoinWg)) ||
       !b->join.d_jterms.alloc(jterms.size() * sizeof(JoinTerm)) ||
       !b->join.d_args.alloc(2 * sizeof(JoinArgs)) ||
@@ -243,9 +392,12 @@ bool build_streams(irs_hip_batch* b) {
     }
   }
   for (size_t i = 0; i < streams.size(); ++i) {
-    streams[i].entries = reinterpret_cast<uint64_t>(b->join.d_entries.as<uint32_t>() + ent_off[i]);
-    streams[i].bounds = reinterpret_cast<uint64_t>(b->join.d_bounds.as<uint32_t>() + bnd_off[i]);
-    streams[i].n_tiles = (b->segs[streams[i].seg]->dev.num_docs + kJoinTile - 1) / kJoinTile;
+    if (where[i] == kPrivate) {
+      ent_at[i] = reinterpret_cast<uint64_t>(b->join.d_entries.as<uint32_t>() + ent_at[i]);
+      bnd_at[i] = reinterpret_cast<uint64_t>(b->join.d_bounds.as<uint32_t>() + bnd_at[i]);
+    }
+    streams[i].entries = ent_at[i];
+    streams[i].bounds = bnd_at[i];
     const Sig& sig = sigs[stream_sig[i]];
     streams[i].kind = sig.kind;
     streams[i].nc = sig.nc;
@@ -305,24 +457,57 @@ bool build_streams(irs_hip_batch* b) {
     }
   }
   // (the slack behind the last stream is only ever read by masked-off look-ahead: zero it once)
-  b->join.slack_zeroed = false;   // (run_impl zeroes it on the run's stream)
+  b->join.slack_zeroed = !b->join.n_private;   // (run_impl zeroes it on the run's stream)
   if (!b->up.copy(b->join.d_streams.p, streams.data(), streams.size() * sizeof(StreamRec)) ||
       !b->up.copy(b->join.d_jterms.p, jterms.data(), jterms.size() * sizeof(JoinTerm)) ||
       !b->up.copy(b->join.d_units.p, b->join.units.data(), b->join.units.size() * 4) ||
       !b->up.copy(b->join.d_order.p, order.data(), order.size() * 4))
     return false;
   b->join.n_streams = uint32_t(streams.size());
-  b->join.n_wgs = uint32_t(wgs.size());
+  b->join.n_wgs = b->join.n_wgs_fill = 0;
+  for (const WgRef& w : wgs) ++(where[w.stream] == kFill ? b->join.n_wgs_fill : b->join.n_wgs);
   b->join.entries = entries;
   return true;
 }
 
+// k_join for what the batch has to decode in this run: its private streams, and — once — the slabs
+// it claimed in the stream cache.  A run whose streams all lie in the cache queues nothing.
 bool launch_join(irs_hip_batch* b, rt::stream_t st) {
-  if (!b->join.n_wgs) return true;
+  const bool fill = b->join.fill_pending;
+  const uint32_t grid = b->join.n_wgs + (fill ? b->join.n_wgs_fill : 0u);
+  b->join.decoded_last = b->join.n_private + (fill ? b->join.n_fill : 0u);
+  if (!grid) return true;
+  bool ok = true;
+  if (fill)   // (the slack behind a slab's last stream is only ever read by masked-off look-ahead)
+    for (const scache::SlabPtr& s : b->join.fills)
+      ok = ok && rt::dmemset(s->mem.as<uint32_t>() + s->entries, 0, kJoinSlack * 4, st);
+  if (!ok) return false;
   with_layout(b->seg->dev.layout, [&](auto L) {
-    RT_LAUNCH((k_join<decltype(L)::value>), b->join.n_wgs, kThreads, 0, st, b->join.d_wgs.as<JoinWg>());
+    RT_LAUNCH((k_join<decltype(L)::value>), grid, kThreads, 0, st, b->join.d_wgs.as<JoinWg>());
   });
-  return rt::last_error_ok();
+  ok = rt::last_error_ok();
+  if (ok && fill) {
+    // from here on other batches are served these slabs: their runs wait for `filled`
+    for (const scache::SlabPtr& s : b->join.fills) {
+      s->fill_stream = st;
+      ok = ok && s->filled.record(st);
+    }
+    if (ok) {
+      scache::Cache& c = scache::of(b->seg->device);
+      std::lock_guard<std::mutex> lock(c.m);
+      for (const scache::SlabPtr& s : b->join.fills) s->queued = true;
+      b->join.fill_pending = false;
+    }
+  }
+  return ok;
+}
+// The slabs the batch reads out of the stream cache may still be filling on another stream (another
+// batch's plan stage, or this batch's own, queued ahead): the run's stream gets behind them.
+bool wait_for_streams(irs_hip_batch* b, rt::stream_t st) {
+  bool ok = true;
+  for (const scache::SlabPtr& s : b->join.pinned)
+    if (s->filled.made && !s->settled.load() && s->fill_stream != st) ok = ok && s->filled.wait(st);
+  return ok;
 }
 
 // Groups of a batch over several segments (irs_hip_batch_set_shared_threshold): the units of one

@@ -133,6 +133,21 @@ struct PoolBuf {  // owning allocation out of the pool of the device that was cu
 using DevBuf = PoolBuf<false>;
 using PinBuf = PoolBuf<true>;
 
+// A HIP event, created on first use and destroyed with its owner (sync / wait fail on one that
+// was never created)
+struct Event {
+  rt::event_t e{};
+  bool made = false;
+  Event() = default;
+  Event(const Event&) = delete;
+  Event& operator=(const Event&) = delete;
+  ~Event() { if (made) rt::event_destroy(e); }
+  bool create() { return made || (made = rt::event_create(&e)); }
+  bool record(rt::stream_t st) { return create() && rt::event_record(e, st); }
+  bool sync() const { return made && rt::event_sync(e); }
+  bool wait(rt::stream_t st) const { return made && rt::stream_wait(st, e); }   // st waits for it
+};
+
 // Host -> device uploads of a batch: the bytes are built in (or copied into) page-locked memory
 // and go out with asynchronous copies on the stream of the batch's next run — no copy from
 // pageable memory (the runtime stages those synchronously), no stream synchronisation, so a

@@ -5,6 +5,11 @@
 
 struct irs_hip_segment {
   int device = 0;
+  // the segment's name in the device's stream cache (an address comes back after a close)
+  uint32_t uid = [] {
+    static std::atomic<uint32_t> next{0};
+    return ++next;
+  }();
   DevSegment dev{};
   DevBuf d_doc, d_norms, d_terms, d_blk_off, d_blk_last, d_blk_bits, d_status;
   DevBuf d_blk_aoff, d_pk;     // packed-payload image (DevSegment::pk) and its offsets

@@ -844,6 +844,14 @@ class QueryBatch:
                    "irs_hip_batch_work")
         return a.value, p.value
 
+    def stream_counts(self):
+        """(distinct (segment, term) streams of the joined units, streams the last run decoded
+        itself): irs_hip_batch_stream_counts — the rest came out of the device's stream cache."""
+        d, n = C.c_uint32(), C.c_uint32()
+        _lib.check(self.L, self.L.irs_hip_batch_stream_counts(self.handle, C.byref(d), C.byref(n)),
+                   "irs_hip_batch_stream_counts")
+        return d.value, n.value
+
     def results(self):
         hits = np.zeros((self.nq, self.k), HIT)
         counts = np.zeros(self.nq, np.uint32)
@@ -902,6 +910,23 @@ class QueryBatch:
             self.close()
         except Exception:
             pass
+
+
+def stream_cache_stats(L=None, device=0):
+    """The device's cache of decoded posting streams (irs_hip_device_stream_cache_stats) as a dict:
+    bytes_held, budget, streams, hits, misses, evictions."""
+    L = L or _lib.lib()
+    st = _lib.StreamCacheStats()
+    _lib.check(L, L.irs_hip_device_stream_cache_stats(device, C.byref(st)),
+               "irs_hip_device_stream_cache_stats")
+    return {name: int(getattr(st, name)) for name, _ in st._fields_}
+
+
+def set_stream_cache(nbytes, L=None, device=0):
+    """The cache's byte budget (irs_hip_device_set_stream_cache); 0 switches it off."""
+    L = L or _lib.lib()
+    _lib.check(L, L.irs_hip_device_set_stream_cache(device, int(nbytes)),
+               "irs_hip_device_set_stream_cache")
 
 
 # -------------------------------------------------------------------- index --

@@ -475,7 +475,8 @@ int irs_hip_batch_configure(irs_hip_batch* batch, uint32_t tile_docs,
  *                        so does every unit with excluded terms (IRS_HIP_EXCLUDE): its own
  *                        mask of docs cannot ride on streams shared with other units (an
  *                        Or / min-match unit runs as work items, an And block driven, a
- *                        phrase on its phrase kernel);
+ *                        phrase on its phrase kernel) — and every unit restricted to a doc set
+ *                        (irs_hip_batch_set_doc_sets), whose mask is one more of that kind;
  *   IRS_HIP_PATH_AUTO    (default) by measured cost: plain disjunctions join when the batch's
  *                        streams are shared enough or its units many enough to pay for decoding
  *                        every distinct stream once (2.9 ps per distinct posting against 0.67 ps
@@ -582,7 +583,8 @@ int irs_hip_batch_profile(irs_hip_batch* batch, int enable);
 int irs_hip_batch_timings(irs_hip_batch* batch, float ms[IRS_HIP_K_COUNT]);
 /* Work accounting for the roofline: algorithmic bytes A(q)
  * summed over the batch = posting bytes of every query term (excluded terms included: their
- * doc blocks are read) + 1 norm byte per scored posting (norm_width) + 8*k result bytes; and the
+ * doc blocks are read) + 1 norm byte per scored posting (norm_width) + 8*k result bytes
+ * + (num_docs + 7) / 8 bytes per unit restricted to a doc set (its row is read); and the
  * number of scored postings. */
 int irs_hip_batch_work(irs_hip_batch* batch, uint64_t* algorithmic_bytes,
                        uint64_t* postings);
@@ -601,8 +603,9 @@ int irs_hip_batch_reruns(irs_hip_batch* batch, uint32_t* count);
 /* The doc mask unit `unit` (= segment * n_queries + query) ran with in the batch's last run, for
  * inspection/tests, in irs_hip_bit_union's layout (bit `doc` of 64-bit little-endian words,
  * n_words of them, docs beyond dropped): the segment's deleted docs plus every doc of the unit's
- * excluded terms — or just the deleted docs for a unit without excluded terms (an empty set when
- * the segment has none).  Waits for the run. */
+ * excluded terms plus — for a unit restricted to a doc set (irs_hip_batch_set_doc_sets) — every doc
+ * 1..num_docs that is not in its row; just the deleted docs for a unit without excluded terms and
+ * without a doc set (an empty set when the segment has none).  Waits for the run. */
 int irs_hip_batch_unit_mask(irs_hip_batch* batch, uint32_t unit, uint64_t* set, uint64_t n_words);
 
 /* filter::prepared::execute with Scorers::kUnordered (core/search/filter.hpp:52-78): the docs every
@@ -631,6 +634,55 @@ int irs_hip_batch_match_sets(irs_hip_batch* batch, uint64_t* sets, uint64_t n_wo
  * disjunction's doc set handed to a consumer on the device (bitset_doc_iterator.hpp). */
 int irs_hip_batch_match_sets_to_device(irs_hip_batch* batch, void* d_sets, uint64_t n_words,
                                        void* d_counts, void* stream);
+
+/* Doc-set filters (a compatible addition to ABI 12): the units of a batch restricted to doc sets on
+ * the device — the conjunction of a scored query with an UNSCORED child: the bitset_doc_iterator a
+ * multi-term query builds from its unscored terms (multiterm_query.cpp:36-87, 133-166), a
+ * column-existence filter, proxy_filter's cached bitset.  MakeConjunction leaves such a child out
+ * of the score (conjunction.hpp:461-467): it only decides which docs match.
+ *   d_sets       device memory, [n_rows][n_words] u64 in irs_hip_bit_union's layout (64-bit
+ *                little-endian words, bit index = doc id) — what irs_hip_batch_match_sets_to_device
+ *                and irs_hip_bit_union produce.  The row stride is n_words and may be larger than a
+ *                segment needs; bit 0 and the bits of docs beyond a segment's num_docs are ignored.
+ *   row_of_unit  host array [n_units], unit = segment * n_queries + query as for
+ *                irs_hip_batch_unit_mask; copied.  IRS_HIP_NO_DOC_SET: the unit is unrestricted.
+ * row_of_unit == NULL or n_rows == 0 clears the filters.  IRS_HIP_EINVAL: a row index >= n_rows;
+ * 64 * n_words <= num_docs of a segment that has a restricted unit; n_words > 2^26 (no segment has
+ * that many docs: the limit irs_hip_batch_match_sets puts on its rows) while a row is referenced;
+ * d_sets == NULL while a row is referenced.
+ * A restricted unit matches what it matches without the filter (the included part, minus deleted
+ * docs, minus the docs of IRS_HIP_EXCLUDE terms) intersected with its row: scores, order and merge
+ * do not change, total_hits counts what remains and the top k is drawn from it — for every op (OR,
+ * AND incl. IRS_HIP_GROUP_ALT, MINMATCH, PHRASE incl. IRS_HIP_PHRASE_ALT / IRS_HIP_PHRASE_REQUIRED)
+ * and for irs_hip_batch_match_sets*: a filtered batch's match sets are the intersections, so
+ * filters chain.  Scorer statistics are the caller's and do not change (the reference's are index
+ * statistics).
+ * The device form BORROWS d_sets: the words are read by the stage that builds the unit masks —
+ * irs_hip_batch_plan if the caller uses it, else irs_hip_batch_run — on that call's stream, and
+ * again in every recovery re-run, so they must stay valid and unchanged until the batch's results
+ * have been fetched or the filters are replaced or cleared.  A producer queued earlier on the same
+ * stream is seen without a host synchronisation.  The host form copies the rows into pool memory of
+ * the batch (IRS_HIP_ENOMEM when it cannot be had: the batch is then left without filters).
+ * Call before the batch's first run or between runs; the units are dealt again as after
+ * irs_hip_batch_configure.  A restricted unit takes the path of a unit with excluded terms
+ * (irs_hip_batch_set_path) and is treated like one by set_wand, set_min_scores, shared thresholds
+ * and set_comm; the unrestricted units of the batch choose their paths and give their results bit
+ * for bit as without the filters.  Whole doc tiles in which a restricted work-item unit can match
+ * nothing get no work items and are not visited; its count stays exact. */
+#define IRS_HIP_NO_DOC_SET 0xFFFFFFFFu
+int irs_hip_batch_set_doc_sets(irs_hip_batch* batch, const void* d_sets, uint64_t n_rows,
+                               uint64_t n_words, const uint32_t* row_of_unit);
+int irs_hip_batch_set_doc_sets_host(irs_hip_batch* batch, const uint64_t* sets, uint64_t n_rows,
+                                    uint64_t n_words, const uint32_t* row_of_unit);
+/* What the doc sets let the batch's last run skip (waits for it).  tiles / tiles_skipped: the doc
+ * tiles of the restricted units that ran as work items, and how many of them held no doc their
+ * unit's mask leaves (no work items, no visit) — exact.  leads / leads_skipped: lead pieces (the
+ * lead-item records: blocks of the lead term, or their pieces) of the restricted block-driven and
+ * phrase units in the last run's full pass, and how many ended after their own decode because none
+ * of their docs was left — counted only under irs_hip_batch_profile bit 1 (the counting mode: it
+ * costs atomics), 0 otherwise.  Any output may be NULL. */
+int irs_hip_batch_doc_set_stats(irs_hip_batch* batch, uint64_t* tiles, uint64_t* tiles_skipped,
+                                uint64_t* leads, uint64_t* leads_skipped);
 
 /* Multi-segment / multi-GPU merge: merges `n_lists` per-query
  * top-k lists (device pointers, each [n_queries][k] hits + [n_queries] counts,

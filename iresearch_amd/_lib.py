@@ -23,6 +23,7 @@ PHRASE_ALT = 0x200   # OR-ed into a phrase entry's kind: one more member of the 
 GROUP_ALT = PHRASE_ALT   # ... into an And entry's kind: one more member of the group (Or) before it
 PHRASE_REQUIRED = 0x400   # ... into a phrase entry's kind: a by_term child of the And that holds the phrase
 NO_TERM = 0xFFFFFFFF
+NO_DOC_SET = 0xFFFFFFFF   # row_of_unit of an unrestricted unit (irs_hip_batch_set_doc_sets)
 PATH_AUTO, PATH_ITEMS, PATH_JOINED = 0, 1, 2
 WAND_NONE, WAND_DIV_NORM, WAND_MAX_FREQ, WAND_MIN_NORM = 0, 1, 2, 3   # Scorer::WandType
 MAX_TERMS, MAX_K, MAX_PHRASE_TERMS, MAX_EXCLUDED = 16, 4096, 8, 16
@@ -87,6 +88,7 @@ SYMBOLS = (
     "irs_hip_segment_wand_source",
     "irs_hip_batch_touched", "irs_hip_batch_unit_mask",
     "irs_hip_batch_match_sets", "irs_hip_batch_match_sets_to_device",
+    "irs_hip_batch_set_doc_sets", "irs_hip_batch_set_doc_sets_host", "irs_hip_batch_doc_set_stats",
     "irs_hip_comm_unique_id", "irs_hip_comm_init_rank", "irs_hip_comm_destroy",
     "irs_hip_comm_library",
     "irs_hip_topk_allgather", "irs_hip_device_alloc", "irs_hip_device_free",
@@ -172,6 +174,12 @@ def bind(L: C.CDLL) -> C.CDLL:
     L.irs_hip_batch_match_sets.restype = C.c_int
     L.irs_hip_batch_match_sets_to_device.argtypes = [vp, vp, u64, vp, vp]
     L.irs_hip_batch_match_sets_to_device.restype = C.c_int
+    L.irs_hip_batch_set_doc_sets.argtypes = [vp, vp, u64, u64, vp]
+    L.irs_hip_batch_set_doc_sets.restype = C.c_int
+    L.irs_hip_batch_set_doc_sets_host.argtypes = [vp, vp, u64, u64, vp]
+    L.irs_hip_batch_set_doc_sets_host.restype = C.c_int
+    L.irs_hip_batch_doc_set_stats.argtypes = [vp, P(u64), P(u64), P(u64), P(u64)]
+    L.irs_hip_batch_doc_set_stats.restype = C.c_int
     L.irs_hip_comm_unique_id.argtypes, L.irs_hip_comm_unique_id.restype = [vp], C.c_int
     L.irs_hip_comm_init_rank.argtypes = [i32, vp, i32, i32, P(vp)]
     L.irs_hip_comm_init_rank.restype = C.c_int

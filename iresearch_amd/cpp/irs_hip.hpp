@@ -26,6 +26,7 @@
 #include <stdexcept>
 #include <utility>
 #include <string>
+#include <optional>
 #include <variant>
 #include <vector>
 
@@ -188,9 +189,19 @@ struct And {
 // scorers).  An And of several terms with Not children is Exclusion{And{...}, ...}; Not(Or of
 // terms) is several excluded terms.  Or with Not children and filters of only Nots match all
 // docs but some (a zero-score fill) and are not offered.
+// A doc set as a child of that And: row `row` of the bitsets the batch is given
+// (QueryBatch::set_doc_sets) — the reference's unscored child of a conjunction: the
+// bitset_doc_iterator of a multi-term query's unscored terms (multiterm_query.cpp:36-87), a
+// column-existence filter, proxy_filter's cached bitset.  It only decides which docs match
+// (MakeConjunction leaves an iterator with the default score out of the score,
+// conjunction.hpp:461-467).
+struct by_doc_set {
+  uint32_t row = 0;
+};
 struct Exclusion {
   std::variant<by_term, Or, And, by_phrase> incl;
   std::vector<by_term> excl;   // at most IRS_HIP_MAX_EXCLUDED
+  std::optional<by_doc_set> doc_set;   // the And's by_doc_set child (next to its Nots, or alone)
 };
 using filter = std::variant<by_term, Or, And, by_phrase, Exclusion>;
 
@@ -214,6 +225,9 @@ struct PreparedQuery {
   // ... unless segment_terms[s][i] names slot i's ordinal in segment s (IRS_HIP_NO_TERM: the
   // segment has no state for it) — what a scored multi-term filter prepares (prepare_expansion)
   std::vector<std::vector<uint32_t>> segment_terms;
+  // the row of the batch's doc sets the query is restricted to (by_doc_set under its And;
+  // IRS_HIP_NO_DOC_SET: none) — no part of what is scored
+  uint32_t doc_set = IRS_HIP_NO_DOC_SET;
 };
 
 // filter::prepare for a list of filters against ALL segments (statistics are index-global:
@@ -410,6 +424,10 @@ std::vector<PreparedQuery> prepare(const std::vector<filter>& filters, const Sco
         e.kind = IRS_HIP_EXCLUDE;
         q.terms.push_back(e);
       }
+      if (x->doc_set) {
+        if (x->doc_set->row == IRS_HIP_NO_DOC_SET) throw illegal_argument(IRS_HIP_EINVAL, "by_doc_set: a row index");
+        q.doc_set = x->doc_set->row;
+      }
     } else {
       fill(q, f);
     }
@@ -483,6 +501,7 @@ class SegmentReader {
 };
 
 // ---- a batch of prepared queries on one or several segments of one device -------------------
+class DeviceBuffer;
 class QueryBatch {
  public:
   struct Results {
@@ -507,8 +526,11 @@ class QueryBatch {
   QueryBatch(const std::vector<const SegmentReader*>& segments,
              const std::vector<PreparedQuery>& prepared, uint32_t k)
     : n_segments_{uint32_t(segments.size())}, n_queries_{uint32_t(prepared.size())}, k_{k} {
-    for (uint32_t q = 0; q < n_queries_; ++q)
-      part_[prepared[q].op == IRS_HIP_OP_PHRASE ? 1 : 0].index.push_back(q);
+    for (uint32_t q = 0; q < n_queries_; ++q) {
+      Part& part = part_[prepared[q].op == IRS_HIP_OP_PHRASE ? 1 : 0];
+      part.index.push_back(q);
+      part.rows.push_back(prepared[q].doc_set);
+    }
     try {
       for (Part& part : part_) {
         if (part.index.empty()) continue;
@@ -638,6 +660,10 @@ class QueryBatch {
     return any;
   }
   QueryBatch& run(void* stream = nullptr) {
+    for (const Part& part : part_)
+      for (uint32_t r : part.rows)
+        if (r != IRS_HIP_NO_DOC_SET && !doc_sets_given_)
+          throw illegal_argument(IRS_HIP_EINVAL, "a query with a by_doc_set needs set_doc_sets before run()");
     for (Part& part : part_)
       if (part.h) check(irs_hip_batch_run(part.h, stream), "irs_hip_batch_run");
     return *this;
@@ -755,6 +781,43 @@ class QueryBatch {
           "irs_hip_batch_match_sets_to_device");
     return *this;
   }
+  // The doc sets the queries' by_doc_set children name rows of (irs_hip_batch_set_doc_sets):
+  // [n_rows][n_words] u64, bit = doc id (irs_hip_bit_union's layout), every segment of the batch
+  // reading the same row for a query.  Device memory is BORROWED — valid and unchanged until the
+  // results have been fetched or the sets are replaced; host memory is copied.  n_rows == 0
+  // clears.  A query with a by_doc_set needs them before run(): illegal_argument otherwise (the
+  // row is beyond the sets).  Before the first run() or between runs.
+  QueryBatch& set_doc_sets(const uint64_t* sets, uint64_t n_rows, uint64_t n_words) {
+    return doc_sets(sets, true, n_rows, n_words);
+  }
+  QueryBatch& set_doc_sets(const DeviceBuffer& d_sets, uint64_t n_rows, uint64_t n_words);
+  QueryBatch& set_doc_sets_device(const void* d_sets, uint64_t n_rows, uint64_t n_words) {
+    return doc_sets(d_sets, false, n_rows, n_words);
+  }
+  // what the doc sets let the last run skip (irs_hip_batch_doc_set_stats): doc tiles of the
+  // restricted work-item units (exact), lead pieces of the block-driven and phrase ones (counted
+  // in a counting run only: irs_hip_batch_profile bit 1)
+  struct DocSetStats { uint64_t tiles = 0, tiles_skipped = 0, leads = 0, leads_skipped = 0; };
+  DocSetStats doc_set_stats() const {
+    DocSetStats total;
+    for (const Part& part : part_) {
+      if (!part.h) continue;
+      DocSetStats s;
+      check(irs_hip_batch_doc_set_stats(part.h, &s.tiles, &s.tiles_skipped, &s.leads, &s.leads_skipped),
+            "irs_hip_batch_doc_set_stats");
+      total.tiles += s.tiles;
+      total.tiles_skipped += s.tiles_skipped;
+      total.leads += s.leads;
+      total.leads_skipped += s.leads_skipped;
+    }
+    return total;
+  }
+  // the counting mode of the block-driven kernels (irs_hip_batch_profile bit 1): a diagnostic run
+  QueryBatch& count_work(bool enable) {
+    for (Part& part : part_)
+      if (part.h) check(irs_hip_batch_profile(part.h, enable ? 2 : 0), "irs_hip_batch_profile");
+    return *this;
+  }
   // the one device batch of a list of queries that are all boolean or all by_phrase
   // (what search_sharded hands to irs_hip_batch_results_to_device)
   irs_hip_batch* single_part() const {
@@ -788,9 +851,26 @@ class QueryBatch {
   struct Part {  // [0] boolean queries, [1] phrase queries
     irs_hip_batch* h = nullptr;
     std::vector<uint32_t> index;  // position of each of its queries in the caller's list
+    std::vector<uint32_t> rows;   // ... and the row of the doc sets it is restricted to
   };
+  QueryBatch& doc_sets(const void* sets, bool host, uint64_t n_rows, uint64_t n_words) {
+    for (Part& part : part_) {
+      if (!part.h) continue;
+      std::vector<uint32_t> row_of;   // [segment][query of the part]
+      for (uint32_t s = 0; s < n_segments_; ++s) row_of.insert(row_of.end(), part.rows.begin(), part.rows.end());
+      const uint32_t* r = n_rows ? row_of.data() : nullptr;
+      if (host)
+        check(irs_hip_batch_set_doc_sets_host(part.h, static_cast<const uint64_t*>(sets), n_rows, n_words, r),
+              "irs_hip_batch_set_doc_sets_host");
+      else
+        check(irs_hip_batch_set_doc_sets(part.h, sets, n_rows, n_words, r), "irs_hip_batch_set_doc_sets");
+    }
+    doc_sets_given_ = n_rows != 0;
+    return *this;
+  }
   Part part_[2];
   uint32_t n_segments_, n_queries_, k_;
+  bool doc_sets_given_ = false;
 };
 
 // ---- the harness: one heap over all segments (utils/index-search.cpp:719-787) ---------------
@@ -1925,6 +2005,11 @@ class DeviceBuffer {
   uint64_t bytes_;
   void* p_ = nullptr;
 };
+
+inline QueryBatch& QueryBatch::set_doc_sets(const DeviceBuffer& d_sets, uint64_t n_rows, uint64_t n_words) {
+  if (d_sets.bytes() < n_rows * n_words * 8u) throw illegal_argument(IRS_HIP_EINVAL, "set_doc_sets: the buffer is smaller than [n_rows][n_words]");
+  return doc_sets(d_sets.get(), false, n_rows, n_words);
+}
 
 class Communicator {
  public:

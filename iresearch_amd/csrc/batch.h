@@ -145,14 +145,32 @@ struct BlockWork {
 // n_pilot, pilot_stride); d_lg, d_lead_of, n_phrase_wgs, `variadic` and `required` stay unused.
 struct AnyWork : BlockWork {};
 
-// Units with excluded terms (IRS_HIP_EXCLUDE, excl.h): one doc mask per distinct (segment, present
-// excluded terms), built by k_excl_mask in every run's plan stage; DevQuery::dead points at it
+// Units with excluded terms (IRS_HIP_EXCLUDE) or a doc set (irs_hip_batch_set_doc_sets), excl.h: one
+// doc mask per distinct (segment, doc-set row, present excluded terms), built by k_excl_mask in
+// every run's plan stage; DevQuery::dead points at it
 struct ExclWork {
   std::vector<ExclMask> masks;   // (the `out` pointers lie in d_words)
   std::vector<uint32_t> terms;   // the masks' term ordinals, ExclMask::first / n
   DevBuf d_words, d_masks, d_terms;
   uint32_t slices = 0;           // k_excl_mask workgroups per mask (of the largest segment's)
   bool on() const { return !masks.empty(); }
+  // what create found per unit — the masks are made anew when the doc sets change:
+  // unit_terms[unit_first[u] .. unit_first[u + 1]) = its present excluded terms, sorted, distinct;
+  // unit_live[u]: some doc may match it at all (it has rows)
+  std::vector<uint32_t> unit_terms, unit_first;
+  std::vector<uint8_t> unit_live;
+  // the doc sets: [set_rows][set_words] u64 on the device — the caller's memory, or d_own (the host
+  // form's copy); row_of[unit] (IRS_HIP_NO_DOC_SET: unrestricted), empty: no unit is restricted
+  const uint64_t* sets = nullptr;
+  uint64_t set_rows = 0, set_words = 0;
+  std::vector<uint32_t> row_of;
+  std::vector<uint8_t> restricted;   // [unit] its mask comes from a doc set
+  DevBuf d_own, d_restricted;
+  DevBuf d_tile_live;            // [tiles.n_total] k_tile_live's bytes (work-item units)
+  DevBuf d_leads;                // 2 x u64: lead pieces of restricted block-driven units / skipped ones
+  bool leads_counted = false;    // ... counted by the last run (irs_hip_batch_profile bit 1)
+  uint64_t set_bytes = 0;        // irs_hip_batch_work: (num_docs + 7) / 8 per restricted unit
+  bool sets_on() const { return !row_of.empty(); }
 };
 
 // Unscored execution (match.h, plan_match.h): the units as k_match_slice reads them, built with the

@@ -480,6 +480,10 @@ k_conj(ConjArgs A, uint32_t pilot) {
   };
   wave::sync();
   if (n == 0) return;   // (a piece behind the end of a short tail)
+  if (qd.dead && wave::ballot(live[0] || live[1]) == 0) {   // (wave-uniform) no lead doc is left
+    lead_skipped(A, unit, counting, bytes, lane);
+    return;
+  }
   const uint32_t dlo = wave::uniform(docs[0]), dhi = wave::uniform(docs[n - 1]);
   // bucket of a doc: (doc - dlo) >> s, below 32 * kConjWords
   const uint32_t span = dhi - dlo;

@@ -17,6 +17,7 @@
 #include <mutex>
 #include <new>
 #include <thread>
+#include <tuple>
 #include <type_traits>
 #include <unordered_map>
 #include <unordered_set>
@@ -226,11 +227,83 @@ bool alloc_scratch(irs_hip_batch* b, uint64_t first_words, uint64_t item_bound) 
         !b->tiles.d_scan_parts.alloc((parts + 1) * sizeof(uint64_t)) ||
         !b->tiles.d_items.alloc(item_bound * sizeof(ItemG)) ||
         !b->tiles.d_args.alloc(sizeof(ScoreArgs)) ||
-        !b->tiles.d_ub.alloc((tiles + 1) * sizeof(float)))
+        !b->tiles.d_ub.alloc((tiles + 1) * sizeof(float)) ||
+        (b->excl.sets_on() && !b->excl.d_tile_live.alloc(tiles + 1)))
       return false;
   }
   // (the unit records last: dealing the units and building the streams filled fields in)
   return b->up.copy(b->d_queries.p, b->queries.data(), b->queries.size() * sizeof(DevQuery));
+}
+
+// The distinct doc masks of the batch, from what create recorded per unit (its present excluded
+// terms) and the doc sets in force: one per (segment, doc-set row, terms), every unit that has one
+// pointing at it, the others at their segment's deleted docs.  The words are one pool block.  At
+// create, and whenever irs_hip_batch_set_doc_sets changes the rows (the batch is quiet then: the
+// tables are replaced).
+int build_masks(irs_hip_batch* b) {
+  ExclWork& x = b->excl;
+  // (tables staged for an upload that never went out: their buffers may change below)
+  b->up.pending.erase(std::remove_if(b->up.pending.begin(), b->up.pending.end(), [&](const Stager::Piece& p) {
+    return p.dst == x.d_masks.p || p.dst == x.d_terms.p || p.dst == x.d_restricted.p;
+  }), b->up.pending.end());
+  x.masks.clear();
+  x.terms.clear();
+  x.restricted.assign(b->nq, 0);
+  x.set_bytes = 0;
+  std::map<std::tuple<uint32_t, uint32_t, std::vector<uint32_t>>, uint32_t> mask_ids;
+  std::vector<uint32_t> mask_of(b->nq, 0);   // [unit] mask + 1, 0: none
+  std::vector<uint32_t> terms;
+  for (uint32_t q = 0; q < b->nq; ++q) {
+    const uint32_t s = q / b->nq_user;
+    const irs_hip_segment* seg = b->segs[s];
+    b->queries[q].dead = seg->dev.dead;
+    const uint32_t row = x.sets_on() ? x.row_of[q] : IRS_HIP_NO_DOC_SET;
+    if (row != IRS_HIP_NO_DOC_SET) x.set_bytes += (uint64_t(seg->dev.num_docs) + 7u) / 8u;
+    terms.assign(x.unit_terms.begin() + x.unit_first[q], x.unit_terms.begin() + x.unit_first[q + 1]);
+    if (!x.unit_live[q] || (terms.empty() && row == IRS_HIP_NO_DOC_SET)) continue;
+    auto ins = mask_ids.emplace(std::make_tuple(s, row, terms), uint32_t(x.masks.size()));
+    if (ins.second) {
+      ExclMask m{};
+      m.seg = s;
+      m.first = uint32_t(x.terms.size());
+      m.n = uint32_t(terms.size());
+      m.words = dead_words(seg->dev.num_docs);
+      m.dead = seg->dev.dead;
+      m.num_docs = seg->dev.num_docs;
+      if (row != IRS_HIP_NO_DOC_SET) {
+        m.set = x.sets + uint64_t(row) * x.set_words;
+        m.set_words = x.set_words;
+      }
+      x.masks.push_back(m);
+      x.terms.insert(x.terms.end(), terms.begin(), terms.end());
+    }
+    mask_of[q] = ins.first->second + 1u;
+    x.restricted[q] = row != IRS_HIP_NO_DOC_SET;
+  }
+  if (x.sets_on() && (!x.d_restricted.alloc(b->nq) || !b->up.copy(x.d_restricted.p, x.restricted.data(), b->nq)))
+    return IRS_HIP_ENOMEM;
+  if (!x.on()) return IRS_HIP_OK;
+  uint64_t words = 0, most = 0;
+  for (const ExclMask& m : x.masks) {
+    words += m.words;
+    most = std::max(most, m.words);
+  }
+  if (!x.d_words.alloc(words * 4) || !x.d_masks.alloc(x.masks.size() * sizeof(ExclMask)) ||
+      !x.d_terms.alloc(std::max<size_t>(x.terms.size(), 1) * 4))
+    return IRS_HIP_ENOMEM;
+  words = 0;
+  for (ExclMask& m : x.masks) {
+    m.out = x.d_words.as<uint32_t>() + words;
+    words += m.words;
+  }
+  for (uint32_t q = 0; q < b->nq; ++q)
+    if (mask_of[q]) b->queries[q].dead = x.masks[mask_of[q] - 1u].out;
+  x.slices = uint32_t((most + b->knobs.excl_slice - 1) / b->knobs.excl_slice);
+  if (uint64_t(x.slices) * x.masks.size() > 0x7FFFFFFFull) return IRS_HIP_EUNSUPPORTED;
+  if (!b->up.copy(x.d_masks.p, x.masks.data(), x.masks.size() * sizeof(ExclMask)) ||
+      !b->up.copy(x.d_terms.p, x.terms.data(), x.terms.size() * 4))
+    return IRS_HIP_ENOMEM;
+  return IRS_HIP_OK;
 }
 
 // The doc masks of the units with excluded terms (excl.h): every distinct mask in one launch — in the
@@ -467,8 +540,8 @@ static int batch_create_multi_impl(irs_hip_segment* const* segs, uint32_t n_segs
     std::vector<DevQTerm> row;
     std::vector<double> smins;
     std::vector<uint32_t> excl;   // a unit's present excluded terms
-    std::map<std::pair<uint32_t, std::vector<uint32_t>>, uint32_t> mask_ids;   // (segment, terms) -> mask
-    std::vector<uint32_t> mask_of(nq, 0);   // [unit] mask + 1, 0: none
+    b->excl.unit_first.assign(1, 0u);
+    b->excl.unit_live.assign(nq, 0);
     std::vector<uint32_t> row_group;        // per present row of a grouped unit: its group
     for (uint32_t q = 0; q < nq && rc == IRS_HIP_OK; ++q) {
       // unit q = (segment q / nq_user, query q % nq_user); the segment's own term entries
@@ -726,25 +799,17 @@ static int batch_create_multi_impl(irs_hip_segment* const* segs, uint32_t n_segs
       if (need == 0xFFu) row.clear();
       // the unit's masked docs: its segment's deleted ones, and for a unit with present excluded
       // terms a mask of its own (dead | their docs), shared by the units with the same terms
+      // (build_masks, behind the loop — and again when the batch gets doc sets)
       dq.dead = seg->dev.dead;
+      b->excl.unit_live[q] = !row.empty();
       if (!row.empty() && !excl.empty()) {
         std::sort(excl.begin(), excl.end());
         excl.erase(std::unique(excl.begin(), excl.end()), excl.end());
-        auto ins = mask_ids.emplace(std::make_pair(q / nq_user, excl), uint32_t(b->excl.masks.size()));
-        if (ins.second) {
-          ExclMask m{};
-          m.seg = q / nq_user;
-          m.first = uint32_t(b->excl.terms.size());
-          m.n = uint32_t(excl.size());
-          m.words = dead_words(seg->dev.num_docs);
-          m.dead = seg->dev.dead;
-          b->excl.masks.push_back(m);
-          b->excl.terms.insert(b->excl.terms.end(), excl.begin(), excl.end());
-        }
-        mask_of[q] = ins.first->second + 1u;
+        b->excl.unit_terms.insert(b->excl.unit_terms.end(), excl.begin(), excl.end());
         // (what k_excl_mask reads for the unit: the excluded terms' doc blocks)
         for (uint32_t t : excl) b->alg_bytes += uint64_t(seg->terms[t].blocks_bytes) + seg->terms[t].tail_bytes;
       }
+      b->excl.unit_first.push_back(uint32_t(b->excl.unit_terms.size()));
       // A doc that exists matches at least `need` terms: c matched postings score at least
       // c times the mean of the `need` smallest per-term minima — the score below which no
       // posting of a matching doc falls ON AVERAGE, which is what bounds the relative error of
@@ -876,31 +941,7 @@ static int batch_create_multi_impl(irs_hip_segment* const* segs, uint32_t n_segs
       b->k_max = std::max(b->k_max, in.k);
     }
     if (b->knobs.acc64) b->acc32 = false;   // tuning / test knob
-    if (rc == IRS_HIP_OK && b->excl.on()) {
-      // the masks' words, one pool block; every unit with a mask points at its own
-      uint64_t words = 0, most = 0;
-      for (const ExclMask& m : b->excl.masks) {
-        words += m.words;
-        most = std::max(most, m.words);
-      }
-      if (!b->excl.d_words.alloc(words * 4) || !b->excl.d_masks.alloc(b->excl.masks.size() * sizeof(ExclMask)) ||
-          !b->excl.d_terms.alloc(b->excl.terms.size() * 4)) {
-        rc = IRS_HIP_ENOMEM;
-      } else {
-        words = 0;
-        for (ExclMask& m : b->excl.masks) {
-          m.out = b->excl.d_words.as<uint32_t>() + words;
-          words += m.words;
-        }
-        for (uint32_t q = 0; q < nq; ++q)
-          if (mask_of[q]) b->queries[q].dead = b->excl.masks[mask_of[q] - 1u].out;
-        b->excl.slices = uint32_t((most + b->knobs.excl_slice - 1) / b->knobs.excl_slice);
-        if (uint64_t(b->excl.slices) * b->excl.masks.size() > 0x7FFFFFFFull) rc = IRS_HIP_EUNSUPPORTED;
-        else if (!b->up.copy(b->excl.d_masks.p, b->excl.masks.data(), b->excl.masks.size() * sizeof(ExclMask)) ||
-                 !b->up.copy(b->excl.d_terms.p, b->excl.terms.data(), b->excl.terms.size() * 4))
-          rc = IRS_HIP_ENOMEM;
-      }
-    }
+    if (rc == IRS_HIP_OK) rc = build_masks(b);
     for (uint32_t q = 0; q < nq && rc == IRS_HIP_OK && q < exps.size(); ++q) {
       const int e = exps[q];
       b->queries[q].fx_mul = std::ldexp(1.f, (b->acc32 ? 30 : 29) - e);
@@ -1073,6 +1114,92 @@ static int batch_set_min_scores_impl(irs_hip_batch* b, const float* min_scores) 
   return IRS_HIP_OK;
 }
 
+// irs_hip_batch_set_doc_sets / _host: the rows ([n_rows][n_words] u64, device memory the caller
+// keeps valid — or host memory, copied into a block of the batch) and every unit's row.  The masks
+// are made anew and the units dealt again: a restricted unit is a masked unit.
+static int batch_set_doc_sets_impl(irs_hip_batch* b, const void* sets, bool host, uint64_t n_rows,
+                                   uint64_t n_words, const uint32_t* row_of_unit) {
+  if (!b) return IRS_HIP_EINVAL;
+  if (!rt::set_device(b->seg->device)) return IRS_HIP_EHIP;
+  std::vector<uint32_t> rows;
+  if (row_of_unit && n_rows) {
+    bool any = false;
+    for (uint32_t u = 0; u < b->nq; ++u) {
+      const uint32_t r = row_of_unit[u];
+      if (r == IRS_HIP_NO_DOC_SET) continue;
+      // every doc of the unit's segment has a bit in its row
+      if (r >= n_rows || 64u * n_words <= uint64_t(b->segs[u / b->nq_user]->dev.num_docs) ||
+          n_words > 0x4000000ull)
+        return IRS_HIP_EINVAL;
+      any = true;
+    }
+    if (any && !sets) return IRS_HIP_EINVAL;
+    if (any) rows.assign(row_of_unit, row_of_unit + b->nq);   // (none restricted: the same as cleared)
+  }
+  if (!quiesce(b)) return IRS_HIP_EHIP;
+  ExclWork& x = b->excl;
+  b->up.pending.erase(std::remove_if(b->up.pending.begin(), b->up.pending.end(), [&](const Stager::Piece& p) {
+    return x.d_own.p && p.dst == x.d_own.p;
+  }), b->up.pending.end());
+  int rc = IRS_HIP_OK;
+  x.sets = static_cast<const uint64_t*>(sets);
+  if (rows.empty() || !host) {
+    x.d_own.release();
+  } else {
+    // the host form: the rows go out with the batch's next uploads, into memory of its own
+    const size_t bytes = size_t(n_rows) * n_words * 8u;
+    void* at = x.d_own.alloc(bytes) ? b->up.put(x.d_own.p, bytes) : nullptr;
+    if (at) {
+      std::memcpy(at, sets, bytes);
+      x.sets = x.d_own.as<uint64_t>();
+    } else {   // (the batch is left without filters)
+      x.d_own.release();
+      rows.clear();
+      rc = IRS_HIP_ENOMEM;
+    }
+  }
+  x.row_of.swap(rows);
+  x.set_rows = x.sets_on() ? n_rows : 0;
+  x.set_words = x.sets_on() ? n_words : 0;
+  if (!x.sets_on()) x.sets = nullptr;
+  b->match.built = false;   // (the match units carry the masks' addresses)
+  b->scratch_ready = false;
+  b->sync.planned = false;  // a plan queued ahead was made for the old masks: run() plans inline
+  const int rc2 = build_masks(b);
+  return rc != IRS_HIP_OK ? rc : rc2;
+}
+
+// irs_hip_batch_doc_set_stats: what the doc sets let the last run skip
+static int batch_doc_set_stats_impl(irs_hip_batch* b, uint64_t* tiles, uint64_t* tiles_skipped,
+                                    uint64_t* leads, uint64_t* leads_skipped) {
+  if (!b || !b->ran) return IRS_HIP_EINVAL;
+  if (!rt::set_device(b->seg->device)) return IRS_HIP_EHIP;
+  uint64_t t = 0, ts = 0, l[2] = {0, 0};
+  const ExclWork& x = b->excl;
+  if (x.sets_on()) {
+    if (!b->sync.done.sync()) return IRS_HIP_EHIP;
+    if (!b->phrase && !b->tiles.units.empty()) {
+      std::vector<uint8_t> live(b->tiles.n_total);
+      if (!live.empty() && (!rt::d2h(live.data(), x.d_tile_live.p, live.size(), nullptr) || !rt::sync(nullptr)))
+        return IRS_HIP_EHIP;
+      for (uint32_t u : b->tiles.units) {
+        if (!x.restricted[u]) continue;
+        const DevQuery& dq = b->queries[u];
+        t += dq.n_tiles;
+        for (uint32_t i = 0; i < dq.n_tiles; ++i) ts += live[dq.tile_base + i] ? 0u : 1u;
+      }
+    }
+    if (x.leads_counted && x.d_leads.p) {
+      if (!rt::d2h(l, x.d_leads.p, sizeof l, nullptr) || !rt::sync(nullptr)) return IRS_HIP_EHIP;
+    }
+  }
+  if (tiles) *tiles = t;
+  if (tiles_skipped) *tiles_skipped = ts;
+  if (leads) *leads = l[0];
+  if (leads_skipped) *leads_skipped = l[1];
+  return IRS_HIP_OK;
+}
+
 // The caller's min scores as score bins, in the scale the units bin with NOW: ensure_scratch may
 // have re-scaled a unit (build_groups: one bound for a query on every rank), so this runs behind it.
 static bool stage_min_bins(irs_hip_batch* b) {
@@ -1242,6 +1369,10 @@ static int run_impl(irs_hip_batch* b, rt::stream_t st) {
     b->join.slack_zeroed = ok;
   }
   ok = ok && rt::dmemset(b->d_zeroed.p, 0, b->d_zeroed.n, st);   // (ensure_scratch: six tables)
+  // (a counting run of a batch with doc sets: the lead pieces' tallies, irs_hip_batch_doc_set_stats)
+  b->excl.leads_counted = b->count_touched && b->excl.sets_on();
+  if (ok && b->excl.leads_counted)
+    ok = (b->excl.d_leads.p || b->excl.d_leads.alloc(16)) && rt::dmemset(b->excl.d_leads.p, 0, 16, st);
   // (streams out of the device's cache that another stream is still filling)
   if (b->join.on()) ok = ok && wait_for_streams(b, st);
   // 1. plan (already queued by irs_hip_batch_plan: wait for it instead)
@@ -1810,6 +1941,15 @@ int irs_hip_batch_touched(irs_hip_batch* b, uint64_t* doc_bytes, uint64_t* posit
 int irs_hip_batch_unit_mask(irs_hip_batch* b, uint32_t unit, uint64_t* set, uint64_t n_words) {
   return settled(b, [&] { return batch_unit_mask_impl(b, unit, set, n_words); });
 }
+int irs_hip_batch_set_doc_sets(irs_hip_batch* b, const void* d_sets, uint64_t n_rows, uint64_t n_words, const uint32_t* row_of_unit) {
+  return settled(b, [&] { return batch_set_doc_sets_impl(b, d_sets, false, n_rows, n_words, row_of_unit); });
+}
+int irs_hip_batch_set_doc_sets_host(irs_hip_batch* b, const uint64_t* sets, uint64_t n_rows, uint64_t n_words, const uint32_t* row_of_unit) {
+  return settled(b, [&] { return batch_set_doc_sets_impl(b, sets, true, n_rows, n_words, row_of_unit); });
+}
+int irs_hip_batch_doc_set_stats(irs_hip_batch* b, uint64_t* tiles, uint64_t* tiles_skipped, uint64_t* leads, uint64_t* leads_skipped) {
+  return settled(b, [&] { return batch_doc_set_stats_impl(b, tiles, tiles_skipped, leads, leads_skipped); });
+}
 int irs_hip_batch_match_sets(irs_hip_batch* b, uint64_t* sets, uint64_t n_words, uint64_t* counts) {
   return settled(b, [&] { return batch_match_sets_impl(b, sets, nullptr, n_words, counts, nullptr, nullptr, false); });
 }
@@ -1846,7 +1986,7 @@ int irs_hip_batch_reruns(irs_hip_batch* b, uint32_t* count) {
 int irs_hip_batch_work(irs_hip_batch* b, uint64_t* algorithmic_bytes, uint64_t* postings) {
   return settled(b, [&]() -> int {
     if (!b) return IRS_HIP_EINVAL;
-    if (algorithmic_bytes) *algorithmic_bytes = b->alg_bytes;
+    if (algorithmic_bytes) *algorithmic_bytes = b->alg_bytes + b->excl.set_bytes;
     if (postings) *postings = b->postings;
     return IRS_HIP_OK;
   });

@@ -438,7 +438,37 @@ struct ConjArgs {
   uint32_t pilot_stride;        // pilot pass: lead items {phase, phase + P, ...}
   uint32_t wand;                // prune lead blocks by block-max bounds
   uint32_t* pruned;             // [unit] set when a lead block was skipped (k_select's underflow check)
+  // doc sets (irs_hip_batch_doc_set_stats), counted like `touched` (null unless the batch counts):
+  // lead pieces of the units whose mask comes from a doc set (`restricted`: [unit] bytes), and how
+  // many of them held no doc the mask leaves
+  unsigned long long* leads;    // [2]
+  const uint8_t* restricted;
 };
+
+// A lead piece of a masked unit, decoded, none of whose docs the mask leaves (one wave-uniform
+// ballot of the lanes' `live`) ends there — nothing of it can match: no other term is sought or
+// decoded, no position read; its hit count, candidate slots and pilot contribution stay zero.  What
+// an exhausted `alive` bitmap tells a few steps later (and all a unit masked by deletions or
+// exclusions alone ever sees of this: the same results); a doc set empties whole doc ranges.
+// lead_skipped: what such a piece leaves behind in a counting run.  Its atomics sit on the path
+// that ends the wavefront, nowhere else: a write to memory in front of the kernels' other loads
+// would turn their scalar loads into vector loads (the compiler could no longer take the tables for
+// unwritten) — which is why the pieces themselves are counted by k_count_leads, not here.
+__device__ __forceinline__ void lead_skipped(const ConjArgs& A, uint32_t unit, bool counting, uint32_t bytes,
+                                             unsigned lane) {
+  if (counting && lane == 0) {
+    atomicAdd(&A.touched[2u * unit], static_cast<unsigned long long>(bytes));
+    if (A.leads && A.restricted[unit]) atomicAdd(&A.leads[1], 1ull);
+  }
+}
+// A counting run of a batch with doc sets: the lead pieces (records) of its restricted units
+__global__ void __launch_bounds__(kThreads)
+k_count_leads(const ConjItem* recs, uint32_t n, const uint8_t* restricted, unsigned long long* leads) {
+  const uint32_t i = blockIdx.x * kThreads + threadIdx.x;
+  const bool on = i < n && restricted[recs[i].unit];
+  const uint32_t c = uint32_t(__builtin_popcountll(wave::ballot(on)));
+  if ((threadIdx.x & 63u) == 0 && c) atomicAdd(&leads[0], static_cast<unsigned long long>(c));
+}
 
 
 // by_phrase, block driven.  The conjunction PhraseIterator::next runs first
@@ -613,6 +643,10 @@ __device__ __forceinline__ void phrase_item(const ConjArgs& A, uint32_t pilot /*
     reinterpret_cast<ConjQuad*>(W.first)[lane] = ConjQuad{0u, 0u, 0u, 0u};
   }
   wave::sync();
+  if (qd.dead && wave::ballot(live[0] || live[1]) == 0) {   // (wave-uniform) no lead doc is left
+    lead_skipped(A, unit, counting, bytes, lane);
+    return;
+  }
   const uint32_t dlo = wave::uniform(docs[0]), dhi = wave::uniform(docs[n - 1]);
   // bucket of a doc: (doc - dlo) >> s, below kConjBuckets (s = 0: one doc per bucket)
   const uint32_t span = dhi - dlo;

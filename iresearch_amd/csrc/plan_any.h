@@ -31,6 +31,7 @@ bool launch_any(irs_hip_batch* b, rt::stream_t st) {
             b->d_segs.as<DevSegment>(), b->d_queries.as<DevQuery>(), b->d_tails.as<DevTail>(),
             b->jt, w.d_units.as<uint32_t>(), w.d_item_base.as<uint32_t>(), uint32_t(w.units.size()),
             w.d_lead_rows.as<uint32_t>(), w.d_seek.as<uint32_t>(), w.d_recs.as<ConjItem>());
+  count_leads(w, a, st);
   if (w.n_pilot) {
     ConjArgs p = a;
     p.wgs = w.d_pilot.as<PhraseWg>();

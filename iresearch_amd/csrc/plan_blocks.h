@@ -218,6 +218,10 @@ ConjArgs block_args(const irs_hip_batch* b, const BlockWork& w, uint32_t pilot_s
   a.hits = b->d_hits.as<unsigned long long>();
   a.hist = w.d_hist.as<uint32_t>();
   a.touched = b->count_touched ? b->d_touched.as<unsigned long long>() : nullptr;
+  if (b->excl.leads_counted && b->excl.d_leads.p) {   // (zeroed by the run)
+    a.leads = b->excl.d_leads.as<unsigned long long>();
+    a.restricted = b->excl.d_restricted.as<uint8_t>();
+  }
   a.seek = w.d_seek.as<uint32_t>();
   a.recs = w.d_recs.as<ConjItem>();
   a.unit_items = w.d_unit_items.as<uint32_t>();
@@ -226,6 +230,14 @@ ConjArgs block_args(const irs_hip_batch* b, const BlockWork& w, uint32_t pilot_s
   a.cand_cap = b->cand_cap;
   a.pilot_stride = pilot_stride;
   return a;
+}
+
+// A counting run of a batch with doc sets: the lead pieces of the restricted units among the
+// records the seek kernel has just written (irs_hip_batch_doc_set_stats)
+void count_leads(const BlockWork& w, const ConjArgs& a, rt::stream_t st) {
+  if (!a.leads || !w.n_items) return;
+  RT_LAUNCH(k_count_leads, (w.n_items + kThreads - 1) / kThreads, kThreads, 0, st, w.d_recs.as<ConjItem>(),
+            w.n_items, a.restricted, a.leads);
 }
 
 // Conjunctions: [pilot pass over every P-th lead block -> threshold bins] -> full pass.
@@ -244,6 +256,7 @@ bool launch_conj(irs_hip_batch* b, rt::stream_t st) {
             b->jt, b->blocks.d_units.as<uint32_t>(), b->blocks.d_item_base.as<uint32_t>(),
             uint32_t(b->blocks.units.size()), static_cast<const uint32_t*>(nullptr),
             b->blocks.d_lg.as<uint32_t>(), b->blocks.d_seek.as<uint32_t>(), b->blocks.d_recs.as<ConjItem>());
+  count_leads(b->blocks, a, st);
   if (b->blocks.n_pilot) {
     ConjArgs p = a;
     p.wgs = b->blocks.d_pilot.as<PhraseWg>();
@@ -281,6 +294,7 @@ bool launch_phrase(irs_hip_batch* b, rt::stream_t st) {
             uint32_t(b->blocks.units.size()), b->blocks.d_lead_of.as<uint32_t>(),
             static_cast<const uint32_t*>(nullptr), b->blocks.d_seek.as<uint32_t>(),
             b->blocks.d_recs.as<ConjItem>());
+  count_leads(b->blocks, a, st);
   if (b->blocks.n_pilot) {
     ConjArgs p = a;
     p.wgs = b->blocks.d_pilot.as<PhraseWg>();
@@ -329,6 +343,7 @@ bool launch_vphrase(irs_hip_batch* b, rt::stream_t st) {
             b->jt, b->blocks.d_units.as<uint32_t>(), b->blocks.d_item_base.as<uint32_t>(),
             uint32_t(b->blocks.units.size()), b->blocks.d_lead_rows.as<uint32_t>(),
             b->blocks.d_seek.as<uint32_t>(), b->blocks.d_recs.as<ConjItem>());
+  count_leads(b->blocks, a, st);
   if (b->blocks.n_pilot) {
     ConjArgs p = a;
     p.wgs = b->blocks.d_pilot.as<PhraseWg>();

@@ -32,6 +32,11 @@ auto with_tile_kernel(const irs_hip_batch* b, F&& f) {
   return b->acc32 ? by_layout(uint32_t{0}) : by_layout(0ull);
 }
 
+// The per-tile "some doc can match" bytes of a batch with doc sets (k_tile_live), else null
+const uint8_t* tile_live(const irs_hip_batch* b) {
+  return b->excl.sets_on() ? b->excl.d_tile_live.as<uint8_t>() : nullptr;
+}
+
 template<typename ACC, int LAYOUT, int TILE, bool AND>
 bool launch_pilot(irs_hip_batch* b, rt::stream_t st, TileKernel<ACC, LAYOUT, TILE, AND>) {
   const size_t smem = tile_smem_bytes<ACC, TILE, AND>() + kBins * sizeof(uint32_t);
@@ -41,7 +46,7 @@ bool launch_pilot(irs_hip_batch* b, rt::stream_t st, TileKernel<ACC, LAYOUT, TIL
             b->tiles.d_units.as<uint32_t>(), b->d_segs.as<DevSegment>(),
             b->d_queries.as<DevQuery>(), b->d_qterms.as<DevQTerm>(), b->stride_eff,
             b->tiles.nw_log2, b->tiles.d_off.as<uint32_t>(), reinterpret_cast<uint64_t>(b->tiles.d_items.p),
-            b->d_bstar.as<uint32_t>(), b->estimate ? kPilotMargin : 0u, min_bins(b));
+            b->d_bstar.as<uint32_t>(), b->estimate ? kPilotMargin : 0u, min_bins(b), tile_live(b));
   return rt::last_error_ok();
 }
 
@@ -72,6 +77,7 @@ bool launch_score(irs_hip_batch* b, rt::stream_t st, TileKernel<ACC, LAYOUT, TIL
   a.work_counter = b->tiles.d_work.as<uint32_t>();
   a.tile_ub = b->wand ? b->tiles.d_ub.as<float>() : nullptr;
   a.pruned = b->d_pruned.as<uint32_t>();
+  a.tile_live = tile_live(b);
   a.cpq = cpq;
   a.n_units = n_units;
   a.nw_log2 = b->tiles.nw_log2;
@@ -102,19 +108,24 @@ bool launch_items(irs_hip_batch* b, rt::stream_t st) {
   uint32_t* off = b->tiles.d_off.as<uint32_t>();
   const uint64_t n = uint64_t(b->tiles.n_total) + 1;   // [n_total] = 0 -> the grand total
   if (!rt::dmemset(off + b->tiles.n_total, 0, 4, st)) return false;
+  const uint32_t tb4 = (b->tiles.n_max + kWaves - 1) / kWaves;
+  // doc sets: which tiles hold a doc their unit's mask leaves (the masks are built: plan_stage)
+  if (b->excl.sets_on())
+    RT_LAUNCH(k_tile_live, b->nq * tb4, kThreads, 0, st, b->d_queries.as<DevQuery>(),
+              b->excl.d_restricted.as<uint8_t>(), b->tiles.docs, tb4, b->excl.d_tile_live.as<uint8_t>());
   const uint32_t tb = (b->tiles.n_max + kThreads - 1) / kThreads;
   RT_LAUNCH(k_items_count, b->nq * tb, kThreads, 0, st, b->d_queries.as<DevQuery>(), b->jt,
-            b->tiles.docs, tb, b->d_first.as<uint32_t>(), b->d_tails.as<DevTail>(), off);
+            b->tiles.docs, tb, b->d_first.as<uint32_t>(), b->d_tails.as<DevTail>(), off, tile_live(b));
   const uint32_t parts = uint32_t((n + kScanChunk - 1) / kScanChunk);
   uint64_t* totals = b->tiles.d_scan_parts.as<uint64_t>();
   RT_LAUNCH(k_scan_totals, parts, kThreads, 0, st, off, n, totals);
   RT_LAUNCH(k_scan_parts, 1, 64, 0, st, totals, parts);
   RT_LAUNCH(k_scan_apply, parts, kThreads, 0, st, off, n, totals);
-  const uint32_t tb4 = (b->tiles.n_max + kWaves - 1) / kWaves;
   RT_LAUNCH(k_items_fill, b->nq * tb4, kThreads, 0, st, b->d_segs.as<DevSegment>(),
             b->d_queries.as<DevQuery>(), b->d_qterms.as<DevQTerm>(), b->jt, b->tiles.docs, tb4,
             b->tiles.nw_log2, caches_off(b), b->d_first.as<uint32_t>(), b->d_tails.as<DevTail>(), off,
-            b->tiles.n_total, b->tiles.d_items.as<ItemG>(), b->wand ? b->tiles.d_ub.as<float>() : nullptr);
+            b->tiles.n_total, b->tiles.d_items.as<ItemG>(), b->wand ? b->tiles.d_ub.as<float>() : nullptr,
+            tile_live(b));
   return rt::last_error_ok();
 }
 

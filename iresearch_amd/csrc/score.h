@@ -756,9 +756,12 @@ __device__ __forceinline__ float term_bound(const DevQTerm& qt, uint32_t tf_boun
 // Per (unit, doc tile): how many work items reach the tile — the blocks of every term that
 // overlap it (from the plan table) plus one item per term whose decoded tail reaches into it.
 // grid = n_units * tb workgroups, tb = ceil(max tiles / kThreads).
+// tile_live (a batch with doc sets, excl.h k_tile_live; else null): a tile none of whose docs the
+// unit's mask leaves gets no work items.
 __global__ void __launch_bounds__(kThreads)
 k_items_count(const DevQuery* queries, uint32_t jt, uint32_t tile_docs, uint32_t tb,
-              const uint32_t* first, const DevTail* tails, uint32_t* tile_cnt) {
+              const uint32_t* first, const DevTail* tails, uint32_t* tile_cnt,
+              const uint8_t* tile_live) {
   const uint32_t unit = blockIdx.x / tb;
   const uint32_t tile = (blockIdx.x % tb) * kThreads + threadIdx.x;
   const DevQuery qd = queries[unit];
@@ -774,6 +777,7 @@ k_items_count(const DevQuery* queries, uint32_t jt, uint32_t tile_docs, uint32_t
     n += b1 > b0 ? b1 - b0 : 0u;
     if (tl[j].n && tl[j].first_doc < lo + tile_docs && tl[j].last_doc >= lo) ++n;
   }
+  if (tile_live && !tile_live[qd.tile_base + tile]) n = 0;
   tile_cnt[qd.tile_base + tile] = n;
 }
 
@@ -786,7 +790,8 @@ k_items_fill(const DevSegment* segs, const DevQuery* queries, const DevQTerm* qt
              uint32_t jt, uint32_t tile_docs, uint32_t tb, uint32_t nw_log2,
              uint32_t caches_off, const uint32_t* first, const DevTail* tails,
              const uint32_t* tile_off, uint32_t total_tiles, ItemG* items,
-             float* tile_ub /*WAND: upper bound of any doc's score in the tile; else null*/) {
+             float* tile_ub /*WAND: upper bound of any doc's score in the tile; else null*/,
+             const uint8_t* tile_live /*doc sets: 0 = no doc of the tile can match; else null*/) {
   __shared__ uint32_t s_pre[kWaves][kMaxTerms + 1];  // exclusive prefix sums of the block counts
   __shared__ uint32_t s_b0[kWaves][kMaxTerms];
   __shared__ uint32_t s_ub[kWaves][kMaxTerms];       // WAND: per term, largest block-max score (float bits)
@@ -803,6 +808,25 @@ k_items_fill(const DevSegment* segs, const DevQuery* queries, const DevQTerm* qt
   const DevQuery qd = queries[unit];
   if (tile >= qd.n_tiles || qd.first_off == kNoPlan) return;   // whole wavefront
   const DevSegment& seg = segs[qd.seg];
+  // readable slack behind the last list (the look-ahead loads of whichever list ends the buffer)
+  auto slack = [&](uint32_t at) {
+    if (qd.tile_base + tile + 1u == total_tiles && lane < kItemSlack) {
+      ItemG I;
+      I.addr = reinterpret_cast<uint64_t>(seg.pk);
+      I.dbits = 1;
+      I.fbits = 1;
+      I.base = 0;
+      I.cs = 0.f;
+      I.tab = caches_off;
+      I.aux = kItemSlow | kItemTail | kItemSolo;
+      items[at + lane] = I;
+    }
+  };
+  if (tile_live && !tile_live[qd.tile_base + tile]) {   // (whole wavefront) no items: k_items_count
+    if (tile_ub && lane == 0) tile_ub[qd.tile_base + tile] = 0.f;
+    slack(tile_off[qd.tile_base + tile]);
+    return;
+  }
   const uint32_t* f0 = first + qd.first_off + uint64_t(tile) * jt;
   const DevTail* tl = tails + uint64_t(unit) * jt;
   const DevQTerm* qts = qterms + qd.first_term;
@@ -943,17 +967,7 @@ k_items_fill(const DevSegment* segs, const DevQuery* queries, const DevQTerm* qt
     for (int sft = 32; sft > 0; sft >>= 1) ub += __shfl_xor(ub, sft, 64);
     if (lane == 0) tile_ub[ut] = ub * (1.f + 1e-6f);
   }
-  if (ut + 1u == total_tiles && lane < kItemSlack) {   // readable slack behind the last list
-    ItemG I;
-    I.addr = pk;
-    I.dbits = 1;
-    I.fbits = 1;
-    I.base = 0;
-    I.cs = 0.f;
-    I.tab = caches_off;
-    I.aux = kItemSlow | kItemTail | kItemSolo;
-    items[off0 + n + lane] = I;
-  }
+  slack(off0 + n);
 }
 
 // ----------------------------------------------------------------- shared --
@@ -1024,7 +1038,8 @@ __global__ void __launch_bounds__(kTileThreadsMax)
 k_pilot(const uint32_t* units, const DevSegment* segs, const DevQuery* queries,
         const DevQTerm* qterms, uint32_t stride, uint32_t nw_log2, const uint32_t* tile_off,
         uint64_t items /*address of the ItemG records*/, uint32_t* bstar, uint32_t margin,
-        const uint32_t* min_bin /*[unit] bin of the caller's score::Min; null: none*/) {
+        const uint32_t* min_bin /*[unit] bin of the caller's score::Min; null: none*/,
+        const uint8_t* tile_live /*doc sets: 0 = no doc of the tile can match; else null*/) {
   RT_DYN_SMEM(smem);
   if (!wave::lds_is_at_zero(smem)) __builtin_trap();  // the tile arrays are addressed absolutely
   unsigned char* rest;
@@ -1056,9 +1071,10 @@ k_pilot(const uint32_t* units, const DevSegment* segs, const DevQuery* queries,
   __syncthreads();
   build_tables(sm, qd.n_caches, qd.n_terms);
   for (uint32_t tile = (q * 7u) % stride; tile < n_tiles; tile += stride) {
+    const uint32_t ut = qd.tile_base + tile;
+    if (tile_live && !tile_live[ut]) continue;   // (workgroup-uniform) nothing of the tile can match
     NormStage<TILE> nrm;
     nrm.load(norms1, norm_count, tile);
-    const uint32_t ut = qd.tile_base + tile;
     const WaveList l = wave_list(items, wave::uniform(tile_off[ut]),
                                  wave::uniform(tile_off[ut + 1]), wv, nw_log2);
     ItemPipe s;
@@ -1179,6 +1195,7 @@ struct ScoreArgs {
   uint32_t* work_counter;
   const float* tile_ub;         // WAND: per-tile score bounds (k_items_fill), else null
   uint32_t* pruned;             // [unit] set when a tile was skipped (k_select's underflow check)
+  const uint8_t* tile_live;     // doc sets: per-tile "a doc of the tile can match" (k_tile_live), else null
   uint32_t cpq;                 // chunk ids per unit
   uint32_t n_units;
   uint32_t nw_log2;
@@ -1251,9 +1268,13 @@ k_score(uint64_t args /*address of a ScoreArgs*/) {
     if (tid < ntile) {
       // WAND: no doc of the tile can reach the threshold bin -> the tile is skipped (its work
       // items are not even read)
+      // A doc set: no doc of the tile is left by the unit's mask -> skipped the same way, but the
+      // count stays exact (nothing in it can match): `pruned` is not set
       const float* ub = IRS_ARG(tile_ub);
-      const bool dead = ub && bs && score_bin(ub[qd.tile_base + tile0 + tid], qd.bin_scale) < bs;
-      tdead[tid] = dead ? 1u : 0u;
+      const uint8_t* lv = IRS_ARG(tile_live);
+      const bool empty = lv && !lv[qd.tile_base + tile0 + tid];
+      const bool dead = !empty && ub && bs && score_bin(ub[qd.tile_base + tile0 + tid], qd.bin_scale) < bs;
+      tdead[tid] = (dead || empty) ? 1u : 0u;
       if (dead) IRS_ARG(pruned)[q] = 1u;
     }
     if (tid == 0) {

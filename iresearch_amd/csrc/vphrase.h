@@ -196,6 +196,10 @@ __device__ __forceinline__ void vphrase_item(const ConjArgs& A, const uint32_t* 
     reinterpret_cast<ConjQuad*>(W.first)[lane] = ConjQuad{0u, 0u, 0u, 0u};
   }
   wave::sync();
+  if (qd.dead && wave::ballot(alive[0] || alive[1]) == 0) {   // (wave-uniform) no lead doc is left
+    lead_skipped(A, unit, counting, bytes, lane);
+    return;
+  }
   const uint32_t dlo = wave::uniform(docs[0]), dhi = wave::uniform(docs[n - 1]);
   const uint32_t span = dhi - dlo;
   const uint32_t s = span < kConjBuckets ? 0u

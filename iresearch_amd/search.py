@@ -185,6 +185,45 @@ class Not:
     filter: object
 
 
+@dataclass
+class by_doc_set:
+    """A doc set as a child of an And: row `row` of the bitsets the batch is given
+    (SegmentReader.batch(..., doc_sets=...), QueryBatch.set_doc_sets) — the reference's unscored
+    child of a conjunction: the bitset_doc_iterator of a multi-term query's unscored terms, a
+    column-existence filter, proxy_filter's cached bitset.  It only decides which docs match
+    (MakeConjunction leaves an iterator with the default score out of the score,
+    conjunction.hpp:461-467).  Taken as a direct child of the outermost And only, next to Not
+    children; one per And."""
+    row: int
+
+
+def split_doc_set(flt):
+    """(filter without its by_doc_set child, row or None): And([f..., by_doc_set(r)]) is the And of
+    its other children restricted to row r; a single other child that is not a Not stands for
+    itself (boolean_filter.cpp:200-208).  An And of only by_doc_set / Not children has nothing that
+    scores: ValueError, as for an And of only Nots."""
+    if isinstance(flt, by_doc_set):
+        raise ValueError("a by_doc_set alone has no scored part: it is a child of an And")
+    if type(flt) is not And or not any(isinstance(s, by_doc_set) for s in flt.subs):
+        return flt, None
+    rows = [s.row for s in flt.subs if isinstance(s, by_doc_set)]
+    if len(rows) > 1:
+        raise ValueError("an And takes ONE by_doc_set child: intersect the rows first")
+    row = int(rows[0])
+    if row < 0 or row >= _lib.NO_DOC_SET:
+        raise ValueError("by_doc_set: a row index")
+    rest = [s for s in flt.subs if not isinstance(s, by_doc_set)]
+    if all(_unwrap_not(s)[1] for s in rest):
+        raise ValueError("an And of only by_doc_set / Not children has no scored part "
+                         "(only Not / doc set): not on the GPU path")
+    if len(rest) == 1:
+        inner = rest[0]
+        if flt.boost != 1.0:   # (the And's boost multiplies into its one child's)
+            inner = replace(inner, boost=float(f32(f32(flt.boost) * f32(inner.boost))))
+        return inner, row
+    return replace(flt, subs=rest), row
+
+
 def _unwrap_not(flt):
     """optimize_not (boolean_filter.cpp:35-48): (filter, negated) with double negations removed."""
     neg = False
@@ -337,6 +376,8 @@ class PreparedQuery:
     required: list | None = None   # OP_PHRASE: True for an entry that is a required term — a by_term
                                    # child of the And that holds the phrase (IRS_HIP_PHRASE_REQUIRED),
                                    # carrying its own scorer; None: a phrase alone
+    doc_set: int | None = None     # by_doc_set under the And: the row of the batch's doc sets the
+                                   # query is restricted to (irs_hip_batch_set_doc_sets); None: none
 
 
 # ------------------------------------------------------------------ segment --
@@ -475,8 +516,11 @@ class SegmentReader:
             "irs_hip_term_blockmax")
         return mf[:cnt.value], mn[:cnt.value]
 
-    def batch(self, prepared, k: int):
-        return QueryBatch(self, prepared, k)
+    def batch(self, prepared, k: int, doc_sets=None):
+        """`doc_sets`: the bitsets the queries' by_doc_set children name rows of — u64[rows][words],
+        bit = doc id: a numpy array (copied to the device) or a torch tensor on the device
+        (borrowed: QueryBatch.set_doc_sets)."""
+        return QueryBatch(self, prepared, k, doc_sets=doc_sets)
 
 
 class QueryArrays:
@@ -490,6 +534,8 @@ class QueryArrays:
 
     @classmethod
     def from_prepared(cls, segs, prepared, k):
+        """(A query's by_doc_set row is no part of the arrays: QueryBatch reads it from the prepared
+        queries it is given, or the caller hands row_of_unit to set_doc_sets.)"""
         n_entries = sum(len(p.terms) + len(p.excluded) for p in prepared)
         queries = np.zeros(len(prepared), QUERY)
         terms = np.zeros((len(segs), max(n_entries, 1)), TERM_SCORER)
@@ -682,7 +728,8 @@ class QueryBatch:
     axis, [n_segs][nq]..., in the order the readers were given.  `prepared`: a list of
     PreparedQuery, or the QueryArrays made from one."""
 
-    def __init__(self, seg, prepared, k: int | None = None):
+    def __init__(self, seg, prepared, k: int | None = None, doc_sets=None):
+        self.handle = None
         self.segs = list(seg) if isinstance(seg, (list, tuple)) else [seg]
         self.multi = isinstance(seg, (list, tuple))
         arrays = prepared if isinstance(prepared, QueryArrays) else \
@@ -699,6 +746,20 @@ class QueryBatch:
             self.terms.ctypes.data, self.terms.shape[1], C.byref(h)),
             "irs_hip_batch_create_multi")
         self.handle = h
+        rows = [] if isinstance(prepared, QueryArrays) else [getattr(p, "doc_set", None) for p in prepared]
+        if any(r is not None for r in rows):
+            try:
+                if doc_sets is None:
+                    raise ValueError("a query with a by_doc_set child needs the batch's doc_sets")
+                one = [_lib.NO_DOC_SET if r is None else int(r) for r in rows]
+                self.set_doc_sets(doc_sets, np.tile(np.array(one, np.uint32), len(self.segs)))
+            except Exception:
+                self.close()
+                raise
+        elif doc_sets is not None:
+            # (QueryArrays carry no rows: the caller names them — set_doc_sets(sets, row_of_unit))
+            self.close()
+            raise ValueError("doc_sets without a by_doc_set query: call set_doc_sets(sets, row_of_unit)")
 
     def configure(self, tile_docs=0, pilot_stride=0, cand_cap=0):
         _lib.check(self.L, self.L.irs_hip_batch_configure(self.handle, tile_docs, pilot_stride,
@@ -806,6 +867,52 @@ class QueryBatch:
         _lib.check(self.L, self.L.irs_hip_batch_unit_mask(self.handle, unit, out.ctypes.data, n_words),
                    "irs_hip_batch_unit_mask")
         return out
+
+    def set_doc_sets(self, sets, row_of_unit=None, n_rows=None, n_words=None):
+        """Restrict units to doc sets (irs_hip_batch_set_doc_sets): `sets` u64[rows][words] in
+        bit_union's layout (bit = doc id), `row_of_unit` [units] row indices, _lib.NO_DOC_SET for an
+        unrestricted unit (unit = segment * n_queries + query).  A numpy array is copied into memory
+        of the batch (the host form); a torch tensor on the device — or a device address with
+        n_rows / n_words — is BORROWED: it stays valid and unchanged until the results have been
+        fetched or the sets are replaced.  None clears the filters."""
+        if sets is None or row_of_unit is None:
+            self._doc_sets = None
+            _lib.check(self.L, self.L.irs_hip_batch_set_doc_sets(self.handle, None, 0, 0, None),
+                       "irs_hip_batch_set_doc_sets")
+            return self
+        rows = np.ascontiguousarray(row_of_unit, np.uint32).reshape(-1)
+        if rows.size != self.nq:
+            raise ValueError("row_of_unit: one row per unit (%d)" % self.nq)
+        if isinstance(sets, np.ndarray):
+            arr = np.ascontiguousarray(sets, np.uint64)
+            if arr.ndim != 2:
+                raise ValueError("doc sets: u64[rows][words]")
+            _lib.check(self.L, self.L.irs_hip_batch_set_doc_sets_host(
+                self.handle, arr.ctypes.data, arr.shape[0], arr.shape[1], rows.ctypes.data),
+                "irs_hip_batch_set_doc_sets_host")
+            self._doc_sets = None
+            return self
+        if hasattr(sets, "data_ptr"):   # a torch tensor: device memory
+            if sets.dim() != 2 or sets.element_size() != 8 or not sets.is_contiguous():
+                raise ValueError("doc sets: a contiguous 64-bit tensor [rows][words]")
+            ptr, n_rows, n_words = sets.data_ptr(), sets.shape[0], sets.shape[1]
+        else:
+            if n_rows is None or n_words is None:
+                raise ValueError("doc sets by device address: n_rows and n_words")
+            ptr = int(sets)
+        _lib.check(self.L, self.L.irs_hip_batch_set_doc_sets(
+            self.handle, ptr, int(n_rows), int(n_words), rows.ctypes.data), "irs_hip_batch_set_doc_sets")
+        self._doc_sets = sets   # (borrowed by the library)
+        return self
+
+    def doc_set_stats(self):
+        """What the doc sets let the last run skip (irs_hip_batch_doc_set_stats): a dict of tiles,
+        tiles_skipped (work-item units; exact), leads, leads_skipped (block-driven and phrase
+        units; counted under profile(2) only)."""
+        v = [C.c_uint64() for _ in range(4)]
+        _lib.check(self.L, self.L.irs_hip_batch_doc_set_stats(self.handle, *[C.byref(x) for x in v]),
+                   "irs_hip_batch_doc_set_stats")
+        return dict(zip(("tiles", "tiles_skipped", "leads", "leads_skipped"), (int(x.value) for x in v)))
 
     def match_words(self) -> int:
         """The fewest 64-bit words a match-set row may have: a bit for every doc id of the batch's
@@ -951,6 +1058,13 @@ def prepare(filters, scorer, segment_stats, required_terms=False):
     ttf = sum(s.total_term_freq for s in segment_stats)
     out = []
     for flt in filters:
+        flt, doc_set = split_doc_set(flt)
+        if doc_set is not None:
+            # (the doc set is no part of what is prepared: no score, no statistic)
+            p = prepare([flt], scorer, segment_stats, required_terms)[0]
+            p.doc_set = doc_set
+            out.append(p)
+            continue
         flt, excluded = split_exclusions(flt)
         if excluded:
             # (the excluded part is prepared without scorers: no score, no statistic)

@@ -11,6 +11,9 @@ boolean round also runs the filters with 0-2 excluded terms each (And(filter, No
 every phrase round also runs variadic phrases (parts of several terms) and phrases with required
 terms (And([by_phrase, by_term...])); every boolean round runs
 Ands of Or groups (with exclusions, wand on and off; every third over two segments in one batch).
+With --doc-sets every round also restricts a random subset of its units to random doc sets
+(irs_hip_batch_set_doc_sets) at densities 0, 0.001, 0.5 and 1, on a path picked at random, and
+compares each against the oracle's run on the segment with the set's complement deleted as well.
 
   python tools/fuzz_parity.py --seconds 120            # on the GPU (libirs_hip.so)
   python tools/fuzz_parity.py --sim --seconds 60       # on the CPU emulator
@@ -57,6 +60,70 @@ def excl_round(sr, seg, filters, scorer, k, st, rng, max_rank):
         parity.check_single_segment(ms, [incl], scorer, k, h[q:q + 1], c[q:q + 1], t[q:q + 1])
     match_round(b, seg, [x[1] for x in trip], t, [x[2] for x in trip])
     b.close()
+
+
+def doc_set_round(sr, seg, filters, scorer, k, st, rng):
+    """Random units restricted to random doc sets (rows of density 0, 0.001, 0.5, 1; a contiguous
+    range now and then), the host form or — every second time — device memory: each query against
+    the oracle's run on the segment with the docs outside its row deleted as well; the unscored
+    counts of the same batch against its totals; wand: the same top k."""
+    import copy
+
+    import parity
+    from iresearch_amd import _lib, search
+    from iresearch_amd.search import by_phrase
+    n = seg.num_docs
+    n_words = n // 64 + 1 + int(rng.integers(0, 4))
+    rows = []
+    for share in (0.0, 0.001, 0.5, 1.0):
+        m = int(share * n)
+        if share == 0.5 and rng.integers(0, 2):
+            lo = int(rng.integers(1, n - m + 1))
+            rows.append(np.arange(lo, lo + m, dtype=np.int64))
+        else:
+            rows.append(np.sort(rng.choice(n, m, replace=False)).astype(np.int64) + 1)
+    sets = np.zeros((len(rows), n_words), np.uint64)
+    for r, d in enumerate(rows):
+        np.bitwise_or.at(sets[r], d // 64, np.uint64(1) << (d % 64).astype(np.uint64))
+    row_of = np.where(rng.random(len(filters)) < 0.7, rng.integers(0, len(rows), len(filters)),
+                      _lib.NO_DOC_SET).astype(np.uint32)
+    gone0 = np.zeros(0, np.int64) if getattr(seg, "doc_mask", None) is None else np.asarray(seg.doc_mask, np.int64)
+    within = []
+    for d in rows:
+        keep = np.zeros(n + 1, bool)
+        keep[d] = True
+        keep[gone0[(gone0 >= 1) & (gone0 <= n)]] = False
+        ms = copy.copy(seg)
+        ms.doc_mask = (np.nonzero(~keep[1:])[0] + 1).astype(np.uint32)
+        within.append(ms)
+    path = int(rng.choice([_lib.PATH_AUTO, _lib.PATH_ITEMS, _lib.PATH_JOINED]))
+    prep = search.prepare(filters, scorer, st)
+    held = None
+    runs = []
+    for wand in (False, True):
+        b = sr.batch(prep, k).set_path(path).set_wand(wand)
+        if rng.integers(0, 2):
+            import torch
+            arch = ctypes.create_string_buffer(64)
+            sr.L.irs_hip_device_arch(0, arch, 64)
+            dev = "cpu" if arch.value.endswith(b"-sim") else "cuda"
+            held = torch.from_numpy(sets.view(np.int64).copy()).to(dev)
+            b.set_doc_sets(held, row_of)
+        else:
+            b.set_doc_sets(sets, row_of)
+        runs.append(tuple(x.copy() for x in b.run().results()))
+        if not wand:
+            _, counts = b.match_sets(sets=False)
+            assert np.array_equal(counts, runs[0][2]), "doc sets: unscored counts vs total hits"
+        b.close()
+    (h, c, t), (wh, wc, _) = runs
+    assert np.array_equal(c, wc), "doc sets: wand counts"
+    check = parity.check_phrase_segment if isinstance(filters[0], by_phrase) else parity.check_single_segment
+    for q, f in enumerate(filters):
+        assert np.array_equal(h[q, :c[q]], wh[q, :c[q]]), ("doc sets: wand top-k", q)
+        ms = seg if row_of[q] == _lib.NO_DOC_SET else within[int(row_of[q])]
+        check(ms, [f], scorer, k, h[q:q + 1], c[q:q + 1], t[q:q + 1])
+    return len(filters)
 
 
 def grouped_round(sr, seg, scorer, k, st, rng, max_rank, term, merge, multi, L):
@@ -133,6 +200,8 @@ def main():
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--sim", action="store_true")
     ap.add_argument("--max-docs", type=int, default=400_000)
+    ap.add_argument("--doc-sets", action="store_true",
+                    help="every round also restricts a random subset of its units to random doc sets")
     args = ap.parse_args()
     import parity
     from iresearch_amd import _lib, search, synth
@@ -187,6 +256,8 @@ def main():
             hits, counts, totals = (x.copy() for x in b.run().results())
             parity.check_phrase_segment(seg, filters, scorer, k, hits, counts, totals)
             match_round(b, seg, filters, totals)
+            if args.doc_sets:
+                queries += doc_set_round(sr, seg, filters, scorer, k, st, rng)
             # variadic phrases (IRS_HIP_PHRASE_ALT): 2-4 parts of 1-4 members near each other's
             # frequency, against the restatement of tests/test_variadic_phrase.py
             import test_variadic_phrase as tv
@@ -238,6 +309,8 @@ def main():
             hits, counts, totals = (x.copy() for x in b.run().results())
             parity.check_single_segment(seg, filters, scorer, k, hits, counts, totals)
             match_round(b, seg, filters, totals)
+            if args.doc_sets:
+                queries += doc_set_round(sr, seg, filters, scorer, k, st, rng)
             if rounds % 3 == 1:   # irs::Not: some queries lose the docs of 1-2 excluded terms
                 excl_round(sr, seg, filters, scorer, k, st, rng, max_rank)
             # And of Or groups (k_conj_any), every round; over two segments every third

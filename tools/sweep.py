@@ -57,6 +57,15 @@ def main():
                          "bitset + its count, and the counts alone) instead of run + results; the scored "
                          "step of the same batch and, for --op or, irs_hip_bit_union_counts over the "
                          "same term sets are timed next to it; then exits")
+    ap.add_argument("--doc-set", default="",
+                    help="restrict every query to one doc set (irs_hip_batch_set_doc_sets): range:SHARE = a "
+                         "contiguous doc range holding SHARE of the docs, random:SHARE = docs drawn uniformly, "
+                         "none = unrestricted; a comma list times each on the same index, an entry may name "
+                         "its own path (none@items: the unfiltered batch forced onto work items, the fair "
+                         "comparison for --op or, whose restricted units leave the joined streams).  The "
+                         "kernel times are those of profiled runs (HIP events around every stage); the skip "
+                         "statistics printed next to them come from the timed runs (tiles) and from one more, "
+                         "untimed counting run (lead pieces) (--op or | and | mm | phrase)")
     args = ap.parse_args()
     import torch
 
@@ -239,10 +248,56 @@ def main():
                       *base, same, both[0] / base[0], only[0] / base[0]), flush=True)
         b.close()
         sys.exit(0)
+    paths = {"auto": _lib.PATH_AUTO, "items": _lib.PATH_ITEMS, "joined": _lib.PATH_JOINED}
+
+    def doc_set(spec):
+        """u64[1][words] of `range:SHARE` / `random:SHARE`, or None."""
+        if spec in ("", "none"):
+            return None
+        kind, share = spec.split(":")
+        n = max(1, int(float(share) * args.docs))
+        if kind == "range":
+            lo = (args.docs - n) // 2 + 1
+            docs = np.arange(lo, lo + n, dtype=np.int64)
+        elif kind == "random":
+            docs = np.random.default_rng(synth.SEED + 9).choice(args.docs, n, replace=False).astype(np.int64) + 1
+        else:
+            raise SystemExit("--doc-set: range:SHARE, random:SHARE or none")
+        row = np.zeros((1, args.docs // 64 + 1), np.uint64)
+        np.bitwise_or.at(row[0], docs // 64, np.uint64(1) << (docs % 64).astype(np.uint64))
+        return row
+    for spec in [x for x in args.doc_set.split(",") if x]:
+        tile, stride = (int(x) for x in args.configs.split(",")[0].split(":"))
+        what, _, own = spec.partition("@")
+        row = doc_set(what)
+        b = sr.batch(prep, args.k).configure(tile, stride, 0).set_path(paths[own or args.path]).profile(True)
+        if row is not None:
+            b.set_doc_sets(row, np.zeros(len(filters), np.uint32))
+        b.run()
+        _, _, totals = b.results()
+        ms = []
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            b.run()
+            ms.append(b.timings())
+        dt = (time.perf_counter() - t0) / args.steps
+        avg = np.mean(ms, axis=0)
+        line = "doc-set %-14s path %-6s step %.2f ms  plan %.2f pilot %.2f score %.2f select %.2f  hits/query mean %.0f  reruns=%d" % (
+            spec, "joined" if b.path() == _lib.PATH_JOINED else "items", dt * 1e3, *avg, float(np.mean(totals)), b.reruns())
+        if row is not None:
+            s = b.doc_set_stats()
+            b.profile(3).run()   # (a counting run: the lead pieces)
+            b.results()
+            c = b.doc_set_stats()
+            line += "  tiles %d skipped %d  leads %d skipped %d" % (s["tiles"], s["tiles_skipped"], c["leads"], c["leads_skipped"])
+        print(line, flush=True)
+        b.close()
+    if args.doc_set:
+        sys.exit(0)
     ref = None
     for cfg in args.configs.split(","):
         tile, stride = (int(x) for x in cfg.split(":"))
-        path = {"auto": _lib.PATH_AUTO, "items": _lib.PATH_ITEMS, "joined": _lib.PATH_JOINED}[args.path]
+        path = paths[args.path]
         b = sr.batch(prep, args.k).configure(tile, stride, 0).set_path(path).profile(True)
         b.run()
         hits, counts, totals = b.results()

@@ -506,7 +506,10 @@ int irs_hip_batch_path(irs_hip_batch* batch, int* path);
  * the look-ups added (about min(3 k / units sharing the threshold, k) docs per term): a 10 M-doc
  * segment at k = 1000 pairs, a lone 1.25 M-doc segment does not — unless a segment of the batch's
  * plain joined units has deleted documents; enable = 2: whatever the size (tests); enable = 0:
- * never — the units run on 32-bit tiles.  Units with excluded terms (IRS_HIP_EXCLUDE) never join
+ * never — the units run on 32-bit tiles.  Whatever enable says, a launch one of whose terms has no
+ * bound image (irs_hip_join_bound_rule: IRS_HIP_EUNSUPPORTED for its scorer signature; a segment
+ * without frequencies) keeps its 32-bit tiles: enable = 2 asks for pairs, it does not guarantee
+ * them.  Units with excluded terms (IRS_HIP_EXCLUDE) never join
  * and so never take paired tiles; the other units of their batch decide as without them.
  * irs_hip_batch_paired_tiles: whether the last run took them. */
 int irs_hip_batch_set_paired_tiles(irs_hip_batch* batch, int enable);
@@ -745,6 +748,30 @@ int irs_hip_device_stream_cache_stats(int32_t device, irs_hip_stream_cache_stats
  * none when every stream was held, none for a replayed run of a batch whose first run filled the
  * cache.  A batch without joined units reports 0, 0.  IRS_HIP_EINVAL before the first run. */
 int irs_hip_batch_stream_counts(irs_hip_batch* batch, uint32_t* distinct, uint32_t* decoded);
+/* Bound images: where a batch's plain disjunctions run on paired doc tiles, the kernel reads, per
+ * (segment, term, scorer signature), a second array in posting order whose entries carry a 16-bit
+ * upper bound of the posting's score factor instead of (tf, norm).  Images are made from the
+ * decoded streams, cached with them under the same budget (bytes_held counts both; streams, hits,
+ * misses and evictions keep counting decoded streams only) and dropped with them.
+ * irs_hip_batch_image_counts: the distinct images the batch reads and how many its last run (or
+ * the plan it used) made itself; 0, 0 for a batch that does not pair.  irs_hip_device_image_count:
+ * the images the cache can serve.
+ * irs_hip_join_bound_rule: THE rule, for tests — u[tf * 256 + norm] for tf, norm in 0 .. 255 under
+ * the signature (kind: the library's scorer kind; tf_bound: the term's largest frequency), the
+ * scale U with T U <= u <= T U + slack for the factor T the exact kernels multiply by the term's
+ * weight, and the docs per paired tile.  IRS_HIP_EUNSUPPORTED: no image for this signature (a
+ * reciprocal-form scorer whose factor never reaches 1/8, a table value that is negative or not
+ * finite).  A diagnostic entry: what both test tiers reach the rule through.
+ * irs_hip_batch_rescore_paths: how the units of the last run's paired launch turned their staged
+ * docs into candidates — paths[0] units looked up only the docs within the window of the k-th
+ * 16-bit sum, paths[1] every staged doc because the window held more docs than are looked up at
+ * once (many ties), paths[2] every staged doc because no more than k were staged.  Zeros for a run
+ * that did not pair. */
+int irs_hip_batch_image_counts(irs_hip_batch* batch, uint32_t* distinct, uint32_t* built);
+int irs_hip_batch_rescore_paths(irs_hip_batch* batch, uint32_t paths[3]);
+int irs_hip_device_image_count(int32_t device, uint64_t* images);
+int irs_hip_join_bound_rule(int32_t kind, float norm_const, float norm_length, uint32_t tf_bound,
+                            uint16_t* u, float* scale, float* slack, uint32_t* tile_docs);
 
 typedef struct irs_hip_comm irs_hip_comm;
 #define IRS_HIP_COMM_ID_BYTES 128u

@@ -108,6 +108,17 @@ struct JoinWork {
   bool pairs_allowed = true;   // irs_hip_batch_set_paired_tiles (0: never; 1: by size; 2: whatever the size)
   bool pairs_forced = false;
   bool pairs_used = false;     // ... and whether the last run's plain disjunctions took them
+  // Bound images (join.h k_join_bound) of the streams the plain disjunctions read, made where that
+  // launch will run paired (join_half_ok at the deal): hits / fills of the stream cache's image
+  // map or private (d_img_entries / d_img_bounds, rebuilt behind k_join in every run).  d_jimgs:
+  // the per-(unit, term) records of k_join_score<kJKHalf>, parallel to d_jterms; d_bwgs: the
+  // private images' k_join_bound workgroups (n_bwgs), then the fills' (n_bwgs_fill).
+  DevBuf d_jimgs, d_bwgs, d_img_entries, d_img_bounds;
+  bool img_on = false;          // every stream of the plain disjunctions has an image
+  uint32_t img_n_max = 0;       // tiles of kJoinBoundTile docs of the plain unit with the most
+  uint32_t n_images = 0, n_img_private = 0, n_img_fill = 0;
+  uint32_t n_bwgs = 0, n_bwgs_fill = 0;
+  uint32_t images_built_last = 0;   // images the last plan stage queued k_join_bound work for
 };
 
 // Block-driven conjunctions (conj.h) and phrases (phrase.h): a wavefront per block of a unit's lead term

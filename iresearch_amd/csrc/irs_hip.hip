@@ -1068,8 +1068,14 @@ static int batch_set_paired_tiles_impl(irs_hip_batch* b, int enable) {
   if (!b) return IRS_HIP_EINVAL;
   if (!rt::set_device(b->seg->device)) return IRS_HIP_EHIP;
   if (!quiesce(b)) return IRS_HIP_EHIP;
-  b->join.pairs_allowed = enable != 0;
-  b->join.pairs_forced = enable == 2;
+  const bool allowed = enable != 0, forced = enable == 2;
+  if (allowed != b->join.pairs_allowed || forced != b->join.pairs_forced) {
+    // (the deal makes bound images only for a launch that will run paired: dealt anew)
+    b->scratch_ready = false;
+    b->sync.planned = false;
+  }
+  b->join.pairs_allowed = allowed;
+  b->join.pairs_forced = forced;
   return IRS_HIP_OK;
 }
 static int batch_set_wand_impl(irs_hip_batch* b, int enable) {
@@ -1901,6 +1907,52 @@ int irs_hip_batch_stream_counts(irs_hip_batch* b, uint32_t* distinct, uint32_t* 
     if (distinct) *distinct = b->join.on() ? b->join.n_streams : 0u;
     if (decoded) *decoded = b->join.on() ? b->join.decoded_last : 0u;
     return IRS_HIP_OK;
+  });
+}
+int irs_hip_batch_image_counts(irs_hip_batch* b, uint32_t* distinct, uint32_t* built) {
+  return settled(b, [&]() -> int {
+    if (!b || !b->ran) return IRS_HIP_EINVAL;
+    const bool on = b->join.on() && b->join.img_on;
+    if (distinct) *distinct = on ? b->join.n_images : 0u;
+    if (built) *built = on ? b->join.images_built_last : 0u;
+    return IRS_HIP_OK;
+  });
+}
+int irs_hip_batch_rescore_paths(irs_hip_batch* b, uint32_t paths[3]) {
+  return settled(b, [&]() -> int {
+    if (!b || !b->ran || !paths) return IRS_HIP_EINVAL;
+    paths[0] = paths[1] = paths[2] = 0;
+    if (!b->join.on() || !b->join.pairs_used) return IRS_HIP_OK;
+    if (!rt::set_device(b->seg->device)) return IRS_HIP_EHIP;
+    if (!rt::d2h(paths, rescore_paths(b), 12, b->stream) || !rt::sync(b->stream)) return IRS_HIP_EHIP;
+    return IRS_HIP_OK;
+  });
+}
+int irs_hip_device_image_count(int32_t device, uint64_t* images) {
+  return guarded([&] {
+    if (!images) return int(IRS_HIP_EINVAL);
+    if (device < 0 || device >= rt::device_count() || !rt::set_device(device)) return int(IRS_HIP_EHIP);
+    scache::Cache& c = scache::of(device);
+    std::lock_guard<std::mutex> lock(c.m);
+    *images = c.imap.size();
+    return int(IRS_HIP_OK);
+  });
+}
+int irs_hip_join_bound_rule(int32_t kind, float norm_const, float norm_length, uint32_t tf_bound,
+                            uint16_t* u, float* scale, float* slack, uint32_t* tile_docs) {
+  return guarded([&] {
+    if (slack) *slack = kJoinBoundSlack;
+    if (tile_docs) *tile_docs = kJoinBoundTile;
+    if (!table_kind(kind)) return int(IRS_HIP_EUNSUPPORTED);
+    const float sup = join_bound_sup(kind, norm_const, norm_length, tf_bound);
+    if (!(sup > 0.f)) return int(IRS_HIP_EUNSUPPORTED);
+    const float U = join_bound_scale(sup);
+    if (scale) *scale = U;
+    if (u)
+      for (uint32_t tf = 0; tf < 256u; ++tf)
+        for (uint32_t n = 0; n < 256u; ++n)
+          u[tf * 256u + n] = uint16_t(join_bound_u(kind, norm_const, norm_length, U, tf, n));
+    return int(IRS_HIP_OK);
   });
 }
 int irs_hip_device_sync(int32_t device, void* stream) {

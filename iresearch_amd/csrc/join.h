@@ -341,6 +341,125 @@ k_tail_norms(DevSegment seg, uint64_t n, uint8_t* tail_norms) {
   tail_norms[i] = (d >= kDocMin && d <= seg.num_docs) ? (seg.norms - seg.norm_min_doc)[d] : 0u;
 }
 
+// ---------------------------------------------------------- bound images --
+
+// A BOUND IMAGE of a stream: the same postings in the same order, cut into tiles of
+// kJoinBoundTile docs, every entry
+//     [ (doc - first doc of its kJoinBoundTile-doc tile) * 4 : 16 | u : 16 ]
+// with u a 16-bit upper bound of the posting's query-independent factor T (score = cs * T): with
+// U = join_bound_scale(signature, tf bound),  T U <= u <= T U + kJoinBoundSlack  for whichever
+// form — table row, v_rcp or v_sqrt expression — join_post evaluates for the posting.  A function
+// of (segment, term, scorer signature) only: k_join_bound makes it once from the exact stream, the
+// stream cache keeps it, and k_join_score<kJKHalf> adds uint(fma(cs 2^-15 / U, u, 2)) per posting
+// without a table.  16320: the largest tile whose 64 dummy words still lie inside an entry's 16
+// address bits (4 * 16320 + 256 = 65536).
+constexpr uint32_t kJoinBoundTile = 16320;
+constexpr float kJoinBoundSlack = 3.f;       // c: u <= T U + c
+constexpr float kJoinBoundSupMin = 0.125f;   // reciprocal kinds: the least Tsup an image is made for
+constexpr uint32_t kJoinBoundPerWg = 4096;   // postings per k_join_bound workgroup
+// tiles per chunk of the paired launch at most: the docs of kJoinChunkTiles exact tiles, so that a
+// chunk stages about as many candidates as before (kJoinCands slots; beyond them the slow path)
+constexpr uint32_t kJoinChunkBound = kJoinChunkTiles * kJoinTile / kJoinBoundTile;
+static_assert(4u * kJoinBoundTile + 256u <= 65536u, "dummy offsets fit an entry's 16 address bits");
+
+// Tsup: what T never exceeds for frequencies up to `tf_bound` — the largest table value at that
+// frequency (every operation of table_entry is monotone in tf, the norms are all tried).  The
+// reciprocal kinds take tf = kJoinTfMax whatever the term (Tsup < 1, what the host's score bound
+// assumes); the square-root kinds the term's own bound (the host bounds them by sqrt(tf_bound)).
+// 0: no image for this signature (a table value that is negative or not finite, or a reciprocal
+// form so flat that the absolute error of 1 - 1/x would not fit the slack) — the launch then
+// keeps its 32-bit tiles.
+__host__ __device__ inline float join_bound_sup(int32_t kind, float nc, float nl, uint32_t tf_bound) {
+  const uint32_t tf = sqrt_kind(kind) ? (tf_bound ? (tf_bound < kJoinTfMax ? tf_bound : kJoinTfMax) : 1u)
+                                      : kJoinTfMax;
+  float sup = 0.f;
+  for (uint32_t n = 0; n < 256u; ++n) {
+    const float t = table_value(kind, nc, nl, n);
+    if (!(t >= 0.f) || !(t <= 3.0e38f)) return 0.f;
+    const float v = table_entry(kind, nc, nl, tf, n);
+    sup = v > sup ? v : sup;
+  }
+  if (!(sup > 0.f) || !(sup <= 3.0e38f)) return 0.f;
+  if (!sqrt_kind(kind) && sup < kJoinBoundSupMin) return 0.f;
+  return sup;
+}
+// U = (65535 - 64) / Tsup: the headroom keeps T U + kJoinBoundSlack below 2^16 for every T the
+// forms can produce (they exceed the table value by a few ulp).
+__host__ __device__ inline float join_bound_scale(float sup) { return (65535.f - 64.f) / sup; }
+// THE RULE: u of a posting with frequency tf and norm byte `norm`.  Tref is the table's own float
+// (table_entry: row tf, or what the row would hold); the general forms stay within 2^-21 of it in
+// absolute terms (reciprocal kinds: v_rcp is 1 ulp of a value <= 1, the subtraction rounds once
+// more) resp. 2^-21 relative (square-root kinds: v_sqrt 1 ulp, two roundings), which the margins
+// 2^-19 relative and 2^-20 absolute cover; + 1.25 before the truncation so that the rounding of the
+// multiply-add (at most 2^-9 below 2^16) cannot bring u under T U.  With U <= 2^19 (Tsup >= 1/8):
+// u <= T U + 65535 2^-19 + (2^-20 + 2^-21) U + 1.25 + 2^-9 < T U + 2.2 <= T U + kJoinBoundSlack.
+__host__ __device__ inline uint32_t join_bound_u(int32_t kind, float nc, float nl, float U,
+                                                 uint32_t tf, uint32_t norm) {
+  const float tref = table_entry(kind, nc, nl, tf ? tf : 1u, norm);
+  const float tb = tref + tref * (1.f / 524288.f) + (sqrt_kind(kind) ? 0.f : (1.f / 1048576.f));
+  const float r = tb * U + 1.25f;
+  const uint32_t u = r >= 65535.f ? 65535u : static_cast<uint32_t>(r);
+  return u;
+}
+
+// k_join_bound work: kJoinBoundPerWg postings of one stream (an empty stream: one record).
+struct alignas(16) BoundWg {
+  uint64_t src, src_bounds;   // the exact stream: entries, bounds[0 .. n_src_tiles]
+  uint64_t dst, dst_bounds;   // the image: entries, bounds[0 .. n_dst_tiles]
+  uint32_t first;             // the workgroup's first posting
+  uint32_t n;                 // postings of the stream
+  uint32_t n_src_tiles, n_dst_tiles;
+  int32_t kind;               // the signature
+  float nc, nl;
+  float U;                    // join_bound_scale of (signature, the term's tf bound)
+};
+static_assert(sizeof(BoundWg) == 64, "BoundWg");
+
+// exact stream -> bound image: 4 bytes in, 4 bytes out per posting.  A posting's doc is its
+// offset plus its kJoinTile-doc tile, found in the stream's boundary table (the largest t with
+// bounds[t] <= i; a thread's postings ascend, so the search resumes where the last one ended);
+// posting i opens every image tile in (tile of posting i - 1, tile of i], the last posting closes
+// the rest.  (Streams of segments with deleted docs get no image: join_half_ok.)
+__global__ void __launch_bounds__(kThreads)
+k_join_bound(const BoundWg* wgs) {
+  const BoundWg W = wgs[blockIdx.x];
+  const uint32_t* src = reinterpret_cast<const uint32_t*>(W.src);
+  const uint32_t* sb = reinterpret_cast<const uint32_t*>(W.src_bounds);
+  uint32_t* dst = reinterpret_cast<uint32_t*>(W.dst);
+  uint32_t* db = reinterpret_cast<uint32_t*>(W.dst_bounds);
+  if (!W.n) {
+    for (uint32_t u = threadIdx.x; u <= W.n_dst_tiles; u += blockDim.x) db[u] = 0u;
+    return;
+  }
+  auto tile_of = [&](uint32_t i, uint32_t lo) {   // largest t in [lo, n_src_tiles) with sb[t] <= i
+    uint32_t hi = W.n_src_tiles;
+    while (hi - lo > 1u) {
+      const uint32_t mid = (lo + hi) >> 1;
+      if (sb[mid] <= i) lo = mid; else hi = mid;
+    }
+    return lo;
+  };
+  uint32_t t = 0;
+  const uint32_t end = W.first + kJoinBoundPerWg < W.n ? W.first + kJoinBoundPerWg : W.n;
+  for (uint32_t i = W.first + threadIdx.x; i < end; i += blockDim.x) {
+    t = tile_of(i, t);
+    const uint32_t e = src[i];
+    const uint32_t doc = t * kJoinTile + (e >> 18);   // (0-based)
+    const uint32_t bt = doc / kJoinBoundTile;
+    const uint32_t off = doc - bt * kJoinBoundTile;
+    const uint32_t u = join_bound_u(W.kind, W.nc, W.nl, W.U, join_tf(e), (e >> 2) & 255u);
+    dst[i] = (off << 18) | u;
+    int32_t tp = -1;
+    if (i) {
+      const uint32_t pt = sb[t] < i ? t : tile_of(i - 1u, 0u);
+      tp = int32_t((pt * kJoinTile + (src[i - 1u] >> 18)) / kJoinBoundTile);
+    }
+    for (int32_t v = tp + 1; v <= int32_t(bt); ++v) db[v] = i;
+    if (i + 1u == W.n)
+      for (uint32_t v = bt + 1u; v <= W.n_dst_tiles; ++v) db[v] = W.n;
+  }
+}
+
 // ----------------------------------------------------------------- score --
 
 // LDS layout of k_join_pilot / k_join_score (byte offsets; the hot path addresses them
@@ -362,6 +481,22 @@ struct JoinOff {
 static_assert(JoinOff::cand % 8u == 0u, "candidate keys are 8-byte aligned");
 static_assert(JoinOff::caches % 16u == 0u && JoinOff::caches <= 65535u, "the table base is a DS immediate");
 static_assert(JoinOff::dummy + 256u <= 65536u, "dummy offsets fit an entry's 16 address bits");
+// ... of k_join_score<kJKHalf> (paired tiles on bound images): no score tables, no scorer records —
+// the accumulators of kJoinBoundTile docs and their dummies fill the 64 KB an entry can address,
+// everything else lies behind.  At most 80 KB: two workgroups stay resident per CU.
+struct JoinOffH {
+  static constexpr uint32_t acc = 0;                                   // [kJoinBoundTile] u32: two u16 sums
+  static constexpr uint32_t dummy = 4u * kJoinBoundTile;               // [64] u32
+  static constexpr uint32_t jts = dummy + 256u;                        // JoinTerm[kMaxTerms] (of the images)
+  static constexpr uint32_t rng = jts + uint32_t(sizeof(JoinTerm)) * kMaxTerms;   // as JoinOff
+  static constexpr uint32_t cum = rng + 4u * (kJoinChunkTiles + 1u) * kMaxTerms;
+  static constexpr uint32_t cand = cum + 4u * kJoinChunkTiles * kMaxTerms;
+  static constexpr uint32_t vars = cand + 8u * 2u * kJoinCands;
+  static constexpr uint32_t end = vars + 64u;
+};
+static_assert(JoinOffH::cand % 8u == 0u && JoinOffH::jts % 16u == 0u, "JoinOffH alignment");
+static_assert(JoinOffH::dummy + 256u <= 65536u, "dummy offsets fit an entry's 16 address bits");
+static_assert(JoinOffH::end <= 80u * 1024u, "two k_join_score<kJKHalf> workgroups per CU");
 
 struct alignas(16) JoinQuad {   // 16 bytes moved at once
   uint32_t x, y, z, w;
@@ -386,6 +521,10 @@ __device__ __forceinline__ int join_form(uint32_t mode) {
 __device__ __forceinline__ uint32_t join_dummy(unsigned lane) {
   return (JoinOff::dummy + 4u * lane) << 16;
 }
+// ... of a bound image: u = 0, the lane's dummy among JoinOffH's
+__device__ __forceinline__ uint32_t join_dummy_img(unsigned lane) {
+  return (JoinOffH::dummy + 4u * lane) << 16;
+}
 
 // N entries per lane (N slabs of 64): table reads back to back, then the multiply-adds, then
 // the LDS adds.  FORM kJTable: every frequency of the term has a table row, score =
@@ -396,15 +535,10 @@ __device__ __forceinline__ uint32_t join_dummy(unsigned lane) {
 // terms that hold the doc — every contribution is rounded to a multiple of 16 units and carries
 // a 1 there (one v_and_or_b32 more per slab: no second LDS access, no counter array); the unit's
 // eligibility bounds the rounding error (irs_hip.hip unit_joinable).
-//
-// HALF (paired tiles, k_join_score<kJKHalf>): the accumulator word of a doc offset is shared by the
-// two tiles of a pair — 16 bits each; a contribution is the 16-bit image of the 32-bit one
-// (cs arrives scaled by 2^-15), rounded UP by at least one unit (+ 2.0 before the truncation) and
-// shifted into its tile's half (`sh`: 0 or 16, wave-uniform): the sums only pick the docs whose
-// exact 32-bit sum k_join_rescore then works out.
-template<int FORM, int N, bool COUNT, bool HALF = false>
+// (Paired tiles, k_join_score<kJKHalf>, read bound images instead: join_post_img.)
+template<int FORM, int N, bool COUNT>
 __device__ __forceinline__ void join_post(const unsigned char* lds, const uint32_t (&e)[4],
-                                          float cs, uint32_t tabofs, uint32_t sh = 0u) {
+                                          float cs, uint32_t tabofs) {
   float t[N];
   uint32_t fx[N];
 #pragma unroll
@@ -417,17 +551,15 @@ __device__ __forceinline__ void join_post(const unsigned char* lds, const uint32
 #pragma unroll
   for (int k = 0; k < N; ++k) {
     if (FORM == kJTable) {
-      fx[k] = static_cast<uint32_t>(wave::fma(cs, t[k], HALF ? 2.f : (COUNT ? kJoinCountRound : 1.f)));
+      fx[k] = static_cast<uint32_t>(wave::fma(cs, t[k], COUNT ? kJoinCountRound : 1.f));
       if (COUNT) fx[k] = (fx[k] & ~kJoinCountMask) | 1u;
-      if (HALF) fx[k] <<= sh;
     } else {
       const float tf = static_cast<float>(join_tf(e[k]));
       float scaled = (FORM == kJSqrt) ? wave::fast_sqrt(tf) * cs * t[k]
                                       : wave::fma(-cs, wave::fast_rcp(wave::fma(tf, t[k], 1.f)), cs);
       wave::keep_f(scaled);
       fx[k] = COUNT ? ((static_cast<uint32_t>(scaled + kJoinCountRound) & ~kJoinCountMask) | 1u)
-                    : (HALF ? (static_cast<uint32_t>(scaled + 2.f) << sh)
-                            : (static_cast<uint32_t>(scaled) | 1u));
+                    : (static_cast<uint32_t>(scaled) | 1u);
     }
   }
 #pragma unroll
@@ -441,34 +573,25 @@ __device__ __forceinline__ void join_post(const unsigned char* lds, const uint32
 // as fall-through switches instead, every slab naming its own registers: no scratch access left on
 // this path, 490 more branches, k_join_score 5.68 -> 6.62 ms; and slab after slab with early
 // exits / always four slabs with dummies: profiles/r06_join_models.txt.  This form stays.)
-template<int FORM, bool COUNT, bool HALF = false>
+template<int FORM, bool COUNT>
 __device__ __forceinline__ void join_post_n(const unsigned char* lds, const uint32_t (&e)[4],
-                                            uint32_t slabs, float cs, uint32_t tabofs, uint32_t sh = 0u) {
-  if (slabs >= 4u) join_post<FORM, 4, COUNT, HALF>(lds, e, cs, tabofs, sh);
-  else if (slabs == 3u) join_post<FORM, 3, COUNT, HALF>(lds, e, cs, tabofs, sh);
-  else if (slabs == 2u) join_post<FORM, 2, COUNT, HALF>(lds, e, cs, tabofs, sh);
-  else join_post<FORM, 1, COUNT, HALF>(lds, e, cs, tabofs, sh);
+                                            uint32_t slabs, float cs, uint32_t tabofs) {
+  if (slabs >= 4u) join_post<FORM, 4, COUNT>(lds, e, cs, tabofs);
+  else if (slabs == 3u) join_post<FORM, 3, COUNT>(lds, e, cs, tabofs);
+  else if (slabs == 2u) join_post<FORM, 2, COUNT>(lds, e, cs, tabofs);
+  else join_post<FORM, 1, COUNT>(lds, e, cs, tabofs);
 }
 // M: kJSimple | kJCount | kJHalf (template mode bits of the tile loop).  kJHalf: paired tiles —
-// lane j < 2 * kMaxTerms is term j % kMaxTerms in tile j / kMaxTerms of the pair; a lane's mode
-// word also says which half its tile's sums live in (kJoinHiHalf; JoinLane of join_lane_half)
+// lane j < 2 * kMaxTerms is term j % kMaxTerms in tile j / kMaxTerms of the pair (JoinLane of
+// join_lane_img); always with kJSimple: a bound image has one form, the mode word of a piece is
+// just the half its tile's sums live in (kJoinHiHalf)
 enum : int { kJSimple = 1, kJCount = 2, kJHalf = 4 };
 template<int M>
 __device__ __forceinline__ void join_post_any(const unsigned char* lds, const uint32_t (&e)[4],
                                               uint32_t slabs, float cs, uint32_t mode) {
+  static_assert((M & kJHalf) == 0, "paired tiles: join_group_img");
   constexpr bool COUNT = (M & kJCount) != 0;
-  if (M & kJHalf) {
-    const uint32_t sh = join_half_shift(mode);
-    if (M & kJSimple) {
-      join_post_n<kJTable, false, true>(lds, e, slabs, cs, 0u, sh);
-    } else {
-      const uint32_t tabofs = mode & kJoinTabMask;
-      const int form = join_form(mode);   // (wave-uniform)
-      if (form == kJTable) join_post_n<kJTable, false, true>(lds, e, slabs, cs, tabofs, sh);
-      else if (form == kJRcp) join_post_n<kJRcp, false, true>(lds, e, slabs, cs, tabofs, sh);
-      else join_post_n<kJSqrt, false, true>(lds, e, slabs, cs, tabofs, sh);
-    }
-  } else if (M & kJSimple) {
+  if (M & kJSimple) {
     join_post_n<kJTable, COUNT>(lds, e, slabs, cs, 0u);
   } else {
     const uint32_t tabofs = mode & kJoinTabMask;
@@ -699,39 +822,44 @@ __device__ __forceinline__ void join_request(const JoinGroup& g, unsigned lane, 
     x[k] = wave::gload_u32(g.base, off < last ? off : last);
   }
 }
-template<int FORM>
-__device__ __forceinline__ void join_group_form(const unsigned char* lds, const uint32_t (&x)[4],
-                                                const JoinGroup& g, uint32_t tabofs, uint32_t sh,
-                                                unsigned lane) {
+// a group of a bound image: per posting one convert, one multiply-add, one LDS add into the half
+// `sh` says (0 or 16, wave-uniform) — uint(fma(ks, u, 2)) with ks = cs 2^-15 / U of the piece, the
+// 16-bit image of the exact contribution rounded up by one to kJoinHalfSlack units
+template<int N>
+__device__ __forceinline__ void join_post_img(const unsigned char* lds, const uint32_t (&e)[4],
+                                              float ks, uint32_t sh) {
+  uint32_t fx[N];
+#pragma unroll
+  for (int k = 0; k < N; ++k)
+    fx[k] = static_cast<uint32_t>(wave::fma(ks, static_cast<float>(e[k] & 0xFFFFu), 2.f)) << sh;
+#pragma unroll
+  for (int k = 0; k < N; ++k) {
+    if (kAblNoAdd) wave::keep(fx[k]);
+    else wave::lds_add(lds, JoinOffH::acc + (e[k] >> 16), fx[k]);
+  }
+}
+__device__ __forceinline__ void join_group_img(const unsigned char* lds, const uint32_t (&x)[4],
+                                               const JoinGroup& g, unsigned lane) {
+  const uint32_t sh = join_half_shift(g.mode);
   if (g.n == kJoinPre) {   // (wave-uniform) a full group: every lane's four entries count
-    join_post<FORM, 4, false, true>(lds, x, g.cs, tabofs, sh);
+    join_post_img<4>(lds, x, g.cs, sh);
     return;
   }
-  const uint32_t dummy = join_dummy(lane);
+  const uint32_t dummy = join_dummy_img(lane);
   uint32_t e[4];
 #pragma unroll
   for (int k = 0; k < 4; ++k) e[k] = lane + 64u * uint32_t(k) < g.n ? x[k] : dummy;
-  join_post_n<FORM, false, true>(lds, e, (g.n + 63u) >> 6, g.cs, tabofs, sh);
-}
-template<int M>
-__device__ __forceinline__ void join_group_post(const unsigned char* lds, const uint32_t (&x)[4],
-                                                const JoinGroup& g, unsigned lane) {
-  const uint32_t sh = join_half_shift(g.mode);
-  if (M & kJSimple) {
-    join_group_form<kJTable>(lds, x, g, 0u, sh, lane);
-  } else {
-    const uint32_t tabofs = g.mode & kJoinTabMask;
-    const int form = join_form(g.mode);   // (wave-uniform)
-    if (form == kJTable) join_group_form<kJTable>(lds, x, g, tabofs, sh, lane);
-    else if (form == kJRcp) join_group_form<kJRcp>(lds, x, g, tabofs, sh, lane);
-    else join_group_form<kJSqrt>(lds, x, g, tabofs, sh, lane);
-  }
+  const uint32_t slabs = (g.n + 63u) >> 6;
+  if (slabs >= 4u) join_post_img<4>(lds, e, g.cs, sh);
+  else if (slabs == 3u) join_post_img<3>(lds, e, g.cs, sh);
+  else if (slabs == 2u) join_post_img<2>(lds, e, g.cs, sh);
+  else join_post_img<1>(lds, e, g.cs, sh);
 }
 
 template<int M>
 __device__ __forceinline__ void join_finish_pairs(const unsigned char* lds, JoinRun& r,
                                                   const JoinLane& T, uint64_t safe, unsigned lane) {
-  static_assert((M & kJHalf) != 0 && (M & kJCount) == 0, "join_finish_pairs: paired tiles");
+  static_assert(M == (kJHalf | kJSimple), "join_finish_pairs: paired tiles on bound images");
   // (the run's scalars crossed a barrier and a loop back edge inside a struct: join_finish)
   const uint32_t pre = wave::uniform(r.pre);
   if (!pre) {   // (nothing requested: nothing at all)
@@ -764,10 +892,10 @@ __device__ __forceinline__ void join_finish_pairs(const unsigned char* lds, Join
   do {
     const bool second = join_next<M>(s, r, T, safe, gb);
     join_request(gb, lane, b);
-    join_group_post<M>(lds, a, ga, lane);
+    join_group_img(lds, a, ga, lane);
     more = join_next<M>(s, r, T, safe, ga);   // (a share that is through stays through)
     join_request(ga, lane, a);
-    if (second) join_group_post<M>(lds, b, gb, lane);
+    if (second) join_group_img(lds, b, gb, lane);
   } while (more);
 }
 
@@ -828,18 +956,18 @@ __device__ __forceinline__ JoinLane join_lane(const unsigned char* smem, unsigne
 }
 
 // ... of a pair of tiles (kJHalf): lane j < 2 * kMaxTerms = term j % kMaxTerms in the pair's tile
-// j / kMaxTerms; cs in 16-bit units (2^-15: exact), mode = the half's shift
-static_assert(kMaxTerms == 16u, "join_lane_half / join_pairs: lane >> 4 is the tile of the pair");
-__device__ __forceinline__ JoinLane join_lane_half(const unsigned char* smem, unsigned lane) {
+// j / kMaxTerms; the records are the IMAGES' (JoinOffH::jts): cs = cs 2^-15 / U, made by the host
+static_assert(kMaxTerms == 16u, "join_lane_img / join_pairs: lane >> 4 is the tile of the pair");
+__device__ __forceinline__ JoinLane join_lane_img(const unsigned char* smem, unsigned lane) {
   JoinLane T{};
   if (lane < 2u * kMaxTerms) {
     const uint32_t j = lane & (kMaxTerms - 1u);
-    const JoinQuad lo = reinterpret_cast<const JoinQuad*>(smem + JoinOff::jts)[kJoinTermQuads * j];
-    const JoinQuad hi = reinterpret_cast<const JoinQuad*>(smem + JoinOff::jts)[kJoinTermQuads * j + 1u];
+    const JoinQuad lo = reinterpret_cast<const JoinQuad*>(smem + JoinOffH::jts)[kJoinTermQuads * j];
+    const JoinQuad hi = reinterpret_cast<const JoinQuad*>(smem + JoinOffH::jts)[kJoinTermQuads * j + 1u];
     T.ent_lo = lo.x;
     T.ent_hi = lo.y;
-    T.cs = __uint_as_float(hi.x) * (1.f / 32768.f);
-    T.mode = hi.y | (lane >= kMaxTerms ? uint32_t(kJoinHiHalf) : 0u);
+    T.cs = __uint_as_float(hi.x);
+    T.mode = lane >= kMaxTerms ? uint32_t(kJoinHiHalf) : 0u;
   }
   return T;
 }
@@ -1223,30 +1351,37 @@ __device__ __forceinline__ void join_tiles(unsigned char* smem, const JoinTileCt
 }
 
 // PAIRED TILES (k_join_score<kJKHalf>).  The per-(query, tile) visit — two barriers, the share
-// bookkeeping, the wait for the first entries, the dense read-and-clear of 48 KB — is what
-// k_join_score spends its time on, not the postings (profiles/r05_pruning.txt: 2.27 of 5.7 ms with
-// no entries at all, and the first quarter of the entries costs as much as the other three).  A
-// visit here covers TWO consecutive tiles: a term's entries of both are contiguous in its stream,
-// and the accumulator word of a doc offset holds the first tile's sum in its low 16 bits and the
-// second tile's in its high 16 bits — 16-bit images of the 32-bit contributions, each rounded up
-// by one to two units (join_post HALF), so that
-//     exact 32-bit sum f >= thr  ==>  16-bit sum >= max(thr >> 15, 1)
-// (f / 2^15 <= sum_i x_i + m * 65 / 2^15 with x_i = cs t_i / 2^15 and 64 units of float rounding
-// per term; every 16-bit contribution exceeds x_i + 1 - 2^-9).  The docs that pass are staged by
-// doc id only; k_join_rescore looks their postings up in the streams, forms f exactly as join_post
-// does and applies the bin test: the candidate list k_select sees is the 32-bit kernel's, bit for
-// bit.  A sum stays below 2^16: sum_i x_i < 2^15 (fx_mul) and at most 2 * 16 units of rounding.
-// (The general forms scale exactly: cs / 2^15 is a power-of-two multiple, so their 16-bit value
-// is the 32-bit one / 2^15 before the + 2.)  Half the visits, the same LDS bytes per visit;
-// eligibility (irs_hip.hip join_half_ok): the plain disjunctions of a batch, no deleted docs in
-// their segments (those entries leave the doc order k_join_rescore's search relies on).
+// bookkeeping, the wait for the first entries, the dense read-and-clear of the accumulators — is
+// what k_join_score spends its time on, not the postings (profiles/r05_pruning.txt: 2.27 of 5.7 ms
+// with no entries at all, and the first quarter of the entries costs as much as the other three).
+// A visit here covers TWO consecutive tiles of kJoinBoundTile docs: a term's entries of both are
+// contiguous in its bound image, and the accumulator word of a doc offset holds the first tile's
+// sum in its low 16 bits and the second tile's in its high 16 bits.  A contribution is
+// uint(fma(cs 2^-15 / U, u, 2)) with u the image's bound of the posting's factor (join_bound_u):
+// with x_i = cs T_i / 2^15 it exceeds x_i + 1 - 2^-7 and stays below x_i + cs 2^-15 c / U + 2 + 2^-7,
+// and since sum_i cs_i Tsup_i < 2^30 (fx_mul) the extra terms sum to less than c (1 + 2^-9) / 2, so
+//     (S - join_half_slack(m)) 2^15  <  f  <  S 2^15      (S: 16-bit sum, f: exact 32-bit sum, m terms)
+// and  f >= thr  ==>  S >= max(thr >> 15, 1).  The docs that pass are staged by doc id with S;
+// k_join_rescore looks their postings up in the EXACT streams, forms f as join_post does and
+// applies the bin test: the candidate list k_select sees is the 32-bit kernel's, bit for bit.  A
+// sum stays below 2^16: sum_i x_i < 2^15 and at most join_half_slack(16) units on top.
+// Eligibility (plan_join.h join_half_ok): the plain disjunctions of a batch, no deleted docs in
+// their segments (those entries leave the doc order k_join_rescore's search relies on), every
+// signature with an image (join_bound_sup).
+// a(m): how far a 16-bit sum can lie above f / 2^15 — per term 2 + 2^-7 + 65 / 2^15 (the + 2, the
+// roundings of the multiply-add and of cs 2^-15 / U, 64 units of float rounding + the truncation on
+// the exact side), plus kJoinBoundSlack (1 + 2^-9) / 2 < 1.51 for the bounds' own slack:
+// below 2 m + 2 for m <= kMaxTerms.  The staging threshold, k_join_rescore's look-up window
+// (S >= S_k - a(m) - 1) and its "k pass whenever a doc is left out" argument all use this one.
+__host__ __device__ __forceinline__ uint32_t join_half_slack(uint32_t m) { return 2u * m + 2u; }
+static_assert(kJoinBoundSlack * 0.51f + kMaxTerms * (1.f / 128.f + 65.f / 32768.f) < 2.f, "join_half_slack");
 template<int M>
 __device__ __forceinline__ void join_pairs(unsigned char* smem, const JoinTileCtx& ctx,
                                            const JoinLane& T, uint32_t tile0, uint32_t ntile,
                                            uint32_t wv, uint32_t nw_log2, uint32_t& my_hits) {
-  static_assert((M & kJHalf) != 0 && (M & kJCount) == 0, "join_pairs: plain disjunctions");
-  const uint32_t* rng = reinterpret_cast<const uint32_t*>(smem + JoinOff::rng);
-  const uint32_t* cum = reinterpret_cast<const uint32_t*>(smem + JoinOff::cum);
+  static_assert(M == (kJHalf | kJSimple), "join_pairs: plain disjunctions on bound images");
+  const uint32_t* rng = reinterpret_cast<const uint32_t*>(smem + JoinOffH::rng);
+  const uint32_t* cum = reinterpret_cast<const uint32_t*>(smem + JoinOffH::cum);
   const uint32_t tid = threadIdx.x;
   const unsigned lane = tid & 63u;
   const uint64_t safe = reinterpret_cast<uint64_t>(ctx.args->jterms);
@@ -1268,10 +1403,10 @@ __device__ __forceinline__ void join_pairs(unsigned char* smem, const JoinTileCt
   begin(1, r1);
   const uint32_t thr = wave::uniform(ctx.thr);       // in 16-bit units, >= 1
   const uint32_t below = (thr - 1u) * 0x00010001u;   // both halves: the largest sum that is no candidate
-  uint32_t hits2 = 0;                                // matches per half (<= 12 per visit and lane)
+  uint32_t hits2 = 0;                                // matches per half (<= 16 per visit and lane)
   auto end_pair = [&](uint32_t p) {
     __syncthreads();   // B1: every accumulation of the pair has landed
-    const uint32_t doc0 = kDocMin + (tile0 + 2u * p) * kJoinTile;
+    const uint32_t doc0 = kDocMin + (tile0 + 2u * p) * kJoinBoundTile;
     auto candidate = [&](uint32_t doc, uint32_t sum16) {   // rare: the doc and its 16-bit sum
       const uint64_t key = (uint64_t(sum16) << 32) | uint64_t(0xFFFFFFFFu - doc);
       const uint32_t slot = atomicAdd(ctx.ncand, 1u);
@@ -1295,14 +1430,14 @@ __device__ __forceinline__ void join_pairs(unsigned char* smem, const JoinTileCt
 #pragma unroll
         for (uint32_t k = 0; k < 4u; ++k) {
           if ((v[k] & 0xFFFFu) >= thr) candidate(doc0 + i + k, v[k] & 0xFFFFu);
-          if ((v[k] >> 16) >= thr) candidate(doc0 + kJoinTile + i + k, v[k] >> 16);
+          if ((v[k] >> 16) >= thr) candidate(doc0 + kJoinBoundTile + i + k, v[k] >> 16);
         }
       }
     };
     const uint32_t step = blockDim.x * 4u;
-    for (uint32_t i = tid * 4u; i < kJoinTile; i += step) {
+    for (uint32_t i = tid * 4u; i < kJoinBoundTile; i += step) {
       uint32_t v0[4];
-      wave::lds_take4(smem, JoinOff::acc + i * 4u, v0);
+      wave::lds_take4(smem, JoinOffH::acc + i * 4u, v0);
       four(i, v0);
     }
     __syncthreads();   // B2: accumulators are clear again
@@ -1366,12 +1501,14 @@ k_join_score(const JoinArgs* __restrict__ args) {
   constexpr bool COUNT = KIND == kJKCount;
   constexpr bool HALF = KIND == kJKHalf;
   if (!wave::lds_is_at_zero(smem)) __builtin_trap();
-  uint32_t* acc = reinterpret_cast<uint32_t*>(smem + JoinOff::acc);
-  uint32_t* rng = reinterpret_cast<uint32_t*>(smem + JoinOff::rng);
-  uint32_t* cum = reinterpret_cast<uint32_t*>(smem + JoinOff::cum);
-  uint32_t* sig = reinterpret_cast<uint32_t*>(smem + JoinOff::sig);
-  uint64_t* lcand = reinterpret_cast<uint64_t*>(smem + JoinOff::cand);
-  uint32_t* vars = reinterpret_cast<uint32_t*>(smem + JoinOff::vars);
+  // (paired tiles: the layout without tables around kJoinBoundTile accumulators, JoinOffH)
+  using Off = typename std::conditional<HALF, JoinOffH, JoinOff>::type;
+  constexpr uint32_t kTile = HALF ? kJoinBoundTile : kJoinTile;
+  uint32_t* acc = reinterpret_cast<uint32_t*>(smem + Off::acc);
+  uint32_t* rng = reinterpret_cast<uint32_t*>(smem + Off::rng);
+  uint32_t* cum = reinterpret_cast<uint32_t*>(smem + Off::cum);
+  uint64_t* lcand = reinterpret_cast<uint64_t*>(smem + Off::cand);
+  uint32_t* vars = reinterpret_cast<uint32_t*>(smem + Off::vars);
   const uint32_t tid = threadIdx.x;
   const unsigned lane = tid & 63u;
   const uint32_t wv = wave::uniform(tid >> 6);
@@ -1379,11 +1516,11 @@ k_join_score(const JoinArgs* __restrict__ args) {
   const uint32_t nw_log2 = args->nw_log2;
   const uint32_t cap = args->cand_cap;
 
-  for (uint32_t i = tid; i < kJoinTile + 64u; i += blockDim.x) acc[i] = 0u;   // (+ the dummies)
+  for (uint32_t i = tid; i < kTile + 64u; i += blockDim.x) acc[i] = 0u;   // (+ the dummies)
   if (tid < 16u) vars[tid] = 0u;
   __syncthreads();
   if (tid == 0) {
-    sig[0] = 0xFFFFFFFFu;
+    if constexpr (!HALF) reinterpret_cast<uint32_t*>(smem + JoinOff::sig)[0] = 0xFFFFFFFFu;
     const uint32_t g0 = blockIdx.x % kJoinQueues;
     uint32_t g = g0;
     vars[kJChunk] = join_pull(args, g0, atomicAdd(&args->work_counter[g0], 1u), g);
@@ -1406,7 +1543,8 @@ k_join_score(const JoinArgs* __restrict__ args) {
     const uint32_t per_chunk = args->chunk_tiles;
     const uint32_t tile0 = (local / n_units) * per_chunk;
     const DevQuery qd = args->queries[q];
-    const uint32_t n_tiles = qd.n_tiles;
+    // (paired tiles: the segment's tiles of kJoinBoundTile docs ride in the image records)
+    const uint32_t n_tiles = !HALF ? qd.n_tiles : (qd.n_terms ? args->jterms[qd.first_term].pad[0] : 0u);
     const uint32_t ntile = tile0 >= n_tiles ? 0u
                            : ((n_tiles - tile0) < per_chunk ? (n_tiles - tile0) : per_chunk);
     const uint32_t bs = args->bstar[q];
@@ -1422,7 +1560,21 @@ k_join_score(const JoinArgs* __restrict__ args) {
           v = reinterpret_cast<const uint32_t*>(args->jterms[qd.first_term + j].bounds)[tile0 + i];
         rng[e] = v;
       }
-      join_prologue(smem, qd, args->qterms, args->jterms);   // (its barrier publishes rng too)
+      if constexpr (HALF) {   // the image records to LDS: a JoinTerm = two 16-byte halves
+        JoinQuad* jts = reinterpret_cast<JoinQuad*>(smem + JoinOffH::jts);
+        if (tid < kJoinTermQuads * kMaxTerms) {
+          const uint32_t j = tid / kJoinTermQuads;
+          uint32_t x = 0, y = 0, z = 0, w = 0;   // (field by field: join_prologue)
+          if (j < qd.n_terms) {
+            const uint32_t* src = reinterpret_cast<const uint32_t*>(args->jterms + qd.first_term) + 4u * tid;
+            x = src[0]; y = src[1]; z = src[2]; w = src[3];
+          }
+          jts[tid].x = x; jts[tid].y = y; jts[tid].z = z; jts[tid].w = w;
+        }
+        __syncthreads();
+      } else {
+        join_prologue(smem, qd, args->qterms, args->jterms);   // (its barrier publishes rng too)
+      }
       // per tile: the inclusive prefix of the terms' entry counts (what join_begin splits)
       if (HALF) {   // per pair of tiles: over the first tile's terms, then the second's
         const uint32_t npair = (ntile + 1u) >> 1;
@@ -1445,10 +1597,10 @@ k_join_score(const JoinArgs* __restrict__ args) {
         }
       }
       __syncthreads();
-      const JoinLane T = HALF ? join_lane_half(smem, lane) : join_lane(smem, lane);
-      // every term through table slot 0?  (wave-uniform, the same in every wavefront)
-      const bool simple = HALF ? wave::ballot((T.mode & ~uint32_t(kJoinHiHalf)) != 0u) == 0ull
-                               : wave::ballot(T.mode != 0u) == 0ull;
+      const JoinLane T = HALF ? join_lane_img(smem, lane) : join_lane(smem, lane);
+      // every term through table slot 0?  (wave-uniform, the same in every wavefront; a bound
+      // image has one form whatever the term)
+      const bool simple = HALF || wave::ballot(T.mode != 0u) == 0ull;
       JoinTileCtx ctx;
       ctx.args = args;
       ctx.q = q;
@@ -1463,8 +1615,7 @@ k_join_score(const JoinArgs* __restrict__ args) {
       if (HALF) {
         const uint32_t thr16 = ctx.thr >> 15;
         ctx.thr = thr16 ? thr16 : 1u;
-        if (simple) join_pairs<kJHalf | kJSimple>(smem, ctx, T, tile0, ntile, wv, nw_log2, my_hits);
-        else join_pairs<kJHalf>(smem, ctx, T, tile0, ntile, wv, nw_log2, my_hits);
+        join_pairs<kJHalf | kJSimple>(smem, ctx, T, tile0, ntile, wv, nw_log2, my_hits);
       } else if (COUNT) {   // conjunction / min-match: accumulators carry match counts
         if (simple) join_tiles<kJSimple | kJCount>(smem, ctx, T, tile0, ntile, wv, nw_log2, my_hits);
         else join_tiles<kJCount>(smem, ctx, T, tile0, ntile, wv, nw_log2, my_hits);
@@ -1538,15 +1689,16 @@ k_join_score(const JoinArgs* __restrict__ args) {
 // expressions, same truncation: integer sums do not depend on the order), then the 32-bit
 // threshold and the exact bin test of join_tiles' candidate() decide.
 //
-// Not every staged doc needs that.  A staged doc carries its 16-bit sum S, and
-//     (S - 2 m - 1) 2^15  <  f  <  S 2^15          (m terms; join_pairs' bounds, both sides)
+// Not every staged doc needs that.  A staged doc carries its 16-bit sum S, and with
+// a = join_half_slack(m)
+//     (S - a) 2^15  <  f  <  S 2^15          (m terms; join_pairs' bounds, both sides)
 // so with S_k the k-th largest S of the unit, the k docs at or above it all have
-// f > (S_k - 2 m - 1) 2^15 while a doc with S <= S_k - 2 m - 3 has f < (S_k - 2 m - 3) 2^15: it
-// is not among the k best and k_select would drop it.  Only the docs with S >= S_k - 2 m - 2 are
-// looked up (about k of the ~3 k an estimated threshold stages), and at least k of them pass the
-// exact test whenever some staged doc is left out: that doc has S <= S_k - 2 m - 3 and was staged,
+// f > (S_k - a) 2^15 while a doc with S <= S_k - a - 2 has f < (S_k - a - 2) 2^15: it is not among
+// the k best and k_select would drop it.  Only the docs with S >= S_k - a - 1 are looked up (about
+// k of the ~3 k an estimated threshold stages), and at least k of them pass the exact test
+// whenever some staged doc is left out: that doc has S <= S_k - a - 2 and was staged,
 // S >= max(thr >> 15, 1), so each of the k docs with S >= S_k has
-//     f > (S_k - 2 m - 1) 2^15 >= (max(thr >> 15, 1) + 2) 2^15 >= thr + 2^15,
+//     f > (S_k - a) 2^15 >= (max(thr >> 15, 1) + 2) 2^15 >= thr + 2^15,
 // and 2^15 units are more than the 1e-6 relative bin_threshold lowers the bin edge by (sums stay
 // below 2^31): they pass the bin test too.  Every staged doc is looked up (kRescoreMax at a time)
 // only when the window holds more than kRescoreMax docs, or when no more than k were staged.  The
@@ -1653,7 +1805,11 @@ __device__ __forceinline__ uint32_t join_find(const uint32_t* ent, uint32_t lo, 
 __global__ void __launch_bounds__(kRescoreThreads)
 k_join_rescore(const uint32_t* units, const DevQuery* queries, const DevQTerm* qterms,
                const JoinTerm* jterms, const uint32_t* bstar, uint64_t* cands,
-               uint32_t* cand_count, uint32_t cap) {
+               uint32_t* cand_count, uint32_t cap,
+               uint32_t* paths /*[3] units by the way they took: the window's docs only, every
+                                 staged doc because the window held more than kRescoreMax (or fewer
+                                 than k of it passed), every staged doc because no more than k were
+                                 staged (irs_hip_batch_rescore_paths)*/) {
   __shared__ uint32_t docs[kRescoreMax];
   __shared__ uint32_t fsum[kRescoreMax];
   __shared__ uint32_t hist[256];
@@ -1735,13 +1891,14 @@ k_join_rescore(const uint32_t* units, const DevQuery* queries, const DevQTerm* q
   };
   bool done = false;
   if (n > qd.k && qd.k) {
-    // the docs whose S is within 2 m + 2 of the k-th largest S: looked up first
+    // the docs whose S is within join_half_slack(m) + 1 of the k-th largest S: looked up first
     digit_pass(8u, 0u, qd.k);
     const uint32_t d1 = vars[kDigit], w1 = vars[kWant];
     __syncthreads();
     digit_pass(0u, d1, w1);
     const uint32_t sk = (d1 << 8) | vars[kDigit];
-    const uint32_t cut = sk > 2u * nt + 2u ? sk - (2u * nt + 2u) : 0u;
+    const uint32_t win = join_half_slack(nt) + 1u;   // S >= S_k - a(m) - 1
+    const uint32_t cut = sk > win ? sk - win : 0u;
     for (uint32_t c = tid; c < n; c += blockDim.x) {
       const uint64_t key = list[c];
       if (uint32_t(key >> 32) >= cut) {
@@ -1787,7 +1944,10 @@ k_join_rescore(const uint32_t* units, const DevQuery* queries, const DevQTerm* q
     }
   }
   __syncthreads();
-  if (tid == 0) cand_count[q] = vars[kOut];
+  if (tid == 0) {
+    cand_count[q] = vars[kOut];
+    atomicAdd(&paths[done ? 0u : ((n > qd.k && qd.k) ? 1u : 2u)], 1u);
+  }
 }
 
 }  // namespace irs_hip

@@ -133,6 +133,8 @@ void abandon_fills(irs_hip_batch* b) {
   for (const scache::SlabPtr& s : b->join.fills) scache::drop_locked(c, s.get(), gone);
 }
 
+bool join_half_ok(const irs_hip_batch* b);
+
 // The batch's distinct (segment, term) streams, k_join's work list and the per-(unit, term)
 // records of k_join_score.  Static per batch: built once.  Every stream is looked up in the
 // device's stream cache (stream_cache.h): a hit costs no k_join work, a miss is decoded once into
@@ -405,6 +407,218 @@ bool build_streams(irs_hip_batch* b) {
   }
   for (irs_hip_segment* sg : b->segs)
     if (prepare_posting_norms(sg) != IRS_HIP_OK) return false;
+  // Bound images (join.h k_join_bound) of the streams the plain disjunctions read — where that
+  // launch will run paired, and every one of those streams can have one (join_bound_sup).  Looked
+  // up in the cache's image map like the streams above: a hit costs nothing, a miss is made once
+  // into an image slab by the deal's first plan stage (behind k_join: an image miss whose exact
+  // stream is a hit runs only k_join_bound), what the budget cannot take is made into the batch's
+  // own buffers in every run.
+  lap("  streams: bound images");
+  std::vector<BoundWg> bwgs;
+  std::vector<JoinTerm> jimgs;
+  b->join.img_on = false;
+  b->join.img_n_max = 0;
+  b->join.n_images = b->join.n_img_private = b->join.n_img_fill = 0;
+  b->join.n_bwgs = b->join.n_bwgs_fill = 0;
+  if (join_half_ok(b)) {
+    std::vector<uint8_t> want(streams.size(), 0), iwhere(streams.size(), kPrivate);
+    std::vector<float> img_U(streams.size(), 0.f);
+    std::vector<uint64_t> img_ent(streams.size(), 0), img_bnd(streams.size(), 0);
+    std::vector<uint32_t> img_tiles(streams.size(), 0), imgs;   // imgs: the streams with an image
+    // Tsup per (signature, frequency bound): 256 table values each, so kept per deal
+    std::vector<std::vector<float>> sup_of(sigs.size(), std::vector<float>(kJoinTfMax + 1u, -1.f));
+    bool all = true;
+    for (uint32_t u : b->join.units) {
+      const DevQuery& dq = b->queries[u];
+      if (query_need(dq.op) > 1u) continue;
+      if (!b->segs[dq.seg]->dev.has_freq) all = false;
+      b->join.img_n_max = std::max(b->join.img_n_max,
+                                   (b->segs[dq.seg]->dev.num_docs + kJoinBoundTile - 1) / kJoinBoundTile);
+      for (uint32_t j = 0; j < dq.n_terms && all; ++j) {
+        const uint32_t si = stream_of[dq.first_term + j];
+        if (want[si]) continue;
+        want[si] = 1;
+        imgs.push_back(si);
+        const Sig& sig = sigs[stream_sig[si]];
+        const uint32_t tfb = sqrt_kind(sig.kind)
+            ? std::min<uint32_t>(std::max<uint32_t>(b->segs[dq.seg]->terms[streams[si].term].tf_bound, 1u), kJoinTfMax)
+            : kJoinTfMax;
+        float& sup = sup_of[stream_sig[si]][tfb];
+        if (sup < 0.f) sup = join_bound_sup(sig.kind, sig.nc, sig.nl, tfb);
+        if (!(sup > 0.f)) { all = false; break; }
+        img_U[si] = join_bound_scale(sup);
+        img_tiles[si] = (b->segs[dq.seg]->dev.num_docs + kJoinBoundTile - 1) / kJoinBoundTile;
+      }
+      if (!all) break;
+    }
+    if (all && !imgs.empty()) {
+      auto ikey = [&](uint32_t si) {
+        const Sig& sig = sigs[stream_sig[si]];
+        scache::ImageKey k;
+        k.seg_uid = b->segs[streams[si].seg]->uid;
+        k.term = streams[si].term;
+        k.kind = sig.kind;
+        std::memcpy(&k.nc, &sig.nc, 4);
+        std::memcpy(&k.nl, &sig.nl, 4);
+        return k;
+      };
+      if (budget) {
+        scache::Cache& c = scache::of(device);
+        std::vector<scache::SlabPtr> gone;
+        std::vector<uint32_t> missed;
+        {
+          std::unordered_set<scache::Slab*> seen;
+          for (const scache::SlabPtr& sp : b->join.pinned) seen.insert(sp.get());
+          std::lock_guard<std::mutex> lock(c.m);
+          for (uint32_t si : imgs) {
+            auto it = c.imap.find(ikey(si));
+            if (it == c.imap.end()) {
+              missed.push_back(si);
+              continue;
+            }
+            scache::Slab* sl = it->second.slab;
+            if (!sl->queued) continue;   // (claimed, not queued yet: not waited for — private)
+            iwhere[si] = kHit;
+            img_ent[si] = it->second.entries;
+            img_bnd[si] = it->second.bounds;
+            sl->last_use = ++c.clock;
+            if (seen.insert(sl).second) {
+              ++sl->pins;
+              for (const scache::SlabPtr& sp : c.slabs)
+                if (sp.get() == sl) b->join.pinned.push_back(sp);
+            }
+          }
+        }
+        std::stable_sort(missed.begin(), missed.end(),
+                         [&](uint32_t x, uint32_t y) { return streams[x].seg < streams[y].seg; });
+        for (size_t from = 0; from < missed.size();) {
+          size_t to = from;
+          uint64_t e = 0, bn = 0;
+          std::vector<uint64_t> e_off, b_off;
+          while (to < missed.size() && streams[missed[to]].seg == streams[missed[from]].seg &&
+                 (to == from || e + streams[missed[to]].n <= scache::kSlabEntries)) {
+            e_off.push_back(e);
+            b_off.push_back(bn);
+            e += (uint64_t(streams[missed[to]].n) + scache::kAlign - 1) / scache::kAlign * scache::kAlign;
+            bn += uint64_t(img_tiles[missed[to]]) + 1;
+            ++to;
+          }
+          const uint64_t bytes = pool::size_class((e + kJoinSlack + bn) * 4);
+          bool room = false;
+          {
+            std::lock_guard<std::mutex> lock(c.m);
+            room = bytes <= budget && scache::make_room_locked(c, bytes, budget, gone);
+            if (room) c.held += bytes;
+          }
+          gone.clear();
+          scache::SlabPtr sl;
+          if (room) {
+            sl = std::make_shared<scache::Slab>();
+            if (!sl->mem.alloc((e + kJoinSlack + bn) * 4)) {
+              std::lock_guard<std::mutex> lock(c.m);
+              c.held -= bytes;
+              sl.reset();
+            }
+          }
+          if (sl) {
+            sl->bytes = bytes;
+            sl->entries = e;
+            sl->seg_uid = b->segs[streams[missed[from]].seg]->uid;
+            sl->n_streams = uint32_t(to - from);
+            sl->pins = 1;
+            sl->listed = true;
+            uint32_t* base = sl->mem.as<uint32_t>();
+            std::lock_guard<std::mutex> lock(c.m);
+            sl->last_use = ++c.clock;
+            for (size_t i = from; i < to; ++i) {
+              const uint32_t si = missed[i];
+              iwhere[si] = kFill;
+              img_ent[si] = reinterpret_cast<uint64_t>(base + e_off[i - from]);
+              img_bnd[si] = reinterpret_cast<uint64_t>(base + e + kJoinSlack + b_off[i - from]);
+              const scache::ImageKey k = ikey(si);
+              if (c.imap.emplace(k, scache::Where{sl.get(), img_ent[si], img_bnd[si]}).second)
+                sl->images.push_back(k);
+            }
+            c.slabs.push_back(sl);
+            b->join.pinned.push_back(sl);
+            b->join.fills.push_back(sl);
+          }
+          from = to;
+        }
+        b->join.fill_pending = !b->join.fills.empty();
+      }
+      uint64_t ie = 0, ib = 0;   // of the private images
+      for (uint32_t si : imgs) {
+        if (iwhere[si] != kPrivate) continue;
+        img_ent[si] = ie;
+        img_bnd[si] = ib;
+        ie += (uint64_t(streams[si].n) + scache::kAlign - 1) / scache::kAlign * scache::kAlign;
+        ib += uint64_t(img_tiles[si]) + 1;
+      }
+      if (ie + ib) {
+        if (!b->join.d_img_entries.alloc((ie + kJoinSlack) * 4) || !b->join.d_img_bounds.alloc((ib + 1) * 4))
+          return false;
+      } else {
+        b->join.d_img_entries.release();
+        b->join.d_img_bounds.release();
+      }
+      // k_join_bound's work: the private images' workgroups first (every run), then the fills'
+      for (uint32_t pass = 0; pass < 2; ++pass) {
+        for (uint32_t si : imgs) {
+          if (iwhere[si] != (pass ? kFill : kPrivate)) continue;
+          if (!pass) {
+            img_ent[si] = reinterpret_cast<uint64_t>(b->join.d_img_entries.as<uint32_t>() + img_ent[si]);
+            img_bnd[si] = reinterpret_cast<uint64_t>(b->join.d_img_bounds.as<uint32_t>() + img_bnd[si]);
+          }
+          ++(pass ? b->join.n_img_fill : b->join.n_img_private);
+          const Sig& sig = sigs[stream_sig[si]];
+          BoundWg w{};
+          w.src = streams[si].entries;
+          w.src_bounds = streams[si].bounds;
+          w.dst = img_ent[si];
+          w.dst_bounds = img_bnd[si];
+          w.n = streams[si].n;
+          w.n_src_tiles = streams[si].n_tiles;
+          w.n_dst_tiles = img_tiles[si];
+          w.kind = sig.kind;
+          w.nc = sig.nc;
+          w.nl = sig.nl;
+          w.U = img_U[si];
+          for (uint64_t first = 0; first == 0 || first < w.n; first += kJoinBoundPerWg) {
+            w.first = uint32_t(first);
+            bwgs.push_back(w);
+            ++(pass ? b->join.n_bwgs_fill : b->join.n_bwgs);
+          }
+        }
+      }
+      if (bwgs.size() > 0x7FFFFFFFull) return false;
+      b->join.n_images = uint32_t(imgs.size());
+      // the per-(unit, term) records of k_join_score<kJKHalf>: the image, cs 2^-15 / U, the tiles
+      jimgs.assign(b->qterms.size(), JoinTerm{});
+      for (uint32_t u : b->join.units) {
+        const DevQuery& dq = b->queries[u];
+        if (query_need(dq.op) > 1u) continue;
+        for (uint32_t j = 0; j < dq.n_terms; ++j) {
+          const uint32_t si = stream_of[dq.first_term + j];
+          JoinTerm& ji = jimgs[dq.first_term + j];
+          ji.entries = img_ent[si];
+          ji.bounds = img_bnd[si];
+          ji.cs = (b->qterms[dq.first_term + j].c0 * dq.fx_mul) * (1.f / 32768.f) / img_U[si];
+          ji.mode = 0;
+          ji.pad[0] = img_tiles[si];
+          ji.pad[1] = 0;
+        }
+      }
+      b->join.img_on = true;
+    }
+  }
+  if (b->join.img_on) {
+    if (!b->join.d_jimgs.alloc(jimgs.size() * sizeof(JoinTerm)) ||
+        !b->join.d_bwgs.alloc(std::max<size_t>(1, bwgs.size()) * sizeof(BoundWg)) ||
+        !b->up.copy(b->join.d_jimgs.p, jimgs.data(), jimgs.size() * sizeof(JoinTerm)) ||
+        (!bwgs.empty() && !b->up.copy(b->join.d_bwgs.p, bwgs.data(), bwgs.size() * sizeof(BoundWg))))
+      return false;
+  }
   lap("  streams: k_join records");
   // the workgroups' records (JoinWg: everything k_join reads before its first payload byte)
   JoinWg* wg_recs = static_cast<JoinWg*>(b->up.put(b->join.d_wgs.p, wgs.size() * sizeof(JoinWg)));
@@ -472,20 +686,33 @@ bool build_streams(irs_hip_batch* b) {
 
 // k_join for what the batch has to decode in this run: its private streams, and — once — the slabs
 // it claimed in the stream cache.  A run whose streams all lie in the cache queues nothing.
+bool wait_for_streams(irs_hip_batch* b, rt::stream_t st);
 bool launch_join(irs_hip_batch* b, rt::stream_t st) {
   const bool fill = b->join.fill_pending;
   const uint32_t grid = b->join.n_wgs + (fill ? b->join.n_wgs_fill : 0u);
+  const uint32_t bgrid = b->join.img_on ? b->join.n_bwgs + (fill ? b->join.n_bwgs_fill : 0u) : 0u;
   b->join.decoded_last = b->join.n_private + (fill ? b->join.n_fill : 0u);
-  if (!grid) return true;
+  b->join.images_built_last = b->join.img_on ? b->join.n_img_private + (fill ? b->join.n_img_fill : 0u) : 0u;
+  if (!grid && !bgrid) return true;
   bool ok = true;
   if (fill)   // (the slack behind a slab's last stream is only ever read by masked-off look-ahead)
     for (const scache::SlabPtr& s : b->join.fills)
       ok = ok && rt::dmemset(s->mem.as<uint32_t>() + s->entries, 0, kJoinSlack * 4, st);
   if (!ok) return false;
-  with_layout(b->seg->dev.layout, [&](auto L) {
-    RT_LAUNCH((k_join<decltype(L)::value>), grid, kThreads, 0, st, b->join.d_wgs.as<JoinWg>());
-  });
+  if (grid)
+    with_layout(b->seg->dev.layout, [&](auto L) {
+      RT_LAUNCH((k_join<decltype(L)::value>), grid, kThreads, 0, st, b->join.d_wgs.as<JoinWg>());
+    });
   ok = rt::last_error_ok();
+  if (ok && bgrid) {
+    // the images' exact streams: this stage's own k_join is ahead in `st`; a slab out of the cache
+    // may still be filling on another stream
+    ok = wait_for_streams(b, st);
+    if (ok) {
+      RT_LAUNCH(k_join_bound, bgrid, kThreads, 0, st, b->join.d_bwgs.as<BoundWg>());
+      ok = rt::last_error_ok();
+    }
+  }
   if (ok && fill) {
     // from here on other batches are served these slabs: their runs wait for `filled`
     for (const scache::SlabPtr& s : b->join.fills) {
@@ -610,6 +837,9 @@ bool join_half_ok(const irs_hip_batch* b) {
   // share of it alone: 0.07 against 0.2 (stays on 32-bit tiles: 0.97 against 1.10 ms); the
   // same as 8 segments of one batch: 0.14 against 0.08 (5.79 -> 5.27 ms).
   // IRS_HIP_JOIN_HALF=1 / set_paired_tiles(2) pair whatever the size (tests on small segments).
+  // (Since the paired launch reads bound images on kJoinBoundTile-doc tiles — a quarter fewer
+  // visits, no table read per posting — these sizes under-state pairing a little more; they are
+  // kept: AUTO pairs wherever it did and nowhere earlier.)
   const bool forced = b->join.pairs_forced || b->knobs.join_half == 1;
   uint64_t visits = 0, lookups = 0;
   for (uint32_t u : b->join.units) {
@@ -626,31 +856,41 @@ bool join_half_ok(const irs_hip_batch* b) {
   return true;
 }
 
+// k_join_rescore's three unit counters: words 4..6 of the block every run starts from zero (the
+// status word's line)
+uint32_t* rescore_paths(irs_hip_batch* b) { return b->d_zeroed.as<uint32_t>() + 4; }
+
 bool launch_join_score(irs_hip_batch* b, rt::stream_t st) {
-  const size_t smem = JoinOff::end;
-  if (!big_smem(k_join_score<kJKPlain>, smem) || !big_smem(k_join_score<kJKCount>, smem) ||
-      !big_smem(k_join_score<kJKHalf>, smem))
-    return false;
-  const bool half = join_half_ok(b);
+  // (paired tiles run on bound images, made at the deal: no images, no pairs)
+  const bool half = join_half_ok(b) && b->join.img_on;
   b->join.pairs_used = half;
+  const size_t smem_plain = JoinOff::end, smem_half = JoinOffH::end;
+  if (!big_smem(k_join_score<kJKPlain>, smem_plain) || !big_smem(k_join_score<kJKCount>, smem_plain) ||
+      !big_smem(k_join_score<kJKHalf>, smem_half))
+    return false;
   const uint32_t waves = b->join.threads / 64;
-  uint32_t per_cu = uint32_t((160u * 1024u) / smem);
-  per_cu = std::max<uint32_t>(1, std::min<uint32_t>(per_cu, 32u / waves));
+  // workgroups resident per CU: what the LDS block leaves of a CU's 160 KB
+  auto resident = [&](size_t smem) {
+    return std::max<uint32_t>(1, std::min<uint32_t>(uint32_t((160u * 1024u) / smem), 32u / waves));
+  };
+  static_assert(2u * JoinOffH::end <= 160u * 1024u && 2u * JoinOff::end <= 160u * 1024u,
+                "two k_join_score workgroups per CU");
   // chunks of up to kJoinChunkTiles tiles, the unit's tiles cut evenly (102 tiles: 4 x 26, not
   // 3 x 32 + 6 — a short last chunk pays the whole per-chunk prologue for a few tiles).  A small
   // batch takes shorter chunks: with fewer than ~20 chunks per resident workgroup the last round
   // of the work queue leaves CUs idle (1000 units x 102 tiles: 8 chunks per workgroup at 26 tiles,
   // 1.12 ms; 21 at 10 tiles, 0.95 ms — profiles/r05_chunks.txt), while a large batch loses to the
   // per-chunk prologue below 26 (10 M docs: 5.61 ms at 32, 5.88 at 16, 6.50 at 8).
-  // (paired tiles: up to kJoinChunkTiles = 64 tiles = 32 visits per chunk, 4.98 -> 4.91 ms)
-  auto chunking = [&](uint32_t cap, uint32_t& cpq, uint32_t& chunk_tiles) {
-    const uint64_t tiles = uint64_t(b->join.units.size()) * b->join.n_max;
+  // (paired tiles: up to the docs of kJoinChunkTiles = 64 exact tiles per chunk, 4.98 -> 4.91 ms:
+  // kJoinChunkBound = 48 image tiles = 24 visits)
+  auto chunking = [&](uint32_t cap, uint32_t n_max, uint32_t per_cu, uint32_t& cpq, uint32_t& chunk_tiles) {
+    const uint64_t tiles = uint64_t(b->join.units.size()) * n_max;
     const uint64_t wgs = uint64_t(b->seg->cus) * per_cu;
     uint32_t max_chunk = uint32_t(std::min<uint64_t>(cap, std::max<uint64_t>(8, tiles / (20 * wgs))));
     const uint32_t v = b->knobs.join_chunk;   // tuning knob: tiles per chunk at most
     if (v >= 1 && v <= cap) max_chunk = v;
-    cpq = std::max<uint32_t>(1, (b->join.n_max + max_chunk - 1) / max_chunk);
-    chunk_tiles = std::max<uint32_t>(1, (b->join.n_max + cpq - 1) / cpq);
+    cpq = std::max<uint32_t>(1, (n_max + max_chunk - 1) / max_chunk);
+    chunk_tiles = std::max<uint32_t>(1, (n_max + cpq - 1) / cpq);
   };
   const uint32_t n_all = uint32_t(b->join.units.size());
   // [0]: the live counters, [1]: their start values (copied over [0] on the device every run)
@@ -659,15 +899,19 @@ bool launch_join_score(irs_hip_batch* b, rt::stream_t st) {
   for (uint32_t part = 0; part < 2; ++part) {
     const uint32_t n_units = part ? n_all - b->join.n_plain : b->join.n_plain;
     if (!n_units) continue;
+    const bool paired = !part && half;   // (its chunks and tiles count kJoinBoundTile docs)
+    const size_t smem = paired ? smem_half : smem_plain;
+    const uint32_t per_cu = resident(smem);
     uint32_t cpq = 1, chunk_tiles = 1;
-    chunking((!part && half) ? kJoinChunkTiles : kJoinChunkPlain, cpq, chunk_tiles);
+    chunking(paired ? kJoinChunkBound : kJoinChunkPlain, paired ? b->join.img_n_max : b->join.n_max,
+             per_cu, cpq, chunk_tiles);
     const uint64_t chunks = uint64_t(n_units) * cpq;
     if (chunks > 0xFFFF0000ull) return false;
     const uint32_t grid = uint32_t(std::min<uint64_t>(chunks, uint64_t(b->seg->cus) * per_cu));
     JoinArgs& a = b->join.args[part];   // read by the kernel from device memory
     a.queries = b->d_queries.as<DevQuery>();
     a.qterms = b->d_qterms.as<DevQTerm>();
-    a.jterms = b->join.d_jterms.as<JoinTerm>();
+    a.jterms = paired ? b->join.d_jimgs.as<JoinTerm>() : b->join.d_jterms.as<JoinTerm>();
     a.bstar = b->d_bstar.as<uint32_t>();
     a.cands = b->d_cands.as<uint64_t>();
     a.cand_count = b->d_cand_count.as<uint32_t>();
@@ -709,7 +953,7 @@ bool launch_join_score(irs_hip_batch* b, rt::stream_t st) {
       RT_LAUNCH(k_join_rescore, n_units, kRescoreThreads, 0, st, b->join.d_order.as<uint32_t>(),
                 b->d_queries.as<DevQuery>(), b->d_qterms.as<DevQTerm>(), b->join.d_jterms.as<JoinTerm>(),
                 b->d_bstar.as<uint32_t>(), b->d_cands.as<uint64_t>(), b->d_cand_count.as<uint32_t>(),
-                b->cand_cap);
+                b->cand_cap, rescore_paths(b));
     } else {
       RT_LAUNCH(k_join_score<kJKPlain>, grid, b->join.threads, smem, st, d_args);
     }

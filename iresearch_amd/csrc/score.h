@@ -107,7 +107,7 @@ __host__ __device__ __forceinline__ bool table_kind(int32_t kind) {
 __host__ __device__ __forceinline__ bool sqrt_kind(int32_t kind) {
   return kind == kTfidf || kind == kTfidfTiny;
 }
-__device__ __forceinline__ float table_value(int32_t kind, float nc, float nl, uint32_t n) {
+__host__ __device__ __forceinline__ float table_value(int32_t kind, float nc, float nl, uint32_t n) {
   switch (kind) {
     case kBM25Tiny: return n ? 1.f / (nc + nl * static_cast<float>(n)) : 0.f;
     case kBM25One: return 1.f / (nc + nl * 1.f);
@@ -120,7 +120,7 @@ __device__ __forceinline__ float table_value(int32_t kind, float nc, float nl, u
 // entry [r][n] of a scorer's table: row 0 holds the norm factor, row r > 0 the whole expression at
 // frequency r (build_tables fills the LDS tables with it; k_join_rescore evaluates it per posting:
 // one function, the same float)
-__device__ __forceinline__ float table_entry(int32_t kind, float nc, float nl, uint32_t r, uint32_t n) {
+__host__ __device__ __forceinline__ float table_entry(int32_t kind, float nc, float nl, uint32_t r, uint32_t n) {
   const float t = table_value(kind, nc, nl, n);
   if (r == 0) return t;
   if (sqrt_kind(kind)) return sqrtf(static_cast<float>(r)) * t;

@@ -9,6 +9,11 @@
 // last one (join.h's look-ahead guarantee, once per slab), then the streams' boundary tables.  A
 // slab is the unit of pinning, of the fill event and of eviction: a tiny stream costs its entries
 // rounded up to 64 bytes, 4 bytes per doc tile of the segment + 4, and a map node on the host.
+//
+// BOUND IMAGES (join.h k_join_bound) are cached next to them: an image is a function of (segment,
+// term, scorer signature), so it has a map of its own with that key, and lives in slabs of the same
+// kind — the same pinning, fill event, LRU order and budget; `held` counts both.  The counters
+// (hits, misses, evictions) and the size of `map` keep counting exact streams only.
 // Included by irs_hip.hip (one translation unit).
 #pragma once
 
@@ -18,6 +23,22 @@ namespace scache {
 constexpr uint64_t kSlabEntries = 64ull << 20;   // entries per slab at most (256 MB; a longer stream gets its own)
 constexpr uint64_t kAlign = 16;                  // a stream starts on a multiple of 16 entries
 
+struct ImageKey {   // (segment, term, scorer signature: kind and the bits of its two floats)
+  uint32_t seg_uid, term;
+  int32_t kind;
+  uint32_t nc, nl;
+  bool operator==(const ImageKey& o) const {
+    return seg_uid == o.seg_uid && term == o.term && kind == o.kind && nc == o.nc && nl == o.nl;
+  }
+};
+struct ImageKeyHash {
+  size_t operator()(const ImageKey& k) const {
+    uint64_t h = (uint64_t(k.seg_uid) << 32) | k.term;
+    h = (h ^ (uint64_t(k.nc) << 32 | k.nl)) * 0x9E3779B97F4A7C15ull;
+    h = (h ^ uint64_t(uint32_t(k.kind)) ^ (h >> 29)) * 0xBF58476D1CE4E5B9ull;
+    return size_t(h ^ (h >> 32));
+  }
+};
 struct Slab {
   DevBuf mem;
   uint64_t bytes = 0;     // mem.cap: what the budget counts
@@ -25,6 +46,7 @@ struct Slab {
   uint32_t seg_uid = 0;
   uint32_t n_streams = 0;
   std::vector<uint32_t> terms;   // the streams the map serves out of this slab
+  std::vector<ImageKey> images;   // ... or the bound images the image map serves out of it
   // Filled by ONE batch's k_join, on whatever stream that batch's plan stage was queued on;
   // `filled` is recorded behind that launch.  (cache mutex) `queued` turns true once it is: only
   // then is the slab served to other batches, whose runs make their own stream wait for `filled`.
@@ -45,6 +67,7 @@ struct Where {
 struct Cache {
   std::mutex m;   // held for table work only: never across a launch, an allocation or a free
   std::unordered_map<uint64_t, Where> map;   // seg_uid << 32 | term
+  std::unordered_map<ImageKey, Where, ImageKeyHash> imap;   // the bound images
   std::vector<SlabPtr> slabs;
   uint64_t held = 0, clock = 0;
   uint64_t hits = 0, misses = 0, evictions = 0;
@@ -85,6 +108,10 @@ inline void drop_locked(Cache& c, Slab* s, std::vector<SlabPtr>& out) {
   for (uint32_t term : s->terms) {
     auto it = c.map.find(key_of(s->seg_uid, term));
     if (it != c.map.end() && it->second.slab == s) c.map.erase(it);
+  }
+  for (const ImageKey& k : s->images) {
+    auto it = c.imap.find(k);
+    if (it != c.imap.end() && it->second.slab == s) c.imap.erase(it);
   }
   s->listed = false;
   c.held -= s->bytes;

@@ -959,6 +959,21 @@ class QueryBatch:
                    "irs_hip_batch_stream_counts")
         return d.value, n.value
 
+    def image_counts(self):
+        """(distinct bound images the paired launch reads, images the last run made itself):
+        irs_hip_batch_image_counts; (0, 0) for a batch that does not pair."""
+        d, n = C.c_uint32(), C.c_uint32()
+        _lib.check(self.L, self.L.irs_hip_batch_image_counts(self.handle, C.byref(d), C.byref(n)),
+                   "irs_hip_batch_image_counts")
+        return d.value, n.value
+
+    def rescore_paths(self):
+        """irs_hip_batch_rescore_paths: units of the last paired launch that looked up (the window's
+        docs only, every staged doc: window too large, every staged doc: no more than k staged)."""
+        p = (C.c_uint32 * 3)()
+        _lib.check(self.L, self.L.irs_hip_batch_rescore_paths(self.handle, p), "irs_hip_batch_rescore_paths")
+        return tuple(int(x) for x in p)
+
     def results(self):
         hits = np.zeros((self.nq, self.k), HIT)
         counts = np.zeros(self.nq, np.uint32)
@@ -1027,6 +1042,29 @@ def stream_cache_stats(L=None, device=0):
     _lib.check(L, L.irs_hip_device_stream_cache_stats(device, C.byref(st)),
                "irs_hip_device_stream_cache_stats")
     return {name: int(getattr(st, name)) for name, _ in st._fields_}
+
+
+def cached_images(L=None, device=0):
+    """The bound images the device's cache can serve (irs_hip_device_image_count)."""
+    L = L or _lib.lib()
+    n = C.c_uint64()
+    _lib.check(L, L.irs_hip_device_image_count(device, C.byref(n)), "irs_hip_device_image_count")
+    return int(n.value)
+
+
+def join_bound_rule(kind, norm_const, norm_length, tf_bound, L=None):
+    """irs_hip_join_bound_rule: (u[256][256] by (tf, norm), U, slack, docs per paired tile), or None
+    where the signature gets no image."""
+    L = L or _lib.lib()
+    u = np.zeros((256, 256), np.uint16)
+    scale, slack, tile = C.c_float(), C.c_float(), C.c_uint32()
+    rc = L.irs_hip_join_bound_rule(kind, norm_const, norm_length, tf_bound,
+                                   u.ctypes.data_as(C.POINTER(C.c_uint16)), C.byref(scale),
+                                   C.byref(slack), C.byref(tile))
+    if rc == _lib.EUNSUPPORTED:
+        return None
+    _lib.check(L, rc, "irs_hip_join_bound_rule")
+    return u, float(scale.value), float(slack.value), int(tile.value)
 
 
 def set_stream_cache(nbytes, L=None, device=0):

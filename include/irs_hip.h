@@ -766,7 +766,15 @@ int irs_hip_batch_stream_counts(irs_hip_batch* batch, uint32_t* distinct, uint32
  * docs into candidates — paths[0] units looked up only the docs within the window of the k-th
  * 16-bit sum, paths[1] every staged doc because the window held more docs than are looked up at
  * once (many ties), paths[2] every staged doc because no more than k were staged.  Zeros for a run
- * that did not pair. */
+ * that did not pair.
+ * irs_hip_join_half_rule: the integer weight k = ceil(cs 2^-15 / scale 2^16) (at least 1) the paired
+ * kernel multiplies an image entry's u by, for a term weight cs (the exact kernels' fixed-point
+ * weight) and an image's scale U.  irs_hip_join_half_probe: the kernel's own per-posting helper,
+ * run by one workgroup over n entries (u: the low 16 bits) under k — out[i] = ((u k) >> 16) + 2 in
+ * the low 16 bits (high_half = 0) or the high 16 bits of the word.  Diagnostic entries. */
+int irs_hip_join_half_rule(float cs, float scale, uint32_t* k);
+int irs_hip_join_half_probe(int32_t device, const uint32_t* entries, uint32_t n, uint32_t k,
+                            uint32_t high_half, uint32_t* out);
 int irs_hip_batch_image_counts(irs_hip_batch* batch, uint32_t* distinct, uint32_t* built);
 int irs_hip_batch_rescore_paths(irs_hip_batch* batch, uint32_t paths[3]);
 int irs_hip_device_image_count(int32_t device, uint64_t* images);

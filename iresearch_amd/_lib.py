@@ -97,7 +97,7 @@ SYMBOLS = (
     "irs_hip_device_set_stream_cache", "irs_hip_device_stream_cache_stats",
     "irs_hip_batch_stream_counts",
     "irs_hip_batch_image_counts", "irs_hip_device_image_count", "irs_hip_join_bound_rule",
-    "irs_hip_batch_rescore_paths",
+    "irs_hip_batch_rescore_paths", "irs_hip_join_half_rule", "irs_hip_join_half_probe",
 )
 
 
@@ -203,6 +203,9 @@ def bind(L: C.CDLL) -> C.CDLL:
     L.irs_hip_join_bound_rule.argtypes = [i32, C.c_float, C.c_float, u32, P(C.c_uint16), P(C.c_float),
                                           P(C.c_float), P(u32)]
     L.irs_hip_join_bound_rule.restype = C.c_int
+    L.irs_hip_join_half_rule.argtypes, L.irs_hip_join_half_rule.restype = [C.c_float, C.c_float, P(u32)], C.c_int
+    L.irs_hip_join_half_probe.argtypes = [i32, P(u32), u32, u32, u32, P(u32)]
+    L.irs_hip_join_half_probe.restype = C.c_int
     return L
 
 

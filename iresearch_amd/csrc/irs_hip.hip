@@ -1955,6 +1955,29 @@ int irs_hip_join_bound_rule(int32_t kind, float norm_const, float norm_length, u
     return int(IRS_HIP_OK);
   });
 }
+int irs_hip_join_half_rule(float cs, float scale, uint32_t* k) {
+  return guarded([&] {
+    if (!k || !(cs >= 0.f) || !(scale > 0.f)) return int(IRS_HIP_EINVAL);
+    *k = join_half_k(cs, scale);
+    return int(IRS_HIP_OK);
+  });
+}
+int irs_hip_join_half_probe(int32_t device, const uint32_t* entries, uint32_t n, uint32_t k,
+                            uint32_t high_half, uint32_t* out) {
+  return guarded([&] {
+    if (!entries || !out || !n || !k || k > 65535u) return int(IRS_HIP_EINVAL);
+    if (device < 0 || device >= rt::device_count() || !rt::set_device(device)) return int(IRS_HIP_EHIP);
+    uint32_t* d = static_cast<uint32_t*>(rt::dmalloc(size_t(n) * 8));
+    if (!d) return int(IRS_HIP_ENOMEM);
+    bool ok = rt::h2d(d, entries, size_t(n) * 4, nullptr) && rt::sync(nullptr);
+    if (ok) {
+      RT_LAUNCH(k_join_half_probe, 1, kThreads, 0, nullptr, d, n, k, high_half, d + n);
+      ok = rt::last_error_ok() && rt::d2h(out, d + n, size_t(n) * 4, nullptr) && rt::sync(nullptr);
+    }
+    rt::dfree(d);
+    return int(ok ? IRS_HIP_OK : IRS_HIP_EHIP);
+  });
+}
 int irs_hip_device_sync(int32_t device, void* stream) {
   return guarded([&] {
     if (!rt::set_device(device)) return int(IRS_HIP_EHIP);

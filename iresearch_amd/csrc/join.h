@@ -350,8 +350,8 @@ k_tail_norms(DevSegment seg, uint64_t n, uint8_t* tail_norms) {
 // U = join_bound_scale(signature, tf bound),  T U <= u <= T U + kJoinBoundSlack  for whichever
 // form — table row, v_rcp or v_sqrt expression — join_post evaluates for the posting.  A function
 // of (segment, term, scorer signature) only: k_join_bound makes it once from the exact stream, the
-// stream cache keeps it, and k_join_score<kJKHalf> adds uint(fma(cs 2^-15 / U, u, 2)) per posting
-// without a table.  16320: the largest tile whose 64 dummy words still lie inside an entry's 16
+// stream cache keeps it, and k_join_score<kJKHalf> adds ((u k) >> 16) + 2, k = ceil(cs 2^-15 / U 2^16),
+// per posting without a table (join_half_term).  16320: the largest tile whose 64 dummy words still lie inside an entry's 16
 // address bits (4 * 16320 + 256 = 65536).
 constexpr uint32_t kJoinBoundTile = 16320;
 constexpr float kJoinBoundSlack = 3.f;       // c: u <= T U + c
@@ -402,10 +402,24 @@ __host__ __device__ inline uint32_t join_bound_u(int32_t kind, float nc, float n
   return u;
 }
 
+// SLAB-ALIGNED LAYOUT.  The entries of a (term, image tile) PIECE with at least one
+// posting start at a multiple of 64 entries from the image's 256-byte-aligned base and are padded
+// to a multiple of 64; an empty piece takes no space.  A padding entry at position p of the image
+// is  [ (4 * kJoinBoundTile + 4 * (p & 63)) : 16 | u = 0 : 16 ]: the dummy word of its own lane — it
+// adds a constant to a word the epilogue never reads.  So k_join_score<kJKHalf> moves whole slabs
+// of 64 entries from 256-byte-aligned addresses and knows no partial slab.  The image's boundary
+// table holds, behind the n_dst_tiles + 1 padded bounds (multiples of 64) the kernel reads, the
+// n_dst_tiles + 1 bounds of the unpadded pieces (what the write pass places postings by).
+// At most join_image_entries(n, tiles) entries: the host sizes an image by that, no read-back.
+__host__ __device__ inline uint64_t join_image_entries(uint64_t n, uint64_t tiles) {
+  return n + 63u * (n < tiles ? n : tiles);
+}
+constexpr uint32_t kJoinSlab = 64;   // entries per slab: one per lane
+
 // k_join_bound work: kJoinBoundPerWg postings of one stream (an empty stream: one record).
 struct alignas(16) BoundWg {
   uint64_t src, src_bounds;   // the exact stream: entries, bounds[0 .. n_src_tiles]
-  uint64_t dst, dst_bounds;   // the image: entries, bounds[0 .. n_dst_tiles]
+  uint64_t dst, dst_bounds;   // the image: entries, bounds[0 .. n_dst_tiles] padded + as many raw
   uint32_t first;             // the workgroup's first posting
   uint32_t n;                 // postings of the stream
   uint32_t n_src_tiles, n_dst_tiles;
@@ -415,22 +429,69 @@ struct alignas(16) BoundWg {
 };
 static_assert(sizeof(BoundWg) == 64, "BoundWg");
 
-// exact stream -> bound image: 4 bytes in, 4 bytes out per posting.  A posting's doc is its
+// exact stream -> bound image, two launches over the same records.
+// k_join_bound_tiles (the stream's first workgroup only): the bounds pass — the first posting of
+// every image tile, found in the exact stream (its kJoinTile-doc tile from the boundary table, a
+// binary search over that tile's doc offsets) — and the padded prefix over the image tiles.
+__global__ void __launch_bounds__(kThreads)
+k_join_bound_tiles(const BoundWg* wgs) {
+  const BoundWg W = wgs[blockIdx.x];
+  if (W.first) return;
+  const uint32_t* src = reinterpret_cast<const uint32_t*>(W.src);
+  const uint32_t* sb = reinterpret_cast<const uint32_t*>(W.src_bounds);
+  uint32_t* db = reinterpret_cast<uint32_t*>(W.dst_bounds);
+  uint32_t* raw = db + W.n_dst_tiles + 1u;
+  __shared__ uint32_t part[kThreads / 64u];
+  __shared__ uint32_t carry;
+  const uint32_t tid = threadIdx.x;
+  for (uint32_t v = tid; v <= W.n_dst_tiles; v += blockDim.x) {
+    // the first posting whose doc (0-based) is >= v * kJoinBoundTile
+    const uint64_t doc = uint64_t(v) * kJoinBoundTile;
+    const uint64_t t = doc / kJoinTile;
+    uint32_t lo = W.n;
+    if (W.n && t < W.n_src_tiles) {
+      const uint32_t want = uint32_t(doc - t * kJoinTile);
+      uint32_t hi = sb[t + 1u];
+      lo = sb[t];
+      while (lo < hi) {
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        if ((src[mid] >> 18) < want) lo = mid + 1u; else hi = mid;
+      }
+    }
+    raw[v] = lo;
+  }
+  if (tid == 0) carry = 0u;
+  __syncthreads();
+  for (uint32_t v0 = 0; v0 <= W.n_dst_tiles; v0 += blockDim.x) {
+    const uint32_t v = v0 + tid;
+    uint32_t c = 0;   // the padded size of piece v
+    if (v < W.n_dst_tiles) c = (raw[v + 1u] - raw[v] + kJoinSlab - 1u) & ~(kJoinSlab - 1u);
+    const uint32_t inc = wave::inclusive_scan(c);
+    if ((tid & 63u) == 63u) part[tid >> 6] = inc;
+    __syncthreads();
+    uint32_t before = carry;
+    for (uint32_t w = 0; w < (tid >> 6); ++w) before += part[w];
+    if (v <= W.n_dst_tiles) db[v] = before + inc - c;
+    __syncthreads();
+    if (tid == blockDim.x - 1u) carry = before + inc;
+    __syncthreads();
+  }
+}
+// k_join_bound: the write pass — 4 bytes in, 4 bytes out per posting.  A posting's doc is its
 // offset plus its kJoinTile-doc tile, found in the stream's boundary table (the largest t with
-// bounds[t] <= i; a thread's postings ascend, so the search resumes where the last one ended);
-// posting i opens every image tile in (tile of posting i - 1, tile of i], the last posting closes
-// the rest.  (Streams of segments with deleted docs get no image: join_half_ok.)
+// bounds[t] <= i; a thread's postings ascend, so the search resumes where the last one ended); it
+// lands as far behind its piece's padded bound as it lies behind the raw one, and the last posting
+// of a piece writes the piece's padding.  (Streams of segments with deleted docs get no image:
+// join_half_ok.)
 __global__ void __launch_bounds__(kThreads)
 k_join_bound(const BoundWg* wgs) {
   const BoundWg W = wgs[blockIdx.x];
+  if (!W.n) return;
   const uint32_t* src = reinterpret_cast<const uint32_t*>(W.src);
   const uint32_t* sb = reinterpret_cast<const uint32_t*>(W.src_bounds);
   uint32_t* dst = reinterpret_cast<uint32_t*>(W.dst);
-  uint32_t* db = reinterpret_cast<uint32_t*>(W.dst_bounds);
-  if (!W.n) {
-    for (uint32_t u = threadIdx.x; u <= W.n_dst_tiles; u += blockDim.x) db[u] = 0u;
-    return;
-  }
+  const uint32_t* db = reinterpret_cast<const uint32_t*>(W.dst_bounds);
+  const uint32_t* raw = db + W.n_dst_tiles + 1u;
   auto tile_of = [&](uint32_t i, uint32_t lo) {   // largest t in [lo, n_src_tiles) with sb[t] <= i
     uint32_t hi = W.n_src_tiles;
     while (hi - lo > 1u) {
@@ -446,17 +507,16 @@ k_join_bound(const BoundWg* wgs) {
     const uint32_t e = src[i];
     const uint32_t doc = t * kJoinTile + (e >> 18);   // (0-based)
     const uint32_t bt = doc / kJoinBoundTile;
+    if (bt >= W.n_dst_tiles) continue;   // (no such doc in a well-formed stream)
     const uint32_t off = doc - bt * kJoinBoundTile;
     const uint32_t u = join_bound_u(W.kind, W.nc, W.nl, W.U, join_tf(e), (e >> 2) & 255u);
-    dst[i] = (off << 18) | u;
-    int32_t tp = -1;
-    if (i) {
-      const uint32_t pt = sb[t] < i ? t : tile_of(i - 1u, 0u);
-      tp = int32_t((pt * kJoinTile + (src[i - 1u] >> 18)) / kJoinBoundTile);
-    }
-    for (int32_t v = tp + 1; v <= int32_t(bt); ++v) db[v] = i;
-    if (i + 1u == W.n)
-      for (uint32_t v = bt + 1u; v <= W.n_dst_tiles; ++v) db[v] = W.n;
+    const uint32_t r0 = raw[bt], r1 = raw[bt + 1u];
+    if (i < r0 || i >= r1) continue;     // (as above: never outside the piece's slabs)
+    const uint32_t at = db[bt] + (i - r0);
+    dst[at] = (off << 18) | u;
+    if (i + 1u == r1)
+      for (uint32_t p = at + 1u, pe = db[bt + 1u]; p < pe; ++p)
+        dst[p] = (4u * kJoinBoundTile + 4u * (p & (kJoinSlab - 1u))) << 16;
   }
 }
 
@@ -520,10 +580,6 @@ __device__ __forceinline__ int join_form(uint32_t mode) {
 // the entry a lane without a posting carries: its own dummy accumulator, table offset 0
 __device__ __forceinline__ uint32_t join_dummy(unsigned lane) {
   return (JoinOff::dummy + 4u * lane) << 16;
-}
-// ... of a bound image: u = 0, the lane's dummy among JoinOffH's
-__device__ __forceinline__ uint32_t join_dummy_img(unsigned lane) {
-  return (JoinOffH::dummy + 4u * lane) << 16;
 }
 
 // N entries per lane (N slabs of 64): table reads back to back, then the multiply-adds, then
@@ -677,7 +733,10 @@ __device__ __forceinline__ void join_begin(JoinRun& r, const JoinLane& T, uint32
   const uint32_t st = lo > first ? lo : first;
   const uint32_t en = hi < c ? hi : c;
   r.cnt = en > st ? en - st : 0u;
-  const uint64_t addr = ((uint64_t(T.ent_hi) << 32) | T.ent_lo) + 4ull * (uint64_t(a) + (st - first));
+  // (paired tiles: a, n, c count slabs of a slab-aligned image — a share is whole slabs)
+  constexpr uint32_t kUnit = (M & kJHalf) ? 4u * kJoinSlab : 4u;              // bytes per counted unit
+  constexpr uint32_t kPre = (M & kJHalf) ? kJoinPre / kJoinSlab : kJoinPre;   // units requested
+  const uint64_t addr = ((uint64_t(T.ent_hi) << 32) | T.ent_lo) + uint64_t(kUnit) * (uint64_t(a) + (st - first));
   r.a_lo = uint32_t(addr);
   r.a_hi = uint32_t(addr >> 32);
   uint64_t mask = wave::ballot(r.cnt != 0u);
@@ -696,12 +755,19 @@ __device__ __forceinline__ void join_begin(JoinRun& r, const JoinLane& T, uint32
     // (paired tiles, one table: the mode word is just the half — the term's index says which)
     if ((M & kJSimple) && (M & kJHalf)) r.mode = j >= kMaxTerms ? uint32_t(kJoinHiHalf) : 0u;
     else if (!(M & kJSimple)) r.mode = wave::read_lane(T.mode, j);
-    take = cnt < kJoinPre ? cnt : kJoinPre;
+    take = cnt < kPre ? cnt : kPre;
     r.left = cnt - take;
-    r.rest = base + 4ull * take;
+    r.rest = base + uint64_t(kUnit) * take;
   }
   r.pre = take;
   r.mask = mask;
+  if (M & kJHalf) {   // slabs past the share's re-read its last one (an empty share: 256 bytes at `safe`)
+    const uint32_t top = take ? take - 1u : 0u;
+#pragma unroll
+    for (uint32_t k = 0; k < 4u; ++k)
+      r.e[k] = wave::gload_u32(base, lane * 4u + 256u * (k < top ? k : top));
+    return;
+  }
   const uint32_t last = take ? (take - 1u) * 4u : 0u;
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
@@ -759,33 +825,36 @@ __device__ __forceinline__ void join_finish(const unsigned char* lds, JoinRun& r
   }
 }
 
-// PAIRED TILES: a share is ONE sequence of groups.  A group is up to kJoinPre entries of one
-// (term, half) piece; the sequence is what begin() requested, then the rest of that piece, then
-// the pieces still in JoinRun::mask, in order.  A share is three to five groups long and every
-// one of them is a round trip to memory that nothing else of the wavefront covers (all the
-// wavefronts of a workgroup stand behind the same barrier), so group n + 1 is REQUESTED BEFORE
-// THE WAIT for group n — whether n is the prefetched group, the last full group in front of a
-// tail, or the last group of a piece, whose successor opens the next piece.  What makes that
-// possible: every group is exactly four loads per lane (offsets clamped to the group's last entry
-// as in join_begin: re-reading a line costs no traffic; lanes past the count take their dummy
-// once the data is there), so the number of loads between a request and its use is a
-// compile-time constant and the wait is s_waitcnt vmcnt(4), not vmcnt(0); and the groups
-// alternate between two NAMED register sets (the loop is unrolled by two), so no entry is copied
-// from one set to the other — a copy is a use, and would wait for the younger group.
+// PAIRED TILES: a share is ONE sequence of groups.  A group is one to four whole SLABS (64 entries
+// at a 256-byte-aligned address: the images are slab-aligned, k_join_bound) of one (term, half)
+// piece; the sequence is what begin() requested, then the rest of that piece, then the pieces still
+// in JoinRun::mask, in order.  A share is three to five groups long and every one of them is a
+// round trip to memory that nothing else of the wavefront covers (all the wavefronts of a
+// workgroup stand behind the same barrier), so group n + 1 is REQUESTED BEFORE THE WAIT for group
+// n — whether n is the prefetched group, the last full group in front of a tail, or the last group
+// of a piece, whose successor opens the next piece.  What makes that possible: every group is
+// exactly four loads per lane (a slab past the group's last re-reads the last: no traffic, never
+// used), so the number of loads between a request and its use is a compile-time constant and the
+// wait is s_waitcnt vmcnt(4), not vmcnt(0); and the groups alternate between two NAMED register
+// sets (the loop is unrolled by two), so no entry is copied from one set to the other — a copy is
+// a use, and would wait for the younger group.  No lane of a slab is without an entry (padding
+// entries carry their own dummy word): no per-lane count, no select.
+constexpr uint32_t kJoinPreSlabs = kJoinPre / kJoinSlab;
+static_assert(kJoinPreSlabs == 4u, "a group is four loads");
 struct JoinGroup {   // (wave-uniform) the descriptor of a group
-  uint64_t base;     // address of its first entry
-  uint32_t n;        // entries: 1 .. kJoinPre
-  float cs;          // of its piece
-  uint32_t mode;     //   half, and table slot | form where the terms have forms of their own
+  uint64_t base;     // address of its first slab
+  uint32_t n;        // slabs: 1 .. kJoinPreSlabs
+  float cs;          // of its piece: the BITS of k (JoinTerm of an image)
+  uint32_t mode;     //   half
 };
 struct JoinSeq {     // (wave-uniform) what is left of a share behind the groups handed out so far
   uint64_t rest;     // the current piece: address,
-  uint32_t left;     //   entries
+  uint32_t left;     //   slabs
   uint64_t mask;     // pieces (lanes of JoinRun::a_lo / a_hi / cnt) still to open
   float cs;          // of the current piece
   uint32_t mode;
 };
-// the next group of the sequence; false: the share is through — the descriptor is then one entry
+// the next group of the sequence; false: the share is through — the descriptor is then one slab
 // at `safe` (join_begin's empty share), for a request that nobody uses
 template<int M>
 __device__ __forceinline__ bool join_next(JoinSeq& s, const JoinRun& r, const JoinLane& T,
@@ -804,56 +873,74 @@ __device__ __forceinline__ bool join_next(JoinSeq& s, const JoinRun& r, const Jo
       more = false;
     }
   }
-  const uint32_t n = s.left < kJoinPre ? s.left : kJoinPre;
+  const uint32_t n = s.left < kJoinPreSlabs ? s.left : kJoinPreSlabs;
   g.base = more ? s.rest : safe;
   g.n = more ? n : 1u;
   g.cs = s.cs;
   g.mode = s.mode;
-  s.rest += 4ull * n;
+  s.rest += 256ull * n;
   s.left -= n;
   return more;
 }
-// four loads, always; RAW like JoinRun::e: lanes past `n` hold the group's last entry
+// four loads, always; clamped by slab: a slab past the group's last holds the last once more
 __device__ __forceinline__ void join_request(const JoinGroup& g, unsigned lane, uint32_t (&x)[4]) {
-  const uint32_t last = (g.n - 1u) * 4u;
+  const uint32_t top = g.n - 1u;
 #pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const uint32_t off = lane * 4u + 256u * uint32_t(k);
-    x[k] = wave::gload_u32(g.base, off < last ? off : last);
-  }
+  for (uint32_t k = 0; k < 4u; ++k)
+    x[k] = wave::gload_u32(g.base, lane * 4u + 256u * (k < top ? k : top));
 }
-// a group of a bound image: per posting one convert, one multiply-add, one LDS add into the half
-// `sh` says (0 or 16, wave-uniform) — uint(fma(ks, u, 2)) with ks = cs 2^-15 / U of the piece, the
-// 16-bit image of the exact contribution rounded up by one to kJoinHalfSlack units
+// THE CONTRIBUTION of a bound-image entry e (u: its low 16 bits) under the weight k = ceil(ks 2^16),
+// 1 <= k <= 32801 (ks = cs 2^-15 / U < 0.5005):  ((u k) >> 16) + 2, in the low half of the result
+// (hi = 0) or the high half (hi != 0).  u k + 2^17 < 2^32, so one 16 x 16 + 32 multiply-add forms
+// it and its top half is the value: the byte permute moves that half where the sums of the piece's
+// tile live (selector 0x0c0c0302: bytes 2, 3 down, zeros above; 0x03020c0c: bytes 2, 3 stay, zeros
+// below).  Exact integer arithmetic: the two forms below agree bit for bit.
+// `add` = 2 << 16 and `sel` = join_half_sel(hi) are wave-uniform; the multiply-add reads one of its
+// operands through the constant bus, so `add` is handed over in a vector register.
+__host__ __device__ __forceinline__ uint32_t join_half_sel(uint32_t hi) { return hi ? 0x03020c0cu : 0x0c0c0302u; }
+__device__ __forceinline__ uint32_t join_half_term(uint32_t e, uint32_t k, uint32_t add, uint32_t sel) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  uint32_t p, out;
+  asm("v_mad_u32_u16 %0, %1, %2, %3" : "=v"(p) : "v"(e), "s"(k), "v"(add));
+  asm("v_perm_b32 %0, %1, %1, %2" : "=v"(out) : "v"(p), "s"(sel));
+  return out;
+#else
+  const uint32_t p = (e & 0xFFFFu) * k + add;
+  return sel == join_half_sel(0u) ? p >> 16 : p & 0xFFFF0000u;
+#endif
+}
+// the helper over n entries under one (k, half): what irs_hip_join_half_probe runs, one workgroup
+__global__ void __launch_bounds__(kThreads)
+k_join_half_probe(const uint32_t* e, uint32_t n, uint32_t k, uint32_t hi, uint32_t* out) {
+  const uint32_t ks = wave::uniform(k), sel = wave::uniform(join_half_sel(hi));
+  uint32_t add = 2u << 16;
+  wave::keep(add);
+  for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) out[i] = join_half_term(e[i], ks, add, sel);
+}
+// N whole slabs of a bound image: per posting one multiply-add, one permute, the address shift and
+// one LDS add
 template<int N>
 __device__ __forceinline__ void join_post_img(const unsigned char* lds, const uint32_t (&e)[4],
-                                              float ks, uint32_t sh) {
+                                              uint32_t k, uint32_t add, uint32_t sel) {
   uint32_t fx[N];
 #pragma unroll
-  for (int k = 0; k < N; ++k)
-    fx[k] = static_cast<uint32_t>(wave::fma(ks, static_cast<float>(e[k] & 0xFFFFu), 2.f)) << sh;
+  for (int i = 0; i < N; ++i) fx[i] = join_half_term(e[i], k, add, sel);
 #pragma unroll
-  for (int k = 0; k < N; ++k) {
-    if (kAblNoAdd) wave::keep(fx[k]);
-    else wave::lds_add(lds, JoinOffH::acc + (e[k] >> 16), fx[k]);
+  for (int i = 0; i < N; ++i) {
+    if (kAblNoAdd) wave::keep(fx[i]);
+    else wave::lds_add(lds, JoinOffH::acc + (e[i] >> 16), fx[i]);
   }
 }
 __device__ __forceinline__ void join_group_img(const unsigned char* lds, const uint32_t (&x)[4],
-                                               const JoinGroup& g, unsigned lane) {
-  const uint32_t sh = join_half_shift(g.mode);
-  if (g.n == kJoinPre) {   // (wave-uniform) a full group: every lane's four entries count
-    join_post_img<4>(lds, x, g.cs, sh);
-    return;
-  }
-  const uint32_t dummy = join_dummy_img(lane);
-  uint32_t e[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) e[k] = lane + 64u * uint32_t(k) < g.n ? x[k] : dummy;
-  const uint32_t slabs = (g.n + 63u) >> 6;
-  if (slabs >= 4u) join_post_img<4>(lds, e, g.cs, sh);
-  else if (slabs == 3u) join_post_img<3>(lds, e, g.cs, sh);
-  else if (slabs == 2u) join_post_img<2>(lds, e, g.cs, sh);
-  else join_post_img<1>(lds, e, g.cs, sh);
+                                               const JoinGroup& g) {
+  const uint32_t k = __float_as_uint(g.cs);
+  const uint32_t sel = join_half_sel(g.mode & uint32_t(kJoinHiHalf));
+  uint32_t add = 2u << 16;
+  wave::keep(add);   // (in a vector register, once per group)
+  if (g.n >= 4u) join_post_img<4>(lds, x, k, add, sel);   // (wave-uniform)
+  else if (g.n == 3u) join_post_img<3>(lds, x, k, add, sel);
+  else if (g.n == 2u) join_post_img<2>(lds, x, k, add, sel);
+  else join_post_img<1>(lds, x, k, add, sel);
 }
 
 template<int M>
@@ -875,7 +962,7 @@ __device__ __forceinline__ void join_finish_pairs(const unsigned char* lds, Join
   // Set A starts as the prefetched group; from then on the sets alternate.  Each half of the
   // loop body: describe the next group, request it into the other set, only then accumulate
   // (= wait for) this one.  A share that is through still gets its four loads per half — of one
-  // entry at `safe`, never used: with a request that depends on a branch, the wait in front of
+  // slab at `safe`, never used: with a request that depends on a branch, the wait in front of
   // the accumulation could count on no younger load at all.  One way in, one way out and plain
   // if / else inside: with exits from the middle, the control-flow lowering adds edges (never
   // taken) along which a set would be requested twice in a row, and the wait-count bookkeeping
@@ -892,10 +979,10 @@ __device__ __forceinline__ void join_finish_pairs(const unsigned char* lds, Join
   do {
     const bool second = join_next<M>(s, r, T, safe, gb);
     join_request(gb, lane, b);
-    join_group_img(lds, a, ga, lane);
+    join_group_img(lds, a, ga);
     more = join_next<M>(s, r, T, safe, ga);   // (a share that is through stays through)
     join_request(ga, lane, a);
-    if (second) join_group_img(lds, b, gb, lane);
+    if (second) join_group_img(lds, b, gb);
   } while (more);
 }
 
@@ -956,7 +1043,8 @@ __device__ __forceinline__ JoinLane join_lane(const unsigned char* smem, unsigne
 }
 
 // ... of a pair of tiles (kJHalf): lane j < 2 * kMaxTerms = term j % kMaxTerms in the pair's tile
-// j / kMaxTerms; the records are the IMAGES' (JoinOffH::jts): cs = cs 2^-15 / U, made by the host
+// j / kMaxTerms; the records are the IMAGES' (JoinOffH::jts): the cs field holds the bits of k
+// (join_half_k), made by the host
 static_assert(kMaxTerms == 16u, "join_lane_img / join_pairs: lane >> 4 is the tile of the pair");
 __device__ __forceinline__ JoinLane join_lane_img(const unsigned char* smem, unsigned lane) {
   JoinLane T{};
@@ -1357,9 +1445,13 @@ __device__ __forceinline__ void join_tiles(unsigned char* smem, const JoinTileCt
 // A visit here covers TWO consecutive tiles of kJoinBoundTile docs: a term's entries of both are
 // contiguous in its bound image, and the accumulator word of a doc offset holds the first tile's
 // sum in its low 16 bits and the second tile's in its high 16 bits.  A contribution is
-// uint(fma(cs 2^-15 / U, u, 2)) with u the image's bound of the posting's factor (join_bound_u):
-// with x_i = cs T_i / 2^15 it exceeds x_i + 1 - 2^-7 and stays below x_i + cs 2^-15 c / U + 2 + 2^-7,
-// and since sum_i cs_i Tsup_i < 2^30 (fx_mul) the extra terms sum to less than c (1 + 2^-9) / 2, so
+// ((u k) >> 16) + 2 (join_half_term) with u the image's bound of the posting's factor (join_bound_u)
+// and k = ceil(ks 2^16), ks = cs 2^-15 / U (join_half_k).  With x_i = cs T_i / 2^15 = ks T_i U,
+// u >= T_i U and k >= ks 2^16:   floor(u k / 2^16) + 2  >  ks u + 1  >=  x_i + 1;   and with
+// k < ks 2^16 + 1, u < 2^16, u <= T_i U + c:   floor(u k / 2^16) + 2  <  ks u + 3  <=  x_i + c ks + 3.
+// Since sum_i cs_i Tsup_i < 2^30 (fx_mul), sum_i ks_i < 2^15 / 65471 < 0.5005 and the c ks_i sum to
+// less than 1.51.  The exact contribution f_i lies within 65 units of x_i 2^15 (64 units of float
+// rounding + the truncation), so
 //     (S - join_half_slack(m)) 2^15  <  f  <  S 2^15      (S: 16-bit sum, f: exact 32-bit sum, m terms)
 // and  f >= thr  ==>  S >= max(thr >> 15, 1).  The docs that pass are staged by doc id with S;
 // k_join_rescore looks their postings up in the EXACT streams, forms f as join_post does and
@@ -1368,13 +1460,19 @@ __device__ __forceinline__ void join_tiles(unsigned char* smem, const JoinTileCt
 // Eligibility (plan_join.h join_half_ok): the plain disjunctions of a batch, no deleted docs in
 // their segments (those entries leave the doc order k_join_rescore's search relies on), every
 // signature with an image (join_bound_sup).
-// a(m): how far a 16-bit sum can lie above f / 2^15 — per term 2 + 2^-7 + 65 / 2^15 (the + 2, the
-// roundings of the multiply-add and of cs 2^-15 / U, 64 units of float rounding + the truncation on
-// the exact side), plus kJoinBoundSlack (1 + 2^-9) / 2 < 1.51 for the bounds' own slack:
-// below 2 m + 2 for m <= kMaxTerms.  The staging threshold, k_join_rescore's look-up window
-// (S >= S_k - a(m) - 1) and its "k pass whenever a doc is left out" argument all use this one.
-__host__ __device__ __forceinline__ uint32_t join_half_slack(uint32_t m) { return 2u * m + 2u; }
-static_assert(kJoinBoundSlack * 0.51f + kMaxTerms * (1.f / 128.f + 65.f / 32768.f) < 2.f, "join_half_slack");
+// a(m): how far a 16-bit sum can lie above f / 2^15 — per term 3 + 65 / 2^15 (the + 2, less than one
+// unit for k's rounding up, 64 units of float rounding + the truncation on the exact side), plus
+// less than 1.51 for the bounds' own slack: below 3 m + 2 for m <= kMaxTerms.  The staging
+// threshold, k_join_rescore's look-up window (S >= S_k - a(m) - 1) and its "k pass whenever a doc
+// is left out" argument all use this one.
+__host__ __device__ __forceinline__ uint32_t join_half_slack(uint32_t m) { return 3u * m + 2u; }
+static_assert(kJoinBoundSlack * 0.5005f + kMaxTerms * (65.f / 32768.f) < 2.f, "join_half_slack");
+static_assert(32768u + 3u * kMaxTerms + 2u < 65536u, "a 16-bit sum of kMaxTerms terms");
+// k of an image's JoinTerm record: ceil(cs 2^-15 / U 2^16), at least 1 (at most 32801: ks < 0.5005)
+inline uint32_t join_half_k(float cs, float U) {
+  const double v = std::ceil(double(cs) / double(U) * 2.0);
+  return v >= 1.0 ? (v < 65535.0 ? uint32_t(v) : 65535u) : 1u;
+}
 template<int M>
 __device__ __forceinline__ void join_pairs(unsigned char* smem, const JoinTileCtx& ctx,
                                            const JoinLane& T, uint32_t tile0, uint32_t ntile,
@@ -1558,7 +1656,7 @@ k_join_score(const JoinArgs* __restrict__ args) {
         uint32_t v = 0;
         if (j < qd.n_terms)
           v = reinterpret_cast<const uint32_t*>(args->jterms[qd.first_term + j].bounds)[tile0 + i];
-        rng[e] = v;
+        rng[e] = HALF ? v / kJoinSlab : v;   // (slab-aligned images: their bounds count slabs)
       }
       if constexpr (HALF) {   // the image records to LDS: a JoinTerm = two 16-byte halves
         JoinQuad* jts = reinterpret_cast<JoinQuad*>(smem + JoinOffH::jts);

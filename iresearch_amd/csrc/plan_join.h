@@ -425,6 +425,14 @@ bool build_streams(irs_hip_batch* b) {
     std::vector<float> img_U(streams.size(), 0.f);
     std::vector<uint64_t> img_ent(streams.size(), 0), img_bnd(streams.size(), 0);
     std::vector<uint32_t> img_tiles(streams.size(), 0), imgs;   // imgs: the streams with an image
+    // what an image takes (join.h: slab-aligned pieces): its entries by join_image_entries' bound,
+    // whole slabs from a 256-byte-aligned offset — known without a read-back — and two boundary
+    // tables, the padded one k_join_score reads and the raw one k_join_bound places postings by
+    auto img_entries = [&](uint32_t si) {
+      return (join_image_entries(streams[si].n, img_tiles[si]) + kJoinSlab - 1) / kJoinSlab * kJoinSlab;
+    };
+    auto img_bounds = [&](uint32_t si) { return 2 * (uint64_t(img_tiles[si]) + 1); };
+    static_assert(kJoinSlab % scache::kAlign == 0, "a slab-aligned image is stream-aligned");
     // Tsup per (signature, frequency bound): 256 table values each, so kept per deal
     std::vector<std::vector<float>> sup_of(sigs.size(), std::vector<float>(kJoinTfMax + 1u, -1.f));
     bool all = true;
@@ -496,11 +504,11 @@ bool build_streams(irs_hip_batch* b) {
           uint64_t e = 0, bn = 0;
           std::vector<uint64_t> e_off, b_off;
           while (to < missed.size() && streams[missed[to]].seg == streams[missed[from]].seg &&
-                 (to == from || e + streams[missed[to]].n <= scache::kSlabEntries)) {
+                 (to == from || e + img_entries(missed[to]) <= scache::kSlabEntries)) {
             e_off.push_back(e);
             b_off.push_back(bn);
-            e += (uint64_t(streams[missed[to]].n) + scache::kAlign - 1) / scache::kAlign * scache::kAlign;
-            bn += uint64_t(img_tiles[missed[to]]) + 1;
+            e += img_entries(missed[to]);
+            bn += img_bounds(missed[to]);
             ++to;
           }
           const uint64_t bytes = pool::size_class((e + kJoinSlack + bn) * 4);
@@ -552,8 +560,8 @@ bool build_streams(irs_hip_batch* b) {
         if (iwhere[si] != kPrivate) continue;
         img_ent[si] = ie;
         img_bnd[si] = ib;
-        ie += (uint64_t(streams[si].n) + scache::kAlign - 1) / scache::kAlign * scache::kAlign;
-        ib += uint64_t(img_tiles[si]) + 1;
+        ie += img_entries(si);
+        ib += img_bounds(si);
       }
       if (ie + ib) {
         if (!b->join.d_img_entries.alloc((ie + kJoinSlack) * 4) || !b->join.d_img_bounds.alloc((ib + 1) * 4))
@@ -593,7 +601,8 @@ bool build_streams(irs_hip_batch* b) {
       }
       if (bwgs.size() > 0x7FFFFFFFull) return false;
       b->join.n_images = uint32_t(imgs.size());
-      // the per-(unit, term) records of k_join_score<kJKHalf>: the image, cs 2^-15 / U, the tiles
+      // the per-(unit, term) records of k_join_score<kJKHalf>: the image, k = ceil(cs 2^-15 / U 2^16)
+      // (its bits in the cs field: join_half_term's integer weight), the tiles
       jimgs.assign(b->qterms.size(), JoinTerm{});
       for (uint32_t u : b->join.units) {
         const DevQuery& dq = b->queries[u];
@@ -603,7 +612,8 @@ bool build_streams(irs_hip_batch* b) {
           JoinTerm& ji = jimgs[dq.first_term + j];
           ji.entries = img_ent[si];
           ji.bounds = img_bnd[si];
-          ji.cs = (b->qterms[dq.first_term + j].c0 * dq.fx_mul) * (1.f / 32768.f) / img_U[si];
+          const uint32_t k16 = join_half_k(b->qterms[dq.first_term + j].c0 * dq.fx_mul, img_U[si]);
+          std::memcpy(&ji.cs, &k16, 4);
           ji.mode = 0;
           ji.pad[0] = img_tiles[si];
           ji.pad[1] = 0;
@@ -613,7 +623,9 @@ bool build_streams(irs_hip_batch* b) {
     }
   }
   if (b->join.img_on) {
-    if (!b->join.d_jimgs.alloc(jimgs.size() * sizeof(JoinTerm)) ||
+    // (k_join_score<kJKHalf> reads one slab, 256 bytes, at the records' address for every request
+    // that nobody uses: join_next)
+    if (!b->join.d_jimgs.alloc(std::max<size_t>(1024, jimgs.size() * sizeof(JoinTerm))) ||
         !b->join.d_bwgs.alloc(std::max<size_t>(1, bwgs.size()) * sizeof(BoundWg)) ||
         !b->up.copy(b->join.d_jimgs.p, jimgs.data(), jimgs.size() * sizeof(JoinTerm)) ||
         (!bwgs.empty() && !b->up.copy(b->join.d_bwgs.p, bwgs.data(), bwgs.size() * sizeof(BoundWg))))
@@ -709,8 +721,13 @@ bool launch_join(irs_hip_batch* b, rt::stream_t st) {
     // may still be filling on another stream
     ok = wait_for_streams(b, st);
     if (ok) {
-      RT_LAUNCH(k_join_bound, bgrid, kThreads, 0, st, b->join.d_bwgs.as<BoundWg>());
+      // the bounds pass and the padded prefix (a stream's first workgroup), then the write pass
+      RT_LAUNCH(k_join_bound_tiles, bgrid, kThreads, 0, st, b->join.d_bwgs.as<BoundWg>());
       ok = rt::last_error_ok();
+      if (ok) {
+        RT_LAUNCH(k_join_bound, bgrid, kThreads, 0, st, b->join.d_bwgs.as<BoundWg>());
+        ok = rt::last_error_ok();
+      }
     }
   }
   if (ok && fill) {

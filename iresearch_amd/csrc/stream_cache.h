@@ -12,7 +12,9 @@
 //
 // BOUND IMAGES (join.h k_join_bound) are cached next to them: an image is a function of (segment,
 // term, scorer signature), so it has a map of its own with that key, and lives in slabs of the same
-// kind — the same pinning, fill event, LRU order and budget; `held` counts both.  The counters
+// kind — the same pinning, fill event, LRU order and budget; `held` counts both.  An image's entries
+// are whole slabs of 64 from a 256-byte-aligned offset, sized by join_image_entries' bound (join.h:
+// every (term, tile) piece padded to a slab), and it has two boundary tables (plan_join.h).  The counters
 // (hits, misses, evictions) and the size of `map` keep counting exact streams only.
 // Included by irs_hip.hip (one translation unit).
 #pragma once

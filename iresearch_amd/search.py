@@ -1067,6 +1067,25 @@ def join_bound_rule(kind, norm_const, norm_length, tf_bound, L=None):
     return u, float(scale.value), float(slack.value), int(tile.value)
 
 
+def join_half_rule(cs, scale, L=None):
+    """irs_hip_join_half_rule: the integer weight k of a term weight cs on an image of scale U."""
+    L = L or _lib.lib()
+    k = C.c_uint32()
+    _lib.check(L, L.irs_hip_join_half_rule(cs, scale, C.byref(k)), "irs_hip_join_half_rule")
+    return int(k.value)
+
+
+def join_half_probe(entries, k, high_half, L=None, device=0):
+    """irs_hip_join_half_probe: the paired kernel's per-posting helper over `entries` (uint32)."""
+    L = L or _lib.lib()
+    e = np.ascontiguousarray(entries, np.uint32)
+    out = np.zeros(e.size, np.uint32)
+    p = C.POINTER(C.c_uint32)
+    _lib.check(L, L.irs_hip_join_half_probe(device, e.ctypes.data_as(p), e.size, int(k), int(bool(high_half)),
+                                            out.ctypes.data_as(p)), "irs_hip_join_half_probe")
+    return out
+
+
 def set_stream_cache(nbytes, L=None, device=0):
     """The cache's byte budget (irs_hip_device_set_stream_cache); 0 switches it off."""
     L = L or _lib.lib()

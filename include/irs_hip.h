@@ -291,6 +291,39 @@ typedef enum irs_hip_scorer_kind {
  * means what it always did, and a kind with the flag was IRS_HIP_EINVAL before. */
 #define IRS_HIP_PHRASE_REQUIRED 0x400
 
+/* OR-ed into the `kind` of an included IRS_HIP_OP_PHRASE entry: an OPTIONAL TERM — a by_term child
+ * of the irs::Or that also holds this phrase, `"new york" hotel cheap` (Or::prepare prepares every
+ * child on its own, boolean_filter.cpp:150-210; MakeDisjunction over {PhraseIterator, term
+ * iterators}, disjunction.hpp:1411-1467; min_match <= 1, merge SUM).  Entry order in [first_term,
+ * first_term + n_terms): the phrase's entries (at least 2), then 1 or more entries with this flag,
+ * then 0 to IRS_HIP_MAX_EXCLUDED IRS_HIP_EXCLUDE entries.  An entry without the flag behind one with
+ * it, the flag on the first entry (fewer than 2 phrase entries in front of the first flagged one),
+ * or the flag on an OR / AND / MINMATCH entry is IRS_HIP_EINVAL.  A flagged entry carries its OWN
+ * scorer values (the by_term's statistics and boost x the Or's boost), validated like any by_term
+ * entry; its phrase_offset is ignored; the word entries carry the phrase's one scorer as always.
+ * Phrase entries + flagged entries <= IRS_HIP_MAX_PHRASE_TERMS (more: IRS_HIP_EUNSUPPORTED); a
+ * query or a batch that mixes this flag with IRS_HIP_PHRASE_ALT or IRS_HIP_PHRASE_REQUIRED is
+ * IRS_HIP_EUNSUPPORTED; merge stays IRS_HIP_MERGE_SUM.  Per segment:
+ *   d matches iff the phrase frequency pf(d) > 0 OR at least one optional term holds d (minus
+ *   deleted docs and IRS_HIP_EXCLUDE terms);
+ *   score(d) = [pf(d) > 0] s_phrase(tf = pf(d), norm(d)) + sum over the optional terms holding d of
+ *   s_j(tf_j(d), norm(d)), in float32, entry order.
+ * An absent phrase word (IRS_HIP_NO_TERM or no docs) empties the phrase child only: the terms still
+ * match; an absent optional term adds nothing; everything absent empties the query in that
+ * segment.  Execution is two passes over disjoint doc sets (the phrase's matches on k_phrase_or,
+ * every other doc of the terms as a plain disjunction masked by the first pass's docs) and a merge
+ * of their top k; total_hits, the top k, re-runs (irs_hip_batch_reruns counts both passes),
+ * irs_hip_batch_configure, irs_hip_batch_set_shared_threshold, irs_hip_batch_set_min_scores and
+ * the match sets (the union) behave as for any batch; irs_hip_batch_plan queues the first pass's
+ * plan stage.  irs_hip_batch_set_doc_sets / _host and irs_hip_batch_set_comm on a batch with such a
+ * query are IRS_HIP_EUNSUPPORTED (the second pass's doc sets are the first pass's output), and
+ * irs_hip_batch_set_wand leaves both passes unpruned.  A batch with such
+ * a query runs all its phrases on k_phrase_or, plain phrases giving bit for bit what they give in
+ * a batch of their own.  A compatible addition to ABI 12: without the flag an entry means what it
+ * always did, and a kind with the flag was IRS_HIP_EINVAL before (batch_create's scorer switch
+ * took 0x800 | kind for an unknown scorer under every op). */
+#define IRS_HIP_PHRASE_OPTIONAL 0x800
+
 /* The same bit OR-ed into the `kind` of an included IRS_HIP_OP_AND entry: one more member of the
  * group opened by the nearest preceding included entry without the flag — an And whose children
  * are Ors of by_term (And::prepare -> make_conjunction over the children, an Or child being its

@@ -22,6 +22,7 @@ EXCLUDE = 0x100   # irs_hip_term_scorer.kind of an excluded term (irs::Not)
 PHRASE_ALT = 0x200   # OR-ed into a phrase entry's kind: one more member of the part before it
 GROUP_ALT = PHRASE_ALT   # ... into an And entry's kind: one more member of the group (Or) before it
 PHRASE_REQUIRED = 0x400   # ... into a phrase entry's kind: a by_term child of the And that holds the phrase
+PHRASE_OPTIONAL = 0x800   # ... into a phrase entry's kind: a by_term child of the Or that holds the phrase
 NO_TERM = 0xFFFFFFFF
 NO_DOC_SET = 0xFFFFFFFF   # row_of_unit of an unrestricted unit (irs_hip_batch_set_doc_sets)
 PATH_AUTO, PATH_ITEMS, PATH_JOINED = 0, 1, 2

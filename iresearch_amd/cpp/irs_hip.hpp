@@ -132,12 +132,6 @@ struct by_term {
   uint32_t term = IRS_HIP_NO_TERM;
   float boost = 1.f;
 };
-struct Or {
-  std::vector<by_term> subs;
-  uint32_t min_match_count = 1;  // irs::Or::min_match_count()
-  irs_hip_merge merge_type = IRS_HIP_MERGE_SUM;  // boolean_filter::merge_type()
-  float boost = 1.f;   // multiplies into its terms' boosts (boolean_filter.cpp:153-154, 204)
-};
 struct by_phrase {
   std::vector<uint32_t> terms;
   std::vector<uint32_t> offsets;  // relative to the first term; empty = consecutive words
@@ -165,6 +159,19 @@ struct by_phrase {
     offsets.push_back(next + offs);
     return *this;
   }
+};
+// irs::Or of by_term children.  `phrases`: ONE by_phrase of plain terms as a child next to the
+// by_terms of `subs` — a phrase or optional terms, `"new york" hotel cheap`
+// (IRS_HIP_PHRASE_OPTIONAL: the phrase's entries with its one blob, then every by_term with its own
+// statistics; the Or's boost multiplies into each child's).  With a phrase: min_match_count <= 1,
+// merge SUM, at most IRS_HIP_MAX_PHRASE_TERMS words and terms in all (anything else:
+// not_supported); without terms in `subs` it is the phrase.
+struct Or {
+  std::vector<by_term> subs;
+  uint32_t min_match_count = 1;  // irs::Or::min_match_count()
+  irs_hip_merge merge_type = IRS_HIP_MERGE_SUM;  // boolean_filter::merge_type()
+  float boost = 1.f;   // multiplies into its terms' boosts (boolean_filter.cpp:153-154, 204)
+  std::vector<by_phrase> phrases;
 };
 // irs::And of by_term children (`subs`) and Or-of-by_term children (`groups`: an And of Ors,
 // IRS_HIP_GROUP_ALT).  Children in that order: subs, then groups.  A group of one term is that term
@@ -320,6 +327,43 @@ std::vector<PreparedQuery> prepare(const std::vector<filter>& filters, const Sco
     if (const auto* t = std::get_if<by_term>(&f)) {
       q.op = IRS_HIP_OP_OR;
       q.terms.push_back(one(*t));
+    } else if (std::get_if<Or>(&f) && !std::get_if<Or>(&f)->phrases.empty()) {
+      // a phrase or optional terms (Or::prepare prepares every child on its own,
+      // boolean_filter.cpp:150-210; MakeDisjunction, disjunction.hpp:1411-1467): the phrase's words
+      // with its ONE blob, then every by_term with its own statistics, flagged IRS_HIP_PHRASE_OPTIONAL
+      const Or& o = *std::get_if<Or>(&f);
+      if (o.phrases.size() > 1)
+        throw not_supported(IRS_HIP_EUNSUPPORTED, "Or: two phrases (ONE by_phrase plus by_terms is taken)");
+      const by_phrase& p = o.phrases[0];
+      if (!p.members.empty())
+        throw not_supported(IRS_HIP_EUNSUPPORTED, "Or: a variadic by_phrase with optional terms "
+                            "(ONE by_phrase of plain terms plus by_terms is taken)");
+      if (o.min_match_count > 1)
+        throw not_supported(IRS_HIP_EUNSUPPORTED, "Or: a by_phrase child with min_match_count > 1");
+      if (o.merge_type != IRS_HIP_MERGE_SUM && !o.subs.empty())
+        throw not_supported(IRS_HIP_EUNSUPPORTED, "Or: a by_phrase child merges with SUM on the GPU path");
+      if (p.terms.size() < 2)
+        throw illegal_argument(IRS_HIP_EINVAL, "Or: a by_phrase of one term is a by_term");
+      if (!p.offsets.empty() && (p.offsets.size() != p.terms.size() || p.offsets[0] != 0))
+        throw illegal_argument(IRS_HIP_EINVAL, "by_phrase: offsets are relative to the first term");
+      if (p.terms.size() + o.subs.size() > IRS_HIP_MAX_PHRASE_TERMS)
+        throw not_supported(IRS_HIP_EUNSUPPORTED, "Or: more than IRS_HIP_MAX_PHRASE_TERMS phrase words "
+                            "and optional terms");
+      q.op = IRS_HIP_OP_PHRASE;
+      TermStats st;  // ONE blob for the phrase, from its own words (FixedPrepareCollect)
+      for (uint32_t t : p.terms) scorer.collect(st, dwf, docs_with_term(t), ttf);
+      irs_hip_term_scorer e = scorer.term_scorer(st, o.boost * p.boost);
+      for (size_t i = 0; i < p.terms.size(); ++i) {
+        e.term = p.terms[i];
+        e.phrase_offset = p.offsets.empty() ? uint32_t(i) : p.offsets[i];
+        q.terms.push_back(e);
+      }
+      for (const auto& t : o.subs) {
+        irs_hip_term_scorer r = one(by_term{t.term, o.boost * t.boost});
+        r.kind |= IRS_HIP_PHRASE_OPTIONAL;
+        r.phrase_offset = 0;
+        q.terms.push_back(r);
+      }
     } else if (const auto* o = std::get_if<Or>(&f)) {
       q.op = o->min_match_count > 1 ? IRS_HIP_OP_MINMATCH : IRS_HIP_OP_OR;
       q.min_match = o->min_match_count > 1 ? o->min_match_count : 0;

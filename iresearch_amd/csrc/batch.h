@@ -141,6 +141,9 @@ struct BlockWork {
   // by_phrase with required terms (IRS_HIP_PHRASE_REQUIRED in any unit: every phrase unit of the
   // batch runs on k_phrase_and): per unit the rows that are phrase words, the required terms' behind
   bool required = false;
+  // ... or optional terms (IRS_HIP_PHRASE_OPTIONAL in any unit: every phrase unit of the batch runs
+  // on k_phrase_or, the lead among the words only); the term pass: irs_hip_batch::opt
+  bool optional = false;
   std::vector<uint32_t> n_phrase;
   DevBuf d_n_phrase;
   DevBuf d_pilot;             // the lead items the pilot pass samples, {unit, item} each
@@ -153,7 +156,8 @@ struct BlockWork {
 // for variadic phrases; n_wgs: k_conj_any workgroups.  Of BlockWork the grouped path uses units,
 // items, n_items, n_wgs, the lead-item tables (d_units, d_items, d_hist, d_item_base, d_unit_items,
 // d_seek, d_recs, d_item_hits), opens / d_opens / d_lead_rows and the pilot list (d_pilot,
-// n_pilot, pilot_stride); d_lg, d_lead_of, n_phrase_wgs, `variadic` and `required` stay unused.
+// n_pilot, pilot_stride); d_lg, d_lead_of, n_phrase_wgs, `variadic`, `required` and `optional` stay
+// unused.
 struct AnyWork : BlockWork {};
 
 // Units with excluded terms (IRS_HIP_EXCLUDE) or a doc set (irs_hip_batch_set_doc_sets), excl.h: one
@@ -306,6 +310,15 @@ struct irs_hip_batch {
   JoinWork join;
   BlockWork blocks;
   AnyWork any;
+  // A batch with optional terms (IRS_HIP_PHRASE_OPTIONAL): this batch is the PHRASE PASS; `opt` — a
+  // batch of its own, created and destroyed with this one, the same units — is the TERM PASS: every
+  // unit's optional terms as a plain disjunction, restricted to the doc sets in d_taken ([unit]
+  // [taken_words] u64, bit = doc id: zeroed at the start of a run, k_phrase_or sets the docs the phrase
+  // matched, k_not_words turns the rows into "not taken").  k_union_topk merges the two passes' top k and totals into d_union_*, which is
+  // what the result calls hand out.
+  irs_hip_batch* opt = nullptr;
+  DevBuf d_taken, d_union_out, d_union_count, d_union_hits;
+  uint64_t taken_words = 0;
   ExclWork excl;
   MatchWork match;
   Groups groups;

@@ -502,6 +502,70 @@ uint64_t irs_hip_segment_live_docs(const irs_hip_segment* seg) { return seg ? se
 // ----------------------------------------------------------------- batch --
 
 static int batch_create_multi_impl(irs_hip_segment* const* segs, uint32_t n_segs,
+                                   const irs_hip_query* queries, uint32_t nq_user,
+                                   const irs_hip_term_scorer* all_terms, uint32_t n_entries,
+                                   irs_hip_batch** out);
+static int batch_set_doc_sets_impl(irs_hip_batch* b, const void* sets, bool host, uint64_t n_rows,
+                                   uint64_t n_words, const uint32_t* row_of_unit);
+
+// The TERM PASS of a batch with optional terms (IRS_HIP_PHRASE_OPTIONAL; batch.h irs_hip_batch::opt):
+// a batch of its own over the same segments and queries — per query its optional entries as a plain
+// Or (the flag taken off, the IRS_HIP_EXCLUDE entries behind them; a query without optional entries:
+// one absent term, an empty unit) — whose units are restricted to the rows of b->d_taken, the doc
+// sets k_phrase_or takes the phrase's matches out of.  Masked units run as work items (k_items_*,
+// k_pilot, k_score) and never join streams.
+static int create_term_pass(irs_hip_batch* b, irs_hip_segment* const* segs, uint32_t n_segs,
+                            const irs_hip_query* queries, const irs_hip_term_scorer* all_terms,
+                            uint32_t n_entries) {
+  std::vector<irs_hip_query> cq(b->nq_user);
+  std::vector<uint32_t> from;   // the term pass's entries: their indices in the caller's, ~0u: the absent one
+  for (uint32_t q = 0; q < b->nq_user; ++q) {
+    const irs_hip_query& in = queries[q];
+    cq[q] = in;
+    cq[q].op = IRS_HIP_OP_OR;
+    cq[q].min_match = 1;
+    cq[q].first_term = uint32_t(from.size());
+    bool any = false;
+    for (uint32_t j = 0; j < in.n_terms; ++j) {
+      const int32_t kind = all_terms[in.first_term + j].kind;
+      const bool optional = kind != IRS_HIP_EXCLUDE && (kind & IRS_HIP_PHRASE_OPTIONAL) != 0;
+      if (optional || (any && kind == IRS_HIP_EXCLUDE)) from.push_back(in.first_term + j);
+      any = any || optional;
+    }
+    if (!any) from.push_back(~0u);
+    cq[q].n_terms = uint32_t(from.size()) - cq[q].first_term;
+  }
+  std::vector<irs_hip_term_scorer> ct(from.size() * n_segs);
+  for (uint32_t s = 0; s < n_segs; ++s) {
+    for (size_t i = 0; i < from.size(); ++i) {
+      irs_hip_term_scorer& t = ct[s * from.size() + i];
+      if (from[i] == ~0u) {
+        t = irs_hip_term_scorer{};
+        t.term = IRS_HIP_NO_TERM;
+        t.kind = IRS_HIP_SCORE_BM1;
+      } else {
+        t = all_terms[size_t(s) * n_entries + from[i]];
+        if (t.kind != IRS_HIP_EXCLUDE) t.kind &= ~IRS_HIP_PHRASE_OPTIONAL;
+        t.phrase_offset = 0;
+      }
+    }
+  }
+  if (const int rc = batch_create_multi_impl(segs, n_segs, cq.data(), b->nq_user, ct.data(),
+                                             uint32_t(from.size()), &b->opt))
+    return rc;
+  uint32_t max_docs = 0;
+  for (uint32_t s = 0; s < n_segs; ++s) max_docs = std::max(max_docs, segs[s]->dev.num_docs);
+  b->taken_words = uint64_t(max_docs) / 64u + 1u;
+  std::vector<uint32_t> row_of(b->nq);
+  for (uint32_t u = 0; u < b->nq; ++u) row_of[u] = u;
+  if (!b->d_taken.alloc(uint64_t(b->nq) * b->taken_words * 8u) ||
+      !b->d_union_out.alloc(uint64_t(b->nq) * b->k_max * sizeof(Hit)) ||
+      !b->d_union_count.alloc(uint64_t(b->nq) * 4u) || !b->d_union_hits.alloc(uint64_t(b->nq) * 8u))
+    return IRS_HIP_ENOMEM;
+  return batch_set_doc_sets_impl(b->opt, b->d_taken.p, false, b->nq, b->taken_words, row_of.data());
+}
+
+static int batch_create_multi_impl(irs_hip_segment* const* segs, uint32_t n_segs,
                                const irs_hip_query* queries, uint32_t nq_user,
                                const irs_hip_term_scorer* all_terms, uint32_t n_entries,
                                irs_hip_batch** out) {
@@ -574,22 +638,29 @@ static int batch_create_multi_impl(irs_hip_segment* const* segs, uint32_t n_segs
       }
       // a phrase with required terms (IRS_HIP_PHRASE_REQUIRED): the phrase's words (n_words, at
       // least 2), then the by_term children of the And that holds it, nothing else behind them
+      // ... or with optional terms (IRS_HIP_PHRASE_OPTIONAL): the by_term children of the Or that
+      // holds it, in the same place; one query takes one of the two flags
       uint32_t n_words = n_incl;
+      int32_t behind = 0;   // the flags of the entries behind the words
       if (in.op == IRS_HIP_OP_PHRASE) {
+        constexpr int32_t kBehind = IRS_HIP_PHRASE_REQUIRED | IRS_HIP_PHRASE_OPTIONAL;
         n_words = 0;
-        while (n_words < n_incl && !(terms[in.first_term + n_words].kind & IRS_HIP_PHRASE_REQUIRED)) ++n_words;
-        for (uint32_t j = n_words; j < n_incl; ++j)
-          if (!(terms[in.first_term + j].kind & IRS_HIP_PHRASE_REQUIRED)) rc = IRS_HIP_EINVAL;
+        while (n_words < n_incl && !(terms[in.first_term + n_words].kind & kBehind)) ++n_words;
+        for (uint32_t j = n_words; j < n_incl; ++j) {
+          if (!(terms[in.first_term + j].kind & kBehind)) rc = IRS_HIP_EINVAL;
+          behind |= terms[in.first_term + j].kind & kBehind;
+        }
         if (rc == IRS_HIP_OK && n_words < n_incl) {
           uint32_t plain = 0;   // (members of a variadic part are no words of their own)
           for (uint32_t j = 0; j < n_words; ++j)
             plain += (terms[in.first_term + j].kind & IRS_HIP_PHRASE_ALT) ? 0u : 1u;
           if (plain < 2) rc = IRS_HIP_EINVAL;
-          else if (alt || n_incl > IRS_HIP_MAX_PHRASE_TERMS) rc = IRS_HIP_EUNSUPPORTED;
+          else if (alt || behind == kBehind || n_incl > IRS_HIP_MAX_PHRASE_TERMS) rc = IRS_HIP_EUNSUPPORTED;
         }
         if (rc != IRS_HIP_OK) break;
       }
-      const bool with_req = n_words < n_incl;
+      const bool with_req = behind == IRS_HIP_PHRASE_REQUIRED;
+      const bool with_opt = behind == IRS_HIP_PHRASE_OPTIONAL;
       // a grouped conjunction: an And whose entries with IRS_HIP_GROUP_ALT are more members of the
       // group (an Or of by_term) opened by the nearest entry before them without it
       bool grouped = false;
@@ -644,11 +715,13 @@ static int batch_create_multi_impl(irs_hip_segment* const* segs, uint32_t n_segs
       for (uint32_t j = 0; j < n_incl; ++j) {
         const irs_hip_term_scorer& ts = terms[in.first_term + j];
         const bool member = is_phrase && (ts.kind & IRS_HIP_PHRASE_ALT) != 0;
-        const bool req = is_phrase && j >= n_words;
-        const int32_t kind = is_phrase ? (ts.kind & ~(IRS_HIP_PHRASE_ALT | IRS_HIP_PHRASE_REQUIRED))
+        const bool req = is_phrase && j >= n_words;   // (a required or an optional term)
+        const bool opt = req && with_opt;   // (no part of the phrase: absent, it is dropped)
+        const int32_t kind = is_phrase ? (ts.kind & ~(IRS_HIP_PHRASE_ALT | IRS_HIP_PHRASE_REQUIRED |
+                                                      IRS_HIP_PHRASE_OPTIONAL))
                              : grouped ? (ts.kind & ~IRS_HIP_PHRASE_ALT) : ts.kind;
         if (grouped && !(ts.kind & IRS_HIP_GROUP_ALT)) ++n_groups;
-        if (is_phrase && !member) {
+        if (is_phrase && !member && !opt) {
           ++n_parts;
           part_first = j;
           part_open = false;
@@ -712,7 +785,7 @@ static int batch_create_multi_impl(irs_hip_segment* const* segs, uint32_t n_segs
           found |= 1u << (n_groups - 1u);
           row_group.push_back(n_groups - 1u);
         }
-        if (is_phrase) {
+        if (is_phrase && !opt) {
           if (!part_open) opens |= 1u << row.size();
           part_open = true;
           found |= 1u << (n_parts - 1u);
@@ -780,8 +853,11 @@ static int batch_create_multi_impl(irs_hip_segment* const* segs, uint32_t n_segs
         need = absent ? 0xFFu : 1u;
         b->blocks.variadic = b->blocks.variadic || alt;
         b->blocks.required = b->blocks.required || with_req;
-        // (k_vphrase takes no required terms, k_phrase_and no variadic parts)
-        if (b->blocks.variadic && b->blocks.required) {
+        b->blocks.optional = b->blocks.optional || with_opt;
+        // (k_vphrase takes no required or optional terms, k_phrase_and no variadic parts, a batch
+        // runs on k_phrase_and or on k_phrase_or)
+        if ((b->blocks.variadic && (b->blocks.required || b->blocks.optional)) ||
+            (b->blocks.required && b->blocks.optional)) {
           rc = IRS_HIP_EUNSUPPORTED;
           break;
         }
@@ -953,6 +1029,7 @@ static int batch_create_multi_impl(irs_hip_segment* const* segs, uint32_t n_segs
   if (rc == IRS_HIP_OK && b->phrase) {
     try {
       rc = build_phrase_work(b);
+      if (rc == IRS_HIP_OK && b->blocks.optional) rc = create_term_pass(b, segs, n_segs, queries, all_terms, n_entries);
     } catch (...) {
       rc = IRS_HIP_ENOMEM;
     }
@@ -993,6 +1070,7 @@ static int batch_create_multi_impl(irs_hip_segment* const* segs, uint32_t n_segs
     }
   }
   if (rc != IRS_HIP_OK) {
+    if (b->opt) irs_hip_batch_destroy(b->opt);
     delete b;
     return rc;
   }
@@ -1030,6 +1108,8 @@ static int batch_configure_impl(irs_hip_batch* b, uint32_t tile_docs, uint32_t p
   b->cand_cap = cand_cap;
   b->scratch_ready = false;
   b->sync.planned = false;   // a plan queued ahead used the old geometry: run() plans inline
+  // (optional terms: the term pass takes the tile, and the same stride and candidate slots)
+  if (b->opt) return batch_configure_impl(b->opt, tile_docs, pilot_stride, cand_cap);
   return IRS_HIP_OK;
 }
 
@@ -1050,11 +1130,13 @@ static int batch_set_shared_threshold_impl(irs_hip_batch* b, int enable) {
   b->groups.shared = enable != 0;
   b->scratch_ready = false;
   b->sync.planned = false;
+  if (b->opt) return batch_set_shared_threshold_impl(b->opt, enable);   // (both passes)
   return IRS_HIP_OK;
 }
 
 static int batch_set_comm_impl(irs_hip_batch* b, irs_hip_comm* comm) {
   if (!b) return IRS_HIP_EINVAL;
+  if (b->opt) return IRS_HIP_EUNSUPPORTED;   // (optional terms: two passes, one rank)
   if (!rt::set_device(b->seg->device)) return IRS_HIP_EHIP;
   if (!quiesce(b)) return IRS_HIP_EHIP;
   if (comm && !b->groups.d_agree.p && !b->groups.d_agree.alloc(64)) return IRS_HIP_ENOMEM;
@@ -1083,6 +1165,7 @@ static int batch_set_wand_impl(irs_hip_batch* b, int enable) {
   if (b->ran) return IRS_HIP_EINVAL;   // before the first run: the segment records are uploaded once
   if (!rt::set_device(b->seg->device)) return IRS_HIP_EHIP;
   if (!quiesce(b)) return IRS_HIP_EHIP;
+  if (b->opt) return IRS_HIP_OK;   // (optional terms: neither pass is pruned)
   b->wand = enable != 0;
   // a plan queued ahead (irs_hip_batch_plan) was made without the tile bounds: run() re-plans
   b->sync.planned = false;
@@ -1101,6 +1184,9 @@ static int batch_set_wand_impl(irs_hip_batch* b, int enable) {
 static int batch_set_min_scores_impl(irs_hip_batch* b, const float* min_scores) {
   if (!b) return IRS_HIP_EINVAL;
   if (!rt::set_device(b->seg->device)) return IRS_HIP_EHIP;
+  // (optional terms: a doc's score is whole in either pass, so both filter by the caller's own)
+  if (b->opt)
+    if (const int rc = batch_set_min_scores_impl(b->opt, min_scores)) return rc;
   if (!min_scores) {
     b->has_min = false;
     return IRS_HIP_OK;
@@ -1126,6 +1212,8 @@ static int batch_set_min_scores_impl(irs_hip_batch* b, const float* min_scores) 
 static int batch_set_doc_sets_impl(irs_hip_batch* b, const void* sets, bool host, uint64_t n_rows,
                                    uint64_t n_words, const uint32_t* row_of_unit) {
   if (!b) return IRS_HIP_EINVAL;
+  // (optional terms: the term pass's doc sets are the phrase pass's output)
+  if (b->opt) return IRS_HIP_EUNSUPPORTED;
   if (!rt::set_device(b->seg->device)) return IRS_HIP_EHIP;
   std::vector<uint32_t> rows;
   if (row_of_unit && n_rows) {
@@ -1334,6 +1422,22 @@ static int batch_plan_impl(irs_hip_batch* b, void* stream) {
   return ok ? IRS_HIP_OK : IRS_HIP_EHIP;
 }
 
+// The union of the two passes of a batch with optional terms (k_union_topk, phrase.h) into
+// d_union_*: behind both passes' k_select on `st`.
+static bool launch_union(irs_hip_batch* b, rt::stream_t st) {
+  const irs_hip_batch* c = b->opt;
+  RT_LAUNCH(k_union_topk, b->nq, kThreads, 0, st, b->d_queries.as<DevQuery>(), b->k_max,
+            b->d_out.as<Hit>(), b->d_out_count.as<uint32_t>(), b->d_hits.as<unsigned long long>(),
+            c->d_out.as<Hit>(), c->d_out_count.as<uint32_t>(), c->d_hits.as<unsigned long long>(),
+            b->d_union_out.as<Hit>(), b->d_union_count.as<uint32_t>(),
+            b->d_union_hits.as<unsigned long long>());
+  return rt::last_error_ok();
+}
+// What the result calls hand out: the batch's own tables, or the union of its two passes
+static void* out_hits(irs_hip_batch* b) { return b->opt ? b->d_union_out.p : b->d_out.p; }
+static void* out_counts(irs_hip_batch* b) { return b->opt ? b->d_union_count.p : b->d_out_count.p; }
+static void* out_totals(irs_hip_batch* b) { return b->opt ? b->d_union_hits.p : b->d_hits.p; }
+
 static int run_impl(irs_hip_batch* b, rt::stream_t st) {
   HostTrace trace("batch_run (scratch + uploads + launches queued)");
   if (!ensure_scratch(b) || !stage_min_bins(b)) return IRS_HIP_ENOMEM;
@@ -1375,6 +1479,8 @@ static int run_impl(irs_hip_batch* b, rt::stream_t st) {
     b->join.slack_zeroed = ok;
   }
   ok = ok && rt::dmemset(b->d_zeroed.p, 0, b->d_zeroed.n, st);   // (ensure_scratch: six tables)
+  // (optional terms: no doc is taken until k_phrase_or matches it)
+  if (b->opt) ok = ok && rt::dmemset(b->d_taken.p, 0, b->d_taken.n, st);
   // (a counting run of a batch with doc sets: the lead pieces' tallies, irs_hip_batch_doc_set_stats)
   b->excl.leads_counted = b->count_touched && b->excl.sets_on();
   if (ok && b->excl.leads_counted)
@@ -1441,6 +1547,18 @@ static int run_impl(irs_hip_batch* b, rt::stream_t st) {
     }
   }
   ok = ok && mark(2 * IRS_HIP_K_SELECT + 1);
+  // optional terms: the term pass behind the phrase pass, on the same stream, then the union of
+  // their results (the batch's `done` covers all three)
+  if (ok && b->opt) {
+    const uint64_t n32 = b->d_taken.n / 4u;   // (taken -> the term pass's doc sets)
+    RT_LAUNCH(k_not_words, uint32_t((n32 + kThreads - 1) / kThreads), kThreads, 0, st, b->d_taken.as<uint32_t>(), n32);
+    if (!rt::last_error_ok()) return IRS_HIP_EHIP;
+    if (const int rc = run_impl(b->opt, st)) {
+      b->ran = true;
+      return rc;
+    }
+    ok = launch_union(b, st);
+  }
   // the status word follows the kernels into page-locked memory; the event marks this run
   if (ok && !b->sync.h_status.p) ok = b->sync.h_status.alloc(64);
   ok = ok && rt::d2h(b->sync.h_status.p, b->d_status.p, 4, st) && b->sync.done.record(st);
@@ -1587,6 +1705,8 @@ static int batch_timings_impl(irs_hip_batch* b, float ms[IRS_HIP_K_COUNT]) {
   return IRS_HIP_OK;
 }
 
+static int verify_term_pass(irs_hip_batch* b);
+
 static int batch_results_impl(irs_hip_batch* b, irs_hip_hit* hits, uint32_t k_stride,
                           uint32_t* counts, uint64_t* total_hits) {
   if (!b || !hits || !counts || !b->ran || k_stride < b->k_max) return IRS_HIP_EINVAL;
@@ -1604,9 +1724,10 @@ static int batch_results_impl(irs_hip_batch* b, irs_hip_hit* hits, uint32_t k_st
     if (rc != IRS_HIP_OK) return rc;
     status = 0;
   }
-  if (!rt::d2h(b->sync.h_pin.p, b->d_out.p, hit_bytes, b->stream) ||
-      !rt::d2h(counts, b->d_out_count.p, size_t(b->nq) * 4, b->stream) ||
-      (total_hits && !rt::d2h(total_hits, b->d_hits.p, size_t(b->nq) * 8, b->stream)) ||
+  if (const int rc = verify_term_pass(b)) return rc;
+  if (!rt::d2h(b->sync.h_pin.p, out_hits(b), hit_bytes, b->stream) ||
+      !rt::d2h(counts, out_counts(b), size_t(b->nq) * 4, b->stream) ||
+      (total_hits && !rt::d2h(total_hits, out_totals(b), size_t(b->nq) * 8, b->stream)) ||
       !rt::sync(b->stream))
     return IRS_HIP_EHIP;
   if (status & kStatusOverflow) return IRS_HIP_EOVERFLOW;
@@ -1633,6 +1754,19 @@ static int verify_run(irs_hip_batch* b) {
     if (rc != IRS_HIP_OK) return rc;
     if (!rt::sync(b->stream)) return IRS_HIP_EHIP;
   }
+  return verify_term_pass(b);
+}
+
+// Optional terms: the phrase pass is through and sound (a re-run of it ran the term pass and the
+// union again); now the term pass's own status.  Its re-run changes nothing the phrase pass wrote —
+// k_phrase_or takes every doc the phrase matches out of the doc sets, whatever the threshold — so
+// only the union is made again.
+static int verify_term_pass(irs_hip_batch* b) {
+  if (!b->opt) return IRS_HIP_OK;
+  const uint32_t before = b->opt->reruns;
+  if (const int rc = verify_run(b->opt)) return rc;
+  if (b->opt->reruns == before) return IRS_HIP_OK;
+  if (!launch_union(b, b->stream) || !rt::sync(b->stream)) return IRS_HIP_EHIP;
   return IRS_HIP_OK;
 }
 
@@ -1642,8 +1776,8 @@ static int batch_device_results_impl(irs_hip_batch* b, void** d_hits, void** d_c
   if (!rt::set_device(b->seg->device)) return IRS_HIP_EHIP;
   const int rc = verify_run(b);
   if (rc != IRS_HIP_OK) return rc;
-  if (d_hits) *d_hits = b->d_out.p;
-  if (d_counts) *d_counts = b->d_out_count.p;
+  if (d_hits) *d_hits = out_hits(b);
+  if (d_counts) *d_counts = out_counts(b);
   if (k_max) *k_max = b->k_max;
   return IRS_HIP_OK;
 }
@@ -1655,8 +1789,8 @@ static int batch_results_to_device_impl(irs_hip_batch* b, void* d_hits, void* d_
   rt::stream_t st = static_cast<rt::stream_t>(stream);
   const int rc = verify_run(b);
   if (rc != IRS_HIP_OK) return rc;
-  if (!rt::d2d(d_hits, b->d_out.p, size_t(b->nq) * b->k_max * sizeof(Hit), st) ||
-      !rt::d2d(d_counts, b->d_out_count.p, size_t(b->nq) * 4, st))
+  if (!rt::d2d(d_hits, out_hits(b), size_t(b->nq) * b->k_max * sizeof(Hit), st) ||
+      !rt::d2d(d_counts, out_counts(b), size_t(b->nq) * 4, st))
     return IRS_HIP_EHIP;
   // (destroy must not hand d_out back to the pool while these copies are queued)
   if (!b->sync.used.record(st)) return IRS_HIP_EHIP;
@@ -1690,9 +1824,9 @@ static int batch_results_to_host_impl(irs_hip_batch* b, void* stream) {
   if (!st) st = b->stream;
   uint8_t* h = b->sync.h_res.as<uint8_t>();
   if (!b->sync.done.wait(st) ||
-      !rt::d2h(h, b->d_out.p, r.hit_bytes, st) ||
-      !rt::d2h(h + r.cnt_off, b->d_out_count.p, size_t(b->nq) * 4, st) ||
-      !rt::d2h(h + r.tot_off, b->d_hits.p, size_t(b->nq) * 8, st) ||
+      !rt::d2h(h, out_hits(b), r.hit_bytes, st) ||
+      !rt::d2h(h + r.cnt_off, out_counts(b), size_t(b->nq) * 4, st) ||
+      !rt::d2h(h + r.tot_off, out_totals(b), size_t(b->nq) * 8, st) ||
       !b->sync.host.record(st))
     return IRS_HIP_EHIP;
   b->sync.host_pending = true;
@@ -1730,6 +1864,8 @@ void irs_hip_batch_destroy(irs_hip_batch* b) {
   if (b->sync.match_pending) waited = waited && b->sync.matched.sync();
   if (!waited && b->ran) waited = rt::sync(b->stream);
   release_streams(b, waited);   // (its pins in the device's stream cache)
+  // (optional terms: the term pass reads this batch's d_taken — it goes first)
+  if (b->opt) irs_hip_batch_destroy(b->opt);
   // (the batch's events go with it)
   delete b;
 }
@@ -2054,7 +2190,7 @@ int irs_hip_batch_timings(irs_hip_batch* b, float ms[IRS_HIP_K_COUNT]) {
 int irs_hip_batch_reruns(irs_hip_batch* b, uint32_t* count) {
   return settled(b, [&]() -> int {
     if (!b || !count) return IRS_HIP_EINVAL;
-    *count = b->reruns;
+    *count = b->reruns + (b->opt ? b->opt->reruns : 0u);   // (optional terms: both passes)
     return IRS_HIP_OK;
   });
 }

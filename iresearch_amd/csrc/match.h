@@ -239,6 +239,25 @@ k_phrase_and_match(ConjArgs A, const uint32_t* n_phrase, uint32_t* sets32, uint6
   __shared__ PhraseWave<MT> s_wave[kPhraseWaves];
   phrase_item<LAYOUT, MT, true, true>(A, 0u, s_wave, sets32, words32, counts, n_phrase);
 }
+// ... with optional terms (k_phrase_or, phrase.h): the phrase's own matches, OR-ed into rows that
+// hold the optional terms' docs already (the term pass's k_match_slice wrote every word of them)
+template<int LAYOUT, int MT>
+__global__ void __launch_bounds__(kPhraseWaves * 64)
+k_phrase_or_match(ConjArgs A, const uint32_t* n_phrase, uint32_t* sets32, uint64_t words32) {
+  __shared__ PhraseWave<MT> s_wave[kPhraseWaves];
+  phrase_item<LAYOUT, MT, true, kPhraseOpt>(A, 0u, s_wave, sets32, words32, nullptr, n_phrase);
+}
+// ... and the counts of the united rows: a workgroup per (unit, slice of 8 * kThreads words)
+__global__ void __launch_bounds__(kThreads)
+k_count_rows(const uint32_t* sets32, uint64_t words32, uint32_t slices, unsigned long long* counts) {
+  const uint32_t unit = blockIdx.x / slices;
+  const uint64_t w0 = uint64_t(blockIdx.x % slices) * (8u * kThreads);
+  uint32_t pop = 0;
+  for (uint32_t i = threadIdx.x; i < 8u * kThreads && w0 + i < words32; i += kThreads)
+    pop += uint32_t(__builtin_popcount(sets32[uint64_t(unit) * words32 + w0 + i]));
+  pop = wave::reduce_add(pop);
+  if ((threadIdx.x & 63u) == 0 && pop) atomicAdd(&counts[unit], static_cast<unsigned long long>(pop));
+}
 template<int LAYOUT>
 __global__ void __launch_bounds__(kPhraseWaves * 64)
 k_vphrase_match(ConjArgs A, const uint32_t* opens, uint32_t* sets32, uint64_t words32,

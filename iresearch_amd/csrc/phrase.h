@@ -499,6 +499,10 @@ k_count_leads(const ConjItem* recs, uint32_t n, const uint8_t* restricted, unsig
 // candidate.  The scored instantiations compile to what they were without the parameter.
 // REQ (k_phrase_and below): rows [n_phrase[unit], m) of the unit are REQUIRED TERMS — the by_term
 // children of the irs::And that holds the phrase (IRS_HIP_PHRASE_REQUIRED) — see there.
+// REQ == kPhraseOpt (k_phrase_or below): those rows are OPTIONAL TERMS — the by_term children of the
+// irs::Or that holds the phrase (IRS_HIP_PHRASE_OPTIONAL): they never lead, drop no doc, and add
+// their score where they hold a doc the phrase matches — see there.
+constexpr int kPhraseReq = 1, kPhraseOpt = 2;   // (REQ: `true` is kPhraseReq)
 template<int MT>
 struct PhraseWave {
   uint32_t docs[kBlock];
@@ -513,12 +517,15 @@ struct PhraseWave {
   uint32_t off[MT];
 };
 
-template<int LAYOUT, int MT, bool MATCH = false, bool REQ = false>
+template<int LAYOUT, int MT, bool MATCH = false, int REQ = 0>
 __device__ __forceinline__ void phrase_item(const ConjArgs& A, uint32_t pilot /*1: histogram the
                                             scores of the sampled lead items, no candidates*/,
                                             PhraseWave<MT>* s_wave, uint32_t* sets32 = nullptr,
                                             uint64_t words32 = 0, unsigned long long* counts = nullptr,
-                                            const uint32_t* n_phrase = nullptr /*REQ: [unit] phrase rows*/) {
+                                            const uint32_t* n_phrase = nullptr /*REQ: [unit] phrase rows*/,
+                                            uint32_t* taken = nullptr /*kPhraseOpt: [unit][words32] bit =
+                                            doc id, zeroed per run: the docs the phrase matched*/) {
+  constexpr bool OPT = REQ == kPhraseOpt;
   const uint32_t tid = threadIdx.x;
   const unsigned lane = tid & 63u;
   const uint32_t wv = wave::uniform(tid >> 6);
@@ -533,14 +540,17 @@ __device__ __forceinline__ void phrase_item(const ConjArgs& A, uint32_t pilot /*
   const ConjItem R = wave::sload<ConjItem>(reinterpret_cast<uint64_t>(A.recs) + uint64_t(e) * sizeof(ConjItem));
   const uint32_t unit = R.unit, item = R.item;
   const DevQuery qd = wave::sload<DevQuery>(reinterpret_cast<uint64_t>(A.queries) + uint64_t(unit) * sizeof(DevQuery));
-  const uint32_t m = qd.n_terms;
-  if (m == 0 || m > uint32_t(MT)) return;
+  uint32_t m_all = qd.n_terms;
+  if (m_all == 0 || m_all > uint32_t(MT)) return;
   // rows [0, mp) are the phrase's words (the lists step 3 merges), rows [mp, m) required terms
-  uint32_t mp = m;
+  uint32_t mp = m_all;
   if constexpr (REQ) {
     mp = wave::uniform(n_phrase[unit]);
-    if (mp == 0u || mp > m) return;
+    if (mp == 0u || mp > m_all) return;
+    // (optional rows decide no match: the match-only form leaves them out altogether)
+    if constexpr (OPT && MATCH) m_all = mp;
   }
+  const uint32_t m = m_all;
   const DevSegment& seg = A.segs[qd.seg];   // (read field by field)
   const uint64_t tl_at = reinterpret_cast<uint64_t>(A.tails) + uint64_t(unit) * A.jt * sizeof(DevTail);
   auto term_tail = [&](uint32_t i) { return wave::sload<DevTail>(tl_at + i * sizeof(DevTail)); };
@@ -563,7 +573,7 @@ __device__ __forceinline__ void phrase_item(const ConjArgs& A, uint32_t pilot /*
   // W.off[mp + r] (no offset lives there) = the r-th cheapest required row, phrase_at = required
   // rows summed in front of the phrase.
   uint32_t phrase_at = 0;
-  if constexpr (REQ) {
+  if constexpr (REQ == kPhraseReq) {
     uint32_t cost = 0xFFFFFFFFu;
     if (lane < m) {
       const DevTail t = A.tails[uint64_t(unit) * A.jt + lane];
@@ -690,6 +700,9 @@ __device__ __forceinline__ void phrase_item(const ConjArgs& A, uint32_t pilot /*
     const DevTail tl = term_tail(i);
     // alive = docs every term so far reached: the lead bitmap, then what the previous term
     // marked; `mark` collects what this term reaches
+    // (kPhraseOpt) an optional row reads what the LAST WORD left alive, marks nothing and leaves
+    // `step` where it is: the next optional row reads the same bitmap
+    const bool opt_row = OPT && i >= mp;
     const uint32_t mk = 1u + (step & 1u);
     const uint32_t* alive = step == 0u ? (masked ? W.bm[2] : W.bm[0]) : W.bm[3u - mk];
     uint32_t* mark = W.bm[mk];
@@ -706,8 +719,9 @@ __device__ __forceinline__ void phrase_item(const ConjArgs& A, uint32_t pilot /*
         return;
       }
     }
-    ++step;
-    const bool more_terms = MT > 2 && step + 1u < m;   // (the last term marks nothing: nobody reads it)
+    if (!opt_row) ++step;
+    const bool more_terms = MT > 2 && !opt_row && step + 1u < m;   // (the last term marks nothing: nobody reads it)
+    const uint32_t n_before = (OPT && i > mp) ? mp : i;   // (an optional row: every WORD holds the doc)
     auto alive_below = [&](uint32_t x) {
       return uint32_t(apre[x >> 5]) + uint32_t(__builtin_popcount(alive[x >> 5] & ((1u << (x & 31u)) - 1u)));
     };
@@ -720,7 +734,7 @@ __device__ __forceinline__ void phrase_item(const ConjArgs& A, uint32_t pilot /*
       if (t == n) return;
       // every earlier term — and the lead, whose deleted docs count as not reached — holds THIS doc
       if (W.tf[lead][t] == 0u) return;
-      for (uint32_t j = 0; j < i; ++j)
+      for (uint32_t j = 0; j < n_before; ++j)
         if (j != lead && W.tf[j][t] == 0u) return;
       W.pidx[i][t] = p;
       W.tf[i][t] = f;
@@ -834,7 +848,7 @@ __device__ __forceinline__ void phrase_item(const ConjArgs& A, uint32_t pilot /*
   for (int h = 0; h < 2; ++h) {
     const uint32_t sl = lane + 64u * uint32_t(h);
     bool all = sl < n;
-    for (uint32_t i = 0; i < m; ++i) all = all && W.tf[i][sl < n ? sl : 0u] != 0u;
+    for (uint32_t i = 0; i < (OPT ? mp : m); ++i) all = all && W.tf[i][sl < n ? sl : 0u] != 0u;
     h01[h] = all;
     m01[h] = wave::ballot(all);
   }
@@ -954,7 +968,17 @@ __device__ __forceinline__ void phrase_item(const ConjArgs& A, uint32_t pilot /*
                             : (item < ld.nblk ? seg.pnorm[(ld.dir_off + item) * kBlock + sl]
                                               : seg.tail_norms[ld.tail_row + sl]);
         score = score_value(qt, pf, nv);
-        if constexpr (REQ) {
+        if constexpr (OPT) {
+          // + the score of every optional term that holds the doc, in entry order; the doc is
+          // taken: the term pass will not see it (a global atomic: matches are sparse)
+          if (mp < m) {
+            for (uint32_t row = mp; row < m; ++row) {
+              const uint32_t tfr = W.tf[row][sl];
+              if (tfr) score += score_value(A.qterms[qd.first_term + row], tfr, nv);
+            }
+            if (taken) atomicOr(&taken[uint64_t(unit) * words32 + (doc >> 5)], 1u << (doc & 31u));
+          }
+        } else if constexpr (REQ) {
           // + every required term's own score at its frequency in the doc, in cost order (each
           // row's scorer read where it is used: up to 6 of them would not stay in registers)
           const uint32_t nreq = m - mp;
@@ -1037,6 +1061,70 @@ __global__ void __launch_bounds__(kPhraseWaves * 64)
 k_phrase_and(ConjArgs A, const uint32_t* n_phrase, uint32_t pilot) {
   __shared__ PhraseWave<MT> s_wave[kPhraseWaves];
   phrase_item<LAYOUT, MT, false, true>(A, pilot, s_wave, nullptr, 0, nullptr, n_phrase);
+}
+
+
+// Or([by_phrase, by_term...]) — a phrase or optional terms (IRS_HIP_PHRASE_OPTIONAL; the reference:
+// Or::prepare, boolean_filter.cpp:150-210 -> MakeDisjunction over {PhraseIterator, term iterators},
+// disjunction.hpp:1411-1467).  This is the PHRASE PASS of such a unit: every doc the phrase matches,
+// scored in full.  phrase_item with rows [n_phrase[unit], m) as optional terms:
+//   lead  the rarest WORD (build_phrase_work); an optional row never leads;
+//   2.    an optional row is probed like a word — against the docs every WORD reached — but marks
+//         nothing alive and drops nothing;
+//   3.    "reached by every row" and the position merge run over the words only;
+//   4.    score = phrase scorer at tf = phrase frequency + the scorer of every optional row that
+//         holds the doc at its own tf, float32, entry order — into the bin, the pilot histogram and
+//         the key; the doc's bit is set in the unit's row of `taken` (zeroed per run).  k_not_words
+//         turns the rows into the doc sets the TERM PASS (a plain disjunction of the optional terms
+//         on the work-item path, a batch of its own behind this one) is restricted to: the two
+//         passes emit disjoint docs.
+// A plain phrase of such a batch has no optional rows: bit for bit what k_phrase gives.
+template<int LAYOUT, int MT>
+__global__ void __launch_bounds__(kPhraseWaves * 64)
+k_phrase_or(ConjArgs A, const uint32_t* n_phrase, uint32_t* taken, uint64_t words32, uint32_t pilot) {
+  __shared__ PhraseWave<MT> s_wave[kPhraseWaves];
+  phrase_item<LAYOUT, MT, false, kPhraseOpt>(A, pilot, s_wave, nullptr, words32, nullptr, n_phrase, taken);
+}
+
+// taken -> not taken, in place: the rows of `taken` as doc sets (bit set = the doc may match)
+__global__ void __launch_bounds__(kThreads)
+k_not_words(uint32_t* words, uint64_t n) {
+  const uint64_t i = uint64_t(blockIdx.x) * kThreads + threadIdx.x;
+  if (i < n) words[i] = ~words[i];
+}
+
+// The union of the two passes of a batch with optional terms, a thread per hit: both lists of a unit
+// are sorted as make_key sorts (score descending, doc ascending) and hold disjoint docs, so a hit's
+// place in the union is its own index plus the hits of the other list in front of it (a binary
+// search).  out[unit] = the first min(k, ca + cb) of the union; total = both passes' totals.
+__global__ void __launch_bounds__(kThreads)
+k_union_topk(const DevQuery* queries, uint32_t k_max, const Hit* a, const uint32_t* ca,
+             const unsigned long long* ta, const Hit* b, const uint32_t* cb, const unsigned long long* tb,
+             Hit* out, uint32_t* out_count, unsigned long long* out_total) {
+  const uint32_t unit = blockIdx.x;
+  const uint32_t k = queries[unit].k;
+  const uint32_t na = ca[unit] < k_max ? ca[unit] : k_max, nb = cb[unit] < k_max ? cb[unit] : k_max;
+  const Hit* la = a + uint64_t(unit) * k_max;
+  const Hit* lb = b + uint64_t(unit) * k_max;
+  Hit* o = out + uint64_t(unit) * k_max;
+  const uint32_t keep = (na + nb < k ? na + nb : k) < k_max ? (na + nb < k ? na + nb : k) : k_max;
+  for (uint32_t i = threadIdx.x; i < na + nb; i += kThreads) {
+    const bool from_a = i < na;
+    const uint32_t at = from_a ? i : i - na;
+    const Hit h = from_a ? la[at] : lb[at];
+    const uint64_t key = make_key(h.score, h.doc);
+    const Hit* other = from_a ? lb : la;
+    uint32_t lo = 0, hi = from_a ? nb : na;   // hits of the other list in front of this one
+    while (lo < hi) {
+      const uint32_t mid = (lo + hi) >> 1;
+      if (make_key(other[mid].score, other[mid].doc) > key) lo = mid + 1; else hi = mid;
+    }
+    if (at + lo < keep) o[at + lo] = h;
+  }
+  if (threadIdx.x == 0) {
+    out_count[unit] = keep;
+    out_total[unit] = ta[unit] + tb[unit];
+  }
 }
 
 }  // namespace irs_hip

@@ -103,7 +103,9 @@ int build_phrase_work(irs_hip_batch* b) {
     if (!dq.n_terms) continue;
     const irs_hip_segment* sg = b->segs[dq.seg];
     uint32_t best = 0xFFFFFFFFu, items = 0;
-    for (uint32_t j = 0; j < dq.n_terms; ++j) {
+    // (optional terms never lead: the rarest of the phrase's words)
+    const uint32_t n_lead = b->blocks.optional ? b->blocks.n_phrase[u] : dq.n_terms;
+    for (uint32_t j = 0; j < n_lead; ++j) {
       const DevTerm& t = sg->terms[b->qterms[dq.first_term + j].term];
       if (t.docs_count < best) {
         best = t.docs_count;
@@ -119,7 +121,7 @@ int build_phrase_work(irs_hip_batch* b) {
   const int rc = stage_lead_items(b, b->blocks, b->blocks.d_lead_of, lead_of);
   b->blocks.n_phrase_wgs = (b->blocks.n_items + kPhraseWaves - 1) / kPhraseWaves;
   // (required terms: the lead above is the rarest of the phrase words AND the required terms)
-  if (rc == IRS_HIP_OK && b->blocks.required &&
+  if (rc == IRS_HIP_OK && (b->blocks.required || b->blocks.optional) &&
       (!b->blocks.d_n_phrase.alloc(uint64_t(b->nq) * 4) ||
        !b->up.copy(b->blocks.d_n_phrase.p, b->blocks.n_phrase.data(), uint64_t(b->nq) * 4)))
     return IRS_HIP_ENOMEM;
@@ -279,7 +281,8 @@ bool launch_conj(irs_hip_batch* b, rt::stream_t st) {
 // by_phrase: lead-item records + start blocks -> pilot pass over every P-th lead block ->
 // threshold bins -> full pass.
 // REQ: a batch with required terms (IRS_HIP_PHRASE_REQUIRED), every unit on k_phrase_and.
-template<int LAYOUT, int MT, bool REQ = false>
+// REQ == kPhraseOpt: a batch with optional terms (IRS_HIP_PHRASE_OPTIONAL), every unit on k_phrase_or.
+template<int LAYOUT, int MT, int REQ = 0>
 bool launch_phrase(irs_hip_batch* b, rt::stream_t st) {
   if (b->blocks.n_phrase_wgs == 0) return true;  // no query has all its terms in its segment
   const uint32_t stride = b->stride_eff;
@@ -300,7 +303,11 @@ bool launch_phrase(irs_hip_batch* b, rt::stream_t st) {
     p.wgs = b->blocks.d_pilot.as<PhraseWg>();
     p.n_pilot = b->blocks.n_pilot;
     p.touched = nullptr;
-    if constexpr (REQ) {
+    if constexpr (REQ == kPhraseOpt) {
+      RT_LAUNCH((k_phrase_or<LAYOUT, MT>), (b->blocks.n_pilot + kPhraseWaves - 1) / kPhraseWaves,
+                kPhraseWaves * 64, 0, st, p, b->blocks.d_n_phrase.as<uint32_t>(),
+                b->d_taken.as<uint32_t>(), 2u * b->taken_words, 1u);
+    } else if constexpr (REQ) {
       RT_LAUNCH((k_phrase_and<LAYOUT, MT>), (b->blocks.n_pilot + kPhraseWaves - 1) / kPhraseWaves,
                 kPhraseWaves * 64, 0, st, p, b->blocks.d_n_phrase.as<uint32_t>(), 1u);
     } else if (MT == 2) {
@@ -315,7 +322,10 @@ bool launch_phrase(irs_hip_batch* b, rt::stream_t st) {
             b->d_queries.as<DevQuery>(), b->blocks.d_units.as<uint32_t>(),
             b->blocks.d_items.as<uint32_t>(), b->blocks.d_hist.as<uint32_t>(), stride,
             b->estimate ? kPilotMargin : 0u, b->d_bstar.as<uint32_t>(), min_bins(b));
-  if constexpr (REQ) {
+  if constexpr (REQ == kPhraseOpt) {
+    RT_LAUNCH((k_phrase_or<LAYOUT, MT>), b->blocks.n_phrase_wgs, kPhraseWaves * 64, 0, st, a,
+              b->blocks.d_n_phrase.as<uint32_t>(), b->d_taken.as<uint32_t>(), 2u * b->taken_words, 0u);
+  } else if constexpr (REQ) {
     RT_LAUNCH((k_phrase_and<LAYOUT, MT>), b->blocks.n_phrase_wgs, kPhraseWaves * 64, 0, st, a,
               b->blocks.d_n_phrase.as<uint32_t>(), 0u);
   } else if (MT == 2) {
@@ -366,8 +376,11 @@ template<int LAYOUT>
 bool launch_phrase_terms(irs_hip_batch* b, rt::stream_t st) {
   if (b->blocks.variadic) return launch_vphrase<LAYOUT>(b, st);
   if (b->blocks.required)
-    return b->jt <= 4 ? launch_phrase<LAYOUT, 4, true>(b, st)
-                      : launch_phrase<LAYOUT, int(kPhraseMaxTerms), true>(b, st);
+    return b->jt <= 4 ? launch_phrase<LAYOUT, 4, kPhraseReq>(b, st)
+                      : launch_phrase<LAYOUT, int(kPhraseMaxTerms), kPhraseReq>(b, st);
+  if (b->blocks.optional)
+    return b->jt <= 4 ? launch_phrase<LAYOUT, 4, kPhraseOpt>(b, st)
+                      : launch_phrase<LAYOUT, int(kPhraseMaxTerms), kPhraseOpt>(b, st);
   if (b->jt <= 2) return launch_phrase<LAYOUT, 2>(b, st);
   if (b->jt <= 4) return launch_phrase<LAYOUT, 4>(b, st);
   return launch_phrase<LAYOUT, int(kPhraseMaxTerms)>(b, st);

@@ -96,6 +96,16 @@ static bool launch_phrase_match(irs_hip_batch* b, rt::stream_t st, uint32_t* set
     }
     return rt::last_error_ok();
   }
+  if (w.optional) {   // (a batch with optional terms: the words' rows only, OR-ed into the term pass's sets)
+    if (b->jt <= 4) {
+      RT_LAUNCH((k_phrase_or_match<LAYOUT, 4>), w.n_phrase_wgs, kPhraseWaves * 64, 0, st, a,
+                w.d_n_phrase.as<uint32_t>(), sets32, words32);
+    } else {
+      RT_LAUNCH((k_phrase_or_match<LAYOUT, int(kPhraseMaxTerms)>), w.n_phrase_wgs, kPhraseWaves * 64, 0, st, a,
+                w.d_n_phrase.as<uint32_t>(), sets32, words32);
+    }
+    return rt::last_error_ok();
+  }
   if (b->jt <= 2) {
     RT_LAUNCH((k_phrase_match<LAYOUT, 2>), w.n_phrase_wgs, kPhraseWaves * 64, 0, st, a, sets32, words32, counts);
   } else if (b->jt <= 4) {
@@ -133,6 +143,12 @@ static int batch_match_sets_impl(irs_hip_batch* b, uint64_t* sets, void* d_sets,
     d_sets = want_sets ? m.d_sets.p : nullptr;
     d_counts = want_counts ? m.d_counts.p : nullptr;
   }
+  // (optional terms: the counts are those of the united rows, so the rows are made either way)
+  const bool own_rows = b->opt && !d_sets;
+  if (own_rows) {
+    if (!m.d_sets.alloc(set_bytes)) return IRS_HIP_ENOMEM;
+    d_sets = m.d_sets.p;
+  }
   // behind the batch's own queued work — a run or a plan stage writes the masks and may have the
   // batch's tables in flight, an earlier call on another stream reads this one's tables
   bool ok = true;
@@ -147,7 +163,22 @@ static int batch_match_sets_impl(irs_hip_batch* b, uint64_t* sets, void* d_sets,
   }
   if (ok && b->excl.on()) ok = launch_excl_masks(b, st);
   if (ok && want_counts) ok = rt::dmemset(d_counts, 0, count_bytes, st);
-  if (ok && b->phrase) {
+  if (ok && b->opt) {
+    // the term pass's rows first — its doc sets all ones, or what a run left: the docs missing from
+    // them are docs of the phrase — every word of every row written; the phrase's docs OR-ed in,
+    // the united rows counted
+    if (!b->ran) ok = rt::dmemset(b->d_taken.p, 0xFF, b->d_taken.n, st);
+    ok = ok && batch_match_sets_impl(b->opt, nullptr, d_sets, n_words, nullptr, nullptr, st, true) == IRS_HIP_OK &&
+         with_layout(b->seg->dev.layout, [&](auto L) {
+           return launch_phrase_match<decltype(L)::value>(b, st, static_cast<uint32_t*>(d_sets), 2u * n_words, nullptr);
+         });
+    if (ok && want_counts) {
+      const uint32_t cs = uint32_t((2u * n_words + 8u * kThreads - 1u) / (8u * kThreads));
+      RT_LAUNCH(k_count_rows, cs * b->nq, kThreads, 0, st, static_cast<const uint32_t*>(d_sets), 2u * n_words, cs,
+                static_cast<unsigned long long*>(d_counts));
+      ok = rt::last_error_ok();
+    }
+  } else if (ok && b->phrase) {
     ok = (!want_sets || rt::dmemset(d_sets, 0, set_bytes, st)) &&
          with_layout(b->seg->dev.layout, [&](auto L) {
            return launch_phrase_match<decltype(L)::value>(b, st, static_cast<uint32_t*>(d_sets), 2u * n_words,
@@ -167,6 +198,11 @@ static int batch_match_sets_impl(irs_hip_batch* b, uint64_t* sets, void* d_sets,
   if (!ok) {
     if (!to_device) m.d_sets.release();
     return IRS_HIP_EHIP;
+  }
+  if (to_device && own_rows) {   // (the rows were scratch: nothing queued may outlive the block)
+    const bool synced = rt::sync(st);
+    m.d_sets.release();
+    return synced ? IRS_HIP_OK : IRS_HIP_EHIP;
   }
   if (to_device) {
     // (a later run, setter or destroy gets behind this: the masks and the tables are still read)

@@ -25,7 +25,7 @@ from dataclasses import dataclass, field, replace
 import numpy as np
 
 from . import _lib
-from ._lib import (EXCLUDE, HIT, NO_TERM, OP_AND, OP_MINMATCH, OP_OR, OP_PHRASE, PHRASE_ALT, PHRASE_REQUIRED, QUERY, SCORE_BM1, SCORE_BM15, SCORE_BM25,
+from ._lib import (EXCLUDE, HIT, NO_TERM, OP_AND, OP_MINMATCH, OP_OR, OP_PHRASE, PHRASE_ALT, PHRASE_OPTIONAL, PHRASE_REQUIRED, QUERY, SCORE_BM1, SCORE_BM15, SCORE_BM25,
                    SCORE_TFIDF, SCORE_TFIDF_NORM, TERM_META, TERM_SCORER, SegmentDesc)
 
 f32 = np.float32
@@ -104,7 +104,10 @@ MERGE_SUM, MERGE_MAX, MERGE_MIN = 0, 1, 2
 @dataclass
 class Or:
     """irs::Or; min_match > 1 is Or::min_match_count() (boolean_filter.hpp); `merge` its
-    merge_type(); `boost` multiplies into the boosts of its terms (boolean_filter.cpp:153-154, 204)."""
+    merge_type(); `boost` multiplies into the boosts of its terms (boolean_filter.cpp:153-154, 204).
+    An Or of ONE by_phrase of plain terms and by_term children — a phrase or optional terms,
+    `"new york" hotel cheap` (IRS_HIP_PHRASE_OPTIONAL; min_match <= 1, merge SUM, at most 8 words
+    and terms in all) — is taken by prepare(..., optional_terms=True)."""
     subs: list
     min_match: int = 1
     merge: int = MERGE_SUM
@@ -136,8 +139,9 @@ class by_phrase:
     by_terms / by_prefix / by_wildcard / by_range visitor yields, in dictionary order (a variadic
     phrase, VariadicPrepareCollect); `offsets[i]` = position of part i relative to the first
     (default: consecutive words).  A phrase of plain terms may also be a child of an And, next to
-    by_term children (required terms) and Nots (prepare(..., required_terms=True)); not of an Or,
-    and not next to another phrase."""
+    by_term children (required terms) and Nots (prepare(..., required_terms=True)), or of an Or
+    next to by_term children (optional terms, prepare(..., optional_terms=True)); not next to
+    another phrase."""
     terms: list
     offsets: list | None = None
     boost: float = 1.0
@@ -378,6 +382,9 @@ class PreparedQuery:
                                    # carrying its own scorer; None: a phrase alone
     doc_set: int | None = None     # by_doc_set under the And: the row of the batch's doc sets the
                                    # query is restricted to (irs_hip_batch_set_doc_sets); None: none
+    optional: list | None = None   # OP_PHRASE: True for an entry that is an optional term — a by_term
+                                   # child of the Or that holds the phrase (IRS_HIP_PHRASE_OPTIONAL),
+                                   # carrying its own scorer; None: no Or around the phrase
 
 
 # ------------------------------------------------------------------ segment --
@@ -545,9 +552,11 @@ class QueryArrays:
             offs = p.offsets if p.offsets is not None else [0] * len(p.terms)
             alts = p.alts if p.alts is not None else [False] * len(p.terms)
             reqs = p.required if p.required is not None else [False] * len(p.terms)
-            for t, (kind, c0, nc, nl), off, alt, req in zip(p.terms, p.scorers, offs, alts, reqs):
+            opts = p.optional if p.optional is not None else [False] * len(p.terms)
+            for t, (kind, c0, nc, nl), off, alt, req, opt in zip(p.terms, p.scorers, offs, alts, reqs, opts):
                 kind = kind | PHRASE_ALT if alt else kind   # (GROUP_ALT for an And: the same bit)
                 kind = kind | PHRASE_REQUIRED if req else kind
+                kind = kind | PHRASE_OPTIONAL if opt else kind
                 for s, sr in enumerate(segs):       # same scorer, the segment's own ordinal
                     present = t is not None and 0 <= t < len(sr.metas)
                     terms[s, at] = (t if present else NO_TERM, kind, c0, nc, nl, off)
@@ -1103,14 +1112,17 @@ class SegmentStats:
     docs_count: np.ndarray  # per term ordinal: term_meta::docs_count
 
 
-def prepare(filters, scorer, segment_stats, required_terms=False):
+def prepare(filters, scorer, segment_stats, required_terms=False, optional_terms=False):
     """filter::prepare for a list of filters against ALL segments: statistics are
     index-global (term_filter.cpp:102-125): D = sum docs_with_field,
     d = sum docs_count of the term, avgdl from the summed field frequency.
     required_terms=True: And([by_phrase, by_term..., Not(...)...]) — a phrase plus required terms,
     IRS_HIP_PHRASE_REQUIRED — is taken.  Off by default: prepare() then refuses the shape as it
     always did (ValueError), so callers that send what prepare() refuses down their CPU path see no
-    change until they ask for it."""
+    change until they ask for it.
+    optional_terms=True: Or([by_phrase, by_term...]) — a phrase or optional terms,
+    IRS_HIP_PHRASE_OPTIONAL — is taken, also as the one included child of And([Or([...]), Not(...)]).
+    Off by default in the same way."""
     dwf = sum(s.docs_with_field for s in segment_stats)
     ttf = sum(s.total_term_freq for s in segment_stats)
     out = []
@@ -1118,14 +1130,14 @@ def prepare(filters, scorer, segment_stats, required_terms=False):
         flt, doc_set = split_doc_set(flt)
         if doc_set is not None:
             # (the doc set is no part of what is prepared: no score, no statistic)
-            p = prepare([flt], scorer, segment_stats, required_terms)[0]
+            p = prepare([flt], scorer, segment_stats, required_terms, optional_terms)[0]
             p.doc_set = doc_set
             out.append(p)
             continue
         flt, excluded = split_exclusions(flt)
         if excluded:
             # (the excluded part is prepared without scorers: no score, no statistic)
-            p = prepare([flt], scorer, segment_stats, required_terms)[0]
+            p = prepare([flt], scorer, segment_stats, required_terms, optional_terms)[0]
             p.excluded = [int(t) for t in excluded]
             out.append(p)
             continue
@@ -1136,6 +1148,9 @@ def prepare(filters, scorer, segment_stats, required_terms=False):
             one = _phrase_scorer(flt, flt.boost, scorer, segment_stats, dwf, ttf)
             out.append(PreparedQuery(OP_PHRASE, list(flt.terms), [one] * len(flt.terms), 0,
                                      [int(o) for o in flt.offsets]))
+            continue
+        if type(flt) is Or and optional_terms and any(isinstance(s, by_phrase) for s in flt.subs):
+            out.append(_prepare_phrase_or(flt, scorer, segment_stats, dwf, ttf))
             continue
         if isinstance(flt, (Or, And)) and any(isinstance(s, by_phrase) for s in flt.subs):
             if type(flt) is And and not required_terms:
@@ -1220,6 +1235,51 @@ def _prepare_phrase_and(flt, scorer, segment_stats, dwf, ttf):
         scorers.append(scorer.term_scorer(scorer.collect(dwf, dwt, ttf), f32(mult * f32(s.boost))))
     return PreparedQuery(OP_PHRASE, terms, scorers, 0, [int(o) for o in ph.offsets] + [0] * len(others),
                          required=[False] * len(ph.terms) + [True] * len(others))
+
+
+def _prepare_phrase_or(flt, scorer, segment_stats, dwf, ttf):
+    """prepare() of Or([by_phrase, by_term...]) — a phrase or optional terms (Or::prepare prepares
+    every child on its own, boolean_filter.cpp:150-210; MakeDisjunction over {PhraseIterator, term
+    iterators}, disjunction.hpp:1411-1467): the phrase gets its FixedPrepareCollect blob from its
+    own words, every by_term its own statistics; the Or's boost (and those of nested SUM Ors of
+    terms, flattened as _or_members does) multiplies into every child's in float32.  Entries: the
+    phrase's words, then the optional terms (IRS_HIP_PHRASE_OPTIONAL).  What is taken: ONE by_phrase
+    of plain terms, min_match <= 1, merge SUM, at most 8 words and terms in all."""
+    taken = ("an Or takes ONE by_phrase of plain terms plus by_term children (and SUM Ors of "
+             "by_term), min_match <= 1, merged with SUM")
+    phrases = [s for s in flt.subs if isinstance(s, by_phrase)]
+    others = [s for s in flt.subs if not isinstance(s, by_phrase)]
+    if len(phrases) > 1:
+        raise ValueError("two phrases in one Or are not on the GPU path: " + taken)
+    ph = phrases[0]
+    if ph.variadic:
+        raise ValueError("a variadic by_phrase with optional terms is not on the GPU path: " + taken)
+    if flt.min_match > 1:
+        raise ValueError("an Or with a by_phrase child and min_match > 1 is not on the GPU path: " + taken)
+    if flt.merge != MERGE_SUM and len(flt.subs) > 1:
+        raise ValueError("an Or with a by_phrase child merges with SUM on the GPU path "
+                         "(MAX / MIN over a phrase and terms are not built)")
+    if any(isinstance(s, And) for s in others):
+        raise ValueError("an And child next to a by_phrase in an Or ((a AND b) OR \"c d\") is not on "
+                         "the GPU path: " + taken)
+    if len(ph.terms) < 2:
+        raise ValueError("a by_phrase of one term is a by_term: " + taken)
+    mult = f32(flt.boost)
+    # (a by_phrase in a nested Or, Not, min_match > 1 or non-SUM nested Ors: refused there)
+    members = _or_members(replace(flt, subs=others), mult)
+    if len(ph.terms) + len(members) > _lib.MAX_PHRASE_TERMS:
+        raise ValueError("a by_phrase plus optional terms has at most %d entries in all"
+                         % _lib.MAX_PHRASE_TERMS)
+    one = _phrase_scorer(ph, f32(mult * f32(ph.boost)), scorer, segment_stats, dwf, ttf)
+    terms, scorers = list(ph.terms), [one] * len(ph.terms)
+    for t, boost in members:
+        dwt = sum(int(st.docs_count[t]) for st in segment_stats if 0 <= t < len(st.docs_count))
+        terms.append(t)
+        scorers.append(scorer.term_scorer(scorer.collect(dwf, dwt, ttf), boost))
+    p = PreparedQuery(OP_PHRASE, terms, scorers, 0, [int(o) for o in ph.offsets] + [0] * len(members))
+    if members:   # (an Or of the phrase alone is the phrase)
+        p.optional = [False] * len(ph.terms) + [True] * len(members)
+    return p
 
 
 def _prepare_groups(flt, scorer, segment_stats, dwf, ttf):

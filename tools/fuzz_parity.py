@@ -9,7 +9,8 @@ checks the results as the parity tests do; the same batch is then re-run with bl
 (top-k must not change) and with the k-th score pushed down as irs::score::Min.  Every third
 boolean round also runs the filters with 0-2 excluded terms each (And(filter, Not(by_term))), and
 every phrase round also runs variadic phrases (parts of several terms) and phrases with required
-terms (And([by_phrase, by_term...])); every boolean round runs
+terms (And([by_phrase, by_term...])) or optional terms (Or([by_phrase, by_term...])); every boolean
+round runs
 Ands of Or groups (with exclusions, wand on and off; every third over two segments in one batch).
 With --doc-sets every round also restricts a random subset of its units to random doc sets
 (irs_hip_batch_set_doc_sets) at densities 0, 0.001, 0.5 and 1, on a path picked at random, and
@@ -287,6 +288,24 @@ def main():
                 tpa.check(f, k, rh[q], rc[q], rt[q], *tpa.expected(seg, f, scorer))
             rb.close()
             queries += len(rf)
+            # a phrase or optional terms (IRS_HIP_PHRASE_OPTIONAL): Or([by_phrase, by_term...]), some
+            # with a Not, against the composition of tests/test_phrase_or.py (the oracle's phrase run
+            # and its disjunction of the optional terms); the match sets are the union
+            import test_phrase_or as tpo
+            of = tpo.random_queries(seg, max(max_rank, 24), 8, int(rng.integers(1, 1 << 30))) + filters[:2]
+            ob = sr.batch(search.prepare(of, scorer, st, optional_terms=True), k)
+            if rng.integers(0, 2):
+                ob.configure(tile_docs=int(rng.choice([4096, 6144, 8192, 12288])))
+            oh, oc, ot = (x.copy() for x in ob.run().results())
+            oexp = [tpo.expected(seg, f, scorer) for f in of]
+            for q, f in enumerate(of):
+                tpo.check(f, k, oh[q], oc[q], ot[q], *oexp[q])
+            osets, ocounts = ob.match_sets()
+            for q, f in enumerate(of):
+                assert np.array_equal(tpo._bits(osets[q], seg.num_docs + 1), oexp[q][1]), ("match set", f)
+                assert int(ocounts[q]) == int(oexp[q][1].sum()), ("match count", f)
+            ob.close()
+            queries += len(of)
         else:
             filters = []
             for _ in range(16):

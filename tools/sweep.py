@@ -52,6 +52,10 @@ def main():
                     help="--op phrase: comma list N,...: And([phrase, N by_terms]) — the same phrases with "
                          "N required terms each (IRS_HIP_PHRASE_REQUIRED), drawn from --lo-rank..--hi-rank; "
                          "0 = the plain phrases.  Times each and exits")
+    ap.add_argument("--optional", default="",
+                    help="--op phrase: comma list N,...: Or([phrase, N by_terms]) — the same phrases with "
+                         "N optional terms each (IRS_HIP_PHRASE_OPTIONAL), drawn from --lo-rank..--hi-rank; "
+                         "0 = the plain phrases.  Times each and exits")
     ap.add_argument("--unscored", action="store_true",
                     help="time irs_hip_batch_match_sets_to_device (every unit's full match set as a "
                          "bitset + its count, and the counts alone) instead of run + results; the scored "
@@ -127,6 +131,36 @@ def main():
             print("alts=%d  %s  step %.2f ms  = %.2f ms per 1000 queries  hits/query mean %.0f  reruns=%d"
                   % (n_alt, "grouped" if n_alt > 1 else "plain", dt * 1e3, dt * 1e3 * 1000 / len(gf),
                      float(np.mean(totals)), b.reruns()), flush=True)
+            b.close()
+        sys.exit(0)
+    if args.optional and args.op == "phrase":
+        for n_opt in (int(x) for x in args.optional.split(",")):
+            rng = np.random.default_rng(synth.SEED + 7)
+            of = []
+            for row in ranks:
+                ph = by_phrase([int(r) - 1 for r in row])
+                opt = []
+                while len(opt) < n_opt:
+                    x = int(rng.integers(args.lo_rank, args.hi_rank + 1)) - 1
+                    if x not in opt:
+                        opt.append(x)
+                of.append(Or([ph] + [by_term(x) for x in opt]) if n_opt else ph)
+            b = sr.batch(search.prepare(of, scorer, [st], optional_terms=True), args.k).profile(True)
+            b.run()
+            _, _, totals = b.results()
+            ms = []
+            t0 = time.perf_counter()
+            for _ in range(args.steps):
+                b.run()
+                b.results()
+                ms.append(b.timings())
+            dt = (time.perf_counter() - t0) / args.steps
+            avg = np.mean(ms, axis=0)
+            # (the stage timings are the phrase pass's; the step holds both passes and the union)
+            print("optional=%d  step %.2f ms  = %.2f ms per 1000 phrases  (phrase pass: plan %.2f pilot %.2f "
+                  "score %.2f select %.2f)  hits/query mean %.1f  reruns=%d"
+                  % (n_opt, dt * 1e3, dt * 1e3 * 1000 / len(of), *avg, float(np.mean(totals)), b.reruns()),
+                  flush=True)
             b.close()
         sys.exit(0)
     if args.required and args.op == "phrase":

@@ -22,6 +22,7 @@ extern "C" {
 #define IRS_HIP_ABI_VERSION 12
 #define IRS_HIP_BLOCK_SIZE 128u  /* postings per block, formats_10.cpp:90 */
 #define IRS_HIP_MAX_TERMS 16u    /* terms per boolean query               */
+#define IRS_HIP_MAX_WIDE_TERMS 64u /* entries of one IRS_HIP_OP_MULTITERM query */
 #define IRS_HIP_MAX_K 4096u      /* largest top-k                         */
 #define IRS_HIP_MAX_PHRASE_TERMS 8u /* terms (parts) of one by_phrase query */
 #define IRS_HIP_MAX_PHRASE_ENTRIES 16u /* included entries of one variadic by_phrase,
@@ -205,7 +206,7 @@ typedef enum irs_hip_op {
   IRS_HIP_OP_MINMATCH = 2, /* irs::Or with min_match_count: MinMatchQuery::execute
                              (boolean_query.cpp:212-247) -> min_match_iterator =
                              block_disjunction<kMinMatch> (disjunction.hpp:1378-1383)   */
-  IRS_HIP_OP_PHRASE = 3   /* irs::by_phrase of plain terms: FixedPhraseQuery::execute
+  IRS_HIP_OP_PHRASE = 3,  /* irs::by_phrase of plain terms: FixedPhraseQuery::execute
                              (phrase_query.cpp:44-111) -> PhraseIterator<Conjunction,
                              FixedPhraseFrequency> (phrase_iterator.hpp:75-166, 540-626).
                              terms[first_term + i] = i-th phrase term with its
@@ -219,7 +220,45 @@ typedef enum irs_hip_op {
                              VariadicPhraseQuery): IRS_HIP_PHRASE_ALT below; a phrase
                              plus required terms (an And of a by_phrase and by_terms):
                              IRS_HIP_PHRASE_REQUIRED below.                            */
+  IRS_HIP_OP_MULTITERM = 4 /* a scored set of up to IRS_HIP_MAX_WIDE_TERMS (term, boost) with
+                             min_match — see below                                        */
 } irs_hip_op;
+
+/* IRS_HIP_OP_MULTITERM: irs::by_terms (by_terms_options: a set of (term, boost) and min_match,
+ * core/search/terms_filter.cpp:110-153), executed as MultiTermQuery::execute does
+ * (core/search/multiterm_query.cpp:114-181): a min_match_iterator over one scored iterator per
+ * term.  It is also what the scored part of by_range / by_prefix / by_wildcard becomes beyond
+ * IRS_HIP_MAX_TERMS states (scored_terms_limit{1024}, core/search/range_filter.hpp:58; the
+ * reference's benchmark passes --scored-terms-limit=16, scripts/search-benchmark.sh:14) and what
+ * by_edit_distance needs once its terms are visited (max_terms = 50, utils/index-search.cpp:413).
+ *   n_terms   1..IRS_HIP_MAX_WIDE_TERMS included entries, each with its own scorer values (c0
+ *             holds term boost x filter boost) and validated like any by_term entry; more than
+ *             IRS_HIP_MAX_WIDE_TERMS is IRS_HIP_EUNSUPPORTED
+ *   min_match 1..n_terms; 0 or more than n_terms is IRS_HIP_EINVAL
+ *   merge     IRS_HIP_MERGE_SUM; MAX / MIN is IRS_HIP_EUNSUPPORTED
+ * Per segment d matches iff at least min_match of the PRESENT entries hold d, minus the segment's
+ * deleted docs; score(d) = the sum of the scores of the entries holding d; total_hits counts the
+ * matching docs.  An absent entry (IRS_HIP_NO_TERM or no docs) adds nothing and counts for
+ * nothing; fewer than min_match present entries empty the query in that segment.  The same term
+ * twice scores twice (it is decoded once).  A zero boost matches with score 0.
+ * Refused at create with IRS_HIP_EUNSUPPORTED (the entries of such a query are postings decoded
+ * once per batch into 4-byte records, scored through tables): a term with a frequency above 255;
+ * a scorer outside the table family (BM25 / BM15 / TF-IDF over a 1-byte Norm2 column or none:
+ * wide and legacy norm columns are outside) or more than 4 distinct (kind, norm_const,
+ * norm_length) in one query; IRS_HIP_EXCLUDE entries.  Refused on a batch that holds such a query,
+ * IRS_HIP_EUNSUPPORTED: irs_hip_batch_set_doc_sets / _host, irs_hip_batch_set_comm,
+ * irs_hip_batch_match_sets / _to_device (the unscored union of many terms is irs_hip_bit_union).
+ * The units run exhaustively on kernels of their own (k_wide_pilot, k_wide_score: one lane per
+ * term, 64-bit fixed-point sums whose low 7 bits count the terms on a doc) over the batch's decoded
+ * posting streams — a term shared with another query, or held by the device's stream cache, is
+ * decoded once or not at all; irs_hip_batch_stream_counts counts these streams too.
+ * irs_hip_batch_set_wand, _set_path and _set_paired_tiles leave them as they are,
+ * irs_hip_batch_set_shared_threshold leaves each a threshold of its own, irs_hip_batch_configure's
+ * tile_docs is ignored by them; cand_cap, pilot_stride, min scores, results, re-runs, profile and
+ * timings (their kernels count into the PILOT and SCORE stages) behave as for any batch.  A batch
+ * may mix these queries with any non-phrase queries: the others give bit for bit what they give in
+ * a batch of their own, on the path they would take there.  A compatible addition to ABI 12: the
+ * op was IRS_HIP_EINVAL before. */
 
 /* Which ScoreFunction Scorer::prepare_scorer would have built. */
 typedef enum irs_hip_scorer_kind {
@@ -371,11 +410,13 @@ typedef enum irs_hip_merge {
 typedef struct irs_hip_query {
   int32_t op;          /* irs_hip_op                                   */
   uint32_t n_terms;    /* included entries: 1..IRS_HIP_MAX_TERMS (PHRASE: ..IRS_HIP_MAX_PHRASE_TERMS;
-                          with IRS_HIP_PHRASE_ALT members ..IRS_HIP_MAX_PHRASE_ENTRIES),
+                          with IRS_HIP_PHRASE_ALT members ..IRS_HIP_MAX_PHRASE_ENTRIES;
+                          MULTITERM: ..IRS_HIP_MAX_WIDE_TERMS),
                           then 0..IRS_HIP_MAX_EXCLUDED IRS_HIP_EXCLUDE entries */
   uint32_t first_term; /* index of the first entry in the `terms` array */
   uint32_t k;          /* top-k, 1..IRS_HIP_MAX_K (index-search --topN) */
-  uint32_t min_match;  /* IRS_HIP_OP_MINMATCH: Or::min_match_count(); else ignored */
+  uint32_t min_match;  /* IRS_HIP_OP_MINMATCH: Or::min_match_count(); IRS_HIP_OP_MULTITERM:
+                          by_terms_options::min_match; else ignored */
   uint32_t merge;      /* irs_hip_merge (OR / AND / MINMATCH); PHRASE: IRS_HIP_MERGE_SUM */
 } irs_hip_query;
 
@@ -781,6 +822,9 @@ int irs_hip_device_stream_cache_stats(int32_t device, irs_hip_stream_cache_stats
  * none when every stream was held, none for a replayed run of a batch whose first run filled the
  * cache.  A batch without joined units reports 0, 0.  IRS_HIP_EINVAL before the first run. */
 int irs_hip_batch_stream_counts(irs_hip_batch* batch, uint32_t* distinct, uint32_t* decoded);
+/* The batch's IRS_HIP_OP_MULTITERM units ((segment, query) pairs), whatever they hold in their
+ * segment. */
+int irs_hip_batch_wide_units(irs_hip_batch* batch, uint32_t* units);
 /* Bound images: where a batch's plain disjunctions run on paired doc tiles, the kernel reads, per
  * (segment, term, scorer signature), a second array in posting order whose entries carry a 16-bit
  * upper bound of the posting's score factor instead of (tf, norm).  Images are made from the

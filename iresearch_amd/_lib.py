@@ -17,6 +17,7 @@ from . import _build
 OK, EINVAL, ECORRUPT, ENOMEM, EHIP, EOVERFLOW, EUNSUPPORTED, EPEER = 0, -1, -2, -3, -4, -5, -6, -7
 LAYOUT_SCALAR, LAYOUT_SIMD4 = 0, 1
 OP_OR, OP_AND, OP_MINMATCH, OP_PHRASE = 0, 1, 2, 3
+OP_MULTITERM = 4   # a scored set of up to MAX_WIDE_TERMS (term, boost) with min_match: by_terms
 SCORE_BM25, SCORE_BM15, SCORE_BM1, SCORE_TFIDF, SCORE_TFIDF_NORM = 0, 1, 2, 3, 4
 EXCLUDE = 0x100   # irs_hip_term_scorer.kind of an excluded term (irs::Not)
 PHRASE_ALT = 0x200   # OR-ed into a phrase entry's kind: one more member of the part before it
@@ -28,6 +29,7 @@ NO_DOC_SET = 0xFFFFFFFF   # row_of_unit of an unrestricted unit (irs_hip_batch_s
 PATH_AUTO, PATH_ITEMS, PATH_JOINED = 0, 1, 2
 WAND_NONE, WAND_DIV_NORM, WAND_MAX_FREQ, WAND_MIN_NORM = 0, 1, 2, 3   # Scorer::WandType
 MAX_TERMS, MAX_K, MAX_PHRASE_TERMS, MAX_EXCLUDED = 16, 4096, 8, 16
+MAX_WIDE_TERMS = 64   # entries of one OP_MULTITERM query
 MAX_PHRASE_ENTRIES = 16   # included entries of a variadic phrase, members counted
 K_PLAN, K_PILOT, K_SCORE, K_SELECT, K_COUNT = 0, 1, 2, 3, 4
 KERNEL_NAMES = ("k_plan", "k_pilot", "k_score", "k_select")
@@ -96,7 +98,7 @@ SYMBOLS = (
     "irs_hip_device_upload", "irs_hip_device_download", "irs_hip_device_sync",
     "irs_hip_device_trim",
     "irs_hip_device_set_stream_cache", "irs_hip_device_stream_cache_stats",
-    "irs_hip_batch_stream_counts",
+    "irs_hip_batch_stream_counts", "irs_hip_batch_wide_units",
     "irs_hip_batch_image_counts", "irs_hip_device_image_count", "irs_hip_join_bound_rule",
     "irs_hip_batch_rescore_paths", "irs_hip_join_half_rule", "irs_hip_join_half_probe",
 )
@@ -197,6 +199,7 @@ def bind(L: C.CDLL) -> C.CDLL:
     L.irs_hip_device_stream_cache_stats.restype = C.c_int
     L.irs_hip_batch_stream_counts.argtypes = [vp, P(u32), P(u32)]
     L.irs_hip_batch_stream_counts.restype = C.c_int
+    L.irs_hip_batch_wide_units.argtypes, L.irs_hip_batch_wide_units.restype = [vp, P(u32)], C.c_int
     L.irs_hip_batch_image_counts.argtypes = [vp, P(u32), P(u32)]
     L.irs_hip_batch_image_counts.restype = C.c_int
     L.irs_hip_device_image_count.argtypes, L.irs_hip_device_image_count.restype = [i32, P(u64)], C.c_int

@@ -205,12 +205,25 @@ struct And {
 struct by_doc_set {
   uint32_t row = 0;
 };
+// irs::by_terms WITH scorers (by_terms_options: a set of (term, boost) and min_match,
+// terms_filter.cpp:110-153; MultiTermQuery::execute, multiterm_query.cpp:114-181): a doc matches
+// when at least `min_match` of the terms present in its segment hold it, its score is the sum of
+// the scores of the terms holding it (IRS_HIP_OP_MULTITERM).  1..IRS_HIP_MAX_WIDE_TERMS terms (more:
+// not_supported), min_match 1..#terms (else illegal_argument); `boost` multiplies into every
+// term's; the same term twice scores twice.  No Not children, no doc set, no match sets
+// (not_supported, as the ABI refuses them).  (The unscored by_terms visitor further down is the
+// term-dictionary side of the same filter.)
+struct by_scored_terms {
+  std::vector<by_term> terms;
+  uint32_t min_match = 1;
+  float boost = 1.f;
+};
 struct Exclusion {
   std::variant<by_term, Or, And, by_phrase> incl;
   std::vector<by_term> excl;   // at most IRS_HIP_MAX_EXCLUDED
   std::optional<by_doc_set> doc_set;   // the And's by_doc_set child (next to its Nots, or alone)
 };
-using filter = std::variant<by_term, Or, And, by_phrase, Exclusion>;
+using filter = std::variant<by_term, Or, And, by_phrase, Exclusion, by_scored_terms>;
 
 // What by_term::prepare reads from one segment without touching postings.
 struct SegmentStats {
@@ -459,7 +472,17 @@ std::vector<PreparedQuery> prepare(const std::vector<filter>& filters, const Sco
   };
   for (const filter& f : filters) {
     PreparedQuery q;
-    if (const auto* x = std::get_if<Exclusion>(&f)) {
+    if (const auto* m = std::get_if<by_scored_terms>(&f)) {
+      // statistics per term exactly as for an Or of by_terms
+      if (m->terms.empty()) throw illegal_argument(IRS_HIP_EINVAL, "by_scored_terms: no terms");
+      if (m->terms.size() > IRS_HIP_MAX_WIDE_TERMS)
+        throw not_supported(IRS_HIP_EUNSUPPORTED, "by_scored_terms: more than IRS_HIP_MAX_WIDE_TERMS terms");
+      if (m->min_match == 0 || m->min_match > m->terms.size())
+        throw illegal_argument(IRS_HIP_EINVAL, "by_scored_terms: min_match is 1..#terms");
+      q.op = IRS_HIP_OP_MULTITERM;
+      q.min_match = m->min_match;
+      for (const auto& t : m->terms) q.terms.push_back(one(by_term{t.term, m->boost * t.boost}));
+    } else if (const auto* x = std::get_if<Exclusion>(&f)) {
       fill(q, x->incl);
       // behind the included entries: one IRS_HIP_EXCLUDE entry per excluded term, no scorer
       for (const by_term& t : x->excl) {
@@ -880,6 +903,16 @@ class QueryBatch {
   // the distinct (segment, term) streams of the batch's joined units, and how many of them its
   // last run decoded itself — the rest came out of the device's stream cache
   struct StreamCounts { uint32_t distinct = 0, decoded = 0; };
+  // the batch's units of by_scored_terms / wide expansion queries (irs_hip_batch_wide_units)
+  uint32_t wide_units() const {
+    uint32_t total = 0;
+    for (const Part& part : part_) {
+      uint32_t n = 0;
+      if (part.h) check(irs_hip_batch_wide_units(part.h, &n), "irs_hip_batch_wide_units");
+      total += n;
+    }
+    return total;
+  }
   StreamCounts stream_counts() const {
     StreamCounts total;
     for (const Part& part : part_) {
@@ -1879,7 +1912,9 @@ DocSet execute_unscored(const SegmentReader& segment, const SegmentStats& stats,
 // offset) keys are scored, each with the statistics of the segments where it IS scored; every other
 // visited term only contributes documents (score 0).
 struct PreparedExpansion {
-  PreparedQuery scored;                            // Or of the scored terms, segment_terms filled
+  PreparedQuery scored;                            // Or of the scored terms (more than IRS_HIP_MAX_TERMS
+                                                   // of them: IRS_HIP_OP_MULTITERM with min_match 1),
+                                                   // segment_terms filled
   std::vector<std::vector<uint32_t>> scored_in;    // [segment]: ordinals scored there (ascending)
   std::vector<std::vector<uint32_t>> unscored_in;  // [segment]: visited, not scored (visit order)
 };
@@ -1924,6 +1959,9 @@ PreparedExpansion prepare_expansion(const std::vector<std::vector<uint32_t>>& vi
                                     const std::vector<SegmentStats>& index, float boost = 1.f) {
   if (visits.size() != index.size())
     throw illegal_argument(IRS_HIP_EINVAL, "prepare_expansion: one visit per segment");
+  // (the scored states are at most `scored_terms_limit` query term slots)
+  if (scored_terms_limit > IRS_HIP_MAX_WIDE_TERMS)
+    throw not_supported(IRS_HIP_EUNSUPPORTED, "prepare_expansion: scored_terms_limit above IRS_HIP_MAX_WIDE_TERMS");
   uint64_t dwf = 0, ttf = 0;
   for (const auto& s : index) {
     dwf += s.docs_with_field;
@@ -1948,7 +1986,8 @@ PreparedExpansion prepare_expansion(const std::vector<std::vector<uint32_t>>& vi
   std::sort(slots.begin(), slots.end());
   slots.erase(std::unique(slots.begin(), slots.end()), slots.end());
   PreparedQuery& q = out.scored;
-  q.op = IRS_HIP_OP_OR;
+  q.op = slots.size() > IRS_HIP_MAX_TERMS ? IRS_HIP_OP_MULTITERM : IRS_HIP_OP_OR;
+  q.min_match = slots.size() > IRS_HIP_MAX_TERMS ? 1u : 0u;
   q.segment_terms.assign(visits.size(), std::vector<uint32_t>(std::max<size_t>(1, slots.size()),
                                                               IRS_HIP_NO_TERM));
   for (size_t j = 0; j < slots.size(); ++j) {

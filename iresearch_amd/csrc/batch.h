@@ -1,5 +1,6 @@
 // batch.h — the state of a batch: what every execution path reads at the top level, and one record
-// per path (work items in doc tiles, joined posting streams, block-driven conjunctions and phrases),
+// per path (work items in doc tiles, joined posting streams, wide multi-term units, block-driven
+// conjunctions and phrases),
 // for thresholds shared across segments and for a run's place on the streams.
 // Included by irs_hip.hip (one translation unit).
 #pragma once
@@ -119,6 +120,18 @@ struct JoinWork {
   uint32_t n_images = 0, n_img_private = 0, n_img_fill = 0;
   uint32_t n_bwgs = 0, n_bwgs_fill = 0;
   uint32_t images_built_last = 0;   // images the last plan stage queued k_join_bound work for
+};
+
+// Scored multi-term queries of up to 64 terms (IRS_HIP_OP_MULTITERM; wide.h, plan_wide.h): the units,
+// fixed at create — they never change path.  Their terms are streams of JoinWork (build_streams),
+// their per-term records lie in join.d_jterms; nothing else of the batch counts them in (acc32,
+// count_precise, jt, tiles.any_and, all_tile_units, all_conj_units).
+struct WideWork {
+  std::vector<uint32_t> units;
+  bool on() const { return !units.empty(); }
+  DevBuf d_units;
+  uint32_t n_max = 0;   // doc tiles of the unit with the most
+  uint32_t n_min = 0;   // ... with the fewest, empty units aside (pilot stride)
 };
 
 // Block-driven conjunctions (conj.h) and phrases (phrase.h): a wavefront per block of a unit's lead term
@@ -308,6 +321,7 @@ struct irs_hip_batch {
   Stager up;
   TileWork tiles;
   JoinWork join;
+  WideWork wide;
   BlockWork blocks;
   AnyWork any;
   // A batch with optional terms (IRS_HIP_PHRASE_OPTIONAL): this batch is the PHRASE PASS; `opt` — a

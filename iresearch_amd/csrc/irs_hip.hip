@@ -31,6 +31,7 @@
 #include "conj.h"
 #include "conj_any.h"
 #include "join.h"
+#include "wide.h"
 #include "excl.h"
 #include "match.h"
 
@@ -43,6 +44,7 @@ using namespace irs_hip;
 #include "plan_tiles.h"
 #include "plan_blocks.h"
 #include "plan_any.h"
+#include "plan_wide.h"
 #include "plan_join.h"
 #include "plan_match.h"
 
@@ -119,10 +121,16 @@ bool size_units(irs_hip_batch* b, uint64_t* first_words, uint64_t* item_bound) {
   b->n_tiles = 0xFFFFFFFFu;
   b->tiles.n_max = 0;
   b->join.n_max = 0;
+  b->wide.n_max = 0;
+  b->wide.n_min = 0xFFFFFFFFu;
   std::vector<uint8_t> is_join(b->nq, 0);
   for (uint32_t u : b->join.units) is_join[u] = 1;
   for (uint32_t u = 0; u < b->nq; ++u) {
     DevQuery& dq = b->queries[u];
+    if (unit_is_wide(dq)) {   // (tiles of its own: nothing of the other units' geometry counts it)
+      size_wide_unit(b, dq);
+      continue;
+    }
     // (conjunctions are block driven unless they run as joined streams)
     const bool tiled = !b->phrase && ((dq.op & 0xFF) != 2 || is_join[u]);
     const uint32_t tile_docs = is_join[u] ? kJoinTile : b->tiles.docs;   // (streams are cut at kJoinTile)
@@ -213,8 +221,8 @@ bool alloc_scratch(irs_hip_batch* b, uint64_t first_words, uint64_t item_bound) 
       !b->d_out.alloc(uint64_t(b->nq) * b->k_max * sizeof(Hit)) ||
       !b->d_out_count.alloc(b->nq * sizeof(uint32_t)) || !b->tiles.d_work.alloc(16))
     return false;
-  if (b->join.on() && !build_streams(b)) return false;
-  if (!build_groups(b)) return false;
+  if (streams_on(b) && !build_streams(b)) return false;
+  if (!alloc_wide(b) || !build_groups(b)) return false;
   if (!b->tiles.units.empty()) {
     if (!b->tiles.d_units.alloc(b->tiles.units.size() * 4) ||
         !b->up.copy(b->tiles.d_units.p, b->tiles.units.data(), b->tiles.units.size() * 4))
@@ -628,13 +636,22 @@ static int batch_create_multi_impl(irs_hip_segment* const* segs, uint32_t n_segs
         rc = IRS_HIP_EUNSUPPORTED;
         break;
       }
+      // a scored multi-term query (IRS_HIP_OP_MULTITERM, wide.h): up to IRS_HIP_MAX_WIDE_TERMS entries
+      const bool wide = in.op == IRS_HIP_OP_MULTITERM;
       if ((in.op != IRS_HIP_OP_OR && in.op != IRS_HIP_OP_AND && in.op != IRS_HIP_OP_MINMATCH &&
-           in.op != IRS_HIP_OP_PHRASE) ||
+           in.op != IRS_HIP_OP_PHRASE && !wide) ||
           n_incl == 0 || in.merge > IRS_HIP_MERGE_MIN ||
           (in.op == IRS_HIP_OP_PHRASE && in.merge != IRS_HIP_MERGE_SUM) ||
-          n_incl > IRS_HIP_MAX_TERMS || n_excl > IRS_HIP_MAX_EXCLUDED || in.k == 0 || in.k > IRS_HIP_MAX_K) {
+          (!wide && n_incl > IRS_HIP_MAX_TERMS) || n_excl > IRS_HIP_MAX_EXCLUDED || in.k == 0 || in.k > IRS_HIP_MAX_K) {
         rc = IRS_HIP_EINVAL;
         break;
+      }
+      if (wide) {
+        // (by_terms_options::min_match is 1..#terms for a posting-list query: 0 is the all-docs
+        // filter, terms_filter.cpp:119-123, more than the terms nothing, :125-128)
+        if (n_incl <= IRS_HIP_MAX_WIDE_TERMS && (in.min_match == 0 || in.min_match > n_incl)) rc = IRS_HIP_EINVAL;
+        else if (n_incl > IRS_HIP_MAX_WIDE_TERMS || n_excl || in.merge != IRS_HIP_MERGE_SUM) rc = IRS_HIP_EUNSUPPORTED;
+        if (rc != IRS_HIP_OK) break;
       }
       // a phrase with required terms (IRS_HIP_PHRASE_REQUIRED): the phrase's words (n_words, at
       // least 2), then the by_term children of the And that holds it, nothing else behind them
@@ -845,6 +862,10 @@ static int batch_create_multi_impl(irs_hip_segment* const* segs, uint32_t n_segs
         }
         const uint32_t m = in.min_match;
         need = (m > n_incl || m > row.size()) ? 0xFFu : m;
+      } else if (wide) {
+        // fewer than min_match present entries empty the query in this segment
+        // (MultiTermQuery::execute, multiterm_query.cpp:163-167)
+        need = in.min_match > row.size() ? 0xFFu : in.min_match;
       }
       if (is_phrase) {
         // no phrase state for a segment lacking one of the terms (phrase_filter.cpp:254-258), or
@@ -899,7 +920,11 @@ static int batch_create_multi_impl(irs_hip_segment* const* segs, uint32_t n_segs
       // low byte of op: 0 = disjunction in doc tiles, 1 = doc tiles with per-doc match
       // counters (min-match), 2 = conjunction, block by block of its rarest term (conj.h)
       dq.op = 0;
-      if (grouped) {
+      if (wide) {
+        // lane j = term j of k_wide_pilot / k_wide_score; the match count rides in the low bits of
+        // the unit's own 64-bit sums whatever min_match is
+        dq.op = int32_t(kWideOp | (need << 8));
+      } else if (grouped) {
         // MakeConjunction sorts its children by cost (conjunction.hpp:450-453): the groups, by the
         // sum of their members' docs_count (the cheapest leads; the members keep their order);
         // always block driven (conj_any.h), whatever the number of rows
@@ -957,11 +982,12 @@ static int batch_create_multi_impl(irs_hip_segment* const* segs, uint32_t n_segs
         }
       }
       dq.op |= int32_t(merge << 16);
-      if (!is_phrase && !grouped) ((dq.op & 0xFF) == 2 ? b->all_conj_units : b->all_tile_units).push_back(q);
+      if (wide) b->wide.units.push_back(q);
+      else if (!is_phrase && !grouped) ((dq.op & 0xFF) == 2 ? b->all_conj_units : b->all_tile_units).push_back(q);
       // match counts in the low bits of a 32-bit accumulator (join.h COUNT) round every posting
       // to 16 fixed-point units (+-8): relative to any doc's score that is at most
       // 8 * upper / (2^29 * min_score) — allowed while it stays below 2e-6
-      b->count_precise[q] = row.size() <= kJoinCountTerms && min_score > 0.0 && upper > 0.0 &&
+      b->count_precise[q] = !wide && row.size() <= kJoinCountTerms && min_score > 0.0 && upper > 0.0 &&
                             upper / min_score <= 125.0;
       // table slots (kernels.h "table_kind"): one per distinct (kind, norm_const, norm_length)
       uint32_t n_caches = 0;
@@ -982,6 +1008,7 @@ static int batch_create_multi_impl(irs_hip_segment* const* segs, uint32_t n_segs
         }
         qt.cache_id = c < kMaxCaches ? c : kMaxCaches;
       }
+      if (wide && (rc = wide_terms_ok(seg, row)) != IRS_HIP_OK) break;
       dq.n_caches = n_caches;
       dq.n_terms = uint32_t(row.size());
       dq.first_term = uint32_t(b->qterms.size());
@@ -994,7 +1021,7 @@ static int batch_create_multi_impl(irs_hip_segment* const* segs, uint32_t n_segs
       }
       dq.bin_scale = row.empty() ? 0.f : float(double(kBins) / upper);
       // (irs_hip_batch_set_comm) the bound every segment of the index computes alike
-      b->groups.upper[q] = (same_bound && !is_phrase && !row.empty() && upper_all > 0.0 &&
+      b->groups.upper[q] = (same_bound && !is_phrase && !wide && !row.empty() && upper_all > 0.0 &&
                            upper_all * (1.0 + 1e-6) >= upper && std::isfinite(upper_all))
                               ? upper_all * (1.0 + 1e-6)
                               : 0.0;
@@ -1009,19 +1036,21 @@ static int batch_create_multi_impl(irs_hip_segment* const* segs, uint32_t n_segs
           break;
         }
         // (grouped units score in floats, block driven: the flat units' accumulators are theirs)
-        if (!grouped && (!(min_score > 0.0) || upper / min_score > 1000.0)) b->acc32 = false;
+        // (wide units carry 64-bit sums of their own and never ask)
+        if (!grouped && !wide && (!(min_score > 0.0) || upper / min_score > 1000.0)) b->acc32 = false;
       }
       exps.push_back(e);
       b->qterms.insert(b->qterms.end(), row.begin(), row.end());
-      b->jt = std::max(b->jt, dq.n_terms);
+      if (!wide) b->jt = std::max(b->jt, dq.n_terms);   // (the plan table's term slots)
       b->k_max = std::max(b->k_max, in.k);
     }
     if (b->knobs.acc64) b->acc32 = false;   // tuning / test knob
     if (rc == IRS_HIP_OK) rc = build_masks(b);
     for (uint32_t q = 0; q < nq && rc == IRS_HIP_OK && q < exps.size(); ++q) {
       const int e = exps[q];
-      b->queries[q].fx_mul = std::ldexp(1.f, (b->acc32 ? 30 : 29) - e);
-      b->queries[q].fx_inv = std::ldexp(1.f, e - (b->acc32 ? 30 : 61));
+      const bool acc32 = b->acc32 && !unit_is_wide(b->queries[q]);
+      b->queries[q].fx_mul = std::ldexp(1.f, (acc32 ? 30 : 29) - e);
+      b->queries[q].fx_inv = std::ldexp(1.f, e - (acc32 ? 30 : 61));
     }
   } catch (...) {
     rc = IRS_HIP_ENOMEM;
@@ -1137,6 +1166,7 @@ static int batch_set_shared_threshold_impl(irs_hip_batch* b, int enable) {
 static int batch_set_comm_impl(irs_hip_batch* b, irs_hip_comm* comm) {
   if (!b) return IRS_HIP_EINVAL;
   if (b->opt) return IRS_HIP_EUNSUPPORTED;   // (optional terms: two passes, one rank)
+  if (b->wide.on()) return IRS_HIP_EUNSUPPORTED;   // (wide units keep thresholds of their own)
   if (!rt::set_device(b->seg->device)) return IRS_HIP_EHIP;
   if (!quiesce(b)) return IRS_HIP_EHIP;
   if (comm && !b->groups.d_agree.p && !b->groups.d_agree.alloc(64)) return IRS_HIP_ENOMEM;
@@ -1214,6 +1244,8 @@ static int batch_set_doc_sets_impl(irs_hip_batch* b, const void* sets, bool host
   if (!b) return IRS_HIP_EINVAL;
   // (optional terms: the term pass's doc sets are the phrase pass's output)
   if (b->opt) return IRS_HIP_EUNSUPPORTED;
+  // (wide units read the streams every unit shares: a mask of their own cannot ride there)
+  if (b->wide.on()) return IRS_HIP_EUNSUPPORTED;
   if (!rt::set_device(b->seg->device)) return IRS_HIP_EHIP;
   std::vector<uint32_t> rows;
   if (row_of_unit && n_rows) {
@@ -1380,7 +1412,7 @@ static bool plan_stage(irs_hip_batch* b, rt::stream_t st) {
               b->d_first.as<uint32_t>(), b->d_tails.as<DevTail>());
     ok = rt::last_error_ok();
   }
-  if (ok && b->join.on()) ok = launch_join(b, st);
+  if (ok && streams_on(b)) ok = launch_join(b, st);
   if (ok && !b->phrase && !b->tiles.units.empty()) ok = launch_items(b, st);
   return ok && mark(2 * IRS_HIP_K_PLAN + 1);
 }
@@ -1473,7 +1505,7 @@ static int run_impl(irs_hip_batch* b, rt::stream_t st) {
   } else {
     ok = b->up.flush(st);
   }
-  if (ok && b->join.on() && !b->join.slack_zeroed) {
+  if (ok && streams_on(b) && !b->join.slack_zeroed) {
     // (the slack behind the last stream is only ever read by masked-off look-ahead: zero it once)
     ok = rt::dmemset(b->join.d_entries.as<uint32_t>() + b->join.entries, 0, kJoinSlack * 4, st);
     b->join.slack_zeroed = ok;
@@ -1486,7 +1518,7 @@ static int run_impl(irs_hip_batch* b, rt::stream_t st) {
   if (ok && b->excl.leads_counted)
     ok = (b->excl.d_leads.p || b->excl.d_leads.alloc(16)) && rt::dmemset(b->excl.d_leads.p, 0, 16, st);
   // (streams out of the device's cache that another stream is still filling)
-  if (b->join.on()) ok = ok && wait_for_streams(b, st);
+  if (streams_on(b)) ok = ok && wait_for_streams(b, st);
   // 1. plan (already queued by irs_hip_batch_plan: wait for it instead)
   const bool tiles = !b->phrase && !b->tiles.units.empty();
   if (b->sync.planned) {
@@ -1499,6 +1531,7 @@ static int run_impl(irs_hip_batch* b, rt::stream_t st) {
   ok = ok && mark(2 * IRS_HIP_K_PILOT);
   if (b->groups.n) ok = ok && rt::dmemset(b->groups.d_hist.p, 0, b->groups.d_hist.n, st);
   if (b->join.on()) ok = ok && launch_join_pilot(b, st);
+  if (b->wide.on()) ok = ok && launch_wide_pilot(b, st);
   ok = ok && launch_group_threshold(b, st);
   if (tiles)
     ok = ok && with_tile_kernel(b, [&](auto k) { return launch_pilot(b, st, k); });
@@ -1510,6 +1543,7 @@ static int run_impl(irs_hip_batch* b, rt::stream_t st) {
   else if (tiles)
     ok = ok && with_tile_kernel(b, [&](auto k) { return launch_score(b, st, k); });
   if (b->join.on()) ok = ok && launch_join_score(b, st);
+  if (b->wide.on()) ok = ok && launch_wide_score(b, st);
   if (!b->phrase) ok = ok && (simd ? launch_conj<kSimd4>(b, st) : launch_conj<kScalar>(b, st));
   if (!b->phrase) ok = ok && (simd ? launch_any<kSimd4>(b, st) : launch_any<kScalar>(b, st));
   ok = ok && mark(2 * IRS_HIP_K_SCORE + 1);
@@ -2040,8 +2074,15 @@ int irs_hip_device_stream_cache_stats(int32_t device, irs_hip_stream_cache_stats
 int irs_hip_batch_stream_counts(irs_hip_batch* b, uint32_t* distinct, uint32_t* decoded) {
   return settled(b, [&]() -> int {
     if (!b || !b->ran) return IRS_HIP_EINVAL;
-    if (distinct) *distinct = b->join.on() ? b->join.n_streams : 0u;
-    if (decoded) *decoded = b->join.on() ? b->join.decoded_last : 0u;
+    if (distinct) *distinct = streams_on(b) ? b->join.n_streams : 0u;
+    if (decoded) *decoded = streams_on(b) ? b->join.decoded_last : 0u;
+    return IRS_HIP_OK;
+  });
+}
+int irs_hip_batch_wide_units(irs_hip_batch* b, uint32_t* units) {
+  return settled(b, [&]() -> int {
+    if (!b || !units) return IRS_HIP_EINVAL;
+    *units = uint32_t(b->wide.units.size());
     return IRS_HIP_OK;
   });
 }
@@ -2162,11 +2203,15 @@ int irs_hip_batch_doc_set_stats(irs_hip_batch* b, uint64_t* tiles, uint64_t* til
   return settled(b, [&] { return batch_doc_set_stats_impl(b, tiles, tiles_skipped, leads, leads_skipped); });
 }
 int irs_hip_batch_match_sets(irs_hip_batch* b, uint64_t* sets, uint64_t n_words, uint64_t* counts) {
-  return settled(b, [&] { return batch_match_sets_impl(b, sets, nullptr, n_words, counts, nullptr, nullptr, false); });
+  return settled(b, [&] {
+    if (b && b->wide.on()) return int(IRS_HIP_EUNSUPPORTED);   // (plan_match.h: 16 rows per unit)
+    return batch_match_sets_impl(b, sets, nullptr, n_words, counts, nullptr, nullptr, false);
+  });
 }
 int irs_hip_batch_match_sets_to_device(irs_hip_batch* b, void* d_sets, uint64_t n_words, void* d_counts,
                                        void* stream) {
   return settled(b, [&] {
+    if (b && b->wide.on()) return int(IRS_HIP_EUNSUPPORTED);
     return batch_match_sets_impl(b, nullptr, d_sets, n_words, nullptr, d_counts,
                                  static_cast<rt::stream_t>(stream), true);
   });

@@ -135,6 +135,10 @@ void abandon_fills(irs_hip_batch* b) {
 
 bool join_half_ok(const irs_hip_batch* b);
 
+// Does the batch read decoded streams at all: units on joined streams, or wide multi-term units
+// (wide.h: their terms are streams of the same set)
+bool streams_on(const irs_hip_batch* b) { return b->join.on() || b->wide.on(); }
+
 // The batch's distinct (segment, term) streams, k_join's work list and the per-(unit, term)
 // records of k_join_score.  Static per batch: built once.  Every stream is looked up in the
 // device's stream cache (stream_cache.h): a hit costs no k_join work, a miss is decoded once into
@@ -155,14 +159,17 @@ bool build_streams(irs_hip_batch* b) {
   std::vector<Sig> sigs;
   std::vector<uint32_t> stream_of(b->qterms.size(), 0xFFFFFFFFu);
   std::vector<uint8_t> stream_sig;
+  // (the joined units' terms first: a batch's streams come out as they do without wide units)
+  std::vector<uint32_t> readers(b->join.units);
+  readers.insert(readers.end(), b->wide.units.begin(), b->wide.units.end());
   {
     size_t slots = 64;
     size_t n_keys = 0;
-    for (uint32_t u : b->join.units) n_keys += b->queries[u].n_terms;
+    for (uint32_t u : readers) n_keys += b->queries[u].n_terms;
     while (slots < 2 * n_keys + 2) slots <<= 1;
     std::vector<uint64_t> hkey(slots, ~0ull);
     std::vector<uint32_t> hval(slots, 0);
-    for (uint32_t u : b->join.units) {
+    for (uint32_t u : readers) {
       const DevQuery& dq = b->queries[u];
       for (uint32_t j = 0; j < dq.n_terms; ++j) {
         const DevQTerm& qt = b->qterms[dq.first_term + j];
@@ -347,8 +354,8 @@ bool build_streams(irs_hip_batch* b) {
       !b->join.d_wgs.alloc(std::max<size_t>(1, wgs.size()) * sizeof(JoinWg)) ||
       !b->join.d_jterms.alloc(jterms.size() * sizeof(JoinTerm)) ||
       !b->join.d_args.alloc(2 * sizeof(JoinArgs)) ||
-      !b->join.d_units.alloc(b->join.units.size() * 4) ||
-      !b->join.d_order.alloc(b->join.units.size() * 4))
+      !b->join.d_units.alloc(std::max<size_t>(1, b->join.units.size()) * 4) ||
+      !b->join.d_order.alloc(std::max<size_t>(1, b->join.units.size()) * 4))
     return false;
   // k_join_score's queues (JoinArgs): per launch — the plain disjunctions, then the units with
   // match counts — the units sorted by (segment, heaviest term) and cut into kJoinQueues runs of
@@ -664,7 +671,7 @@ bool build_streams(irs_hip_batch* b) {
     w.pad2 = 0;
   }
   lap("  streams: per-term records");
-  for (uint32_t u : b->join.units) {
+  for (uint32_t u : readers) {   // (a wide unit's cs carries its own 64-bit scale: DevQuery::fx_mul)
     DevQuery& dq = b->queries[u];
     const uint32_t rows = table_rows(dq.n_caches);
     for (uint32_t j = 0; j < dq.n_terms; ++j) {
@@ -680,6 +687,7 @@ bool build_streams(irs_hip_batch* b) {
       const bool general = qt.pad1 >= rows;
       jt.mode = (qt.cache_id * rows * 1024u) |
                 (general ? kJoinGeneral | (sqrt_kind(qt.kind) ? kJoinSqrt : 0u) : 0u);
+      if (qt.kind == kBM1) jt.mode = kWideConst;   // (wide units only: joined units are of the table family)
     }
   }
   // (the slack behind the last stream is only ever read by masked-off look-ahead: zero it once)

@@ -9,6 +9,7 @@ turns statistics into per-term score functions.
   irs::TFIDF::collect         core/search/tfidf.cpp:263-278    -> TFIDF.collect
   by_term::prepare            core/search/term_filter.cpp:92-129 -> prepare()
   by_phrase (FixedPrepareCollect) core/search/phrase_filter.cpp:212-293 -> prepare()
+  by_terms::prepare           core/search/terms_filter.cpp:110-153 -> prepare()
   filter::prepared::execute   core/search/filter.hpp:52-78     -> SegmentReader.execute()
   utils/index-search.cpp:719-787 (heap over all segments)     -> Index.search()
 
@@ -25,7 +26,7 @@ from dataclasses import dataclass, field, replace
 import numpy as np
 
 from . import _lib
-from ._lib import (EXCLUDE, HIT, NO_TERM, OP_AND, OP_MINMATCH, OP_OR, OP_PHRASE, PHRASE_ALT, PHRASE_OPTIONAL, PHRASE_REQUIRED, QUERY, SCORE_BM1, SCORE_BM15, SCORE_BM25,
+from ._lib import (EXCLUDE, HIT, NO_TERM, OP_AND, OP_MINMATCH, OP_MULTITERM, OP_OR, OP_PHRASE, PHRASE_ALT, PHRASE_OPTIONAL, PHRASE_REQUIRED, QUERY, SCORE_BM1, SCORE_BM15, SCORE_BM25,
                    SCORE_TFIDF, SCORE_TFIDF_NORM, TERM_META, TERM_SCORER, SegmentDesc)
 
 f32 = np.float32
@@ -130,6 +131,32 @@ class And:
     min_match: int = 0
     merge: int = MERGE_SUM
     boost: float = 1.0
+
+
+@dataclass
+class by_terms:
+    """irs::by_terms (by_terms_options, terms_filter.cpp:110-153): a set of (term, boost) and
+    min_match, scored as MultiTermQuery::execute does (multiterm_query.cpp:114-181) — a doc matches
+    when at least `min_match` of the terms present in its segment hold it, its score is the sum of
+    the scores of the terms holding it.  `terms`: ordinals or (ordinal, boost) pairs, 1..64 of them
+    (IRS_HIP_OP_MULTITERM); `boost` multiplies into every term's.  The same term twice scores
+    twice."""
+    terms: list
+    min_match: int = 1
+    boost: float = 1.0
+
+    def pairs(self):
+        """[(ordinal, boost)]"""
+        return [(int(t[0]), float(t[1])) if isinstance(t, (tuple, list)) else (int(t), 1.0)
+                for t in self.terms]
+
+    def check(self):
+        n = len(self.terms)
+        if not 1 <= n <= _lib.MAX_WIDE_TERMS:
+            raise ValueError("by_terms takes 1..%d terms, not %d" % (_lib.MAX_WIDE_TERMS, n))
+        if not 1 <= int(self.min_match) <= n:
+            raise ValueError("by_terms: min_match is 1..%d (the number of terms), not %d" %
+                             (n, int(self.min_match)))
 
 
 @dataclass
@@ -632,6 +659,15 @@ def prepare_filters(filters, scorer, segment_stats, segs, k):
             tl.append(flt.term)
             bl.append(flt.boost)
             continue
+        if cls is by_terms:
+            flt.check()
+            pairs = flt.pairs()
+            ops[q], nts[q], mms[q], mgs[q] = OP_MULTITERM, len(pairs), int(flt.min_match), MERGE_SUM
+            tl += [t for t, _ in pairs]
+            bl += [tb if flt.boost == 1.0 else f32(f32(flt.boost) * f32(tb)) for _, tb in pairs]
+            if ol_any:
+                ol += [0] * len(pairs)
+            continue
         if isinstance(flt, by_phrase):
             if flt.variadic:
                 raise ValueError("variadic by_phrase (a part of several terms) is taken by "
@@ -968,6 +1004,13 @@ class QueryBatch:
                    "irs_hip_batch_stream_counts")
         return d.value, n.value
 
+    def wide_units(self) -> int:
+        """irs_hip_batch_wide_units: the batch's units of by_terms / wide expansion queries
+        (IRS_HIP_OP_MULTITERM), (segment, query) pairs."""
+        n = C.c_uint32()
+        _lib.check(self.L, self.L.irs_hip_batch_wide_units(self.handle, C.byref(n)), "irs_hip_batch_wide_units")
+        return n.value
+
     def image_counts(self):
         """(distinct bound images the paired launch reads, images the last run made itself):
         irs_hip_batch_image_counts; (0, 0) for a batch that does not pair."""
@@ -1140,6 +1183,17 @@ def prepare(filters, scorer, segment_stats, required_terms=False, optional_terms
             p = prepare([flt], scorer, segment_stats, required_terms, optional_terms)[0]
             p.excluded = [int(t) for t in excluded]
             out.append(p)
+            continue
+        if isinstance(flt, by_terms):
+            # statistics per term exactly as for an Or of by_terms: the field's over the whole
+            # index, the term's summed over the segments that hold it
+            flt.check()
+            scorers = []
+            for t, tb in flt.pairs():
+                dwt = sum(int(st.docs_count[t]) for st in segment_stats if 0 <= t < len(st.docs_count))
+                stats = scorer.collect(dwf, dwt, ttf)
+                scorers.append(scorer.term_scorer(stats, tb if flt.boost == 1.0 else f32(f32(flt.boost) * f32(tb))))
+            out.append(PreparedQuery(OP_MULTITERM, [t for t, _ in flt.pairs()], scorers, int(flt.min_match)))
             continue
         if isinstance(flt, by_phrase) and flt.variadic:
             out.append(_prepare_variadic(flt, scorer, segment_stats, dwf, ttf))
@@ -1371,8 +1425,11 @@ def merge_topk_host(per_segment, k: int):
 #
 # On this path: the scored part is an ordinary Or of <= IRS_HIP_MAX_TERMS by_term filters — the
 # scored_terms_limit of the reference's benchmark (scripts/search-benchmark.sh:
-# --scored-terms-limit=16) fits — with a term absent from the segments where it is unscored; the
-# unscored part and the total are irs_hip_bit_union, as in the reference.
+# --scored-terms-limit=16) fits — with a term absent from the segments where it is unscored; with
+# more scored states, up to IRS_HIP_MAX_WIDE_TERMS (limits up to 64: ArangoSearch ships 128, the
+# reference's default is 1024, range_filter.hpp:58), it is one by_terms query with min_match 1
+# (IRS_HIP_OP_MULTITERM) over the same slots.  The unscored part and the total are
+# irs_hip_bit_union, as in the reference.
 
 def scored_states(visits_docs_counts, limit: int):
     """limited_sample_collector::collect over the segments' visits in order.
@@ -1446,7 +1503,7 @@ class PreparedExpansion:
     """One scored multi-term filter prepared against all segments."""
 
     def __init__(self, scored, scored_in, unscored_in, scorers, visited_in=None, slots=None,
-                 present=None, c0=None):
+                 present=None, c0=None, limit=None):
         self.scored = scored            # distinct scored term ordinals (query term slots)
         self.scored_in = scored_in      # [segment] -> set of scored ordinals there
         self._unscored_in = unscored_in  # (None: worked out from visited_in when asked for)
@@ -1455,6 +1512,7 @@ class PreparedExpansion:
         self.slots = slots              # `scored` as np.uint32
         self.present = present          # bool [segment][slot]: the slot's term is scored in the segment
         self.c0 = c0                    # float32 per slot (scorers[j][1])
+        self.limit = limit              # the scored_terms_limit it was prepared with (None: not known)
 
     @property
     def unscored_in(self):
@@ -1556,7 +1614,10 @@ def prepare_expansions(visits, limit, scorer, segment_stats, boost=1.0):
     """filter::prepare of scored multi-term filters: visits[q][s] = term ordinals the filter's
     visitor yields in segment s (ascending term order, as term_reader::iterator() enumerates).
     The statistics of all scored terms of all filters are worked out at once (numpy), value for
-    value what scorer.collect / term_scorer yield one term at a time."""
+    value what scorer.collect / term_scorer yield one term at a time.  `limit` (scored_terms_limit):
+    the scored states of a filter are at most `limit` query term slots.  Limits up to 64 are taken
+    (expansion_arrays); a filter prepared with a larger one is what it always was — an Or of all its
+    slots, which batch create refuses beyond IRS_HIP_MAX_TERMS."""
     dwf = sum(s.docs_with_field for s in segment_stats)
     ttf = sum(s.total_term_freq for s in segment_stats)
     dcs = [np.asarray(st.docs_count) for st in segment_stats]
@@ -1617,20 +1678,25 @@ def prepare_expansions(visits, limit, scorer, segment_stats, boost=1.0):
         else:
             present = np.array([[t in sc for t in slot_list] for sc in scored_in], bool).reshape(n_segs, n)
         out.append(PreparedExpansion(slot_list, scored_in, unscored_in,
-                                     [(kind, x, nc, nl) for x in mine], visited_in, slots, present, mine))
+                                     [(kind, x, nc, nl) for x in mine], visited_in, slots, present, mine,
+                                     limit))
     return out
 
 
 def expansion_arrays(segs, prepared, k):
     """The scored parts of a list of prepared expansions as ONE batch: an Or per filter whose term
-    slots are absent (NO_TERM) in the segments where the term is unscored.  Filters without any
-    scored term get a one-slot query of an absent term (matches nothing)."""
+    slots are absent (NO_TERM) in the segments where the term is unscored — a by_terms query with
+    min_match 1 (OP_MULTITERM) where a filter prepared with a limit of up to 64 has more than
+    IRS_HIP_MAX_TERMS slots.  Filters
+    without any scored term get a one-slot query of an absent term (matches nothing)."""
     n_segs, nq = len(segs), len(prepared)
     n_slots = np.fromiter((max(1, len(p.scored)) for p in prepared), np.int64, nq)
     first = np.cumsum(n_slots) - n_slots
     n_entries = int(n_slots.sum())
     queries = np.zeros(nq, QUERY)
     queries["op"], queries["n_terms"], queries["first_term"] = OP_OR, n_slots, first
+    taken = np.fromiter((p.limit is None or p.limit <= _lib.MAX_WIDE_TERMS for p in prepared), bool, nq)
+    queries["op"][(n_slots > _lib.MAX_TERMS) & (n_slots <= _lib.MAX_WIDE_TERMS) & taken] = OP_MULTITERM
     queries["k"], queries["min_match"], queries["merge"] = int(k), 1, MERGE_SUM
     terms = np.zeros((n_segs, n_entries), TERM_SCORER)
     terms["term"] = NO_TERM                      # (also the one slot of a filter without scored terms)

@@ -18,7 +18,11 @@ turns (category, text) into a filter:
                                                 index-search.cpp:363-399: search.prepare_expansions /
                                                 execute_expansions) or, without scorers, ONE
                                                 bit_union
-  Fuzzy1 / Fuzzy2 / *NGram                      not on this path
+  Fuzzy1 / Fuzzy2                               by_edit_distance: the term visit is not on this
+                                                path; what it ends in — a scored disjunction of
+                                                max_terms = 50 boosted terms (index-search.cpp:413)
+                                                — is search.by_terms (IRS_HIP_OP_MULTITERM)
+  *NGram                                        not on this path
 
 The synthetic index has ranks, not words.  A task's words carry their document frequency in the
 reference's benchmark index (`# freq=541190`, Wikipedia lines, 5 M docs in

@@ -11,7 +11,9 @@ boolean round also runs the filters with 0-2 excluded terms each (And(filter, No
 every phrase round also runs variadic phrases (parts of several terms) and phrases with required
 terms (And([by_phrase, by_term...])) or optional terms (Or([by_phrase, by_term...])); every boolean
 round runs
-Ands of Or groups (with exclusions, wand on and off; every third over two segments in one batch).
+Ands of Or groups (with exclusions, wand on and off; every third over two segments in one batch)
+and by_terms queries of 17..64 entries (IRS_HIP_OP_MULTITERM) mixed into a batch of the round's
+ordinary filters.
 With --doc-sets every round also restricts a random subset of its units to random doc sets
 (irs_hip_batch_set_doc_sets) at densities 0, 0.001, 0.5 and 1, on a path picked at random, and
 compares each against the oracle's run on the segment with the set's complement deleted as well.
@@ -178,6 +180,47 @@ def grouped_round(sr, seg, scorer, k, st, rng, max_rank, term, merge, multi, L):
     return len(filters)
 
 
+def wide_round(sr, seg, filters, scorer, k, st, rng, max_rank):
+    """by_terms of 17..64 entries (frequent, rare and absent ranks, boosts with zeros, any
+    min_match) interleaved with some of the round's ordinary filters: the wide ones against the
+    oracle (tests/test_multiterm.py), the ordinary ones bit for bit what a batch without them gives."""
+    import test_multiterm as tm
+    from iresearch_amd import _lib, search
+    from iresearch_amd.search import by_terms
+    wide = []
+    for _ in range(6):
+        n = int(rng.integers(17, 65))
+        hi = int(rng.choice([min(64, max_rank), max_rank, max_rank + 20]))
+        ent = [(int(rng.integers(0, hi)), float(rng.choice([1.0, 1.0, 0.25, 0.5, 2.0, 4.0, 0.0]))) for _ in range(n)]
+        mm = int(rng.choice([1, 1, 2, int(rng.integers(1, n + 1))]))
+        wide.append(by_terms(ent, mm, boost=float(rng.choice([1.0, 1.0, 1.5]))))
+    mixed = []
+    for i, w in enumerate(wide):
+        mixed += [w] + filters[i:i + 1]
+    path = int(rng.choice([_lib.PATH_AUTO, _lib.PATH_ITEMS, _lib.PATH_JOINED]))
+    try:
+        b = sr.batch(search.prepare(mixed, scorer, st), k).set_path(path)
+    except _lib.IrsHipError as e:   # (a frequency above 255 in one of the lists: not on this path)
+        assert e.status == _lib.EUNSUPPORTED, e
+        return 0
+    if rng.integers(0, 3) == 0:
+        b.configure(cand_cap=max(k, 64))
+    h, c, t = (x.copy() for x in b.run().results())
+    assert b.wide_units() == len(wide)
+    b.close()
+    plain = [f for f in mixed if not isinstance(f, by_terms)]
+    if plain:
+        pb = sr.batch(search.prepare(plain, scorer, st), k).set_path(path)
+        ph, pc, pt = pb.run().results()
+        at = [i for i, f in enumerate(mixed) if not isinstance(f, by_terms)]
+        assert np.array_equal(h[at], ph) and np.array_equal(c[at], pc) and np.array_equal(t[at], pt), "mixed batch"
+        pb.close()
+    for q, f in enumerate(mixed):
+        if isinstance(f, by_terms):
+            tm.check(f, k, h[q], c[q], t[q], *tm.expected(seg, f, scorer))
+    return len(mixed)
+
+
 def match_round(b, seg, filters, totals, excl=None):
     """Unscored execution of the same batch (irs_hip_batch_match_sets): every unit's set bit for bit
     against the oracle (tests/test_match_sets.py want_set), the counts against the scored totals.
@@ -334,6 +377,7 @@ def main():
                 excl_round(sr, seg, filters, scorer, k, st, rng, max_rank)
             # And of Or groups (k_conj_any), every round; over two segments every third
             queries += grouped_round(sr, seg, scorer, k, st, rng, max_rank, term, merge, rounds % 3 == 2, L)
+            queries += wide_round(sr, seg, filters, scorer, k, st, rng, max_rank)
             if rounds % 3 == 0:   # the same results through page-locked host memory, a run later
                 hh, hc, ht = b.run().results_to_host().host_results()
                 assert np.array_equal(hc, counts) and np.array_equal(ht, totals), "host results: counts"

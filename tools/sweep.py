@@ -23,11 +23,15 @@ def main():
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--configs", default="4096:16")
     ap.add_argument("--nocheck", action="store_true")
-    ap.add_argument("--op", default="or", choices=["or", "and", "mm", "phrase"],
-                    help="Or / And / Or(min_match=terms-1) / by_phrase of --terms consecutive words")
+    ap.add_argument("--op", default="or", choices=["or", "and", "mm", "phrase", "terms"],
+                    help="Or / And / Or(min_match=terms-1) / by_phrase of --terms consecutive words / "
+                         "by_terms of --terms terms with --min-match (IRS_HIP_OP_MULTITERM, up to 64 terms)")
     ap.add_argument("--lo-rank", type=int, default=16)
     ap.add_argument("--hi-rank", type=int, default=4096)
-    ap.add_argument("--terms", type=int, default=8)
+    ap.add_argument("--terms", default="8",
+                    help="terms per query; --op terms and --op or take a comma list (17,32,50,64): each is "
+                         "timed on the same index, one line per count, then exits")
+    ap.add_argument("--min-match", type=int, default=1, help="--op terms: by_terms_options::min_match")
     ap.add_argument("--layout", type=int, default=1, help="0 = scalar (1_5), 1 = simd4 (1_5simd)")
     ap.add_argument("--scorer", default="bm25", choices=["bm25", "tfidf", "bm15"])
     ap.add_argument("--lib", default=None, help="alternative build of libirs_hip.so (A/B runs)")
@@ -71,10 +75,14 @@ def main():
                          "statistics printed next to them come from the timed runs (tiles) and from one more, "
                          "untimed counting run (lead pieces) (--op or | and | mm | phrase)")
     args = ap.parse_args()
+    term_counts = [int(x) for x in str(args.terms).split(",")]
+    args.terms = term_counts[0]
+    if (args.op == "terms" or len(term_counts) > 1) and args.op not in ("terms", "or"):
+        raise SystemExit("--terms takes a list with --op terms or --op or")
     import torch
 
     from iresearch_amd import _lib, search, synth
-    from iresearch_amd.search import BM25, TFIDF, And, Not, Or, by_phrase, by_term
+    from iresearch_amd.search import BM25, TFIDF, And, Not, Or, by_phrase, by_term, by_terms
     L = _lib.bind(ctypes.CDLL(args.lib)) if args.lib else _lib.lib()
     t0 = time.perf_counter()
     kw = dict(topic_docs=4096, topic_percent=85, topic_terms=12) if args.clustered else {}
@@ -99,6 +107,37 @@ def main():
     scorer = {"bm25": BM25(), "tfidf": TFIDF(True), "bm15": BM25(1.2, 0.0)}[args.scorer]
     st = search.SegmentStats(seg.docs_with_field, seg.total_term_freq,
                              np.asarray(seg.metas["docs_count"]))
+    if args.op == "terms" or len(term_counts) > 1:
+        # one line per term count: by_terms on the wide kernels (k_wide_pilot / k_wide_score in the
+        # pilot / score stages) or the Or of as many by_terms on the paths it takes today
+        tile, stride = (int(x) for x in args.configs.split(",")[0].split(":"))
+        paths = {"auto": _lib.PATH_AUTO, "items": _lib.PATH_ITEMS, "joined": _lib.PATH_JOINED}
+        for n in term_counts:
+            rows = synth.make_queries(args.queries, n, args.lo_rank, args.hi_rank, synth.SEED + 2)
+            if args.op == "terms":
+                fl = [by_terms([int(r) - 1 for r in row], min(args.min_match, n)) for row in rows]
+            else:
+                fl = [Or([by_term(int(r) - 1) for r in row]) for row in rows]
+            b = sr.batch(search.prepare(fl, scorer, [st]), args.k).configure(0 if args.op == "terms" else tile, stride, 0)
+            b.set_path(paths[args.path]).profile(True)
+            b.run()
+            _, _, totals = b.results()
+            ms = []
+            t0 = time.perf_counter()
+            for _ in range(args.steps):
+                b.run()
+                ms.append(b.timings())
+            dt = (time.perf_counter() - t0) / args.steps
+            avg = np.mean(ms, axis=0)
+            alg, post = b.work()
+            print("%s terms=%d%s  %s  step %.2f ms  plan %.2f pilot %.2f score %.2f select %.2f  %.1f M postings  "
+                  "streams (distinct, decoded) %s  hits/query mean %.0f  reruns=%d" % (
+                      args.op, n, " min_match=%d" % min(args.min_match, n) if args.op == "terms" else "",
+                      "wide units %d" % b.wide_units() if args.op == "terms" else
+                      "path %s" % ("joined" if b.path() == _lib.PATH_JOINED else "items"),
+                      dt * 1e3, *avg, post / 1e6, b.stream_counts(), float(np.mean(totals)), b.reruns()), flush=True)
+            b.close()
+        sys.exit(0)
     plain_prep = None
     if args.exclude:
         rng = np.random.default_rng(synth.SEED + 3)

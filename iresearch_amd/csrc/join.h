@@ -36,6 +36,7 @@
 // decoding only the blocks the rarest term's docs fall into (irs_hip.hip unit_joinable).
 #pragma once
 #include "score.h"
+#include "wave_join.h"
 
 namespace irs_hip {
 
@@ -697,6 +698,26 @@ __device__ __forceinline__ void join_run(const unsigned char* lds, uint64_t base
   }
 }
 
+// PAIRED TILES: the four slabs from `base` (wave-uniform, 256-byte aligned) on: one per-lane
+// offset, the slab in the instruction's immediate field — no clamp, no address arithmetic per
+// load.  A group of n < 4 slabs leaves 4 - n of them unused; what they read is readable whatever
+// n is: further slabs of the same piece (this wavefront's or its neighbour's share), the image's
+// next piece, the next image of the cache slab or private buffer, or the kJoinSlack entries
+// behind the last one; and kJoinSafeBytes at `safe` for the request of a share that is through.
+constexpr uint32_t kJoinSafeBytes = 4u * 256u;   // what a request reads, whatever it is used for
+static_assert(kJoinSlack * 4u >= kJoinSafeBytes, "a request behind the last image stays inside the slack");
+// `off` = lane * 4, the caller's ONE copy of it, handed through every request: the empty statement
+// redefines it in place, so that its extension to 64 bits stays next to the loads instead of being
+// hoisted out of the loops as a register pair — only then does instruction selection see
+// base + offset + immediate, and no copy is made because the old value is dead.
+__device__ __forceinline__ void join_load4(uint64_t base, uint32_t& off, uint32_t (&x)[4]) {
+  wave::keep(off);
+  x[0] = wave::gload_u32_imm<0u>(base, off);
+  x[1] = wave::gload_u32_imm<256u>(base, off);
+  x[2] = wave::gload_u32_imm<512u>(base, off);
+  x[3] = wave::gload_u32_imm<768u>(base, off);
+}
+
 // A wavefront's share of one tile.  The entries of the query's terms in the tile, term after
 // term, are one sequence of N entries; wavefront w of nw takes [N*w/nw, N*(w+1)/nw) — a
 // contiguous piece that touches one or two terms, rarely more.  begin() intersects that piece
@@ -719,12 +740,13 @@ struct JoinRun {
 
 // a = first entry of term j in the tile (index into its stream), n = its entries there,
 // c = inclusive prefix sum of n over the terms (lanes beyond the query's terms: n = 0).
-// Always issues exactly four loads (to `safe`, any readable address, when the share is empty;
-// lanes past the end re-read the share's last entry): two runs are in flight at a time — the
-// next tile's and the one after — and only a FIXED number of younger loads lets the wait for
-// the older run's data leave the younger one's in flight (s_waitcnt vmcnt(4)).
+// Always issues exactly four loads (to `safe`, kJoinSafeBytes readable bytes, when the share is
+// empty; lanes past the end re-read the share's last entry — paired tiles: the caller does, with
+// join_load4): two runs are in flight at a time — the next tile's and the one after — and only a
+// FIXED number of younger loads lets the wait for the older run's data leave the younger one's in
+// flight (s_waitcnt vmcnt(4)).
 template<int M>
-__device__ __forceinline__ void join_begin(JoinRun& r, const JoinLane& T, uint32_t a, uint32_t n,
+__device__ __forceinline__ uint64_t join_begin(JoinRun& r, const JoinLane& T, uint32_t a, uint32_t n,
                                            uint32_t c, uint32_t wv, uint32_t nw_log2,
                                            uint64_t safe, unsigned lane) {
   const uint32_t N = wave::read_lane(c, ((M & kJHalf) ? 2u * kMaxTerms : kMaxTerms) - 1u);
@@ -761,19 +783,14 @@ __device__ __forceinline__ void join_begin(JoinRun& r, const JoinLane& T, uint32
   }
   r.pre = take;
   r.mask = mask;
-  if (M & kJHalf) {   // slabs past the share's re-read its last one (an empty share: 256 bytes at `safe`)
-    const uint32_t top = take ? take - 1u : 0u;
-#pragma unroll
-    for (uint32_t k = 0; k < 4u; ++k)
-      r.e[k] = wave::gload_u32(base, lane * 4u + 256u * (k < top ? k : top));
-    return;
-  }
+  if (M & kJHalf) return base;   // (the caller requests the four slabs from `base` on: join_load4)
   const uint32_t last = take ? (take - 1u) * 4u : 0u;
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
     const uint32_t off = lane * 4u + 256u * uint32_t(k);
     r.e[k] = wave::gload_u32(base, off < last ? off : last);
   }
+  return base;
 }
 
 template<int M>
@@ -833,12 +850,12 @@ __device__ __forceinline__ void join_finish(const unsigned char* lds, JoinRun& r
 // workgroup stand behind the same barrier), so group n + 1 is REQUESTED BEFORE THE WAIT for group
 // n — whether n is the prefetched group, the last full group in front of a tail, or the last group
 // of a piece, whose successor opens the next piece.  What makes that possible: every group is
-// exactly four loads per lane (a slab past the group's last re-reads the last: no traffic, never
-// used), so the number of loads between a request and its use is a compile-time constant and the
-// wait is s_waitcnt vmcnt(4), not vmcnt(0); and the groups alternate between two NAMED register
-// sets (the loop is unrolled by two), so no entry is copied from one set to the other — a copy is
-// a use, and would wait for the younger group.  No lane of a slab is without an entry (padding
-// entries carry their own dummy word): no per-lane count, no select.
+// exactly four loads per lane (the four slabs from its first on — a slab past its last is read and
+// never used: join_load4), so the number of loads between a request and its use is a compile-time
+// constant and the wait is s_waitcnt vmcnt(4), not vmcnt(0); and the groups alternate between two
+// NAMED register sets (the loop is unrolled by two), so no entry is copied from one set to the
+// other — a copy is a use, and would wait for the younger group.  No lane of a slab is without an
+// entry (padding entries carry their own dummy word): no per-lane count, no select.
 constexpr uint32_t kJoinPreSlabs = kJoinPre / kJoinSlab;
 static_assert(kJoinPreSlabs == 4u, "a group is four loads");
 struct JoinGroup {   // (wave-uniform) the descriptor of a group
@@ -854,8 +871,8 @@ struct JoinSeq {     // (wave-uniform) what is left of a share behind the groups
   float cs;          // of the current piece
   uint32_t mode;
 };
-// the next group of the sequence; false: the share is through — the descriptor is then one slab
-// at `safe` (join_begin's empty share), for a request that nobody uses
+// the next group of the sequence; false: the share is through — the descriptor is then `safe`
+// (join_begin's empty share), for a request that nobody uses
 template<int M>
 __device__ __forceinline__ bool join_next(JoinSeq& s, const JoinRun& r, const JoinLane& T,
                                           uint64_t safe, JoinGroup& g) {
@@ -882,12 +899,9 @@ __device__ __forceinline__ bool join_next(JoinSeq& s, const JoinRun& r, const Jo
   s.left -= n;
   return more;
 }
-// four loads, always; clamped by slab: a slab past the group's last holds the last once more
-__device__ __forceinline__ void join_request(const JoinGroup& g, unsigned lane, uint32_t (&x)[4]) {
-  const uint32_t top = g.n - 1u;
-#pragma unroll
-  for (uint32_t k = 0; k < 4u; ++k)
-    x[k] = wave::gload_u32(g.base, lane * 4u + 256u * (k < top ? k : top));
+// four loads, always, of the kJoinPreSlabs slabs from the group's first on: join_load4
+__device__ __forceinline__ void join_request(const JoinGroup& g, uint32_t& lane4, uint32_t (&x)[4]) {
+  join_load4(g.base, lane4, x);
 }
 // THE CONTRIBUTION of a bound-image entry e (u: its low 16 bits) under the weight k = ceil(ks 2^16),
 // 1 <= k <= 32801 (ks = cs 2^-15 / U < 0.5005):  ((u k) >> 16) + 2, in the low half of the result
@@ -945,7 +959,7 @@ __device__ __forceinline__ void join_group_img(const unsigned char* lds, const u
 
 template<int M>
 __device__ __forceinline__ void join_finish_pairs(const unsigned char* lds, JoinRun& r,
-                                                  const JoinLane& T, uint64_t safe, unsigned lane) {
+                                                  const JoinLane& T, uint64_t safe, uint32_t& lane4) {
   static_assert(M == (kJHalf | kJSimple), "join_finish_pairs: paired tiles on bound images");
   // (the run's scalars crossed a barrier and a loop back edge inside a struct: join_finish)
   const uint32_t pre = wave::uniform(r.pre);
@@ -978,10 +992,10 @@ __device__ __forceinline__ void join_finish_pairs(const unsigned char* lds, Join
   bool more;
   do {
     const bool second = join_next<M>(s, r, T, safe, gb);
-    join_request(gb, lane, b);
+    join_request(gb, lane4, b);
     join_group_img(lds, a, ga);
     more = join_next<M>(s, r, T, safe, ga);   // (a share that is through stays through)
-    join_request(ga, lane, a);
+    join_request(ga, lane4, a);
     if (second) join_group_img(lds, b, gb);
   } while (more);
 }
@@ -1484,6 +1498,7 @@ __device__ __forceinline__ void join_pairs(unsigned char* smem, const JoinTileCt
   const unsigned lane = tid & 63u;
   const uint64_t safe = reinterpret_cast<uint64_t>(ctx.args->jterms);
   const uint32_t npair = (ntile + 1u) >> 1;
+  uint32_t lane4 = lane * 4u;   // every request's per-lane offset: join_load4
   auto begin = [&](uint32_t p, JoinRun& r) {   // (p >= npair: an empty share)
     uint32_t a = 0, n = 0, c = 0;
     if (lane < 2u * kMaxTerms && p < npair) {
@@ -1494,14 +1509,18 @@ __device__ __forceinline__ void join_pairs(unsigned char* smem, const JoinTileCt
       }
       c = cum[p * 2u * kMaxTerms + lane];
     }
-    join_begin<M>(r, T, a, n, c, wv, nw_log2, safe, lane);
+    join_load4(join_begin<M>(r, T, a, n, c, wv, nw_log2, safe, lane), lane4, r.e);
   };
   JoinRun r0, r1;
   begin(0, r0);
   begin(1, r1);
   const uint32_t thr = wave::uniform(ctx.thr);       // in 16-bit units, >= 1
   const uint32_t below = (thr - 1u) * 0x00010001u;   // both halves: the largest sum that is no candidate
-  uint32_t hits2 = 0;                                // matches per half (<= 16 per visit and lane)
+  // matches per half: a thread of the smallest workgroup (256) reads kJoinBoundTile / 256 words per
+  // visit, a chunk is at most kJoinChunkBound / 2 visits — neither half comes near 2^16, which is
+  // what count_nonzero_halves4_nc asks for
+  static_assert((kJoinBoundTile / 256u + 1u) * (kJoinChunkBound / 2u + 1u) < 65536u, "hits2: no carry");
+  uint32_t hits2 = 0;
   auto end_pair = [&](uint32_t p) {
     __syncthreads();   // B1: every accumulation of the pair has landed
     const uint32_t doc0 = kDocMin + (tile0 + 2u * p) * kJoinBoundTile;
@@ -1522,7 +1541,7 @@ __device__ __forceinline__ void join_pairs(unsigned char* smem, const JoinTileCt
       }
     };
     auto four = [&](uint32_t i, const uint32_t (&v)[4]) {
-      wave::count_nonzero_halves4(hits2, v[0], v[1], v[2], v[3]);
+      wave::count_nonzero_halves4_nc(hits2, v[0], v[1], v[2], v[3]);   // (no carry: see hits2)
       const uint32_t top = wave::pk_max_u16(wave::pk_max_u16(v[0], v[1]), wave::pk_max_u16(v[2], v[3]));
       if (wave::pk_max_u16(top, below) != below) {   // rare: some half reaches the threshold
 #pragma unroll
@@ -1541,10 +1560,10 @@ __device__ __forceinline__ void join_pairs(unsigned char* smem, const JoinTileCt
     __syncthreads();   // B2: accumulators are clear again
   };
   for (uint32_t p = 0; p < npair; p += 2u) {
-    join_finish_pairs<M>(smem, r0, T, safe, lane);
+    join_finish_pairs<M>(smem, r0, T, safe, lane4);
     begin(p + 2u, r0);
     end_pair(p);
-    join_finish_pairs<M>(smem, r1, T, safe, lane);
+    join_finish_pairs<M>(smem, r1, T, safe, lane4);
     begin(p + 3u, r1);
     if (p + 1u < npair) end_pair(p + 1u);
   }

@@ -630,9 +630,10 @@ bool build_streams(irs_hip_batch* b) {
     }
   }
   if (b->join.img_on) {
-    // (k_join_score<kJKHalf> reads one slab, 256 bytes, at the records' address for every request
-    // that nobody uses: join_next)
-    if (!b->join.d_jimgs.alloc(std::max<size_t>(1024, jimgs.size() * sizeof(JoinTerm))) ||
+    // (k_join_score<kJKHalf> reads kJoinSafeBytes at the records' address for every request that
+    // nobody uses: join_load4)
+    const size_t jimgs_bytes = std::max<size_t>(kJoinSafeBytes, jimgs.size() * sizeof(JoinTerm));
+    if (!b->join.d_jimgs.alloc(jimgs_bytes) || b->join.d_jimgs.n < kJoinSafeBytes ||
         !b->join.d_bwgs.alloc(std::max<size_t>(1, bwgs.size()) * sizeof(BoundWg)) ||
         !b->up.copy(b->join.d_jimgs.p, jimgs.data(), jimgs.size() * sizeof(JoinTerm)) ||
         (!bwgs.empty() && !b->up.copy(b->join.d_bwgs.p, bwgs.data(), bwgs.size() * sizeof(BoundWg))))

@@ -2,6 +2,12 @@
 // per path (work items in doc tiles, joined posting streams, wide multi-term units, block-driven
 // conjunctions and phrases),
 // for thresholds shared across segments and for a run's place on the streams.
+// The unit lists and who fills them (units.h: commit_unit is create's only writer per unit):
+//   all_tile_units, all_conj_units, wide.units   commit_unit, fixed at create
+//   blocks.units   a phrase batch: build_phrase_work at create; else deal_units, from all_conj_units
+//   any.units      build_any_work at create, from the grouped units commit_unit listed
+//   tiles.units, join.units   deal_units (ensure_scratch), from all_tile_units / all_conj_units
+//   excl.unit_terms / unit_first / unit_live   commit_unit; build_masks makes the masks from them
 // Included by irs_hip.hip (one translation unit).
 #pragma once
 

@@ -47,6 +47,7 @@ using namespace irs_hip;
 #include "plan_wide.h"
 #include "plan_join.h"
 #include "plan_match.h"
+#include "units.h"
 
 namespace {
 
@@ -132,7 +133,7 @@ bool size_units(irs_hip_batch* b, uint64_t* first_words, uint64_t* item_bound) {
       continue;
     }
     // (conjunctions are block driven unless they run as joined streams)
-    const bool tiled = !b->phrase && ((dq.op & 0xFF) != 2 || is_join[u]);
+    const bool tiled = !b->phrase && (query_run(dq.op) != kRunConj || is_join[u]);
     const uint32_t tile_docs = is_join[u] ? kJoinTile : b->tiles.docs;   // (streams are cut at kJoinTile)
     dq.n_tiles = tiled ? (b->segs[dq.seg]->dev.num_docs + tile_docs - 1) / tile_docs : 0u;
     if (b->phrase) dq.n_tiles = 1;
@@ -509,74 +510,40 @@ uint64_t irs_hip_segment_live_docs(const irs_hip_segment* seg) { return seg ? se
 
 // ----------------------------------------------------------------- batch --
 
-static int batch_create_multi_impl(irs_hip_segment* const* segs, uint32_t n_segs,
-                                   const irs_hip_query* queries, uint32_t nq_user,
-                                   const irs_hip_term_scorer* all_terms, uint32_t n_entries,
-                                   irs_hip_batch** out);
-static int batch_set_doc_sets_impl(irs_hip_batch* b, const void* sets, bool host, uint64_t n_rows,
-                                   uint64_t n_words, const uint32_t* row_of_unit);
-
-// The TERM PASS of a batch with optional terms (IRS_HIP_PHRASE_OPTIONAL; batch.h irs_hip_batch::opt):
-// a batch of its own over the same segments and queries — per query its optional entries as a plain
-// Or (the flag taken off, the IRS_HIP_EXCLUDE entries behind them; a query without optional entries:
-// one absent term, an empty unit) — whose units are restricted to the rows of b->d_taken, the doc
-// sets k_phrase_or takes the phrase's matches out of.  Masked units run as work items (k_items_*,
-// k_pilot, k_score) and never join streams.
-static int create_term_pass(irs_hip_batch* b, irs_hip_segment* const* segs, uint32_t n_segs,
-                            const irs_hip_query* queries, const irs_hip_term_scorer* all_terms,
-                            uint32_t n_entries) {
-  std::vector<irs_hip_query> cq(b->nq_user);
-  std::vector<uint32_t> from;   // the term pass's entries: their indices in the caller's, ~0u: the absent one
-  for (uint32_t q = 0; q < b->nq_user; ++q) {
-    const irs_hip_query& in = queries[q];
-    cq[q] = in;
-    cq[q].op = IRS_HIP_OP_OR;
-    cq[q].min_match = 1;
-    cq[q].first_term = uint32_t(from.size());
-    bool any = false;
-    for (uint32_t j = 0; j < in.n_terms; ++j) {
-      const int32_t kind = all_terms[in.first_term + j].kind;
-      const bool optional = kind != IRS_HIP_EXCLUDE && (kind & IRS_HIP_PHRASE_OPTIONAL) != 0;
-      if (optional || (any && kind == IRS_HIP_EXCLUDE)) from.push_back(in.first_term + j);
-      any = any || optional;
-    }
-    if (!any) from.push_back(~0u);
-    cq[q].n_terms = uint32_t(from.size()) - cq[q].first_term;
+// What create leaves on the device: the segments' records and the units' rows (d_queries goes out
+// from ensure_scratch, once the units' tile geometry is in)
+static int upload_create_tables(irs_hip_batch* b) {
+  if (b->jt == 0) b->jt = 1;
+  if (b->qterms.empty()) b->qterms.push_back(DevQTerm{});
+  std::vector<DevSegment> dsegs;
+  for (irs_hip_segment* sg : b->segs) {
+    // (another thread's batch may be adding the lazily built tables to `dev` right now)
+    std::lock_guard<std::mutex> lock(sg->wand_mutex);
+    dsegs.push_back(sg->dev);
   }
-  std::vector<irs_hip_term_scorer> ct(from.size() * n_segs);
-  for (uint32_t s = 0; s < n_segs; ++s) {
-    for (size_t i = 0; i < from.size(); ++i) {
-      irs_hip_term_scorer& t = ct[s * from.size() + i];
-      if (from[i] == ~0u) {
-        t = irs_hip_term_scorer{};
-        t.term = IRS_HIP_NO_TERM;
-        t.kind = IRS_HIP_SCORE_BM1;
-      } else {
-        t = all_terms[size_t(s) * n_entries + from[i]];
-        if (t.kind != IRS_HIP_EXCLUDE) t.kind &= ~IRS_HIP_PHRASE_OPTIONAL;
-        t.phrase_offset = 0;
-      }
-    }
-  }
-  if (const int rc = batch_create_multi_impl(segs, n_segs, cq.data(), b->nq_user, ct.data(),
-                                             uint32_t(from.size()), &b->opt))
-    return rc;
-  uint32_t max_docs = 0;
-  for (uint32_t s = 0; s < n_segs; ++s) max_docs = std::max(max_docs, segs[s]->dev.num_docs);
-  b->taken_words = uint64_t(max_docs) / 64u + 1u;
-  std::vector<uint32_t> row_of(b->nq);
-  for (uint32_t u = 0; u < b->nq; ++u) row_of[u] = u;
-  if (!b->d_taken.alloc(uint64_t(b->nq) * b->taken_words * 8u) ||
-      !b->d_union_out.alloc(uint64_t(b->nq) * b->k_max * sizeof(Hit)) ||
-      !b->d_union_count.alloc(uint64_t(b->nq) * 4u) || !b->d_union_hits.alloc(uint64_t(b->nq) * 8u))
+  if (!b->d_queries.alloc(b->queries.size() * sizeof(DevQuery)) ||
+      !b->d_qterms.alloc(b->qterms.size() * sizeof(DevQTerm)) ||
+      !b->d_segs.alloc(dsegs.size() * sizeof(DevSegment)) ||
+      !b->up.copy(b->d_segs.p, dsegs.data(), dsegs.size() * sizeof(DevSegment)) ||
+      !b->up.copy(b->d_qterms.p, b->qterms.data(), b->qterms.size() * sizeof(DevQTerm)))
     return IRS_HIP_ENOMEM;
-  return batch_set_doc_sets_impl(b->opt, b->d_taken.p, false, b->nq, b->taken_words, row_of.data());
+  return IRS_HIP_OK;
 }
 
+// A batch under construction: a failed create takes its term pass with it
+struct BatchDeleter {
+  void operator()(irs_hip_batch* b) const {
+    if (b->opt) irs_hip_batch_destroy(b->opt);
+    delete b;
+  }
+};
+
+// The steps of create (units.h; DESIGN.md "From queries to units").  Whatever it throws is a failed
+// allocation: IRS_HIP_ENOMEM.  *out stays null on every failure.
 static int batch_create_multi_impl(irs_hip_segment* const* segs, uint32_t n_segs,
                                const irs_hip_query* queries, uint32_t nq_user,
                                const irs_hip_term_scorer* all_terms, uint32_t n_entries,
-                               irs_hip_batch** out) {
+                               irs_hip_batch** out) try {
   if (!segs || !n_segs || !queries || !all_terms || !out || !nq_user) return IRS_HIP_EINVAL;
   HostTrace trace("batch_create (query records)");
   *out = nullptr;
@@ -589,522 +556,73 @@ static int batch_create_multi_impl(irs_hip_segment* const* segs, uint32_t n_segs
     if (segs[s]->dev.layout != segs[0]->dev.layout) return IRS_HIP_EUNSUPPORTED;
   }
   if (!rt::set_device(segs[0]->device)) return IRS_HIP_EHIP;
-  irs_hip_batch* b = new (std::nothrow) irs_hip_batch;
+  std::unique_ptr<irs_hip_batch, BatchDeleter> owner(new (std::nothrow) irs_hip_batch);
+  irs_hip_batch* b = owner.get();
   if (!b) return IRS_HIP_ENOMEM;
   b->seg = segs[0];
   b->knobs = Knobs::from_env();
   const uint32_t nq = n_segs * nq_user;
   b->nq = nq;
   b->nq_user = nq_user;
-  int rc = IRS_HIP_OK;
+  b->segs.assign(segs, segs + n_segs);
+  b->queries.resize(nq);
+  b->count_precise.assign(nq, 0);
+  b->groups.upper.assign(nq, 0.0);
+  b->blocks.opens.assign(nq, 0);
+  b->blocks.n_phrase.assign(nq, 0);
+  b->any.opens.assign(nq, 0);
+  b->qterms.reserve(size_t(n_entries) * n_segs);
+  b->excl.unit_first.assign(1, 0u);
+  b->excl.unit_live.assign(nq, 0);
   std::vector<uint32_t> grouped_units;   // units of grouped conjunctions (IRS_HIP_GROUP_ALT)
-  try {
-    b->segs.assign(segs, segs + n_segs);
-    b->queries.resize(nq);
-    b->count_precise.assign(nq, 0);
-    b->groups.upper.assign(nq, 0.0);
-    b->blocks.opens.assign(nq, 0);
-    b->blocks.n_phrase.assign(nq, 0);
-    b->any.opens.assign(nq, 0);
-    b->qterms.reserve(size_t(n_entries) * n_segs);
-    std::vector<int> exps;
-    exps.reserve(nq);
-    std::vector<DevQTerm> row;
-    std::vector<double> smins;
-    std::vector<uint32_t> excl;   // a unit's present excluded terms
-    b->excl.unit_first.assign(1, 0u);
-    b->excl.unit_live.assign(nq, 0);
-    std::vector<uint32_t> row_group;        // per present row of a grouped unit: its group
-    for (uint32_t q = 0; q < nq && rc == IRS_HIP_OK; ++q) {
-      // unit q = (segment q / nq_user, query q % nq_user); the segment's own term entries
-      irs_hip_segment* seg = segs[q / nq_user];
-      const irs_hip_term_scorer* terms = all_terms + size_t(q / nq_user) * n_entries;
-      const irs_hip_query& in = queries[q % nq_user];
-      if (uint64_t(in.first_term) + in.n_terms > n_entries) {
-        rc = IRS_HIP_EINVAL;
-        break;
-      }
-      // the included entries, then the excluded ones (IRS_HIP_EXCLUDE): n_incl of the n_terms
-      uint32_t n_incl = 0;
-      while (n_incl < in.n_terms && terms[in.first_term + n_incl].kind != IRS_HIP_EXCLUDE) ++n_incl;
-      const uint32_t n_excl = in.n_terms - n_incl;
-      // a variadic phrase (IRS_HIP_PHRASE_ALT members): up to IRS_HIP_MAX_PHRASE_ENTRIES entries
-      bool alt = false;
-      for (uint32_t j = 0; j < n_incl && in.op == IRS_HIP_OP_PHRASE; ++j)
-        alt = alt || (terms[in.first_term + j].kind & IRS_HIP_PHRASE_ALT) != 0;
-      if (alt && n_incl > IRS_HIP_MAX_PHRASE_ENTRIES) {
-        rc = IRS_HIP_EUNSUPPORTED;
-        break;
-      }
-      // a scored multi-term query (IRS_HIP_OP_MULTITERM, wide.h): up to IRS_HIP_MAX_WIDE_TERMS entries
-      const bool wide = in.op == IRS_HIP_OP_MULTITERM;
-      if ((in.op != IRS_HIP_OP_OR && in.op != IRS_HIP_OP_AND && in.op != IRS_HIP_OP_MINMATCH &&
-           in.op != IRS_HIP_OP_PHRASE && !wide) ||
-          n_incl == 0 || in.merge > IRS_HIP_MERGE_MIN ||
-          (in.op == IRS_HIP_OP_PHRASE && in.merge != IRS_HIP_MERGE_SUM) ||
-          (!wide && n_incl > IRS_HIP_MAX_TERMS) || n_excl > IRS_HIP_MAX_EXCLUDED || in.k == 0 || in.k > IRS_HIP_MAX_K) {
-        rc = IRS_HIP_EINVAL;
-        break;
-      }
-      if (wide) {
-        // (by_terms_options::min_match is 1..#terms for a posting-list query: 0 is the all-docs
-        // filter, terms_filter.cpp:119-123, more than the terms nothing, :125-128)
-        if (n_incl <= IRS_HIP_MAX_WIDE_TERMS && (in.min_match == 0 || in.min_match > n_incl)) rc = IRS_HIP_EINVAL;
-        else if (n_incl > IRS_HIP_MAX_WIDE_TERMS || n_excl || in.merge != IRS_HIP_MERGE_SUM) rc = IRS_HIP_EUNSUPPORTED;
-        if (rc != IRS_HIP_OK) break;
-      }
-      // a phrase with required terms (IRS_HIP_PHRASE_REQUIRED): the phrase's words (n_words, at
-      // least 2), then the by_term children of the And that holds it, nothing else behind them
-      // ... or with optional terms (IRS_HIP_PHRASE_OPTIONAL): the by_term children of the Or that
-      // holds it, in the same place; one query takes one of the two flags
-      uint32_t n_words = n_incl;
-      int32_t behind = 0;   // the flags of the entries behind the words
-      if (in.op == IRS_HIP_OP_PHRASE) {
-        constexpr int32_t kBehind = IRS_HIP_PHRASE_REQUIRED | IRS_HIP_PHRASE_OPTIONAL;
-        n_words = 0;
-        while (n_words < n_incl && !(terms[in.first_term + n_words].kind & kBehind)) ++n_words;
-        for (uint32_t j = n_words; j < n_incl; ++j) {
-          if (!(terms[in.first_term + j].kind & kBehind)) rc = IRS_HIP_EINVAL;
-          behind |= terms[in.first_term + j].kind & kBehind;
-        }
-        if (rc == IRS_HIP_OK && n_words < n_incl) {
-          uint32_t plain = 0;   // (members of a variadic part are no words of their own)
-          for (uint32_t j = 0; j < n_words; ++j)
-            plain += (terms[in.first_term + j].kind & IRS_HIP_PHRASE_ALT) ? 0u : 1u;
-          if (plain < 2) rc = IRS_HIP_EINVAL;
-          else if (alt || behind == kBehind || n_incl > IRS_HIP_MAX_PHRASE_TERMS) rc = IRS_HIP_EUNSUPPORTED;
-        }
-        if (rc != IRS_HIP_OK) break;
-      }
-      const bool with_req = behind == IRS_HIP_PHRASE_REQUIRED;
-      const bool with_opt = behind == IRS_HIP_PHRASE_OPTIONAL;
-      // a grouped conjunction: an And whose entries with IRS_HIP_GROUP_ALT are more members of the
-      // group (an Or of by_term) opened by the nearest entry before them without it
-      bool grouped = false;
-      for (uint32_t j = 0; j < n_incl && in.op == IRS_HIP_OP_AND; ++j)
-        grouped = grouped || (terms[in.first_term + j].kind & IRS_HIP_GROUP_ALT) != 0;
-      if (grouped && (terms[in.first_term].kind & IRS_HIP_GROUP_ALT)) {
-        rc = IRS_HIP_EINVAL;
-        break;
-      }
-      // excluded terms: the docs of those present here leave the unit's matches (exclusion.hpp); an
-      // absent one has no effect (boolean_query.cpp:131-134)
-      excl.clear();
-      for (uint32_t j = n_incl; j < in.n_terms && rc == IRS_HIP_OK; ++j) {
-        const irs_hip_term_scorer& ts = terms[in.first_term + j];
-        if (ts.kind != IRS_HIP_EXCLUDE || (ts.term != IRS_HIP_NO_TERM && ts.term >= seg->dev.num_terms))
-          rc = IRS_HIP_EINVAL;
-        else if (ts.term != IRS_HIP_NO_TERM && seg->terms[ts.term].docs_count)
-          excl.push_back(ts.term);
-      }
-      if (rc != IRS_HIP_OK) break;
-      const bool is_phrase = in.op == IRS_HIP_OP_PHRASE;
-      if (q == 0) b->phrase = is_phrase;
-      if (is_phrase != b->phrase) {  // a batch holds phrase queries only, or none
-        rc = IRS_HIP_EUNSUPPORTED;
-        break;
-      }
-      if (is_phrase) {
-        uint32_t n_parts = 0;
-        for (uint32_t j = 0; j < n_incl; ++j)
-          n_parts += (terms[in.first_term + j].kind & IRS_HIP_PHRASE_ALT) ? 0u : 1u;
-        if (n_parts > IRS_HIP_MAX_PHRASE_TERMS || (terms[in.first_term].kind & IRS_HIP_PHRASE_ALT) ||
-            terms[in.first_term].phrase_offset != 0) {
-          rc = IRS_HIP_EINVAL;
-          break;
-        }
-        if (!seg->dev.pos) {  // FixedPhraseQuery needs FREQ | POS (phrase_query.cpp:63-66)
-          rc = IRS_HIP_EUNSUPPORTED;
-          break;
-        }
-      }
-      row.clear();     // (one allocation for the whole batch: 8000 units otherwise pay 16000)
-      smins.clear();   // per present term: the smallest score of one posting
-      bool absent = false, same_bound = true;
-      double upper = 0.0, min_score = 1e300, upper_all = 0.0;
-      // phrase parts: entries [part_first, j) so far form the current one; bit r of `opens` = row r
-      // is the first present member of its part; `found` = the parts with a present member
-      // (a grouped conjunction: n_groups so far, `found` = the groups with a present member)
-      uint32_t n_parts = 0, part_first = 0, opens = 0, found = 0, n_groups = 0;
-      bool part_open = false;
-      row_group.clear();
-      uint32_t word_rows = 0;   // present rows that are phrase words (the required terms' follow)
-      for (uint32_t j = 0; j < n_incl; ++j) {
-        const irs_hip_term_scorer& ts = terms[in.first_term + j];
-        const bool member = is_phrase && (ts.kind & IRS_HIP_PHRASE_ALT) != 0;
-        const bool req = is_phrase && j >= n_words;   // (a required or an optional term)
-        const bool opt = req && with_opt;   // (no part of the phrase: absent, it is dropped)
-        const int32_t kind = is_phrase ? (ts.kind & ~(IRS_HIP_PHRASE_ALT | IRS_HIP_PHRASE_REQUIRED |
-                                                      IRS_HIP_PHRASE_OPTIONAL))
-                             : grouped ? (ts.kind & ~IRS_HIP_PHRASE_ALT) : ts.kind;
-        if (grouped && !(ts.kind & IRS_HIP_GROUP_ALT)) ++n_groups;
-        if (is_phrase && !member && !opt) {
-          ++n_parts;
-          part_first = j;
-          part_open = false;
-        } else if (member) {
-          // one more member of the part: at the part's offset, a term not yet in it
-          const irs_hip_term_scorer& head = terms[in.first_term + part_first];
-          if (ts.phrase_offset != head.phrase_offset) rc = IRS_HIP_EINVAL;
-          for (uint32_t x = part_first; x < j && ts.term != IRS_HIP_NO_TERM; ++x)
-            if (terms[in.first_term + x].term == ts.term) rc = IRS_HIP_EINVAL;
-          if (rc != IRS_HIP_OK) break;
-        }
-        DevQTerm qt{};
-        qt.term = ts.term;
-        qt.c0 = ts.c0;
-        qt.norm_const = ts.norm_const;
-        qt.norm_length = ts.norm_length;
-        qt.cache_id = kMaxCaches;
-        qt.pad0 = (is_phrase && !req) ? ts.phrase_offset : 0u;
-        if (ts.term != IRS_HIP_NO_TERM && ts.term >= seg->dev.num_terms) rc = IRS_HIP_EINVAL;
-        if (!(ts.c0 >= 0.f) || !std::isfinite(ts.c0)) rc = IRS_HIP_EINVAL;
-        if (rc != IRS_HIP_OK) break;
-        // (a zero boost is legal: every posting then scores 0 — the fixed-point accumulators
-        // still mark the doc as matched, and sums below kMaxTerms units come back as 0)
-        const bool norms = seg->dev.norms != nullptr;
-        const bool legacy = norms && seg->dev.norm_legacy;
-        switch (kind) {
-          case IRS_HIP_SCORE_BM25:
-            qt.kind = !norms ? kBM25One
-                      : legacy ? kBM25Legacy
-                               : (seg->dev.norm_width == 1 ? kBM25Tiny : kBM25Wide);
-            if (!(ts.norm_const + ts.norm_length > 0.f)) rc = IRS_HIP_EINVAL;
-            break;
-          case IRS_HIP_SCORE_BM15:
-            qt.kind = kBM15;
-            if (!(ts.norm_const > 0.f)) rc = IRS_HIP_EINVAL;
-            break;
-          case IRS_HIP_SCORE_BM1: qt.kind = kBM1; break;
-          case IRS_HIP_SCORE_TFIDF: qt.kind = kTfidf; break;
-          case IRS_HIP_SCORE_TFIDF_NORM:
-            qt.kind = !norms ? kTfidf
-                      : legacy ? kTfidfLegacy
-                               : (seg->dev.norm_width == 1 ? kTfidfTiny : kTfidfWide);
-            break;
-          default: rc = IRS_HIP_EINVAL;
-        }
-        if (rc != IRS_HIP_OK) break;
-        // (BM25 family: a posting scores below its boost c0 whatever the segment holds; the
-        // TF-IDF bound grows with the segment's largest frequency)
-        same_bound = same_bound && (kind == IRS_HIP_SCORE_BM25 || kind == IRS_HIP_SCORE_BM15 ||
-                                    kind == IRS_HIP_SCORE_BM1);
-        upper_all += double(ts.c0);
-        // TermQuery::execute: no term state in this segment -> empty iterator
-        // (term_query.cpp:41-43)
-        if (qt.term == IRS_HIP_NO_TERM || seg->terms[qt.term].docs_count == 0) {
-          // (a phrase / grouped conjunction: an absent member is dropped; a part / group without
-          // a present one is `absent`)
-          if (!is_phrase && !grouped) absent = true;
-          continue;
-        }
-        if (grouped) {
-          found |= 1u << (n_groups - 1u);
-          row_group.push_back(n_groups - 1u);
-        }
-        if (is_phrase && !opt) {
-          if (!part_open) opens |= 1u << row.size();
-          part_open = true;
-          found |= 1u << (n_parts - 1u);
-        }
-        const DevTerm& t = seg->terms[qt.term];
-        qt.pad1 = t.tf_bound;
-        {
-          // smallest score one posting of this term can have (tf = 1, longest doc)
-          const double c0 = qt.c0, nc = qt.norm_const, nl = qt.norm_length;
-          double smin = 0.0;
-          switch (qt.kind) {
-            case kBM1: smin = c0; break;
-            case kBM15: smin = c0 - c0 / (1.0 + 1.0 / nc); break;
-            case kBM25Tiny: smin = c0 - c0 / (1.0 + 1.0 / (nc + nl * 255.0)); break;
-            case kBM25One: smin = c0 - c0 / (1.0 + 1.0 / (nc + nl)); break;
-            case kTfidf: smin = c0; break;
-            case kTfidfTiny: smin = c0 / std::sqrt(255.0); break;
-            default: smin = 0.0;  // wide norms: unbounded below
-          }
-          min_score = std::min(min_score, smin);
-          smins.push_back(smin);
-        }
-        const bool tfidf = qt.kind == kTfidf || qt.kind == kTfidfTiny || qt.kind == kTfidfWide ||
-                           qt.kind == kTfidfLegacy;
-        // (a phrase's frequency is at most the sum of the tf_bound of its first part's members; the
-        // sum over every row of sqrt(tf_bound) bounds the square root of that, sqrt being subadditive)
-        upper += tfidf ? double(qt.c0) * std::sqrt(double(t.tf_bound)) : double(qt.c0);
-        b->postings += t.docs_count;
-        b->alg_bytes += uint64_t(t.blocks_bytes) + t.tail_bytes;
-        if (qt.kind == kBM25Tiny || qt.kind == kBM25Wide || qt.kind == kTfidfTiny ||
-            qt.kind == kTfidfWide || qt.kind == kBM25Legacy || qt.kind == kTfidfLegacy)
-          b->alg_bytes += uint64_t(t.docs_count) * seg->dev.norm_width;
-        row.push_back(qt);
-        if (!req) ++word_rows;
-      }
-      if (rc != IRS_HIP_OK) break;
-      b->alg_bytes += 8ull * in.k;
-      DevQuery& dq = b->queries[q];
-      dq.k = in.k;
-      dq.seg = q / nq_user;
-      // How many of the (present) terms a doc must match.  Or: 1.  And: all, and one absent
-      // term empties it (MakeScoreAdapters<true>, boolean_query.cpp:50-53).  MinMatch(m)
-      // (MinMatchQuery::execute, boolean_query.cpp:212-247): m > #sub-queries or m > #present
-      // -> empty; m == #present -> conjunction; m <= 1 -> disjunction; otherwise the
-      // min-match block disjunction: every matching term scores, docs with < m matches drop.
-      uint32_t need = 1;
-      if (in.op == IRS_HIP_OP_AND) {
-        // (a grouped one: a group without a present member empties it)
-        if (grouped) absent = found != (1u << n_groups) - 1u;
-        need = absent ? 0xFFu : uint32_t(row.size());
-      } else if (in.op == IRS_HIP_OP_MINMATCH) {
-        // Or::prepare turns min_match_count == 0 into the all-docs filter
-        // (boolean_filter.cpp:213): not a posting-list query, not on this path
-        if (in.min_match == 0) {
-          rc = IRS_HIP_EUNSUPPORTED;
-          break;
-        }
-        const uint32_t m = in.min_match;
-        need = (m > n_incl || m > row.size()) ? 0xFFu : m;
-      } else if (wide) {
-        // fewer than min_match present entries empty the query in this segment
-        // (MultiTermQuery::execute, multiterm_query.cpp:163-167)
-        need = in.min_match > row.size() ? 0xFFu : in.min_match;
-      }
-      if (is_phrase) {
-        // no phrase state for a segment lacking one of the terms (phrase_filter.cpp:254-258), or
-        // a part with none of its members (:370-379)
-        absent = found != (1u << n_parts) - 1u;
-        need = absent ? 0xFFu : 1u;
-        b->blocks.variadic = b->blocks.variadic || alt;
-        b->blocks.required = b->blocks.required || with_req;
-        b->blocks.optional = b->blocks.optional || with_opt;
-        // (k_vphrase takes no required or optional terms, k_phrase_and no variadic parts, a batch
-        // runs on k_phrase_and or on k_phrase_or)
-        if ((b->blocks.variadic && (b->blocks.required || b->blocks.optional)) ||
-            (b->blocks.required && b->blocks.optional)) {
-          rc = IRS_HIP_EUNSUPPORTED;
-          break;
-        }
-        // the phrase's scorer is one stats blob: every word's entry must carry the same values (a
-        // required term carries its own)
-        for (uint32_t r = 0; r < word_rows; ++r) {
-          const DevQTerm& qt = row[r];
-          if (qt.kind != row[0].kind || qt.c0 != row[0].c0 ||
-              qt.norm_const != row[0].norm_const || qt.norm_length != row[0].norm_length)
-            rc = IRS_HIP_EINVAL;
-        }
-        if (rc != IRS_HIP_OK) break;
-        b->blocks.n_phrase[q] = word_rows;
-      }
-      if (need == 0xFFu) row.clear();
-      // the unit's masked docs: its segment's deleted ones, and for a unit with present excluded
-      // terms a mask of its own (dead | their docs), shared by the units with the same terms
-      // (build_masks, behind the loop — and again when the batch gets doc sets)
-      dq.dead = seg->dev.dead;
-      b->excl.unit_live[q] = !row.empty();
-      if (!row.empty() && !excl.empty()) {
-        std::sort(excl.begin(), excl.end());
-        excl.erase(std::unique(excl.begin(), excl.end()), excl.end());
-        b->excl.unit_terms.insert(b->excl.unit_terms.end(), excl.begin(), excl.end());
-        // (what k_excl_mask reads for the unit: the excluded terms' doc blocks)
-        for (uint32_t t : excl) b->alg_bytes += uint64_t(seg->terms[t].blocks_bytes) + seg->terms[t].tail_bytes;
-      }
-      b->excl.unit_first.push_back(uint32_t(b->excl.unit_terms.size()));
-      // A doc that exists matches at least `need` terms: c matched postings score at least
-      // c times the mean of the `need` smallest per-term minima — the score below which no
-      // posting of a matching doc falls ON AVERAGE, which is what bounds the relative error of
-      // a fixed-point sum that loses a constant per posting
-      if (need > 1 && need != 0xFFu && !smins.empty() && !is_phrase) {
-        std::sort(smins.begin(), smins.end());
-        double sm = 0.0;
-        for (uint32_t i = 0; i < need && i < smins.size(); ++i) sm += smins[i];
-        min_score = sm / double(need);
-      }
-      // low byte of op: 0 = disjunction in doc tiles, 1 = doc tiles with per-doc match
-      // counters (min-match), 2 = conjunction, block by block of its rarest term (conj.h)
-      dq.op = 0;
-      if (wide) {
-        // lane j = term j of k_wide_pilot / k_wide_score; the match count rides in the low bits of
-        // the unit's own 64-bit sums whatever min_match is
-        dq.op = int32_t(kWideOp | (need << 8));
-      } else if (grouped) {
-        // MakeConjunction sorts its children by cost (conjunction.hpp:450-453): the groups, by the
-        // sum of their members' docs_count (the cheapest leads; the members keep their order);
-        // always block driven (conj_any.h), whatever the number of rows
-        if (!row.empty()) {
-          std::vector<uint64_t> cost(n_groups, 0);
-          for (size_t r = 0; r < row.size(); ++r) cost[row_group[r]] += seg->terms[row[r].term].docs_count;
-          std::vector<uint32_t> order(n_groups);
-          for (uint32_t g = 0; g < n_groups; ++g) order[g] = g;
-          std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return cost[x] < cost[y]; });
-          std::vector<DevQTerm> sorted;
-          opens = 0;
-          for (uint32_t g : order) {
-            bool first = true;
-            for (size_t r = 0; r < row.size(); ++r) {
-              if (row_group[r] != g) continue;
-              if (first) opens |= 1u << sorted.size();
-              first = false;
-              sorted.push_back(row[r]);
-            }
-          }
-          row.swap(sorted);
-          b->any.opens[q] = opens;
-          grouped_units.push_back(q);
-        }
-        dq.op = int32_t(2u | (uint32_t(row.size()) << 8));
-      } else if (need > 1 && !row.empty() && !is_phrase) {
-        if (need == row.size()) {
-          // MakeConjunction sorts by cost (conjunction.hpp:450-453): the cheapest leads, and
-          // the scores are summed in that order
-          std::stable_sort(row.begin(), row.end(), [&](const DevQTerm& x, const DevQTerm& y) {
-            return seg->terms[x.term].docs_count < seg->terms[y.term].docs_count;
-          });
-          dq.op = int32_t(2u | (need << 8));
-        } else {
-          dq.op = int32_t(1u | (need << 8));
-          b->tiles.any_and = true;
-        }
-      }
-      // The filter's ScoreMergeType (boolean_filter.hpp:39-43).  One sub-iterator: its score as
-      // it is (MakeDisjunction :1422-1426, MakeConjunction :444).  kMin in a disjunction merges
-      // with the 0 of every sub-iterator that is not on the doc (basic_disjunction,
-      // disjunction.hpp:338-351) resp. with the zeroed score buffer (block_disjunction
-      // :1308-1351): two sub-iterators -> min where both match, else 0; more (or the
-      // min-match block disjunction) -> 0 for every doc.
-      uint32_t merge = row.size() > 1 ? in.merge : uint32_t(IRS_HIP_MERGE_SUM);
-      if (merge == IRS_HIP_MERGE_MIN && (dq.op & 0xFF) != 2) {
-        if ((dq.op & 0xFF) == 0 && row.size() == 2) {
-          dq.op |= int32_t(1u << 18);
-          b->tiles.any_and = true;   // (the per-doc match counters tell "both")
-        } else {
-          for (DevQTerm& qt : row) qt.c0 = 0.f;
-          upper = 0.0;
-          min_score = 0.0;
-          merge = IRS_HIP_MERGE_SUM;
-        }
-      }
-      dq.op |= int32_t(merge << 16);
-      if (wide) b->wide.units.push_back(q);
-      else if (!is_phrase && !grouped) ((dq.op & 0xFF) == 2 ? b->all_conj_units : b->all_tile_units).push_back(q);
-      // match counts in the low bits of a 32-bit accumulator (join.h COUNT) round every posting
-      // to 16 fixed-point units (+-8): relative to any doc's score that is at most
-      // 8 * upper / (2^29 * min_score) — allowed while it stays below 2e-6
-      b->count_precise[q] = !wide && row.size() <= kJoinCountTerms && min_score > 0.0 && upper > 0.0 &&
-                            upper / min_score <= 125.0;
-      // table slots (kernels.h "table_kind"): one per distinct (kind, norm_const, norm_length)
-      uint32_t n_caches = 0;
-      float cnc[kMaxCaches], cnl[kMaxCaches];
-      int32_t ckind[kMaxCaches];
-      for (DevQTerm& qt : row) {
-        if (qt.kind != kBM25Tiny && qt.kind != kBM25One && qt.kind != kBM15 &&
-            qt.kind != kTfidf && qt.kind != kTfidfTiny)
-          continue;
-        uint32_t c = 0;
-        for (; c < n_caches; ++c)
-          if (ckind[c] == qt.kind && cnc[c] == qt.norm_const && cnl[c] == qt.norm_length) break;
-        if (c == n_caches && n_caches < kMaxCaches) {
-          ckind[c] = qt.kind;
-          cnc[c] = qt.norm_const;
-          cnl[c] = qt.norm_length;
-          ++n_caches;
-        }
-        qt.cache_id = c < kMaxCaches ? c : kMaxCaches;
-      }
-      if (wide && (rc = wide_terms_ok(seg, row)) != IRS_HIP_OK) break;
-      dq.n_caches = n_caches;
-      dq.n_terms = uint32_t(row.size());
-      dq.first_term = uint32_t(b->qterms.size());
-      if (is_phrase && !row.empty()) b->blocks.opens[q] = opens;
-      upper *= 1.0 + 1e-6;
-      if (!row.empty() && upper == 0.0) upper = 1.0;   // every boost is 0: all scores are 0
-      if (!row.empty() && !(upper > 0.0 && std::isfinite(upper))) {
-        rc = IRS_HIP_EUNSUPPORTED;
-        break;
-      }
-      dq.bin_scale = row.empty() ? 0.f : float(double(kBins) / upper);
-      // (irs_hip_batch_set_comm) the bound every segment of the index computes alike
-      b->groups.upper[q] = (same_bound && !is_phrase && !wide && !row.empty() && upper_all > 0.0 &&
-                           upper_all * (1.0 + 1e-6) >= upper && std::isfinite(upper_all))
-                              ? upper_all * (1.0 + 1e-6)
-                              : 0.0;
-      // fixed-point accumulation: upper < 2^e.  32-bit accumulators (2^(30-e) units) lose at
-      // most one unit per posting, i.e. <= upper / (2^29 * min_score) relative to any doc's
-      // score: used only while that stays below 2e-6 for every query of the batch.
-      int e = 0;
-      if (!row.empty()) {
-        (void)std::frexp(upper, &e);
-        if (e < -60 || e > 60) {
-          rc = IRS_HIP_EUNSUPPORTED;
-          break;
-        }
-        // (grouped units score in floats, block driven: the flat units' accumulators are theirs)
-        // (wide units carry 64-bit sums of their own and never ask)
-        if (!grouped && !wide && (!(min_score > 0.0) || upper / min_score > 1000.0)) b->acc32 = false;
-      }
-      exps.push_back(e);
-      b->qterms.insert(b->qterms.end(), row.begin(), row.end());
-      if (!wide) b->jt = std::max(b->jt, dq.n_terms);   // (the plan table's term slots)
-      b->k_max = std::max(b->k_max, in.k);
-    }
-    if (b->knobs.acc64) b->acc32 = false;   // tuning / test knob
-    if (rc == IRS_HIP_OK) rc = build_masks(b);
-    for (uint32_t q = 0; q < nq && rc == IRS_HIP_OK && q < exps.size(); ++q) {
-      const int e = exps[q];
-      const bool acc32 = b->acc32 && !unit_is_wide(b->queries[q]);
-      b->queries[q].fx_mul = std::ldexp(1.f, (acc32 ? 30 : 29) - e);
-      b->queries[q].fx_inv = std::ldexp(1.f, e - (acc32 ? 30 : 61));
-    }
-  } catch (...) {
-    rc = IRS_HIP_ENOMEM;
+  UnitScratch scratch;
+  for (uint32_t q = 0; q < nq; ++q) {
+    // unit q = (segment q / nq_user, query q % nq_user); the segment's own term entries
+    const irs_hip_segment* seg = segs[q / nq_user];
+    const irs_hip_term_scorer* terms = all_terms + size_t(q / nq_user) * n_entries;
+    const irs_hip_query& in = queries[q % nq_user];
+    Unit u;
+    int rc = unit_shape(in, terms, n_entries, seg, u.shape, scratch.excl);
+    if (rc != IRS_HIP_OK) return rc;
+    const irs_hip_term_scorer* ents = terms + in.first_term;
+    rc = phrase_only_rule(b, q, u.shape);
+    if (rc == IRS_HIP_OK && u.shape.phrase()) rc = phrase_parts_ok(ents, u.shape, seg);
+    if (rc == IRS_HIP_OK) rc = unit_rows(ents, seg, u, scratch);
+    if (rc == IRS_HIP_OK) rc = phrase_kernel_rule(b, u.shape);
+    if (rc == IRS_HIP_OK) rc = unit_need(in, u, scratch);
+    if (rc != IRS_HIP_OK) return rc;
+    unit_run(in, seg, u, scratch);
+    u.n_caches = assign_table_slots(scratch.row);
+    if (u.shape.wide()) rc = wide_terms_ok(seg, scratch.row);
+    if (rc == IRS_HIP_OK) rc = unit_scale(u, !scratch.row.empty());
+    if (rc != IRS_HIP_OK) return rc;
+    commit_unit(b, q, in, seg, u, scratch, grouped_units);
   }
-  if (rc == IRS_HIP_OK && b->phrase) {
-    try {
-      rc = build_phrase_work(b);
-      if (rc == IRS_HIP_OK && b->blocks.optional) rc = create_term_pass(b, segs, n_segs, queries, all_terms, n_entries);
-    } catch (...) {
-      rc = IRS_HIP_ENOMEM;
-    }
+  if (b->knobs.acc64) b->acc32 = false;   // tuning / test knob
+  if (const int rc = build_masks(b)) return rc;
+  widen_fixed_point(b);
+  if (b->phrase) {
+    if (const int rc = build_phrase_work(b)) return rc;
+    if (b->blocks.optional)
+      if (const int rc = create_term_pass(b, segs, n_segs, queries, all_terms, n_entries)) return rc;
   }
-  if (rc == IRS_HIP_OK && !grouped_units.empty()) {
-    try {
-      rc = build_any_work(b, grouped_units);
-    } catch (...) {
-      rc = IRS_HIP_ENOMEM;
-    }
-  }
+  if (!grouped_units.empty())
+    if (const int rc = build_any_work(b, grouped_units)) return rc;
   // (the block-driven kernels read the norms of a lead block's docs from the posting-order copy)
   // — a permanent copy per segment, one byte per posting (irs_hip_segment_device_bytes counts
   // it): built the first time a conjunction / phrase whose scorer reads norms arrives
-  if (rc == IRS_HIP_OK && (b->phrase || !b->all_conj_units.empty() || !b->any.units.empty())) {
+  if (b->phrase || !b->all_conj_units.empty() || !b->any.units.empty()) {
     bool wanted = false;
     for (const DevQTerm& qt : b->qterms) wanted = wanted || needs_norm(qt.kind);
     for (irs_hip_segment* sg : b->segs)
-      if (wanted && rc == IRS_HIP_OK) rc = prepare_posting_norms(sg);
+      if (wanted)
+        if (const int rc = prepare_posting_norms(sg)) return rc;
   }
-  if (rc == IRS_HIP_OK) {
-    if (b->jt == 0) b->jt = 1;
-    if (b->qterms.empty()) b->qterms.push_back(DevQTerm{});
-    std::vector<DevSegment> dsegs;
-    for (irs_hip_segment* sg : b->segs) {
-      // (another thread's batch may be adding the lazily built tables to `dev` right now)
-      std::lock_guard<std::mutex> lock(sg->wand_mutex);
-      dsegs.push_back(sg->dev);
-    }
-    if (!b->d_queries.alloc(b->queries.size() * sizeof(DevQuery)) ||
-        !b->d_qterms.alloc(b->qterms.size() * sizeof(DevQTerm)) ||
-        !b->d_segs.alloc(dsegs.size() * sizeof(DevSegment))) {
-      rc = IRS_HIP_ENOMEM;
-    } else if (!b->up.copy(b->d_segs.p, dsegs.data(), dsegs.size() * sizeof(DevSegment)) ||
-               !b->up.copy(b->d_qterms.p, b->qterms.data(), b->qterms.size() * sizeof(DevQTerm))) {
-      // (d_queries goes out from ensure_scratch, once the units' tile geometry is in)
-      rc = IRS_HIP_ENOMEM;
-    }
-  }
-  if (rc != IRS_HIP_OK) {
-    if (b->opt) irs_hip_batch_destroy(b->opt);
-    delete b;
-    return rc;
-  }
-  *out = b;
+  if (const int rc = upload_create_tables(b)) return rc;
+  *out = owner.release();
   return IRS_HIP_OK;
+} catch (...) {
+  return IRS_HIP_ENOMEM;
 }
 
 // Before a setter re-deals the units (buffers are reallocated, tables rewritten): whatever of the

@@ -82,7 +82,7 @@ int join_or_forced(const irs_hip_batch* b) {   // -1: decide by cost
   return b->knobs.join_or;   // tuning / test knob (-1: not set)
 }
 bool unit_counts_matches(const DevQuery& dq) {   // min-match / the kMin disjunction of two
-  return (dq.op & 0xFF) == 1 || query_min_both(dq.op);
+  return query_run(dq.op) == kRunCount || query_min_both(dq.op);
 }
 bool unit_joinable(const irs_hip_batch* b, uint32_t u) {
   const DevQuery& dq = b->queries[u];
@@ -90,7 +90,7 @@ bool unit_joinable(const irs_hip_batch* b, uint32_t u) {
   // a unit with excluded terms: k_join applies the SEGMENT's deleted docs while it decodes the
   // streams every unit shares, the unit's own mask (excl.h) cannot ride there
   if (dq.dead != b->segs[dq.seg]->dev.dead) return false;
-  if ((dq.op & 0xFF) != 0) {
+  if (query_run(dq.op) != kRunTiles) {
     // min-match / conjunction: the match count rides in the accumulator's low bits (join.h
     // COUNT) where that costs no precision that matters
     if (!dq.n_terms || !b->count_precise[u] || !b->knobs.join_counts) return false;

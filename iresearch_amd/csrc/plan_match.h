@@ -9,9 +9,9 @@ namespace {
 bool ensure_scratch(irs_hip_batch* b);
 bool launch_excl_masks(irs_hip_batch* b, rt::stream_t st);
 
-// MatchUnit records of every unit, from what create left in b->queries / b->qterms: the low byte of
-// DevQuery::op tells doc tiles (0: Or), doc tiles with match counters (1: min-match, need in bits
-// 8..15) or a conjunction (2); a grouped one has its groups' first rows in AnyWork::opens
+// MatchUnit records of every unit, from what create left in b->queries / b->qterms: query_run of
+// DevQuery::op tells doc tiles (Or), doc tiles with match counters (min-match, its query_need) or a
+// conjunction; a grouped one has its groups' first rows in AnyWork::opens
 static int build_match_work(irs_hip_batch* b) {
   MatchWork& m = b->match;
   if (m.built) return IRS_HIP_OK;
@@ -33,13 +33,12 @@ static int build_match_work(irs_hip_batch* b) {
     mu.seg = dq.seg;
     mu.first = uint32_t(m.rows.size());
     mu.n_rows = dq.n_terms;
-    const uint32_t low = uint32_t(dq.op) & 0xFFu;
-    if (low == 2u) {
+    if (query_run(dq.op) == kRunConj) {
       mu.op = kMatchAnd;
       mu.opens = grouped[q] ? b->any.opens[q] : (1u << dq.n_terms) - 1u;
-    } else if (low == 1u) {
+    } else if (query_run(dq.op) == kRunCount) {
       mu.op = kMatchMin;
-      mu.need = (uint32_t(dq.op) >> 8) & 0xFFu;
+      mu.need = query_need(dq.op);
     } else {
       mu.op = kMatchOr;
     }

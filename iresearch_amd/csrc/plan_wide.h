@@ -6,7 +6,7 @@
 
 namespace {
 
-bool unit_is_wide(const DevQuery& dq) { return (uint32_t(dq.op) & 0xFFu) == kWideOp; }
+bool unit_is_wide(const DevQuery& dq) { return query_run(dq.op) == kRunWide; }
 
 // What batch_create refuses of an IRS_HIP_OP_MULTITERM query's present terms (`row`, table slots
 // assigned): the per-term rules are unit_joinable's — a scorer of the table family with a slot of

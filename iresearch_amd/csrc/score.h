@@ -206,14 +206,24 @@ __device__ __forceinline__ float from_fixed(ACC a, float fx_inv) {
   return static_cast<float>(a) * fx_inv;
 }
 
-// DevQuery::op: bits 0..7 how the unit runs (0 doc tiles, 1 doc tiles with match counters,
-// 2 block-driven conjunction), 8..15 the matches a doc needs, 16..17 the boolean filter's
-// ScoreMergeType (scorer.hpp:224-236: 0 sum, 1 max, 2 min), bit 18: a kMin disjunction of two
-// sub-iterators — a doc only one of them holds scores 0 (disjunction.hpp:338-351).
+// DevQuery::op, written by make_op (units.h unit_run) and read through query_*:
+//   bits 0..7   how the unit runs: kRunTiles — a disjunction in doc tiles; kRunCount — doc tiles with
+//               per-doc match counters (min-match); kRunConj — a conjunction, block by block of its
+//               rarest term (conj.h; a grouped one: conj_any.h) or on joined streams with match
+//               counts; kRunWide — a scored multi-term unit (wide.h)
+//   bits 8..15  the matches a doc needs (0xFF: nothing of the segment can match)
+//   bits 16..17 the boolean filter's ScoreMergeType (scorer.hpp:224-236: 0 sum, 1 max, 2 min)
+//   bit 18      a kMin disjunction of two sub-iterators — a doc only one of them holds scores 0
+//               (disjunction.hpp:338-351)
+enum : uint32_t { kRunTiles = 0, kRunCount = 1, kRunConj = 2, kRunWide = 3 };
 enum : uint32_t { kScoreSum = 0, kScoreMax = 1, kScoreMin = 2 };
+__host__ __device__ __forceinline__ uint32_t query_run(int32_t op) { return uint32_t(op) & 0xFFu; }
 __host__ __device__ __forceinline__ uint32_t query_merge(int32_t op) { return (uint32_t(op) >> 16) & 3u; }
 __host__ __device__ __forceinline__ uint32_t query_need(int32_t op) { return (uint32_t(op) >> 8) & 0xFFu; }
 __host__ __device__ __forceinline__ bool query_min_both(int32_t op) { return (uint32_t(op) >> 18) & 1u; }
+inline int32_t make_op(uint32_t run, uint32_t need, uint32_t merge, bool min_both) {
+  return int32_t(run | (need << 8) | (merge << 16) | (uint32_t(min_both) << 18));
+}
 // Max/Min merged accumulators hold max(fixed) resp. max(~fixed) (0 = untouched either way);
 // back to the fixed-point score:
 template<typename ACC>
@@ -1091,7 +1101,7 @@ k_pilot(const uint32_t* units, const DevSegment* segs, const DevQuery* queries,
       sm.acc[i] = ACC(0);
       bool m = a != ACC(0);
       const uint32_t c = AND ? (sm.cnt[i >> 2] >> (8u * (i & 3u))) & 0xFFu : 0u;
-      if (AND && (qd.op & 0xFF) == 1)  // AND / min-match: op = 1 | required matches << 8
+      if (AND && query_run(qd.op) == kRunCount)  // AND / min-match: the required matches in query_need
         m = c >= query_need(qd.op);
       // (a deleted doc never leaves the iterator: SegmentReaderImpl::mask)
       if (dead && m) m = !doc_dead(dead, kDocMin + tile * uint32_t(TILE) + i);
@@ -1341,7 +1351,7 @@ k_score(uint64_t args /*address of a ScoreArgs*/) {
         }
       };
       if (!wave::uniform(tdead[u])) {   // (a skipped tile accumulated nothing)
-        const bool is_and = AND && (qd.op & 0xFF) == 1;  // op = 1 | required matches << 8
+        const bool is_and = AND && query_run(qd.op) == kRunCount;
         const uint32_t need = query_need(qd.op);
         const bool min_both = AND && query_min_both(qd.op);
         // eight accumulators per lane per step: two 4-wide LDS reads in flight, two wide clears.

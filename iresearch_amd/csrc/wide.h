@@ -40,7 +40,6 @@ constexpr uint32_t kWideThreads = 1024;    // 16 wavefronts share a tile's entri
 constexpr uint32_t kWideWavesLog2 = 4;
 constexpr uint32_t kWideChunkTiles = 16;   // consecutive tiles per k_wide_score workgroup, at most
 constexpr uint32_t kWideCands = 512;       // candidate staging slots per chunk
-constexpr uint32_t kWideOp = 3;            // DevQuery::op low byte: the unit runs on this path
 constexpr unsigned long long kWideCountMask = 127ull;
 constexpr uint32_t kWideConst = 1u << 28;  // JoinTerm::mode of a wide unit's term: a constant score (BM1: k = 0)
 static_assert(kMaxWideTerms <= kWideCountMask, "the low bits of a sum count its terms");

@@ -2567,3 +2567,190 @@ def case_errors(L):
     cnt = C.c_uint32()
     assert L.irs_hip_decode_term(sr.handle, 10_000, None, None, 0, C.byref(cnt)) == _lib.EINVAL
     sr.close()
+
+
+def case_create_status(L):
+    """The refusals of irs_hip_batch_create_multi, one rule at a time: a table of batches that break
+    ONE rule of the query -> unit step, each with the exact status it gets, `*out` left null, and the
+    same batch without the violation created and run.  One row per status a caller can reach
+    through the ABI, in the order create checks them; where create chooses between EINVAL and
+    EUNSUPPORTED for neighbouring conditions (a wide query's min_match / size, a phrase's words in
+    front of required terms / its flags) the table holds both.  Not reachable from here: segments on
+    different devices, a segment without frequencies (test_match_sets.py), the allocation failures,
+    a score bound that is not finite (a sum of finite float boosts in a double always is).  Rows
+    that other files assert as well, in their own settings: test_multiterm.py (wide queries),
+    test_exclusion.py (excluded entries), test_variadic_phrase.py (PHRASE_ALT), test_phrase_and.py /
+    test_phrase_or.py (REQUIRED / OPTIONAL), test_nested_boolean.py (GROUP_ALT), case_errors and
+    case_phrase_errors above (k, 17 entries, positions, phrase and boolean queries mixed)."""
+    seg = synth.build_segment(2000, 64, with_positions=True)
+    sr = search.SegmentReader.from_synth(seg, L=L)
+    sr_plain = search.SegmentReader.from_synth(synth.build_segment(2000, 64), L=L)
+    sr_scalar = search.SegmentReader.from_synth(
+        synth.build_segment(2000, 64, with_positions=True, layout=synth.LAYOUT_SCALAR), L=L)
+    n_terms_seg = len(seg.metas)
+    B, X = _lib.SCORE_BM25, _lib.EXCLUDE
+    A, G, R, O = _lib.PHRASE_ALT, _lib.GROUP_ALT, _lib.PHRASE_REQUIRED, _lib.PHRASE_OPTIONAL
+    INV, UNS = _lib.EINVAL, _lib.EUNSUPPORTED
+
+    def e(term, kind=B, c0=1.0, nc=0.3, nl=0.01, off=0):
+        return (term, kind, c0, nc, nl, off)
+
+    def x(term):
+        return (term, X, 0.0, 0.0, 0.0, 0)
+
+    def q(op, entries, k=10, min_match=0, merge=search.MERGE_SUM, **raw):
+        return dict(op=op, entries=list(entries), k=k, min_match=min_match, merge=merge, raw=raw)
+
+    def arrays(batch, n_segs):
+        n = sum(len(qq["entries"]) for qq in batch)
+        queries = np.zeros(len(batch), _lib.QUERY)
+        terms = np.zeros((n_segs, max(n, 1)), _lib.TERM_SCORER)
+        at = 0
+        for i, qq in enumerate(batch):
+            queries[i] = (qq["op"], len(qq["entries"]), at, qq["k"], qq["min_match"], qq["merge"])
+            for name, v in qq["raw"].items():
+                queries[i][name] = v
+            for ent in qq["entries"]:
+                terms[:, at] = ent
+                at += 1
+        return search.QueryArrays(n_segs, queries, terms, 10)
+
+    def status(batch, readers):
+        arr = arrays(batch, len(readers))
+        h = C.c_void_p(1)   # (not null going in)
+        handles = (C.c_void_p * len(readers))(*[r.handle for r in readers])
+        rc = L.irs_hip_batch_create_multi(handles, len(readers), arr.queries.ctypes.data,
+                                          len(arr.queries), arr.terms.ctypes.data, arr.terms.shape[1],
+                                          C.byref(h))
+        if rc == _lib.OK:
+            assert h.value
+            L.irs_hip_batch_destroy(h)
+        else:
+            assert h.value is None, "*out after a refusal"
+        return rc
+
+    ran = set()
+
+    def runs(name, batch, readers):   # every distinct good batch: created and run once
+        if name in ran:
+            return
+        ran.add(name)
+        b = search.QueryBatch(list(readers), arrays(batch, len(readers)))
+        hits, counts, totals = b.run().results()
+        assert counts.shape == totals.shape == (len(readers), len(batch)), name
+        b.close()
+
+    OR, AND, MIN, PHR, WIDE = _lib.OP_OR, _lib.OP_AND, _lib.OP_MINMATCH, _lib.OP_PHRASE, _lib.OP_MULTITERM
+    words = [e(1), e(2, off=1), e(3, off=2)]
+    wide20 = [e(10 + j) for j in range(20)]
+    good = {
+        "or": [q(OR, [e(1), e(2), e(3), x(5)]), q(OR, [e(4)])],
+        "bm15": [q(OR, [e(1, _lib.SCORE_BM15), e(2, _lib.SCORE_BM15)])],
+        "and": [q(AND, [e(1), e(2), e(3)])],
+        "grouped": [q(AND, [e(1), e(2, B | G), e(3)])],
+        "minmatch": [q(MIN, [e(1), e(2), e(3)], min_match=2)],
+        "wide": [q(WIDE, wide20, min_match=2)],
+        "wide64": [q(WIDE, [e(j) for j in range(64)], min_match=1)],
+        "wide4": [q(WIDE, [e(10 + j, nc=0.3 + 0.1 * (j % 4)) for j in range(8)], min_match=1)],
+        "phrase": [q(PHR, words), q(PHR, [e(2), e(4, off=1)])],
+        "phrase8": [q(PHR, [e(1 + j, off=j) for j in range(8)])],
+        "variadic": [q(PHR, [e(1), e(2, B | A), e(3, off=1)])],
+        "variadic16": [q(PHR, [e(2 * j + m, B | (A if m else 0), off=j) for j in range(8) for m in range(2)])],
+        "required": [q(PHR, [e(1), e(2, off=1), e(4, B | R), e(5, B | R)])],
+        "required8": [q(PHR, [e(1), e(2, off=1)] + [e(4 + j, B | R) for j in range(6)])],
+        "optional": [q(PHR, [e(1), e(2, off=1), e(4, B | O), e(5, B | O)])],
+        "16+16": [q(OR, [e(j) for j in range(16)] + [x(20 + j) for j in range(16)])],
+    }
+    one, both, plain_only, mixed = [sr], [sr, sr], [sr_plain], [sr, sr_scalar]
+
+    def edit(name, i, j=None, **fields):   # good[name] with query i (its entry j) changed
+        batch = [dict(qq, entries=list(qq["entries"]), raw=dict(qq["raw"])) for qq in good[name]]
+        for f, v in fields.items():
+            if j is None:
+                batch[i][f] = v
+            else:
+                ent = list(batch[i]["entries"][j])
+                ent[("term", "kind", "c0", "nc", "nl", "off").index(f)] = v
+                batch[i]["entries"][j] = tuple(ent)
+        return batch
+
+    def more(name, i, entries, at=None):
+        batch = edit(name, i)
+        at = len(batch[i]["entries"]) if at is None else at
+        batch[i]["entries"][at:at] = entries
+        return batch
+
+    # (what, the good batch, the batch with the violation, its status[, the readers of the bad one])
+    table = [
+        ("first_term + n_terms > n_entries", "or", edit("or", 1, raw=dict(n_terms=2)), INV),
+        ("first_term past the entries", "or", edit("or", 1, raw=dict(first_term=5)), INV),
+        ("17 entries of a variadic phrase", "variadic16", more("variadic16", 0, [e(40, B | A, off=7)]), UNS),
+        ("op 5", "or", edit("or", 0, op=5), INV),
+        ("op -1", "or", edit("or", 0, op=-1), INV),
+        ("n_terms 0", "or", edit("or", 1, entries=[]), INV),
+        ("excluded entries only", "or", edit("or", 1, entries=[x(4)]), INV),
+        ("merge 3", "or", edit("or", 0, merge=3), INV),
+        ("merge 3 of a wide query", "wide", edit("wide", 0, merge=3), INV),
+        ("a phrase with merge max", "phrase", edit("phrase", 0, merge=search.MERGE_MAX), INV),
+        ("17 included entries", "16+16", more("16+16", 0, [e(40)], at=16), INV),
+        ("17 excluded entries", "16+16", more("16+16", 0, [x(40)]), INV),
+        ("k 0", "or", edit("or", 1, k=0), INV),
+        ("k > MAX_K", "or", edit("or", 1, k=_lib.MAX_K + 1), INV),
+        ("wide: min_match 0", "wide", edit("wide", 0, min_match=0), INV),
+        ("wide: min_match above its entries", "wide", edit("wide", 0, min_match=21), INV),
+        ("wide: 65 entries", "wide64", more("wide64", 0, [e(0)]), UNS),
+        ("wide: 65 entries and min_match 0", "wide64", edit("wide64", 0, entries=[e(j % 64) for j in range(65)],
+                                                        min_match=0), UNS),
+        ("wide: an excluded entry", "wide", more("wide", 0, [x(5)]), UNS),
+        ("wide: merge max", "wide", edit("wide", 0, merge=search.MERGE_MAX), UNS),
+        ("a plain entry behind a required one", "required", edit("required", 0, 3, kind=B), INV),
+        ("a plain entry behind an optional one", "optional", edit("optional", 0, 3, kind=B), INV),
+        ("one word in front of required terms", "required", edit("required", 0, 1, kind=B | R), INV),
+        ("one word and its member in front of optional terms", "optional", edit("optional", 0, 1, kind=B | A, off=0), INV),
+        ("a variadic part and required terms", "required", more("required", 0, [e(6, B | A, off=1)], at=2), UNS),
+        ("a variadic part and optional terms", "optional", more("optional", 0, [e(6, B | A, off=1)], at=2), UNS),
+        ("required and optional in one query", "required", edit("required", 0, 3, kind=B | O), UNS),
+        ("both flags on one entry", "required", edit("required", 0, 3, kind=B | R | O), UNS),
+        ("9 entries with required terms", "required8", more("required8", 0, [e(20, B | R)]), UNS),
+        ("GROUP_ALT on the first entry", "grouped", edit("grouped", 0, 0, kind=B | G), INV),
+        ("an included entry behind an excluded one", "or", more("or", 0, [e(6)]), INV),
+        ("an excluded term >= num_terms", "or", edit("or", 0, 3, term=n_terms_seg), INV),
+        ("a phrase behind a boolean query", "or", edit("or", 1, op=PHR), UNS),
+        ("a boolean query behind a phrase", "phrase", edit("phrase", 1, op=OR), UNS),
+        ("9 parts", "phrase8", more("phrase8", 0, [e(9, off=8)]), INV),
+        ("PHRASE_ALT on the first entry", "variadic", edit("variadic", 0, 0, kind=B | A), INV),
+        ("the first entry's offset not 0", "phrase", edit("phrase", 0, 0, off=1), INV),
+        ("a phrase on a segment without positions", "phrase", good["phrase"], UNS, plain_only),
+        ("a member at another offset", "variadic", edit("variadic", 0, 1, off=1), INV),
+        ("a member repeating a term", "variadic", edit("variadic", 0, 1, term=1), INV),
+        ("an included term >= num_terms", "or", edit("or", 0, 1, term=n_terms_seg), INV),
+        ("a negative boost", "or", edit("or", 0, 1, c0=-1.0), INV),
+        ("a NaN boost", "or", edit("or", 0, 1, c0=float("nan")), INV),
+        ("an infinite boost", "or", edit("or", 0, 1, c0=float("inf")), INV),
+        ("BM25: norm_const + norm_length <= 0", "or", edit("or", 0, 1, nc=0.0, nl=0.0), INV),
+        ("BM15: norm_const <= 0", "bm15", edit("bm15", 0, 1, nc=0.0), INV),
+        ("scorer kind 7", "or", edit("or", 0, 1, kind=7), INV),
+        ("GROUP_ALT in an Or", "or", edit("or", 0, 1, kind=B | G), INV),
+        ("min-match: min_match 0", "minmatch", edit("minmatch", 0, min_match=0), UNS),
+        ("required and optional in one batch", "required", good["required"] + good["optional"], UNS),
+        ("optional and required in one batch", "optional", good["optional"] + good["required"], UNS),
+        ("variadic and required in one batch", "variadic", good["variadic"] + good["required"], UNS),
+        ("optional and variadic in one batch", "optional", good["optional"] + good["variadic"], UNS),
+        ("phrase words with differing boosts", "phrase", edit("phrase", 0, 1, c0=0.5), INV),
+        ("phrase words with differing scorers", "phrase", edit("phrase", 0, 2, kind=_lib.SCORE_BM1), INV),
+        ("wide: five distinct table slots", "wide4", edit("wide4", 0, 0, nc=0.9), UNS),
+        ("a boost beyond 2^60", "or", edit("or", 0, 1, c0=1e30), UNS),
+        ("boosts below 2^-60", "and", [q(AND, [e(1, c0=1e-30), e(2, c0=1e-30), e(3, c0=1e-30)])], UNS),
+        ("segments on different layouts", "or", good["or"], UNS, mixed),
+    ]
+    names = [row[0] for row in table]
+    assert len(set(names)) == len(names)
+    for what, name, bad, want, *rest in table:
+        readers = both if name == "or" else one   # (the Or batch: on two segments of one layout)
+        assert status(good[name], readers) == _lib.OK, (what, name)
+        runs(name, good[name], readers)
+        got = status(bad, rest[0] if rest else readers)
+        assert got == want, (what, got, want)
+    assert ran == set(good), set(good) - ran
+    for r in (sr, sr_plain, sr_scalar):
+        r.close()

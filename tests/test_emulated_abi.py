@@ -266,3 +266,7 @@ def test_wand_equals_exhaustive(simlib):
 
 def test_errors(simlib):
     cases.case_errors(simlib)
+
+
+def test_create_status(simlib):
+    cases.case_create_status(simlib)

@@ -325,6 +325,10 @@ def test_errors(gpulib):
     cases.case_errors(gpulib)
 
 
+def test_create_status(gpulib):
+    cases.case_create_status(gpulib)
+
+
 def test_config1_by_term_top10_100k(gpulib):
     """BASELINE config 1: single by_term BM25 top-10 on a 100k-doc index."""
     from iresearch_amd import _lib

@@ -476,8 +476,20 @@ int irs_hip_batch_create_multi(irs_hip_segment* const* segs, uint32_t n_segs,
  * call on the batch (irs_hip_batch_device_results waits for the run; irs_hip_batch_results_to_device
  * / _to_host queue their copies behind it), or switch the hand-over off for that batch.  The same
  * holds for a device pointer obtained from irs_hip_batch_device_results BEFORE a re-run of the
- * batch: use it only behind a later call on the batch. */
+ * batch: use it only behind a later call on the batch.
+ * Nor is the END of a run ordered by `stream`: the library may queue the last kernels of a run on
+ * a stream of its own.  A batch whose whole score stage is one paired launch of plain disjunctions
+ * (no conjunction, phrase, multi-term or grouped unit, no shared threshold, no communicator) runs
+ * its rescoring pass, its top-k selection and its status copy on the device's TAIL stream, beside
+ * the pilot pass of the next batch queued on `stream`; the score launch of every later run on the
+ * device waits for that tail.  irs_hip_batch_results* (also _to_device / _to_host, which queue
+ * their copies behind the run's end), irs_hip_batch_device_results, irs_hip_batch_timings and
+ * irs_hip_batch_destroy get behind the whole run, a hipStreamSynchronize(stream) does not.
+ * IRS_HIP_TAIL_STREAM=0 in the environment when a batch is created keeps its runs on `stream`
+ * from end to end (A/B runs, tests); the results are the same either way.
+ * irs_hip_batch_tail_stream_used: whether the batch's last run took the tail stream. */
 int irs_hip_batch_run(irs_hip_batch* batch, void* stream);
+int irs_hip_batch_tail_stream_used(irs_hip_batch* batch, int* used);
 /* Per batch: 1 = hand the host half of irs_hip_batch_run to the library's worker thread, 0 = keep
  * it on the caller's thread, -1 = the process default (on; IRS_HIP_ASYNC_RUN=0 turns it off).  A
  * batch with a communicator (irs_hip_batch_set_comm) issues its collectives — also those of a

@@ -36,6 +36,7 @@ struct Knobs {
   bool acc64 = false;        // IRS_HIP_ACC=64: 64-bit accumulators whatever the queries
   uint32_t excl_slice = kExclSliceWords;   // IRS_HIP_EXCL_SLICE: mask words per k_excl_mask workgroup (64..8192, a power of two)
   uint32_t match_slice = kMatchSliceWords;   // IRS_HIP_MATCH_SLICE: bitmap words per k_match_slice workgroup (64..8192, a power of two)
+  bool tail_stream = true;   // IRS_HIP_TAIL_STREAM=0: k_join_rescore and k_select stay on the caller's stream
   static Knobs from_env() {
     Knobs k;
     int v = 0;
@@ -59,6 +60,7 @@ struct Knobs {
       k.excl_slice = uint32_t(v);
     if (set("IRS_HIP_MATCH_SLICE") && v >= 64 && uint32_t(v) <= kMatchSliceMax && (v & (v - 1)) == 0)
       k.match_slice = uint32_t(v);
+    if (set("IRS_HIP_TAIL_STREAM")) k.tail_stream = v != 0;
     return k;
   }
 };
@@ -239,6 +241,12 @@ struct RunSync {
   // queued on the stream since), and the status word that run left in page-locked memory
   Event done;
   PinBuf h_status;
+  // a run whose score stage is the one paired launch (tail_ok) ends on the device's tail stream:
+  // `scored` lies behind k_join_score<kJKHalf> on the caller's stream, the tail waits for it, and
+  // `done` is recorded on the tail stream — NOTHING of such a run is ordered by the caller's
+  // stream behind `scored`: whoever reads what the run leaves gets behind `done`
+  Event scored;
+  bool tail_used = false;      // the last run took the tail stream
   // irs_hip_batch_plan: the planning stage of the NEXT run was queued ahead (on another stream)
   Event plan;
   bool planned = false;        // ... and the next run may use it (same geometry)
@@ -337,6 +345,7 @@ struct irs_hip_batch {
   // matched, k_not_words turns the rows into "not taken").  k_union_topk merges the two passes' top k and totals into d_union_*, which is
   // what the result calls hand out.
   irs_hip_batch* opt = nullptr;
+  bool term_pass = false;   // this batch IS the term pass of another (the union follows it in stream order)
   DevBuf d_taken, d_union_out, d_union_count, d_union_hits;
   uint64_t taken_words = 0;
   ExclWork excl;

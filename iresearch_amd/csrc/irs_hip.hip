@@ -625,6 +625,20 @@ static int batch_create_multi_impl(irs_hip_segment* const* segs, uint32_t n_segs
   return IRS_HIP_ENOMEM;
 }
 
+// The host gets behind the batch's last run AND whatever else is queued on its stream.  The run
+// itself may have ended on the device's tail stream: `done` marks its end, the stream does not.
+static bool run_done(const irs_hip_batch* b) { return !b->sync.done.made || b->sync.done.sync(); }
+static bool after_run(irs_hip_batch* b) {
+  const bool ok = run_done(b);
+  return rt::sync(b->stream) && ok;
+}
+// The status word of the batch's last run, out of the page-locked word that run copied it to
+static bool run_status(const irs_hip_batch* b, uint32_t* status) {
+  if (!b->sync.h_status.p || !b->sync.done.sync()) return false;
+  *status = *b->sync.h_status.as<uint32_t>();
+  return true;
+}
+
 // Before a setter re-deals the units (buffers are reallocated, tables rewritten): whatever of the
 // batch is still queued must be through — its last run AND a plan stage queued ahead.
 static bool quiesce(irs_hip_batch* b) {
@@ -633,7 +647,7 @@ static bool quiesce(irs_hip_batch* b) {
     ok = b->sync.plan.sync();
     b->sync.plan_pending = false;
   }
-  if (b->ran) ok = rt::sync(b->stream) && ok;
+  if (b->ran) ok = after_run(b) && ok;
   if (b->sync.match_pending) {
     ok = b->sync.matched.sync() && ok;
     b->sync.match_pending = false;
@@ -892,7 +906,7 @@ static int batch_touched_impl(irs_hip_batch* b, uint64_t* doc_bytes, uint64_t* p
   if (!b || !b->ran || !b->count_touched) return IRS_HIP_EINVAL;
   if (!rt::set_device(b->seg->device)) return IRS_HIP_EHIP;
   std::vector<uint64_t> v(size_t(b->nq) * 2);
-  if (!rt::d2h(v.data(), b->d_touched.p, v.size() * 8, b->stream) || !rt::sync(b->stream))
+  if (!run_done(b) || !rt::d2h(v.data(), b->d_touched.p, v.size() * 8, b->stream) || !rt::sync(b->stream))
     return IRS_HIP_EHIP;
   uint64_t bytes = 0, pos = 0;
   for (uint32_t u = 0; u < b->nq; ++u) {
@@ -999,6 +1013,10 @@ static int run_impl(irs_hip_batch* b, rt::stream_t st) {
     if (!b->sync.host.wait(st)) return IRS_HIP_EHIP;
     b->sync.host_pending = false;
   }
+  // the batch's own previous run ended on the tail stream (a replay, a recovery re-run): the fill
+  // of d_zeroed, the uploads and the pilot below rewrite what that tail may still read — stream
+  // order on `st` does not cover it
+  if (b->ran && b->sync.tail_used && b->sync.done.made && !b->sync.done.wait(st)) return IRS_HIP_EHIP;
   const bool simd = b->seg->dev.layout == kSimd4;
   auto mark = [&](int i) { return !b->profile || b->sync.prof[i].record(st); };
   // the batch's tables (built in page-locked memory since create) go out: before the batch's
@@ -1054,19 +1072,34 @@ static int run_impl(irs_hip_batch* b, rt::stream_t st) {
   if (tiles)
     ok = ok && with_tile_kernel(b, [&](auto k) { return launch_pilot(b, st, k); });
   ok = ok && mark(2 * IRS_HIP_K_PILOT + 1);
-  // 3. score every tile / every lead block
+  // 3. score every tile / every lead block — behind the tail queued last on the device (pool.h):
+  // a started k_join_score workgroup holds the LDS that tail's k_select asks for
+  ok = ok && wait_for_tail(b->seg->device, st);
   ok = ok && mark(2 * IRS_HIP_K_SCORE);
+  // (a batch that passes tail_ok: from behind its paired launch on, the run is queued on the
+  // device's tail stream `ts`, and nothing of it follows on `st`)
+  bool tail = false;
+  rt::stream_t ts = st;
+  if (ok && tail_ok(b)) {
+    rt::stream_t s = tail_stream(b->seg->device, &tail);
+    if (tail) ts = s;
+  }
+  b->sync.tail_used = tail;
+  Tail& dev_tail = tail_of(b->seg->device);
+  std::unique_lock<std::mutex> tail_lock(dev_tail.m, std::defer_lock);
+  if (tail) tail_lock.lock();
+  auto mark_tail = [&](int i) { return !b->profile || b->sync.prof[i].record(ts); };
   if (b->phrase)
     ok = ok && (simd ? launch_phrase_terms<kSimd4>(b, st) : launch_phrase_terms<kScalar>(b, st));
   else if (tiles)
     ok = ok && with_tile_kernel(b, [&](auto k) { return launch_score(b, st, k); });
-  if (b->join.on()) ok = ok && launch_join_score(b, st);
+  if (b->join.on()) ok = ok && launch_join_score(b, st, tail ? &ts : nullptr);
   if (b->wide.on()) ok = ok && launch_wide_score(b, st);
   if (!b->phrase) ok = ok && (simd ? launch_conj<kSimd4>(b, st) : launch_conj<kScalar>(b, st));
   if (!b->phrase) ok = ok && (simd ? launch_any<kSimd4>(b, st) : launch_any<kScalar>(b, st));
-  ok = ok && mark(2 * IRS_HIP_K_SCORE + 1);
+  ok = ok && mark_tail(2 * IRS_HIP_K_SCORE + 1);
   // 4. exact top-k
-  ok = ok && mark(2 * IRS_HIP_K_SELECT);
+  ok = ok && mark_tail(2 * IRS_HIP_K_SELECT);
   if (ok) {
     uint32_t sort_cap = 64;
     while (sort_cap < b->k_max) sort_cap <<= 1;
@@ -1074,7 +1107,7 @@ static int run_impl(irs_hip_batch* b, rt::stream_t st) {
     const size_t smem = size_t(sort_cap + stage_cap) * sizeof(uint64_t);
     ok = big_smem(k_select, smem);
     if (ok) {
-      RT_LAUNCH(k_select, b->nq, kThreads, smem, st, b->d_queries.as<DevQuery>(),
+      RT_LAUNCH(k_select, b->nq, kThreads, smem, ts, b->d_queries.as<DevQuery>(),
                 b->d_cands.as<uint64_t>(), b->cand_cap, b->d_cand_count.as<uint32_t>(),
                 b->d_hits.as<unsigned long long>(), b->d_out.as<Hit>(), b->k_max,
                 b->d_out_count.as<uint32_t>(), b->d_status.as<uint32_t>(), stage_cap, sort_cap,
@@ -1098,7 +1131,7 @@ static int run_impl(irs_hip_batch* b, rt::stream_t st) {
       ok = ok && rt::last_error_ok();
     }
   }
-  ok = ok && mark(2 * IRS_HIP_K_SELECT + 1);
+  ok = ok && mark_tail(2 * IRS_HIP_K_SELECT + 1);
   // optional terms: the term pass behind the phrase pass, on the same stream, then the union of
   // their results (the batch's `done` covers all three)
   if (ok && b->opt) {
@@ -1113,7 +1146,13 @@ static int run_impl(irs_hip_batch* b, rt::stream_t st) {
   }
   // the status word follows the kernels into page-locked memory; the event marks this run
   if (ok && !b->sync.h_status.p) ok = b->sync.h_status.alloc(64);
-  ok = ok && rt::d2h(b->sync.h_status.p, b->d_status.p, 4, st) && b->sync.done.record(st);
+  ok = ok && rt::d2h(b->sync.h_status.p, b->d_status.p, 4, ts) && b->sync.done.record(ts);
+  if (tail) {
+    // (whatever of the tail got queued: the next score launch of the device waits for it)
+    if (dev_tail.done.record(ts)) dev_tail.recorded = true;
+    else ok = false;
+    tail_lock.unlock();
+  }
   if (!ok) abandon_fills(b);
   b->ran = true;
   return ok ? IRS_HIP_OK : IRS_HIP_EHIP;
@@ -1163,7 +1202,7 @@ static int recover_overflow(irs_hip_batch* b) {
     // only when that is not affordable, a full histogram pass (stride 1: the tightest sound
     // threshold) comes first — it costs as much as the scoring pass itself.
     std::vector<uint32_t> cc(b->nq);
-    if (!rt::d2h(cc.data(), b->d_cand_count.p, size_t(b->nq) * 4, b->stream) ||
+    if (!run_done(b) || !rt::d2h(cc.data(), b->d_cand_count.p, size_t(b->nq) * 4, b->stream) ||
         !rt::sync(b->stream))
       return IRS_HIP_EHIP;
     const uint64_t need = uint64_t(*std::max_element(cc.begin(), cc.end())) + 1024;
@@ -1189,8 +1228,7 @@ static int recover_overflow(irs_hip_batch* b) {
     int rc = run_impl(b, b->stream);
     if (rc != IRS_HIP_OK) return rc;
     uint32_t status = 0;
-    if (!rt::d2h(&status, b->d_status.p, 4, b->stream) || !rt::sync(b->stream))
-      return IRS_HIP_EHIP;
+    if (!run_status(b, &status)) return IRS_HIP_EHIP;
     if (!(status & kStatusOverflow)) return IRS_HIP_OK;
   }
   return IRS_HIP_EOVERFLOW;
@@ -1201,7 +1239,7 @@ static int recover_now(irs_hip_batch* b, uint32_t status) {
   if (std::getenv("IRS_HIP_TRACE")) {   // which units made the batch run again
     std::vector<uint32_t> cc(b->nq), oc(b->nq);
     std::vector<unsigned long long> hh(b->nq);
-    if (rt::d2h(cc.data(), b->d_cand_count.p, size_t(b->nq) * 4, b->stream) &&
+    if (run_done(b) && rt::d2h(cc.data(), b->d_cand_count.p, size_t(b->nq) * 4, b->stream) &&
         rt::d2h(oc.data(), b->d_out_count.p, size_t(b->nq) * 4, b->stream) &&
         rt::d2h(hh.data(), b->d_hits.p, size_t(b->nq) * 8, b->stream) && rt::sync(b->stream)) {
       uint32_t under = 0, over = 0, first_u = ~0u, first_o = ~0u;
@@ -1229,8 +1267,7 @@ static int recover_now(irs_hip_batch* b, uint32_t status) {
     if (const int all = all_ranks_can(b, can)) return all;
     const int rc = run_impl(b, b->stream);
     if (rc != IRS_HIP_OK) return rc;
-    if (!rt::d2h(&status, b->d_status.p, 4, b->stream) || !rt::sync(b->stream))
-      return IRS_HIP_EHIP;
+    if (!run_status(b, &status)) return IRS_HIP_EHIP;
     if (status & kStatusUnderflow) return IRS_HIP_EHIP;  // cannot happen with a sound threshold
   }
   return (status & kStatusOverflow) ? recover_overflow(b) : IRS_HIP_OK;
@@ -1269,8 +1306,9 @@ static int batch_results_impl(irs_hip_batch* b, irs_hip_hit* hits, uint32_t k_st
   const size_t hit_bytes = size_t(b->nq) * b->k_max * sizeof(Hit);
   if (b->sync.h_pin.n < hit_bytes && !b->sync.h_pin.alloc(hit_bytes)) return IRS_HIP_ENOMEM;
   const Hit* tmp = b->sync.h_pin.as<Hit>();
-  if (!rt::d2h(&status, b->d_status.p, 4, b->stream) || !rt::sync(b->stream))
-    return IRS_HIP_EHIP;
+  // (behind the run's own end — `done`, which may lie on the tail stream — AND, as ever, behind
+  // whatever else the caller's stream holds)
+  if (!run_status(b, &status) || !rt::sync(b->stream)) return IRS_HIP_EHIP;
   if (status & (kStatusOverflow | kStatusUnderflow)) {
     const int rc = recover(b, status);
     if (rc != IRS_HIP_OK) return rc;
@@ -1304,7 +1342,7 @@ static int verify_run(irs_hip_batch* b) {
   if (status & (kStatusOverflow | kStatusUnderflow)) {
     const int rc = recover(b, status);
     if (rc != IRS_HIP_OK) return rc;
-    if (!rt::sync(b->stream)) return IRS_HIP_EHIP;
+    if (!after_run(b)) return IRS_HIP_EHIP;
   }
   return verify_term_pass(b);
 }
@@ -1414,7 +1452,11 @@ void irs_hip_batch_destroy(irs_hip_batch* b) {
   if (b->sync.used_pending) waited = waited && b->sync.used.sync();
   if (b->sync.host_pending) waited = waited && b->sync.host.sync();
   if (b->sync.match_pending) waited = waited && b->sync.matched.sync();
-  if (!waited && b->ran) waited = rt::sync(b->stream);
+  if (!waited && b->ran) {
+    bool made = false;
+    rt::stream_t ts = tail_stream(b->seg->device, &made);
+    waited = rt::sync(b->stream) && (!b->sync.tail_used || !made || rt::sync(ts));
+  }
   release_streams(b, waited);   // (its pins in the device's stream cache)
   // (optional terms: the term pass reads this batch's d_taken — it goes first)
   if (b->opt) irs_hip_batch_destroy(b->opt);
@@ -1515,6 +1557,13 @@ int irs_hip_batch_paired_tiles(irs_hip_batch* b, int* used) {
   return settled(b, [&]() -> int {
     if (!b || !used) return IRS_HIP_EINVAL;
     *used = (b->join.on() && b->join.pairs_used) ? 1 : 0;
+    return IRS_HIP_OK;
+  });
+}
+int irs_hip_batch_tail_stream_used(irs_hip_batch* b, int* used) {
+  return settled(b, [&]() -> int {
+    if (!b || !used) return IRS_HIP_EINVAL;
+    *used = (b->ran && b->sync.tail_used) ? 1 : 0;
     return IRS_HIP_OK;
   });
 }
@@ -1619,7 +1668,8 @@ int irs_hip_batch_rescore_paths(irs_hip_batch* b, uint32_t paths[3]) {
     paths[0] = paths[1] = paths[2] = 0;
     if (!b->join.on() || !b->join.pairs_used) return IRS_HIP_OK;
     if (!rt::set_device(b->seg->device)) return IRS_HIP_EHIP;
-    if (!rt::d2h(paths, rescore_paths(b), 12, b->stream) || !rt::sync(b->stream)) return IRS_HIP_EHIP;
+    if (!run_done(b) || !rt::d2h(paths, rescore_paths(b), 12, b->stream) || !rt::sync(b->stream))
+      return IRS_HIP_EHIP;
     return IRS_HIP_OK;
   });
 }

@@ -886,7 +886,21 @@ bool join_half_ok(const irs_hip_batch* b) {
 // status word's line)
 uint32_t* rescore_paths(irs_hip_batch* b) { return b->d_zeroed.as<uint32_t>() + 4; }
 
-bool launch_join_score(irs_hip_batch* b, rt::stream_t st) {
+// A batch whose whole score stage is the one paired launch — the headline batch — ends its run on
+// the device's tail stream (pool.h): k_join_rescore and k_select beside the k_join_pilot of the next
+// batch.  Every other batch queues what it always did: a COUNT launch, work items, wide units, block-
+// driven units and phrases follow the paired launch in stream order, group thresholds and collectives
+// are ordered against other ranks, and the union of a batch with optional terms follows both passes.
+bool tail_ok(const irs_hip_batch* b) {
+  if (!b->knobs.tail_stream || b->term_pass || b->phrase || b->opt || b->groups.n || b->comm) return false;
+  if (!b->join.on() || b->join.n_plain != b->join.units.size()) return false;
+  if (!b->tiles.units.empty() || b->wide.on() || !b->blocks.units.empty() || !b->any.units.empty()) return false;
+  return join_half_ok(b) && b->join.img_on;
+}
+
+// `tail`: the stream k_join_rescore goes to (a batch that passes tail_ok: it waits for `scored`,
+// recorded behind the paired launch on `st`); null: everything on `st`
+bool launch_join_score(irs_hip_batch* b, rt::stream_t st, const rt::stream_t* tail) {
   // (paired tiles run on bound images, made at the deal: no images, no pairs)
   const bool half = join_half_ok(b) && b->join.img_on;
   b->join.pairs_used = half;
@@ -976,7 +990,8 @@ bool launch_join_score(irs_hip_batch* b, rt::stream_t st) {
     } else if (half) {
       // (join.d_order: the plain units first — one k_join_rescore workgroup each)
       RT_LAUNCH(k_join_score<kJKHalf>, grid, b->join.threads, smem, st, d_args);
-      RT_LAUNCH(k_join_rescore, n_units, kRescoreThreads, 0, st, b->join.d_order.as<uint32_t>(),
+      if (tail && !(rt::last_error_ok() && b->sync.scored.record(st) && b->sync.scored.wait(*tail))) return false;
+      RT_LAUNCH(k_join_rescore, n_units, kRescoreThreads, 0, tail ? *tail : st, b->join.d_order.as<uint32_t>(),
                 b->d_queries.as<DevQuery>(), b->d_qterms.as<DevQTerm>(), b->join.d_jterms.as<JoinTerm>(),
                 b->d_bstar.as<uint32_t>(), b->d_cands.as<uint64_t>(), b->d_cand_count.as<uint32_t>(),
                 b->cand_cap, rescore_paths(b));

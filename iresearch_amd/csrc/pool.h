@@ -192,22 +192,52 @@ struct Stager {
 // they would start only when the previous batch's kernels are through (0.2 ms of idle compute per
 // step for the headline batch's 5 MB); on their own stream they travel while those kernels run,
 // and the run waits for them by an event.
-inline rt::stream_t copy_stream(int device, int which) {
+// (`made`: whether the stream exists — the emulator's streams are all null)
+inline rt::stream_t copy_stream(int device, int which, bool* made = nullptr) {
+  struct Made { rt::stream_t s; bool ok; };
   static std::mutex m;
-  static std::map<int, rt::stream_t> streams;
+  static std::map<int, Made> streams;
   std::lock_guard<std::mutex> lock(m);
-  const int key = device * 2 + which;
+  const int key = device * 4 + which;
   auto it = streams.find(key);
-  if (it != streams.end()) return it->second;
-  rt::stream_t s = nullptr;
-  if (!rt::stream_create(&s)) s = nullptr;   // (null: the caller keeps its own stream)
-  streams[key] = s;
-  return s;
+  if (it == streams.end()) {
+    Made s{nullptr, false};
+    s.ok = rt::stream_create(&s.s);
+    if (!s.ok) s.s = nullptr;   // (null: the caller keeps its own stream)
+    it = streams.emplace(key, s).first;
+  }
+  if (made) *made = it->second.ok;
+  return it->second.s;
 }
 inline rt::stream_t upload_stream(int device) { return copy_stream(device, 0); }
 // ... and one for results on their way to page-locked host memory (irs_hip_batch_results_to_host):
 // the copy of batch i travels while the kernels of batch i + 1 run
 inline rt::stream_t download_stream(int device) { return copy_stream(device, 1); }
+
+// One tail stream per device: behind a batch whose whole score stage is the one paired launch
+// (k_join_score<kJKHalf>, which holds every wave slot of the chip), k_join_rescore and k_select
+// leave more than half of the slots empty — on a stream of their own they share the chip with
+// the k_join_pilot of the NEXT batch the caller has queued (tail_ok / queue_tail, irs_hip.hip).
+// `done`: re-recorded behind every tail; the score stage of every later run waits for the record
+// made last (a started k_join_score workgroup holds the LDS the previous k_select asks for).
+// The worker thread and callers with asynchronous runs off both come here: `m` is held across
+// the queuing of a whole tail and around every wait.
+struct Tail {
+  std::mutex m;
+  Event done;
+  bool recorded = false;
+};
+inline Tail& tail_of(int device) {
+  static Tail* tails = new Tail[pool::kMaxDevices];   // (never destroyed: the runtime may go first)
+  return tails[device >= 0 && device < pool::kMaxDevices ? device : 0];
+}
+inline rt::stream_t tail_stream(int device, bool* made) { return copy_stream(device, 2, made); }
+// `st` gets behind the tail queued last on the device
+inline bool wait_for_tail(int device, rt::stream_t st) {
+  Tail& t = tail_of(device);
+  std::lock_guard<std::mutex> lock(t.m);
+  return !t.recorded || t.done.wait(st);
+}
 
 // IRS_HIP_TRACE=1: host-side stage times on stderr (what a batch costs before its first kernel)
 struct HostTrace {

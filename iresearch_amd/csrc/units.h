@@ -584,6 +584,7 @@ int create_term_pass(irs_hip_batch* b, irs_hip_segment* const* segs, uint32_t n_
   if (const int rc = batch_create_multi_impl(segs, n_segs, cq.data(), b->nq_user, ct.data(),
                                              uint32_t(from.size()), &b->opt))
     return rc;
+  b->opt->term_pass = true;
   uint32_t max_docs = 0;
   for (uint32_t s = 0; s < n_segs; ++s) max_docs = std::max(max_docs, segs[s]->dev.num_docs);
   b->taken_words = uint64_t(max_docs) / 64u + 1u;

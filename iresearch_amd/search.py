@@ -861,6 +861,13 @@ class QueryBatch:
                    "irs_hip_batch_paired_tiles")
         return bool(v.value)
 
+    def tail_stream_used(self):
+        """Whether the last run ended on the device's tail stream (irs_hip_batch_tail_stream_used)."""
+        v = C.c_int(0)
+        _lib.check(self.L, self.L.irs_hip_batch_tail_stream_used(self.handle, C.byref(v)),
+                   "irs_hip_batch_tail_stream_used")
+        return bool(v.value)
+
     def set_wand(self, enable=True):
         """ExecutionContext::wand (index-search --search-mode wand): block-max pruning."""
         _lib.check(self.L, self.L.irs_hip_batch_set_wand(self.handle, int(enable)),

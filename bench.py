@@ -14,8 +14,18 @@ all-gather of per-segment top-k per step ("strong" scaling: total work fixed).
 Rank 0 prints ONE JSON line.  `value` is whole-job queries/sec with the index
 already resident in HBM.  `roofline` prices the dominant kernel (k_score)
 against HBM bandwidth using ALGORITHMIC bytes and its average
-duration measured with HIP events on the launch stream.  `cpu_baseline` is the
-oracle's restatement of utils/index-search timed on this host (N = 1, rank 0).
+duration measured with HIP events on the launch stream (the timed steps' own
+events: no run of its own).
+
+A plain run does what `value` needs and no more: set-up (which ends with three
+isolated steps: they fill the library's pool and stream cache, and the timed
+steps are measurably slower without them), warm-up, the timed steps, the dump,
+the line.  `--full` adds what takes runs of its own, and the line then carries
+it where a plain run prints null: `value_with_results_on_host` (the same steps
+with the hits copied to the host) and `cpu_baseline`, the oracle's restatement
+of utils/index-search timed on this host (N = 1, rank 0; `--no-cpu` leaves
+that leg out); with `--config 5`, the counted run behind
+`bytes_touched_per_step` and the roofline's `achieved`, and its `cpu_baseline`.
 `--dump-outputs DIR`: rank 0 also writes the top-k of the last timed step
 (scores, docs, counts; segments where merged) as DIR/<name>.npy, so that two builds
 run with the same arguments (same seeded inputs) can be compared output for output.
@@ -166,7 +176,11 @@ def main():
                          "block directory and open time at a real dictionary's size)")
     ap.add_argument("--tile", type=int, default=0)
     ap.add_argument("--stride", type=int, default=0)
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what `value` does not need, in runs of their own: the steps with "
+                         "results on the host, the counted run of config 5, the cpu_baseline (a plain "
+                         "run prints null for them)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the cpu_baseline leg")
     ap.add_argument("--two-streams", action="store_true",
                     help="config 5: queue the AND batch and the phrase batch on a stream each (measured: "
                          "41.3 against 42.0 ms per step, DESIGN.md §3.12; the stage times then overlap)")
@@ -292,6 +306,8 @@ def main():
     # --query-sets N > 0: the round-1..3 protocol (N persistent batches replayed in rotation).
     replay = args.query_sets > 0
     n_probe = 3            # isolated (unpipelined) fresh batches, timed one by one
+    # (n_host: the steps with results on the host, --full.  A plain run draws their query sets
+    # too, so that a step's number means the same set of queries with and without --full)
     n_host = 0 if world > 1 else max(2, min(args.steps, 20))
     n_rows = max(1, args.query_sets) if replay else min(64, n_probe + args.warmup + args.steps + n_host + 2)
     rank_sets = [synth.make_queries(args.queries, args.terms, 16, 4096,
@@ -430,7 +446,11 @@ def main():
 
     # isolated executions of never-seen batches (no pipelining: host preparation + kernels +
     # verification in sequence), timed one by one — includes whatever re-run a misled threshold
-    # estimate costs; the first also pays the allocations the pool keeps from then on
+    # estimate costs; the first also pays the allocations the pool keeps from then on.
+    # They stay in a run without --full: `value` is defined behind them.  They fill the library's
+    # pool and its stream cache, and without them the same timed steps measured 0.4 % slower at
+    # --warmup 5, 7 % at --warmup 1 and 45 % at --warmup 0 (k_join decodes what the cache does not
+    # hold yet).  Together they take some 30 ms, and reading the clock around them is free.
     first_ms = []
     for _ in range(n_rows if replay else n_probe):
         sync()
@@ -471,9 +491,9 @@ def main():
             dump = topk_arrays(ex.send[:nq * k].view(nq, k), ex.send[ex.hit_words:].view(torch.int32)[:nq])
         write_outputs(args.dump_outputs, dump)
     reruns_timed = total_reruns() - reruns_warm
-    # the same steps with the hits copied to host memory in every step (not `value`)
+    # --full: the same steps with the hits copied to host memory in every step (not `value`)
     host_elapsed = None
-    if n_host:
+    if n_host and args.full:
         for _ in range(2):               # (warm-up: the page-locked result buffers enter the pool)
             step(host_results=True)
         flush()
@@ -595,7 +615,7 @@ def main():
                               if comm_thr is not None else "one per query and rank")},
             "roofline": roof,
         }
-    if rank == 0 and not multi and not args.no_cpu:
+    if rank == 0 and not multi and args.full and not args.no_cpu:
         for bs in (batch_sets or []):
             for b in bs.values():
                 b.close()
@@ -797,15 +817,18 @@ def main_config5(args):
         elapsed = float(t.item())
     bat = make_batches(0)
     alg = {n: b.work() for n, b in bat.items()}
-    # what the kernels really decoded: one extra, untimed run with the counters on
-    touched = {}
-    for n, b in bat.items():
-        b.profile(3)
-        b.run(sptr)
-        b.results()
-        touched[n] = b.touched()
-    vals = [alg["and"][0], alg["phrase"][0], touched["and"][0], touched["phrase"][0],
-            touched["phrase"][1]]
+    # --full: what the kernels really decoded: one extra, untimed run with the counters on
+    touched = None
+    if args.full:
+        touched = {}
+        for n, b in bat.items():
+            b.profile(3)
+            b.run(sptr)
+            b.results()
+            touched[n] = b.touched()
+    vals = [alg["and"][0], alg["phrase"][0]]
+    if touched is not None:
+        vals += [touched["and"][0], touched["phrase"][0], touched["phrase"][1]]
     if world > 1:
         t = torch.tensor(vals, dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.SUM)
@@ -814,8 +837,10 @@ def main_config5(args):
         ms = {n: float(np.mean([x[n][_lib.K_SCORE] for x in kms])) for n in bat}
         stages = {n: [round(float(v), 4) for v in np.mean([x[n] for x in kms], axis=0)] for n in bat}
         tr5 = measured_traffic("traffic_config5_latest.json") if world == 1 else None
-        rank0_touched = touched["and"][0] + touched["phrase"][0]
         rank0_alg = alg["and"][0] + alg["phrase"][0]
+        kernel_s = (ms["and"] + ms["phrase"]) * 1e-3
+        # bytes actually decoded over kernel time (--full: the counted run above; null without it)
+        achieved = None if touched is None else (touched["and"][0] + touched["phrase"][0]) / kernel_s / 1e9
         out = {
             "metric": "queries/sec AND + by_phrase (positions), block-max WAND, TF-IDF, 50M-doc index @N GPU",
             "value": round(args.steps * 2 * nq / elapsed, 2), "unit": "queries/s", "n_gpus": world,
@@ -829,7 +854,8 @@ def main_config5(args):
                             "AND batch" % (nq, nq, k, docs, n_segments),
                 "segments": n_segments, "queries_per_step": 2 * nq,
                 "algorithmic_bytes_per_step": {"and": int(vals[0]), "phrase_doc_side": int(vals[1])},
-                "bytes_touched_per_step": {"and_doc_and_norm": int(vals[2]),
+                "bytes_touched_per_step": None if touched is None else
+                                          {"and_doc_and_norm": int(vals[2]),
                                            "phrase_doc": int(vals[3]),
                                            "phrase_positions_read": int(vals[4])},
                 "batches": "every step creates, runs and destroys its two batches (%d query sets in "
@@ -845,11 +871,11 @@ def main_config5(args):
                 "rccl_library": None if comm is None else comm.library(),
                 "ranks_seen": None if comm is None else comm.ranks_seen},
             "roofline": {"bound": "hbm", "kernel": "k_conj + k_phrase (rank 0)",
-                         "achieved": round(rank0_touched / ((ms["and"] + ms["phrase"]) * 1e-3) / 1e9, 2),
+                         "achieved": None if achieved is None else round(achieved, 2),
                          "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(rank0_touched / ((ms["and"] + ms["phrase"]) * 1e-3) / 1e9 / HBM_PEAK_GBS, 5),
+                         "frac": None if achieved is None else round(achieved / HBM_PEAK_GBS, 5),
                          "peak_measured": HBM_MEASURED_GBS,
-                         "frac_of_measured": round(rank0_touched / ((ms["and"] + ms["phrase"]) * 1e-3) / 1e9 / HBM_MEASURED_GBS, 5),
+                         "frac_of_measured": None if achieved is None else round(achieved / HBM_MEASURED_GBS, 5),
                          # (name and launch time only: the AND stage's bytes are not its)
                          "dominant_kernel": {"name": "k_phrase2" if ms["phrase"] >= ms["and"] else "k_conj",
                                              "stage_ms": round(max(ms["phrase"], ms["and"]), 4)},
@@ -861,15 +887,15 @@ def main_config5(args):
                          # the same kernel time priced on A(q): every byte of the queries' lists
                          # (what the reference's iterators would at most decode)
                          "on_algorithmic_bytes": {
-                             "achieved": round(rank0_alg / ((ms["and"] + ms["phrase"]) * 1e-3) / 1e9, 2),
-                             "frac": round(rank0_alg / ((ms["and"] + ms["phrase"]) * 1e-3) / 1e9 / HBM_PEAK_GBS, 5)},
+                             "achieved": round(rank0_alg / kernel_s / 1e9, 2),
+                             "frac": round(rank0_alg / kernel_s / 1e9 / HBM_PEAK_GBS, 5)},
                          "stage_ms": {"order": ["plan", "pilot", "score", "select"], **stages},
                          "note": "achieved = bytes actually decoded / kernel time (block-driven "
-                                 "kernels touch less than A(q))"},
+                                 "kernels touch less than A(q)); counted in a run of its own: --full"},
             "cpu_baseline": None,
         }
         out["config"]["host_ms_between_steps"] = step_marks_ms   # (the last entry: flush)
-        if world == 1 and not sim and not args.no_cpu:
+        if world == 1 and not sim and args.full and not args.no_cpu:
             for b in bat.values():
                 b.close()
             out["cpu_baseline"] = cpu_baseline_config5([segs[s] for s in range(n_segments)], ands,

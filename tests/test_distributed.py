@@ -408,7 +408,8 @@ def test_bench_is_launchable_on_two_ranks(simlib):
 def test_bench_config5_is_launchable_on_two_ranks(simlib):
     """`bench.py --config 5` (AND + by_phrase, TF-IDF, block-max WAND, segments with positions
     sharded over ranks) under the driver's launch line, emulator dry run: two batches per rank
-    and step, two exchanges, ONE JSON line with the bytes actually decoded."""
+    and step, two exchanges, ONE JSON line with the bytes actually decoded (--full: the counted
+    run behind them is not part of a plain run)."""
     import json
     import subprocess
     import sys
@@ -418,7 +419,8 @@ def test_bench_config5_is_launchable_on_two_ranks(simlib):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(port),
            os.path.join(root, "bench.py"), "--config", "5", "--gpus", "2", "--steps", "2",
-           "--warmup", "1", "--docs", "40000", "--queries", "6", "--k", "20", "--segments", "4"]
+           "--warmup", "1", "--docs", "40000", "--queries", "6", "--k", "20", "--segments", "4",
+           "--full"]
     out = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -471,3 +473,40 @@ def test_bench_dumps_the_last_timed_step(simlib, tmp_path):
         assert np.array_equal(got["scores"][q, :n], hits["score"][q, :n]), q
         assert np.array_equal(got["docs"][q, :n], hits["doc"][q, :n]), q
         assert (got["docs"][q, n:] == -1).all() and (got["scores"][q, n:] == 0).all(), q
+
+
+def test_bench_full_adds_its_legs_and_keeps_the_timed_steps(simlib, tmp_path):
+    """A plain `bench.py` run (emulator dry run) carries null where `--full` measures in runs of
+    its own — the steps with results on the host, the CPU baseline — and both runs time the
+    same steps behind the same three isolated ones: the same line otherwise, the same dumped
+    top-k."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, IRS_BENCH_SIM=simlib._name, OMP_NUM_THREADS="1")
+    nq, k, warmup, steps = 5, 20, 1, 2
+    lines = {}
+    for name, extra in (("plain", []), ("full", ["--full", "--no-cpu"])):
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(steps),
+               "--warmup", str(warmup), "--docs", "48000", "--queries", str(nq), "--k", str(k),
+               "--dump-outputs", str(tmp_path / name)] + extra
+        out = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=900)
+        assert out.returncode == 0, out.stderr[-3000:]
+        found = [l for l in out.stdout.splitlines() if l.startswith("{")]
+        assert len(found) == 1, out.stdout
+        lines[name] = json.loads(found[0])
+    plain, full = lines["plain"], lines["full"]
+    assert plain["value_with_results_on_host"] is None and plain["cpu_baseline"] is None
+    assert full["value_with_results_on_host"] > 0 and full["cpu_baseline"] is None   # (--no-cpu)
+    for d in (plain, full):
+        assert d["value"] > 0 and d["ms_per_step"] > 0 and d["roofline"]["kernel_ms"]
+        assert len(d["config"]["first_run_ms_per_set"]) == 3
+        assert d["steps"] == steps and d["warmup"] == warmup
+    for key in ("metric", "unit", "higher_is_better", "dtype"):
+        assert plain[key] == full[key], key
+    cfg = ("workload", "query_sets", "postings_per_step", "algorithmic_bytes_per_step", "path")
+    assert [plain["config"][c] for c in cfg] == [full["config"][c] for c in cfg]
+    for n in ("scores", "docs", "counts", "query_rows"):
+        a, b = (np.load(tmp_path / name / (n + ".npy")) for name in ("plain", "full"))
+        assert a.dtype == b.dtype and np.array_equal(a, b), n

@@ -7,7 +7,7 @@
 #   tests          pytest -m gpu                                   -> TAG_gpu_tests.txt
 #   smoke          __graft_entry__.smoke()
 #   tune           tools/join_tune.py --runs "$RUNS"               -> TAG_tune.txt
-#   bench          bench.py as the driver runs it (cpu baseline)   -> TAG_bench_plain.json
+#   bench          bench.py --full (every leg, cpu baseline)       -> TAG_bench_plain.json
 #   quick          bench.py --no-cpu, short                        -> TAG_bench_quick.json
 #   stats          bench.py under --kernel-trace --stats           -> TAG_stats/
 #   pmc            the six counter groups over bench.py            -> TAG_pmc_<i>/
@@ -45,7 +45,7 @@ for stage in "$@"; do
     tests) (cd $R && timeout 1500 python -m pytest tests -m gpu -q ${PYTEST_ARGS} > $O/${TAG}_gpu_tests.txt 2>&1; tail -3 $O/${TAG}_gpu_tests.txt) ;;
     smoke) (cd $R && python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1) ;;
     tune) (cd $R && timeout 900 python tools/join_tune.py --runs $RUNS ${TUNE_ARGS} 2>&1 | grep -E "path|Error|error" | tee $O/${TAG}_tune.txt) ;;
-    bench) py $R/bench.py --gpus 1 --steps ${STEPS:-20} --warmup 5 > $O/${TAG}_bench_plain.json 2> $O/${TAG}_bench_plain.err; line $O/${TAG}_bench_plain.json ;;
+    bench) py $R/bench.py --gpus 1 --steps ${STEPS:-20} --warmup 5 --full > $O/${TAG}_bench_plain.json 2> $O/${TAG}_bench_plain.err; line $O/${TAG}_bench_plain.json ;;
     quick) py $R/bench.py --steps ${STEPS:-10} --warmup 3 --no-cpu ${BENCH_ARGS} > $O/${TAG}_bench_quick.json 2> $O/${TAG}_bench_quick.err; line $O/${TAG}_bench_quick.json ;;
     stats) rocprofv3 --kernel-trace --stats -d $O/${TAG}_stats -o $TAG --output-format csv -- \
              python $R/bench.py --steps 5 --warmup 3 --no-cpu > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err; line $O/${TAG}_bench.json ;;
@@ -53,11 +53,11 @@ for stage in "$@"; do
            rocprofv3 --pmc $grp -d $O/${TAG}_pmc_$i -o p --output-format csv -- \
              python $R/bench.py --steps 2 --warmup 1 --no-cpu > $O/${TAG}_pmc_$i.log 2>&1; echo "group $i rc=$?"; done ;;
     pmc_tune) bash $R/tools/gpu/pmc_join.sh $TAG $RUNS ;;
-    replay) py $R/bench.py --steps 20 --warmup 5 --no-cpu --query-sets 4 > $O/${TAG}_bench_replay.json 2>/dev/null; line $O/${TAG}_bench_replay.json ;;
+    replay) py $R/bench.py --steps 20 --warmup 5 --full --no-cpu --query-sets 4 > $O/${TAG}_bench_replay.json 2>/dev/null; line $O/${TAG}_bench_replay.json ;;
     seg) rocprofv3 --kernel-trace --stats -d $O/${TAG}_stats_seg -o ${TAG}seg --output-format csv -- \
            python $R/bench.py --steps 5 --warmup 2 --force-segments --no-cpu > $O/${TAG}_bench_seg.json 2> $O/${TAG}_bench_seg.err; line $O/${TAG}_bench_seg.json ;;
     shares) bash $R/tools/gpu/shares.sh 2>/dev/null | tee $O/${TAG}_shares.txt ;;
-    c5) py $R/bench.py --config 5 --steps ${STEPS:-5} --warmup 5 ${C5_ARGS} > $O/${TAG}_bench_c5.json 2> $O/${TAG}_bench_c5.err; line $O/${TAG}_bench_c5.json ;;
+    c5) py $R/bench.py --config 5 --steps ${STEPS:-5} --warmup 5 --full ${C5_ARGS} > $O/${TAG}_bench_c5.json 2> $O/${TAG}_bench_c5.err; line $O/${TAG}_bench_c5.json ;;
     c5stats) rocprofv3 --kernel-trace --stats -d $O/${TAG}_stats_c5 -o ${TAG}c5 --output-format csv -- \
                python $R/bench.py --config 5 --steps 3 --warmup 4 --no-cpu > $O/${TAG}_bench_c5_rocprof.json 2> $O/${TAG}_bench_c5_rocprof.err; line $O/${TAG}_bench_c5_rocprof.json ;;
     c5pmc) i=0; for grp in "FETCH_SIZE" "WRITE_SIZE"; do i=$((i+1))

@@ -1,7 +1,9 @@
 // batch.h — the state of a batch: what every execution path reads at the top level, and one record
 // per path (work items in doc tiles, joined posting streams, wide multi-term units, block-driven
 // conjunctions and phrases),
-// for thresholds shared across segments and for a run's place on the streams.
+// for thresholds shared across segments and for a run's place on the streams (RunSync) — and, at
+// the end, the waits of a batch: one function per thing a caller is about to touch (a run, a plan
+// stage, match sets, a setter's re-deal, a reader of the last run, destroy).  The run itself: run.h.
 // The unit lists and who fills them (units.h: commit_unit is create's only writer per unit):
 //   all_tile_units, all_conj_units, wide.units   commit_unit, fixed at create
 //   blocks.units   a phrase batch: build_phrase_work at create; else deal_units, from all_conj_units
@@ -235,11 +237,15 @@ struct Groups {
   std::vector<double> upper;   // [unit] a score bound that is the same on every segment, 0: none
 };
 
-// A run's place on the streams, what waits for it, and where its results land on the host
+// A run's place on the streams, what waits for it, and where its results land on the host.  Whoever
+// touches a batch's buffers asks for its waits by name (the functions at the end of this file); the
+// Pendings here are recorded and read by those and by the stages of a run (run.h) only.
 struct RunSync {
-  // what verify_run waits for: the batch's OWN last run (not whatever else the caller has
-  // queued on the stream since), and the status word that run left in page-locked memory
-  Event done;
+  // the end of the batch's OWN last run (not whatever else the caller has queued on the stream
+  // since), and the status word that run left in page-locked memory.  Pending: a run recorded it —
+  // it stays so for the batch's life, a host wait does not clear it (sync_keep: later stream waits
+  // for the same run are issued all the same)
+  Pending done;
   PinBuf h_status;
   // a run whose score stage is the one paired launch (tail_ok) ends on the device's tail stream:
   // `scored` lies behind k_join_score<kJKHalf> on the caller's stream, the tail waits for it, and
@@ -247,28 +253,24 @@ struct RunSync {
   // stream behind `scored`: whoever reads what the run leaves gets behind `done`
   Event scored;
   bool tail_used = false;      // the last run took the tail stream
-  // irs_hip_batch_plan: the planning stage of the NEXT run was queued ahead (on another stream)
-  Event plan;
-  bool planned = false;        // ... and the next run may use it (same geometry)
-  // a plan stage is queued on some stream and may still be running — whether or not the next run
-  // will use its tables (`planned` is dropped by every setter that re-deals the units; the kernels
-  // it queued keep reading and writing the batch's buffers until `plan`)
-  bool plan_pending = false;
-  // the last copy OUT of the batch's buffers queued by irs_hip_batch_results_to_device (destroy
-  // waits for it and for `done` — never for the stream, which may hold other batches' work)
-  Event used;
-  bool used_pending = false;
+  // irs_hip_batch_plan: the planning stage of the NEXT run was queued ahead (on another stream).
+  // Pending whether or not the next run will use its tables: the kernels it queued keep reading and
+  // writing the batch's buffers
+  Pending plan;
+  bool planned = false;        // ... and the next run may use it (same geometry: deal_is_stale drops it)
+  // the last copy OUT of the batch's buffers queued by irs_hip_batch_results_to_device
+  Pending used;
   // the last irs_hip_batch_match_sets_to_device queued on some stream: it reads the exclusion masks
-  // and the match tables (a run, a setter's re-deal and destroy get behind it)
-  Event matched;
-  bool match_pending = false;
+  // and the match tables
+  Pending matched;
   Event uploaded;   // the first run's table uploads (the device's copy stream)
   Event prof[2 * IRS_HIP_K_COUNT];   // irs_hip_batch_profile: around every stage of a run
   PinBuf h_pin;                // page-locked staging for irs_hip_batch_results
   // irs_hip_batch_results_to_host: hits, counts and totals in page-locked memory of the batch
+  // (`host` pending: the copy may be in flight AND h_res holds the last run's results — the next
+  // run settles it, irs_hip_batch_host_results refuses from then on)
   PinBuf h_res;
-  Event host;
-  bool host_pending = false;
+  Pending host;
   // irs_hip_batch_run hands the host half of a run (units dealt, streams and work lists built,
   // uploads and launches queued: ~1 ms for 1000 queries) to the device's worker thread and returns;
   // every other entry point waits here for it first.  async_rc: what that run returned.
@@ -373,6 +375,95 @@ static uint32_t default_cand_cap(const irs_hip_batch* b) {
   if (b->phrase || !b->all_conj_units.empty() || !b->any.units.empty())
     for (const irs_hip_segment* sg : b->segs) learned = std::max<uint64_t>(learned, sg->cand_cap_hint.load());
   return uint32_t(std::min<uint64_t>(std::max<uint64_t>({per_k * b->k_max, 16384, learned}), 262144));
+}
+
+// ---- the waits of a batch, once each, by what the caller is about to touch ----------------------
+// (a Pending that was never recorded waits for nothing: none of these asks whether there was a run,
+// a plan queued ahead, a copy)
+
+// The host is about to read what the last run left (status word, results, timings, unit masks,
+// doc-set tallies): behind that run's own end — not behind the stream, see RunSync::scored.
+static bool run_done(const irs_hip_batch* b) { return b->sync.done.sync_keep(); }
+// ... AND behind whatever else is queued on that run's stream
+static bool after_run(const irs_hip_batch* b) {
+  const bool ok = run_done(b);
+  return rt::sync(b->stream) && ok;
+}
+// A copy queued on `st` is about to read what the last run left: `st` behind that run's end
+static bool run_done_on(const irs_hip_batch* b, rt::stream_t st) { return b->sync.done.wait(st); }
+// The status word of the batch's last run, out of the page-locked word that run copied it to
+static bool run_status(const irs_hip_batch* b, uint32_t* status) {
+  if (!b->sync.h_status.p || !run_done(b)) return false;
+  *status = *b->sync.h_status.as<uint32_t>();
+  return true;
+}
+
+// The host is about to re-deal the units (buffers are reallocated, tables rewritten): whatever of
+// the batch is still queued is through — a plan stage queued ahead, its last run and that run's
+// stream, match sets on another stream.
+static bool quiesce(irs_hip_batch* b) {
+  bool ok = b->sync.plan.sync();
+  if (b->ran) ok = after_run(b) && ok;
+  return b->sync.matched.sync() && ok;
+}
+
+// A plan stage is about to rewrite the plan tables and the masks on `st`: behind the batch's last
+// run (it reads them), a plan queued earlier and never used (it may run on ANOTHER stream), match
+// sets on another stream (they read the masks).
+static bool plan_get_behind(const irs_hip_batch* b, rt::stream_t st) {
+  return b->sync.done.wait(st) && b->sync.plan.wait(st) && b->sync.matched.wait(st);
+}
+
+// Match sets are about to read the masks and the tables on `st`, and to rewrite the masks: behind a
+// plan stage and a run (they write the masks and may have the tables in flight) and an earlier
+// call's kernels on another stream.
+static bool match_get_behind(const irs_hip_batch* b, rt::stream_t st) {
+  return b->sync.plan.wait(st) && b->sync.done.wait(st) && b->sync.matched.wait(st);
+}
+
+// A run is about to rewrite the batch's tables and outputs on `st`, and — a first run with tables
+// staged since create — to upload on the device's copy stream (*up_st, else null).  Behind:
+//   host      a copy of the PREVIOUS run's results to host memory may still read d_out / d_hits
+//             (those host results are stale from here on: irs_hip_batch_host_results refuses them)
+//   done      the batch's own last run, if it ended on the tail stream (a replay, a recovery
+//             re-run): stream order on `st` does not cover that tail
+//   plan      a plan stage still queued — used by this run or made stale by a setter — reads and
+//             writes the tables this run uploads and rewrites: both streams
+//   matched   match sets on another stream read the masks and the tables: both streams
+// `host` and `matched` are settled here though only a stream waited: whatever touches these
+// buffers later — a run, a plan stage, match sets, a setter, destroy — gets behind this run's
+// `done`, which is recorded behind everything `st` has waited for.
+static bool run_get_behind(irs_hip_batch* b, rt::stream_t st, rt::stream_t* up_st) {
+  RunSync& s = b->sync;
+  if (!s.host.wait(st)) return false;
+  s.host.settle();
+  if (s.tail_used && !s.done.wait(st)) return false;
+  if (!s.plan.wait(st)) return false;
+  *up_st = (!b->ran && !b->up.pending.empty()) ? upload_stream(b->seg->device) : nullptr;
+  if (*up_st && !s.plan.wait(*up_st)) return false;
+  if (!s.matched.wait(st) || (*up_st && !s.matched.wait(*up_st))) return false;
+  s.matched.settle();
+  return true;
+}
+
+// The batch is about to go away, its buffers back to the pool: every piece of queued work that
+// touches them is through — its own last run, a plan queued ahead, copies out of d_out, match sets.
+// Not the caller's stream, which may hold the NEXT batch.  false: a wait failed, or a run ended
+// without recording its end (the caller falls back to the streams themselves).
+static bool quiet_for_destroy(irs_hip_batch* b) {
+  RunSync& s = b->sync;
+  const bool ended = !b->ran || s.done.pending();
+  return s.done.sync() && s.plan.sync() && s.used.sync() && s.host.sync() && s.matched.sync() && ended;
+}
+
+// A setter is about to change what the deal of the units depends on: the batch's device, and the
+// batch quiet ...
+static bool quiet_for_setter(irs_hip_batch* b) { return rt::set_device(b->seg->device) && quiesce(b); }
+// ... and afterwards the deal is made anew, and a plan queued ahead — made for the old geometry,
+// path, masks — is not used: the next run plans inline
+static void deal_is_stale(irs_hip_batch* b) {
+  b->scratch_ready = false;
+  b->sync.planned = false;
 }
 
 }  // namespace

@@ -625,36 +625,6 @@ static int batch_create_multi_impl(irs_hip_segment* const* segs, uint32_t n_segs
   return IRS_HIP_ENOMEM;
 }
 
-// The host gets behind the batch's last run AND whatever else is queued on its stream.  The run
-// itself may have ended on the device's tail stream: `done` marks its end, the stream does not.
-static bool run_done(const irs_hip_batch* b) { return !b->sync.done.made || b->sync.done.sync(); }
-static bool after_run(irs_hip_batch* b) {
-  const bool ok = run_done(b);
-  return rt::sync(b->stream) && ok;
-}
-// The status word of the batch's last run, out of the page-locked word that run copied it to
-static bool run_status(const irs_hip_batch* b, uint32_t* status) {
-  if (!b->sync.h_status.p || !b->sync.done.sync()) return false;
-  *status = *b->sync.h_status.as<uint32_t>();
-  return true;
-}
-
-// Before a setter re-deals the units (buffers are reallocated, tables rewritten): whatever of the
-// batch is still queued must be through — its last run AND a plan stage queued ahead.
-static bool quiesce(irs_hip_batch* b) {
-  bool ok = true;
-  if (b->sync.plan_pending) {
-    ok = b->sync.plan.sync();
-    b->sync.plan_pending = false;
-  }
-  if (b->ran) ok = after_run(b) && ok;
-  if (b->sync.match_pending) {
-    ok = b->sync.matched.sync() && ok;
-    b->sync.match_pending = false;
-  }
-  return ok;
-}
-
 static int batch_configure_impl(irs_hip_batch* b, uint32_t tile_docs, uint32_t pilot_stride,
                             uint32_t cand_cap) {
   if (!b) return IRS_HIP_EINVAL;
@@ -662,13 +632,11 @@ static int batch_configure_impl(irs_hip_batch* b, uint32_t tile_docs, uint32_t p
       tile_docs != 12288)
     return IRS_HIP_EINVAL;
   if (cand_cap && cand_cap < b->k_max) return IRS_HIP_EINVAL;
-  if (!rt::set_device(b->seg->device)) return IRS_HIP_EHIP;
-  if (!quiesce(b)) return IRS_HIP_EHIP;
+  if (!quiet_for_setter(b)) return IRS_HIP_EHIP;
   if (!b->phrase) b->tiles.asked = b->tiles.docs = tile_docs;  // phrase tiles are fixed; 0: by the units' needs
   if (pilot_stride) b->stride = pilot_stride;
   b->cand_cap = cand_cap;
-  b->scratch_ready = false;
-  b->sync.planned = false;   // a plan queued ahead used the old geometry: run() plans inline
+  deal_is_stale(b);
   // (optional terms: the term pass takes the tile, and the same stride and candidate slots)
   if (b->opt) return batch_configure_impl(b->opt, tile_docs, pilot_stride, cand_cap);
   return IRS_HIP_OK;
@@ -676,21 +644,17 @@ static int batch_configure_impl(irs_hip_batch* b, uint32_t tile_docs, uint32_t p
 
 static int batch_set_path_impl(irs_hip_batch* b, int path) {
   if (!b || path < IRS_HIP_PATH_AUTO || path > IRS_HIP_PATH_JOINED) return IRS_HIP_EINVAL;
-  if (!rt::set_device(b->seg->device)) return IRS_HIP_EHIP;
-  if (!quiesce(b)) return IRS_HIP_EHIP;
+  if (!quiet_for_setter(b)) return IRS_HIP_EHIP;
   b->path_pref = path;
-  b->scratch_ready = false;
-  b->sync.planned = false;   // (a plan queued ahead was made for the other path)
+  deal_is_stale(b);
   return IRS_HIP_OK;
 }
 
 static int batch_set_shared_threshold_impl(irs_hip_batch* b, int enable) {
   if (!b) return IRS_HIP_EINVAL;
-  if (!rt::set_device(b->seg->device)) return IRS_HIP_EHIP;
-  if (!quiesce(b)) return IRS_HIP_EHIP;
+  if (!quiet_for_setter(b)) return IRS_HIP_EHIP;
   b->groups.shared = enable != 0;
-  b->scratch_ready = false;
-  b->sync.planned = false;
+  deal_is_stale(b);
   if (b->opt) return batch_set_shared_threshold_impl(b->opt, enable);   // (both passes)
   return IRS_HIP_OK;
 }
@@ -699,25 +663,19 @@ static int batch_set_comm_impl(irs_hip_batch* b, irs_hip_comm* comm) {
   if (!b) return IRS_HIP_EINVAL;
   if (b->opt) return IRS_HIP_EUNSUPPORTED;   // (optional terms: two passes, one rank)
   if (b->wide.on()) return IRS_HIP_EUNSUPPORTED;   // (wide units keep thresholds of their own)
-  if (!rt::set_device(b->seg->device)) return IRS_HIP_EHIP;
-  if (!quiesce(b)) return IRS_HIP_EHIP;
+  if (!quiet_for_setter(b)) return IRS_HIP_EHIP;
   if (comm && !b->groups.d_agree.p && !b->groups.d_agree.alloc(64)) return IRS_HIP_ENOMEM;
   b->comm = comm;
-  b->scratch_ready = false;
-  b->sync.planned = false;
+  deal_is_stale(b);
   return IRS_HIP_OK;
 }
 
 static int batch_set_paired_tiles_impl(irs_hip_batch* b, int enable) {
   if (!b) return IRS_HIP_EINVAL;
-  if (!rt::set_device(b->seg->device)) return IRS_HIP_EHIP;
-  if (!quiesce(b)) return IRS_HIP_EHIP;
+  if (!quiet_for_setter(b)) return IRS_HIP_EHIP;
   const bool allowed = enable != 0, forced = enable == 2;
-  if (allowed != b->join.pairs_allowed || forced != b->join.pairs_forced) {
-    // (the deal makes bound images only for a launch that will run paired: dealt anew)
-    b->scratch_ready = false;
-    b->sync.planned = false;
-  }
+  // (the deal makes bound images only for a launch that will run paired: dealt anew)
+  if (allowed != b->join.pairs_allowed || forced != b->join.pairs_forced) deal_is_stale(b);
   b->join.pairs_allowed = allowed;
   b->join.pairs_forced = forced;
   return IRS_HIP_OK;
@@ -725,13 +683,11 @@ static int batch_set_paired_tiles_impl(irs_hip_batch* b, int enable) {
 static int batch_set_wand_impl(irs_hip_batch* b, int enable) {
   if (!b) return IRS_HIP_EINVAL;
   if (b->ran) return IRS_HIP_EINVAL;   // before the first run: the segment records are uploaded once
-  if (!rt::set_device(b->seg->device)) return IRS_HIP_EHIP;
-  if (!quiesce(b)) return IRS_HIP_EHIP;
+  if (!quiet_for_setter(b)) return IRS_HIP_EHIP;
   if (b->opt) return IRS_HIP_OK;   // (optional terms: neither pass is pruned)
   b->wand = enable != 0;
-  // a plan queued ahead (irs_hip_batch_plan) was made without the tile bounds: run() re-plans
-  b->sync.planned = false;
-  b->scratch_ready = false;   // (which path the batch takes depends on it)
+  // (which path the batch takes depends on it; a plan queued ahead was made without the tile bounds)
+  deal_is_stale(b);
   if (!b->wand) return IRS_HIP_OK;
   std::vector<DevSegment> dsegs;
   for (irs_hip_segment* sg : b->segs) {
@@ -821,8 +777,7 @@ static int batch_set_doc_sets_impl(irs_hip_batch* b, const void* sets, bool host
   x.set_words = x.sets_on() ? n_words : 0;
   if (!x.sets_on()) x.sets = nullptr;
   b->match.built = false;   // (the match units carry the masks' addresses)
-  b->scratch_ready = false;
-  b->sync.planned = false;  // a plan queued ahead was made for the old masks: run() plans inline
+  deal_is_stale(b);
   const int rc2 = build_masks(b);
   return rc != IRS_HIP_OK ? rc : rc2;
 }
@@ -835,7 +790,7 @@ static int batch_doc_set_stats_impl(irs_hip_batch* b, uint64_t* tiles, uint64_t*
   uint64_t t = 0, ts = 0, l[2] = {0, 0};
   const ExclWork& x = b->excl;
   if (x.sets_on()) {
-    if (!b->sync.done.sync()) return IRS_HIP_EHIP;
+    if (!run_done(b)) return IRS_HIP_EHIP;
     if (!b->phrase && !b->tiles.units.empty()) {
       std::vector<uint8_t> live(b->tiles.n_total);
       if (!live.empty() && (!rt::d2h(live.data(), x.d_tile_live.p, live.size(), nullptr) || !rt::sync(nullptr)))
@@ -856,23 +811,6 @@ static int batch_doc_set_stats_impl(irs_hip_batch* b, uint64_t* tiles, uint64_t*
   if (leads) *leads = l[0];
   if (leads_skipped) *leads_skipped = l[1];
   return IRS_HIP_OK;
-}
-
-// The caller's min scores as score bins, in the scale the units bin with NOW: ensure_scratch may
-// have re-scaled a unit (build_groups: one bound for a query on every rank), so this runs behind it.
-static bool stage_min_bins(irs_hip_batch* b) {
-  if (!b->has_min || !b->min_dirty) return true;
-  std::vector<uint32_t> bins(b->nq, 0u);
-  for (uint32_t u = 0; u < b->nq; ++u) {
-    // the bin score_bin() puts a score of m into: docs at or above m land in it or higher
-    const float x = std::fmin(b->min_scores[u] * b->queries[u].bin_scale, float(kBins - 1));
-    bins[u] = uint32_t(x);
-  }
-  if (!b->up.copy(b->d_min_bin.p, bins.data(), bins.size() * 4) ||
-      !b->up.copy(b->d_min_score.p, b->min_scores.data(), b->min_scores.size() * 4))
-    return false;
-  b->min_dirty = false;
-  return true;
 }
 
 static int comm_init_rank_impl(int32_t device, const uint8_t* id, int32_t n_ranks, int32_t rank,
@@ -929,31 +867,11 @@ static int batch_profile_impl(irs_hip_batch* b, int enable) {
   return IRS_HIP_OK;
 }
 
-// The planning stage of a run: tile -> first block tables, per-term records, the work items of
-// the tile kernels.  A pure function of (batch, segments): it touches nothing a run of ANOTHER
-// batch reads, so a caller may queue it ahead on a second stream (irs_hip_batch_plan).
-static bool plan_stage(irs_hip_batch* b, rt::stream_t st) {
-  auto mark = [&](int i) { return !b->profile || b->sync.prof[i].record(st); };
-  bool ok = mark(2 * IRS_HIP_K_PLAN);
-  // the doc masks of the units with excluded terms (excl.h), before anything reads them
-  if (ok && b->excl.on()) ok = launch_excl_masks(b, st);
-  // (a joined batch without conjunctions needs none of k_plan's tables)
-  if (ok && (b->phrase || !b->tiles.units.empty() || !b->blocks.units.empty() || !b->any.units.empty())) {
-    RT_LAUNCH(k_plan, b->nq * b->jt, kThreads, 0, st, b->d_segs.as<DevSegment>(),
-              b->d_queries.as<DevQuery>(), b->d_qterms.as<DevQTerm>(), b->jt, b->tiles.docs,
-              b->d_first.as<uint32_t>(), b->d_tails.as<DevTail>());
-    ok = rt::last_error_ok();
-  }
-  if (ok && streams_on(b)) ok = launch_join(b, st);
-  if (ok && !b->phrase && !b->tiles.units.empty()) ok = launch_items(b, st);
-  return ok && mark(2 * IRS_HIP_K_PLAN + 1);
-}
-
 // irs_hip_batch_unit_mask: the mask the unit's last run tested, in irs_hip_bit_union's layout
 static int batch_unit_mask_impl(irs_hip_batch* b, uint32_t unit, uint64_t* set, uint64_t n_words) {
   if (!b || !set || unit >= b->nq || !b->ran) return IRS_HIP_EINVAL;
   if (!rt::set_device(b->seg->device)) return IRS_HIP_EHIP;
-  if (!b->sync.done.sync()) return IRS_HIP_EHIP;
+  if (!run_done(b)) return IRS_HIP_EHIP;
   const DevQuery& dq = b->queries[unit];
   const uint32_t num_docs = b->segs[dq.seg]->dev.num_docs;
   std::fill(set, set + n_words, uint64_t(0));
@@ -967,196 +885,9 @@ static int batch_unit_mask_impl(irs_hip_batch* b, uint32_t unit, uint64_t* set, 
   return IRS_HIP_OK;
 }
 
-static int batch_plan_impl(irs_hip_batch* b, void* stream) {
-  if (!b) return IRS_HIP_EINVAL;
-  if (!rt::set_device(b->seg->device)) return IRS_HIP_EHIP;
-  if (!ensure_scratch(b) || !stage_min_bins(b)) return IRS_HIP_ENOMEM;
-  rt::stream_t st = static_cast<rt::stream_t>(stream);
-  bool ok = b->sync.plan.create();
-  // (the tables are rewritten: the batch's own previous run must be through with them)
-  if (ok && b->sync.done.made && b->ran) ok = b->sync.done.wait(st);
-  // (a plan queued earlier and never consumed may still run on ANOTHER stream)
-  if (ok && b->sync.plan_pending) ok = b->sync.plan.wait(st);
-  // (match sets queued on another stream read the masks this stage rewrites)
-  if (ok && b->sync.match_pending) ok = b->sync.matched.wait(st);
-  ok = ok && b->up.flush(st) && plan_stage(b, st) && b->sync.plan.record(st);
-  if (!ok) abandon_fills(b);
-  b->sync.planned = ok;
-  b->sync.plan_pending = b->sync.plan_pending || b->sync.plan.made;   // (whatever got queued)
-  return ok ? IRS_HIP_OK : IRS_HIP_EHIP;
-}
-
-// The union of the two passes of a batch with optional terms (k_union_topk, phrase.h) into
-// d_union_*: behind both passes' k_select on `st`.
-static bool launch_union(irs_hip_batch* b, rt::stream_t st) {
-  const irs_hip_batch* c = b->opt;
-  RT_LAUNCH(k_union_topk, b->nq, kThreads, 0, st, b->d_queries.as<DevQuery>(), b->k_max,
-            b->d_out.as<Hit>(), b->d_out_count.as<uint32_t>(), b->d_hits.as<unsigned long long>(),
-            c->d_out.as<Hit>(), c->d_out_count.as<uint32_t>(), c->d_hits.as<unsigned long long>(),
-            b->d_union_out.as<Hit>(), b->d_union_count.as<uint32_t>(),
-            b->d_union_hits.as<unsigned long long>());
-  return rt::last_error_ok();
-}
-// What the result calls hand out: the batch's own tables, or the union of its two passes
-static void* out_hits(irs_hip_batch* b) { return b->opt ? b->d_union_out.p : b->d_out.p; }
-static void* out_counts(irs_hip_batch* b) { return b->opt ? b->d_union_count.p : b->d_out_count.p; }
-static void* out_totals(irs_hip_batch* b) { return b->opt ? b->d_union_hits.p : b->d_hits.p; }
-
-static int run_impl(irs_hip_batch* b, rt::stream_t st) {
-  HostTrace trace("batch_run (scratch + uploads + launches queued)");
-  if (!ensure_scratch(b) || !stage_min_bins(b)) return IRS_HIP_ENOMEM;
-  b->stream = st;
-  // a copy of the PREVIOUS run's results to host memory may still be reading d_out / d_hits on the
-  // download stream: this run rewrites them only behind it (and those host results are stale then:
-  // irs_hip_batch_host_results refuses them until the next irs_hip_batch_results_to_host)
-  if (b->sync.host_pending) {
-    if (!b->sync.host.wait(st)) return IRS_HIP_EHIP;
-    b->sync.host_pending = false;
-  }
-  // the batch's own previous run ended on the tail stream (a replay, a recovery re-run): the fill
-  // of d_zeroed, the uploads and the pilot below rewrite what that tail may still read — stream
-  // order on `st` does not cover it
-  if (b->ran && b->sync.tail_used && b->sync.done.made && !b->sync.done.wait(st)) return IRS_HIP_EHIP;
-  const bool simd = b->seg->dev.layout == kSimd4;
-  auto mark = [&](int i) { return !b->profile || b->sync.prof[i].record(st); };
-  // the batch's tables (built in page-locked memory since create) go out: before the batch's
-  // first run on the device's copy stream (nothing on the GPU reads or writes these buffers yet),
-  // afterwards in the run's own stream order (a running kernel may still read what they replace)
-  bool ok = true;
-  // a plan stage that is still queued (used below, or made stale by a setter) reads and writes
-  // the tables this run uploads and rewrites: both streams get behind it
-  const bool after_plan = b->sync.plan_pending && b->sync.plan.made;
-  if (after_plan) ok = b->sync.plan.wait(st);
-  rt::stream_t up_st = (!b->ran && !b->up.pending.empty()) ? upload_stream(b->seg->device) : nullptr;
-  if (up_st && after_plan) ok = ok && b->sync.plan.wait(up_st);
-  // match sets queued on another stream (irs_hip_batch_match_sets_to_device) read the exclusion
-  // masks this run's plan stage rewrites and the tables its uploads replace
-  if (b->sync.match_pending) {
-    ok = ok && b->sync.matched.wait(st) && (!up_st || b->sync.matched.wait(up_st));
-    b->sync.match_pending = !ok;
-  }
-  b->sync.plan_pending = false;
-  if (up_st) {
-    ok = ok && b->up.flush(up_st) && b->sync.uploaded.record(up_st) && b->sync.uploaded.wait(st);
-  } else {
-    ok = b->up.flush(st);
-  }
-  if (ok && streams_on(b) && !b->join.slack_zeroed) {
-    // (the slack behind the last stream is only ever read by masked-off look-ahead: zero it once)
-    ok = rt::dmemset(b->join.d_entries.as<uint32_t>() + b->join.entries, 0, kJoinSlack * 4, st);
-    b->join.slack_zeroed = ok;
-  }
-  ok = ok && rt::dmemset(b->d_zeroed.p, 0, b->d_zeroed.n, st);   // (ensure_scratch: six tables)
-  // (optional terms: no doc is taken until k_phrase_or matches it)
-  if (b->opt) ok = ok && rt::dmemset(b->d_taken.p, 0, b->d_taken.n, st);
-  // (a counting run of a batch with doc sets: the lead pieces' tallies, irs_hip_batch_doc_set_stats)
-  b->excl.leads_counted = b->count_touched && b->excl.sets_on();
-  if (ok && b->excl.leads_counted)
-    ok = (b->excl.d_leads.p || b->excl.d_leads.alloc(16)) && rt::dmemset(b->excl.d_leads.p, 0, 16, st);
-  // (streams out of the device's cache that another stream is still filling)
-  if (streams_on(b)) ok = ok && wait_for_streams(b, st);
-  // 1. plan (already queued by irs_hip_batch_plan: wait for it instead)
-  const bool tiles = !b->phrase && !b->tiles.units.empty();
-  if (b->sync.planned) {
-    ok = ok && b->sync.plan.wait(st);
-    b->sync.planned = false;
-  } else {
-    ok = ok && plan_stage(b, st);
-  }
-  // 2. pilot: per-query score-bin threshold (phrase batches have none: few docs match)
-  ok = ok && mark(2 * IRS_HIP_K_PILOT);
-  if (b->groups.n) ok = ok && rt::dmemset(b->groups.d_hist.p, 0, b->groups.d_hist.n, st);
-  if (b->join.on()) ok = ok && launch_join_pilot(b, st);
-  if (b->wide.on()) ok = ok && launch_wide_pilot(b, st);
-  ok = ok && launch_group_threshold(b, st);
-  if (tiles)
-    ok = ok && with_tile_kernel(b, [&](auto k) { return launch_pilot(b, st, k); });
-  ok = ok && mark(2 * IRS_HIP_K_PILOT + 1);
-  // 3. score every tile / every lead block — behind the tail queued last on the device (pool.h):
-  // a started k_join_score workgroup holds the LDS that tail's k_select asks for
-  ok = ok && wait_for_tail(b->seg->device, st);
-  ok = ok && mark(2 * IRS_HIP_K_SCORE);
-  // (a batch that passes tail_ok: from behind its paired launch on, the run is queued on the
-  // device's tail stream `ts`, and nothing of it follows on `st`)
-  bool tail = false;
-  rt::stream_t ts = st;
-  if (ok && tail_ok(b)) {
-    rt::stream_t s = tail_stream(b->seg->device, &tail);
-    if (tail) ts = s;
-  }
-  b->sync.tail_used = tail;
-  Tail& dev_tail = tail_of(b->seg->device);
-  std::unique_lock<std::mutex> tail_lock(dev_tail.m, std::defer_lock);
-  if (tail) tail_lock.lock();
-  auto mark_tail = [&](int i) { return !b->profile || b->sync.prof[i].record(ts); };
-  if (b->phrase)
-    ok = ok && (simd ? launch_phrase_terms<kSimd4>(b, st) : launch_phrase_terms<kScalar>(b, st));
-  else if (tiles)
-    ok = ok && with_tile_kernel(b, [&](auto k) { return launch_score(b, st, k); });
-  if (b->join.on()) ok = ok && launch_join_score(b, st, tail ? &ts : nullptr);
-  if (b->wide.on()) ok = ok && launch_wide_score(b, st);
-  if (!b->phrase) ok = ok && (simd ? launch_conj<kSimd4>(b, st) : launch_conj<kScalar>(b, st));
-  if (!b->phrase) ok = ok && (simd ? launch_any<kSimd4>(b, st) : launch_any<kScalar>(b, st));
-  ok = ok && mark_tail(2 * IRS_HIP_K_SCORE + 1);
-  // 4. exact top-k
-  ok = ok && mark_tail(2 * IRS_HIP_K_SELECT);
-  if (ok) {
-    uint32_t sort_cap = 64;
-    while (sort_cap < b->k_max) sort_cap <<= 1;
-    const uint32_t stage_cap = std::min<uint32_t>(b->cand_cap, kSelectStage);
-    const size_t smem = size_t(sort_cap + stage_cap) * sizeof(uint64_t);
-    ok = big_smem(k_select, smem);
-    if (ok) {
-      RT_LAUNCH(k_select, b->nq, kThreads, smem, ts, b->d_queries.as<DevQuery>(),
-                b->d_cands.as<uint64_t>(), b->cand_cap, b->d_cand_count.as<uint32_t>(),
-                b->d_hits.as<unsigned long long>(), b->d_out.as<Hit>(), b->k_max,
-                b->d_out_count.as<uint32_t>(), b->d_status.as<uint32_t>(), stage_cap, sort_cap,
-                b->d_bstar.as<uint32_t>(), min_bins(b), b->d_pruned.as<uint32_t>(),
-                b->has_min ? b->d_min_score.as<float>() : static_cast<const float*>(nullptr),
-                b->groups.n ? b->groups.d_of.as<uint32_t>() : static_cast<const uint32_t*>(nullptr));
-      if (b->groups.n) {
-        RT_LAUNCH(k_group_sums, (b->groups.n + 63u) / 64u, 64, 0, st, b->d_queries.as<DevQuery>(),
-                  b->groups.d_members.as<uint32_t>(), uint32_t(b->segs.size()), b->groups.n,
-                  b->d_out_count.as<uint32_t>(), b->d_hits.as<unsigned long long>(),
-                  b->d_bstar.as<uint32_t>(), min_bins(b), b->d_status.as<uint32_t>(),
-                  b->groups.d_sums.as<uint32_t>());
-        ok = rt::last_error_ok();
-        if (ok && b->comm && !b->phrase)
-          ok = rt::comm::all_reduce_u32(b->comm->h, b->groups.d_sums.p,
-                                        size_t(b->groups.n) * kGroupSumWords + 2, st);
-        if (ok)
-          RT_LAUNCH(k_group_verdict, (b->groups.n + 63u) / 64u, 64, 0, st, b->d_queries.as<DevQuery>(),
-                    b->groups.n, b->groups.d_sums.as<uint32_t>(), b->d_status.as<uint32_t>());
-      }
-      ok = ok && rt::last_error_ok();
-    }
-  }
-  ok = ok && mark_tail(2 * IRS_HIP_K_SELECT + 1);
-  // optional terms: the term pass behind the phrase pass, on the same stream, then the union of
-  // their results (the batch's `done` covers all three)
-  if (ok && b->opt) {
-    const uint64_t n32 = b->d_taken.n / 4u;   // (taken -> the term pass's doc sets)
-    RT_LAUNCH(k_not_words, uint32_t((n32 + kThreads - 1) / kThreads), kThreads, 0, st, b->d_taken.as<uint32_t>(), n32);
-    if (!rt::last_error_ok()) return IRS_HIP_EHIP;
-    if (const int rc = run_impl(b->opt, st)) {
-      b->ran = true;
-      return rc;
-    }
-    ok = launch_union(b, st);
-  }
-  // the status word follows the kernels into page-locked memory; the event marks this run
-  if (ok && !b->sync.h_status.p) ok = b->sync.h_status.alloc(64);
-  ok = ok && rt::d2h(b->sync.h_status.p, b->d_status.p, 4, ts) && b->sync.done.record(ts);
-  if (tail) {
-    // (whatever of the tail got queued: the next score launch of the device waits for it)
-    if (dev_tail.done.record(ts)) dev_tail.recorded = true;
-    else ok = false;
-    tail_lock.unlock();
-  }
-  if (!ok) abandon_fills(b);
-  b->ran = true;
-  return ok ? IRS_HIP_OK : IRS_HIP_EHIP;
-}
+// the stages of a run, run_impl and batch_plan_impl (here, behind everything they call: the kernel
+// templates they launch are instantiated — and laid out in the code object — in this order)
+#include "run.h"
 
 static int batch_run_impl(irs_hip_batch* b, void* stream) {
   if (!b) return IRS_HIP_EINVAL;
@@ -1287,8 +1018,7 @@ static int recover(irs_hip_batch* b, uint32_t status) {
 static int batch_timings_impl(irs_hip_batch* b, float ms[IRS_HIP_K_COUNT]) {
   if (!b || !ms || !b->profile || !b->ran) return IRS_HIP_EINVAL;
   // (the batch's own last run: later work on the stream is not waited for)
-  if (!rt::set_device(b->seg->device) || !b->sync.done.sync())
-    return IRS_HIP_EHIP;
+  if (!rt::set_device(b->seg->device) || !run_done(b)) return IRS_HIP_EHIP;
   for (int i = 0; i < IRS_HIP_K_COUNT; ++i)
     if (!rt::event_elapsed(&ms[i], b->sync.prof[2 * i].e, b->sync.prof[2 * i + 1].e)) return IRS_HIP_EHIP;
   return IRS_HIP_OK;
@@ -1337,8 +1067,8 @@ static int batch_results_impl(irs_hip_batch* b, irs_hip_hit* hits, uint32_t k_st
 // Waits for the batch's own last run (its event: work the caller queued behind it on the same
 // stream — the next batch's kernels, say — keeps running) and reads the status it left.
 static int verify_run(irs_hip_batch* b) {
-  if (!b->sync.h_status.p || !b->sync.done.sync()) return IRS_HIP_EHIP;
-  const uint32_t status = *b->sync.h_status.as<uint32_t>();
+  uint32_t status = 0;
+  if (!run_status(b, &status)) return IRS_HIP_EHIP;
   if (status & (kStatusOverflow | kStatusUnderflow)) {
     const int rc = recover(b, status);
     if (rc != IRS_HIP_OK) return rc;
@@ -1383,9 +1113,7 @@ static int batch_results_to_device_impl(irs_hip_batch* b, void* d_hits, void* d_
       !rt::d2d(d_counts, out_counts(b), size_t(b->nq) * 4, st))
     return IRS_HIP_EHIP;
   // (destroy must not hand d_out back to the pool while these copies are queued)
-  if (!b->sync.used.record(st)) return IRS_HIP_EHIP;
-  b->sync.used_pending = true;
-  return IRS_HIP_OK;
+  return b->sync.used.mark(st) ? IRS_HIP_OK : IRS_HIP_EHIP;
 }
 
 // sync.h_res: the hits, then the counts, then the totals of irs_hip_batch_results_to_host
@@ -1407,27 +1135,25 @@ static int batch_results_to_host_impl(irs_hip_batch* b, void* stream) {
   const int rc = verify_run(b);
   if (rc != IRS_HIP_OK) return rc;
   const HostResults r(b);
-  if (b->sync.host_pending && !b->sync.host.sync()) return IRS_HIP_EHIP;   // (the previous copy)
-  b->sync.host_pending = false;
+  if (!b->sync.host.sync()) return IRS_HIP_EHIP;   // (the previous copy)
   if (b->sync.h_res.n < r.total && !b->sync.h_res.alloc(r.total)) return IRS_HIP_ENOMEM;
   rt::stream_t st = stream ? static_cast<rt::stream_t>(stream) : download_stream(b->seg->device);
   if (!st) st = b->stream;
   uint8_t* h = b->sync.h_res.as<uint8_t>();
-  if (!b->sync.done.wait(st) ||
+  if (!run_done_on(b, st) ||
       !rt::d2h(h, out_hits(b), r.hit_bytes, st) ||
       !rt::d2h(h + r.cnt_off, out_counts(b), size_t(b->nq) * 4, st) ||
       !rt::d2h(h + r.tot_off, out_totals(b), size_t(b->nq) * 8, st) ||
-      !b->sync.host.record(st))
+      !b->sync.host.mark(st))
     return IRS_HIP_EHIP;
-  b->sync.host_pending = true;
   return IRS_HIP_OK;
 }
 
 static int batch_host_results_impl(irs_hip_batch* b, const irs_hip_hit** hits, uint32_t* k_stride,
                                    const uint32_t** counts, const uint64_t** total_hits) {
-  if (!b || !b->sync.host_pending) return IRS_HIP_EINVAL;
+  if (!b || !b->sync.host.pending()) return IRS_HIP_EINVAL;   // (no copy since the last run)
   if (!rt::set_device(b->seg->device)) return IRS_HIP_EHIP;
-  if (!b->sync.host.sync()) return IRS_HIP_EHIP;
+  if (!b->sync.host.sync_keep()) return IRS_HIP_EHIP;   // (they stay there to be handed out again)
   const HostResults r(b);
   const uint8_t* h = b->sync.h_res.as<uint8_t>();
   static_assert(sizeof(irs_hip_hit) == sizeof(Hit), "irs_hip_hit is the device's Hit");
@@ -1442,16 +1168,8 @@ void irs_hip_batch_destroy(irs_hip_batch* b) {
   if (!b) return;
   settle(b);
   rt::set_device(b->seg->device);
-  // Its buffers go back to the pool: every piece of queued work that touches them must be
-  // through — the batch's own last run (sync.done), a plan queued ahead, copies out of d_out.
-  // Not the whole stream: the caller may have queued the NEXT batch behind this one.
-  bool waited = true;
-  if (b->ran) waited = b->sync.done.sync();
-  if (b->sync.planned || b->sync.plan_pending)
-    waited = waited && b->sync.plan.sync();
-  if (b->sync.used_pending) waited = waited && b->sync.used.sync();
-  if (b->sync.host_pending) waited = waited && b->sync.host.sync();
-  if (b->sync.match_pending) waited = waited && b->sync.matched.sync();
+  // (its buffers go back to the pool)
+  bool waited = quiet_for_destroy(b);
   if (!waited && b->ran) {
     bool made = false;
     rt::stream_t ts = tail_stream(b->seg->device, &made);

@@ -692,7 +692,7 @@ bool build_streams(irs_hip_batch* b) {
     }
   }
   // (the slack behind the last stream is only ever read by masked-off look-ahead: zero it once)
-  b->join.slack_zeroed = !b->join.n_private;   // (run_impl zeroes it on the run's stream)
+  b->join.slack_zeroed = !b->join.n_private;   // (run_uploads_and_fills zeroes it on the run's stream)
   if (!b->up.copy(b->join.d_streams.p, streams.data(), streams.size() * sizeof(StreamRec)) ||
       !b->up.copy(b->join.d_jterms.p, jterms.data(), jterms.size() * sizeof(JoinTerm)) ||
       !b->up.copy(b->join.d_units.p, b->join.units.data(), b->join.units.size() * 4) ||
@@ -743,7 +743,7 @@ bool launch_join(irs_hip_batch* b, rt::stream_t st) {
     // from here on other batches are served these slabs: their runs wait for `filled`
     for (const scache::SlabPtr& s : b->join.fills) {
       s->fill_stream = st;
-      ok = ok && s->filled.record(st);
+      ok = ok && s->filled.mark(st);
     }
     if (ok) {
       scache::Cache& c = scache::of(b->seg->device);
@@ -759,7 +759,7 @@ bool launch_join(irs_hip_batch* b, rt::stream_t st) {
 bool wait_for_streams(irs_hip_batch* b, rt::stream_t st) {
   bool ok = true;
   for (const scache::SlabPtr& s : b->join.pinned)
-    if (s->filled.made && !s->settled.load() && s->fill_stream != st) ok = ok && s->filled.wait(st);
+    if (!s->settled.load() && s->fill_stream != st) ok = ok && s->filled.wait(st);
   return ok;
 }
 

@@ -150,11 +150,7 @@ static int batch_match_sets_impl(irs_hip_batch* b, uint64_t* sets, void* d_sets,
   }
   // behind the batch's own queued work — a run or a plan stage writes the masks and may have the
   // batch's tables in flight, an earlier call on another stream reads this one's tables
-  bool ok = true;
-  if (b->sync.plan_pending && b->sync.plan.made) ok = b->sync.plan.wait(st);
-  if (ok && b->ran) ok = b->sync.done.wait(st);
-  if (ok && b->sync.match_pending) ok = b->sync.matched.wait(st);
-  ok = ok && b->up.flush(st);   // (the segments' records and the masks' tables, staged since create)
+  bool ok = match_get_behind(b, st) && b->up.flush(st);   // (the segments' records and the masks' tables, staged since create)
   if (ok && !b->phrase && !m.sent) {
     ok = rt::h2d(m.d_units.p, m.units.data(), m.units.size() * sizeof(MatchUnit), st) &&
          rt::h2d(m.d_rows.p, m.rows.data(), m.rows.size() * 4, st);
@@ -205,9 +201,7 @@ static int batch_match_sets_impl(irs_hip_batch* b, uint64_t* sets, void* d_sets,
   }
   if (to_device) {
     // (a later run, setter or destroy gets behind this: the masks and the tables are still read)
-    if (!b->sync.matched.record(st)) return IRS_HIP_EHIP;
-    b->sync.match_pending = true;
-    return IRS_HIP_OK;
+    return b->sync.matched.mark(st) ? IRS_HIP_OK : IRS_HIP_EHIP;
   }
   const bool copied = (!want_sets || rt::d2h(sets, d_sets, set_bytes, st)) &&
                       (!want_counts || rt::d2h(counts, d_counts, count_bytes, st));

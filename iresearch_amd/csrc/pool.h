@@ -148,6 +148,36 @@ struct Event {
   bool wait(rt::stream_t st) const { return made && rt::stream_wait(st, e); }   // st waits for it
 };
 
+// An event together with "something recorded on it may still be in flight".  Whoever is about to
+// touch what that work reads or writes calls wait() or sync() and names no guard of its own: on a
+// Pending that nothing was ever recorded on — or whose work is known to be through — both do
+// nothing and succeed.
+struct Pending {
+  bool mark(rt::stream_t st) {   // recorded on `st`: pending from here on
+    if (!e.record(st)) return false;
+    on = true;
+    return true;
+  }
+  // `st` gets behind it.  It stays pending: a stream wait proves nothing to the host or to another stream.
+  bool wait(rt::stream_t st) const { return !on || e.wait(st); }
+  // the host gets behind it: through, no longer pending
+  bool sync() {
+    if (!sync_keep()) return false;
+    on = false;
+    return true;
+  }
+  // ... and it stays pending: for a reader that cannot speak for the later ones (a const owner), or
+  // where the mark also says that what the work left is there to be read
+  bool sync_keep() const { return !on || e.sync(); }
+  bool pending() const { return on; }
+  // a stream is behind it AND everything that touches the same memory later is ordered behind that
+  // stream's work: the caller says why
+  void settle() { on = false; }
+ private:
+  Event e;
+  bool on = false;
+};
+
 // Host -> device uploads of a batch: the bytes are built in (or copied into) page-locked memory
 // and go out with asynchronous copies on the stream of the batch's next run — no copy from
 // pageable memory (the runtime stages those synchronously), no stream synchronisation, so a
@@ -192,7 +222,7 @@ struct Stager {
 // they would start only when the previous batch's kernels are through (0.2 ms of idle compute per
 // step for the headline batch's 5 MB); on their own stream they travel while those kernels run,
 // and the run waits for them by an event.
-// (`made`: whether the stream exists — the emulator's streams are all null)
+// (`made`: whether the stream exists)
 inline rt::stream_t copy_stream(int device, int which, bool* made = nullptr) {
   struct Made { rt::stream_t s; bool ok; };
   static std::mutex m;
@@ -224,8 +254,7 @@ inline rt::stream_t download_stream(int device) { return copy_stream(device, 1);
 // the queuing of a whole tail and around every wait.
 struct Tail {
   std::mutex m;
-  Event done;
-  bool recorded = false;
+  Pending done;
 };
 inline Tail& tail_of(int device) {
   static Tail* tails = new Tail[pool::kMaxDevices];   // (never destroyed: the runtime may go first)
@@ -236,7 +265,7 @@ inline rt::stream_t tail_stream(int device, bool* made) { return copy_stream(dev
 inline bool wait_for_tail(int device, rt::stream_t st) {
   Tail& t = tail_of(device);
   std::lock_guard<std::mutex> lock(t.m);
-  return !t.recorded || t.done.wait(st);
+  return t.done.wait(st);
 }
 
 // IRS_HIP_TRACE=1: host-side stage times on stderr (what a batch costs before its first kernel)

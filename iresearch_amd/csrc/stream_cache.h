@@ -52,7 +52,7 @@ struct Slab {
   // Filled by ONE batch's k_join, on whatever stream that batch's plan stage was queued on;
   // `filled` is recorded behind that launch.  (cache mutex) `queued` turns true once it is: only
   // then is the slab served to other batches, whose runs make their own stream wait for `filled`.
-  Event filled;
+  Pending filled;
   rt::stream_t fill_stream{};   // where (a run on the same stream is behind the fill anyway)
   bool queued = false;
   std::atomic<bool> settled{false};   // the filling batch has waited for its run: nobody needs `filled`

@@ -12,13 +12,43 @@
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
+#include <map>
+#include <mutex>
+#include <string>
 
 #include "hip_sim.h"
 
 namespace rt {
 
 using stream_t = void*;
-using event_t = double;
+struct event_t {
+  double ms = 0;     // when it was recorded last
+  uint64_t id = 0;   // which event this is (event_create), for the log below
+};
+
+// IRS_SIM_SYNC_LOG=<file> (tests only; read at every call, so a test switches it on and off): every
+// event_record, stream_wait and event_sync appends one line "<op> e<event> s<stream>" — events
+// numbered from 1 by first appearance in that file, streams as the integers they are (0: the null
+// stream, small numbers: stream_create's), event_sync with "s-".  The emulator is synchronous, so
+// a test cannot see ORDER on the device; here it sees which waits the host code asked for.
+inline void sync_log(const char* op, const event_t& e, const stream_t* st) {
+  const char* path = std::getenv("IRS_SIM_SYNC_LOG");
+  if (!path || !*path) return;
+  static std::mutex m;
+  static std::string file;
+  static std::map<uint64_t, unsigned> seen;
+  std::lock_guard<std::mutex> lock(m);
+  if (file != path) {
+    file = path;
+    seen.clear();
+  }
+  const unsigned n = seen.emplace(e.id, unsigned(seen.size()) + 1u).first->second;
+  if (FILE* f = std::fopen(path, "a")) {
+    if (st) std::fprintf(f, "%s e%u s%llu\n", op, n, static_cast<unsigned long long>(reinterpret_cast<uintptr_t>(*st)));
+    else std::fprintf(f, "%s e%u s-\n", op, n);
+    std::fclose(f);
+  }
+}
 
 inline int device_count() { return 1; }
 inline bool set_device(int dev) { return dev == 0; }
@@ -62,13 +92,24 @@ inline bool dmemset(void* d, int v, size_t n, stream_t) {
   return true;
 }
 inline bool sync(stream_t) { return true; }
-inline bool stream_create(stream_t* s) { *s = nullptr; return true; }
+// (distinct small tokens, never null — the null stream is the caller's default; nothing here
+// dereferences a stream)
+inline bool stream_create(stream_t* s) {
+  static std::atomic<uintptr_t> made{0};
+  *s = reinterpret_cast<stream_t>(made.fetch_add(1) + 1);
+  return true;
+}
 inline bool last_error_ok() { return true; }
 inline bool allow_dynamic_smem(const void*, size_t bytes) { return bytes <= sim::kMaxSmem; }
 
-inline bool event_sync(event_t) { return true; }
+inline bool event_sync(const event_t& e) {
+  sync_log("sync", e, nullptr);
+  return true;
+}
 inline bool event_create(event_t* e) {
-  *e = 0;
+  static std::atomic<uint64_t> made{0};
+  e->ms = 0;
+  e->id = made.fetch_add(1) + 1;
   return true;
 }
 inline void event_destroy(event_t) {}
@@ -77,13 +118,23 @@ inline double now_ms() {
            std::chrono::steady_clock::now().time_since_epoch())
     .count();
 }
-inline bool event_record(event_t& e, stream_t) {
-  e = now_ms();
+// (a test of the host code's failure paths sets it: event_record fails and records nothing)
+inline bool& fail_records() {
+  static bool fail = false;
+  return fail;
+}
+inline bool event_record(event_t& e, stream_t st) {
+  if (fail_records()) return false;
+  e.ms = now_ms();
+  sync_log("record", e, &st);
   return true;
 }
-inline bool stream_wait(stream_t, const event_t&) { return true; }   // (everything is synchronous)
+inline bool stream_wait(stream_t st, const event_t& e) {   // (everything is synchronous)
+  sync_log("wait", e, &st);
+  return true;
+}
 inline bool event_elapsed(float* ms, event_t a, event_t b) {
-  *ms = float(b - a);
+  *ms = float(b.ms - a.ms);
   return true;
 }
 

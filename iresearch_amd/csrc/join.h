@@ -545,17 +545,27 @@ static_assert(JoinOff::dummy + 256u <= 65536u, "dummy offsets fit an entry's 16 
 // ... of k_join_score<kJKHalf> (paired tiles on bound images): no score tables, no scorer records —
 // the accumulators of kJoinBoundTile docs and their dummies fill the 64 KB an entry can address,
 // everything else lies behind.  At most 80 KB: two workgroups stay resident per CU.
+// No rng / cum tables here: what a visit's shares are cut from — per (term, half) piece its first
+// slab, its slabs and their running sum over the pair's pieces — is one 8-byte row per (visit,
+// piece), worked out once per chunk (join_pair_rows).  A chunk is at most kJoinChunkBound / 2
+// visits; begin() looks up to three visits past the last one (empty rows).
+struct alignas(8) JoinRow {
+  uint32_t a;    // the piece's first slab in its image
+  uint32_t cn;   // [ n: the piece's slabs : 16 | c: slabs of the pair's pieces up to and with this one : 16 ]
+};
+constexpr uint32_t kJoinPairRows = kJoinChunkBound / 2u + 3u;
 struct JoinOffH {
   static constexpr uint32_t acc = 0;                                   // [kJoinBoundTile] u32: two u16 sums
   static constexpr uint32_t dummy = 4u * kJoinBoundTile;               // [64] u32
   static constexpr uint32_t jts = dummy + 256u;                        // JoinTerm[kMaxTerms] (of the images)
-  static constexpr uint32_t rng = jts + uint32_t(sizeof(JoinTerm)) * kMaxTerms;   // as JoinOff
-  static constexpr uint32_t cum = rng + 4u * (kJoinChunkTiles + 1u) * kMaxTerms;
-  static constexpr uint32_t cand = cum + 4u * kJoinChunkTiles * kMaxTerms;
+  static constexpr uint32_t rows = jts + uint32_t(sizeof(JoinTerm)) * kMaxTerms;   // JoinRow[kJoinPairRows][2 * kMaxTerms]
+  static constexpr uint32_t cand = rows + uint32_t(sizeof(JoinRow)) * 2u * kMaxTerms * kJoinPairRows;
   static constexpr uint32_t vars = cand + 8u * 2u * kJoinCands;
   static constexpr uint32_t end = vars + 64u;
 };
-static_assert(JoinOffH::cand % 8u == 0u && JoinOffH::jts % 16u == 0u, "JoinOffH alignment");
+static_assert(kJoinChunkBound % 2u == 0u, "kJoinPairRows: a full chunk is whole pairs");
+static_assert((kJoinBoundTile / kJoinSlab + 1u) * 2u * kMaxTerms < 65536u, "JoinRow::cn: 16 bits each");
+static_assert(JoinOffH::cand % 8u == 0u && JoinOffH::jts % 16u == 0u && JoinOffH::rows % 8u == 0u, "JoinOffH alignment");
 static_assert(JoinOffH::dummy + 256u <= 65536u, "dummy offsets fit an entry's 16 address bits");
 static_assert(JoinOffH::end <= 80u * 1024u, "two k_join_score<kJKHalf> workgroups per CU");
 
@@ -1487,27 +1497,58 @@ inline uint32_t join_half_k(float cs, float U) {
   const double v = std::ceil(double(cs) / double(U) * 2.0);
   return v >= 1.0 ? (v < 65535.0 ? uint32_t(v) : 65535u) : 1u;
 }
+// Chunk prologue, whole workgroup: the JoinRow of every (visit, piece) of the chunk, from the
+// images' tile bounds (`jt`: the query's image records in device memory; a bound counts entries of
+// a slab-aligned image, a row counts slabs).  A wavefront takes two visits at a time — lanes 0 .. 31
+// the pieces of one, lanes 32 .. 63 of the next — and sums the pieces' slabs with one scan; every
+// wavefront makes the same number of passes with all its lanes, as the scan asks.  Rows of the
+// visits past the chunk's last, and of the second tile of a lone last tile's pair, hold no slabs.
+// The caller's barrier publishes them.
+__device__ __forceinline__ void join_pair_rows(unsigned char* smem, const JoinTerm* jt, uint32_t n_terms,
+                                               uint32_t tile0, uint32_t ntile, uint32_t wv, unsigned lane) {
+  JoinRow* rows = reinterpret_cast<JoinRow*>(smem + JoinOffH::rows);
+  const uint32_t l = lane & (2u * kMaxTerms - 1u), j = l & (kMaxTerms - 1u);
+  const uint32_t waves = blockDim.x >> 6;
+  for (uint32_t v = 2u * wv; v < kJoinPairRows; v += 2u * waves) {
+    const uint32_t p = v + (lane >> 5), i = 2u * p + (l >> 4);
+    uint32_t a = 0, n = 0;
+    if (j < n_terms && i < ntile) {
+      const uint32_t* b = reinterpret_cast<const uint32_t*>(jt[j].bounds) + tile0 + i;
+      a = b[0] / kJoinSlab;
+      n = b[1] / kJoinSlab - a;
+    }
+    uint32_t c = wave::inclusive_scan(n);
+    const uint32_t c_first = wave::read_lane(c, 2u * kMaxTerms - 1u);   // all of the first visit's
+    if (lane >= 2u * kMaxTerms) c -= c_first;
+    if (p < kJoinPairRows) {
+      JoinRow row;
+      row.a = a;
+      row.cn = (n << 16) | c;
+      rows[p * 2u * kMaxTerms + l] = row;
+    }
+  }
+}
+
 template<int M>
 __device__ __forceinline__ void join_pairs(unsigned char* smem, const JoinTileCtx& ctx,
                                            const JoinLane& T, uint32_t tile0, uint32_t ntile,
                                            uint32_t wv, uint32_t nw_log2, uint32_t& my_hits) {
   static_assert(M == (kJHalf | kJSimple), "join_pairs: plain disjunctions on bound images");
-  const uint32_t* rng = reinterpret_cast<const uint32_t*>(smem + JoinOffH::rng);
-  const uint32_t* cum = reinterpret_cast<const uint32_t*>(smem + JoinOffH::cum);
+  const JoinRow* rows = reinterpret_cast<const JoinRow*>(smem + JoinOffH::rows);
   const uint32_t tid = threadIdx.x;
   const unsigned lane = tid & 63u;
   const uint64_t safe = reinterpret_cast<uint64_t>(ctx.args->jterms);
   const uint32_t npair = (ntile + 1u) >> 1;
   uint32_t lane4 = lane * 4u;   // every request's per-lane offset: join_load4
-  auto begin = [&](uint32_t p, JoinRun& r) {   // (p >= npair: an empty share)
+  // (p < npair + 3 <= kJoinPairRows: the rows past the chunk's visits are there and hold no
+  // slabs — an empty share; so are the rows of a lone last tile's missing neighbour)
+  auto begin = [&](uint32_t p, JoinRun& r) {
     uint32_t a = 0, n = 0, c = 0;
-    if (lane < 2u * kMaxTerms && p < npair) {
-      const uint32_t i = 2u * p + (lane >> 4), j = lane & (kMaxTerms - 1u);
-      if (i < ntile) {   // (an odd tile count: the last pair's second tile is empty)
-        a = rng[i * kMaxTerms + j];
-        n = rng[(i + 1u) * kMaxTerms + j] - a;
-      }
-      c = cum[p * 2u * kMaxTerms + lane];
+    if (lane < 2u * kMaxTerms) {
+      const JoinRow row = rows[p * 2u * kMaxTerms + lane];
+      a = row.a;
+      n = row.cn >> 16;
+      c = row.cn & 0xFFFFu;
     }
     join_load4(join_begin<M>(r, T, a, n, c, wv, nw_log2, safe, lane), lane4, r.e);
   };
@@ -1622,8 +1663,9 @@ k_join_score(const JoinArgs* __restrict__ args) {
   using Off = typename std::conditional<HALF, JoinOffH, JoinOff>::type;
   constexpr uint32_t kTile = HALF ? kJoinBoundTile : kJoinTile;
   uint32_t* acc = reinterpret_cast<uint32_t*>(smem + Off::acc);
-  uint32_t* rng = reinterpret_cast<uint32_t*>(smem + Off::rng);
-  uint32_t* cum = reinterpret_cast<uint32_t*>(smem + Off::cum);
+  // (the 32-bit kernels' tile bounds and their prefix sums; paired tiles keep JoinRows instead)
+  uint32_t* rng = reinterpret_cast<uint32_t*>(smem + JoinOff::rng);
+  uint32_t* cum = reinterpret_cast<uint32_t*>(smem + JoinOff::cum);
   uint64_t* lcand = reinterpret_cast<uint64_t*>(smem + Off::cand);
   uint32_t* vars = reinterpret_cast<uint32_t*>(smem + Off::vars);
   const uint32_t tid = threadIdx.x;
@@ -1669,15 +1711,9 @@ k_join_score(const JoinArgs* __restrict__ args) {
     uint64_t* lc = lcand + parity * kJoinCands;
     uint32_t* ncand = vars + kJNc + parity;
     if (ntile) {
-      // tile boundaries of the chunk, every term: rng[i][j] = bounds_j[tile0 + i]
-      for (uint32_t e = tid; e < (ntile + 1u) * kMaxTerms; e += blockDim.x) {
-        const uint32_t i = e / kMaxTerms, j = e % kMaxTerms;
-        uint32_t v = 0;
-        if (j < qd.n_terms)
-          v = reinterpret_cast<const uint32_t*>(args->jterms[qd.first_term + j].bounds)[tile0 + i];
-        rng[e] = HALF ? v / kJoinSlab : v;   // (slab-aligned images: their bounds count slabs)
-      }
-      if constexpr (HALF) {   // the image records to LDS: a JoinTerm = two 16-byte halves
+      if constexpr (HALF) {
+        // the image records to LDS: a JoinTerm = two 16-byte halves; and what the visits' shares
+        // are cut from, a row per (visit, piece): join_pair_rows
         JoinQuad* jts = reinterpret_cast<JoinQuad*>(smem + JoinOffH::jts);
         if (tid < kJoinTermQuads * kMaxTerms) {
           const uint32_t j = tid / kJoinTermQuads;
@@ -1688,23 +1724,18 @@ k_join_score(const JoinArgs* __restrict__ args) {
           }
           jts[tid].x = x; jts[tid].y = y; jts[tid].z = z; jts[tid].w = w;
         }
-        __syncthreads();
+        join_pair_rows(smem, args->jterms + qd.first_term, qd.n_terms, tile0, ntile, wv, lane);
       } else {
-        join_prologue(smem, qd, args->qterms, args->jterms);   // (its barrier publishes rng too)
-      }
-      // per tile: the inclusive prefix of the terms' entry counts (what join_begin splits)
-      if (HALF) {   // per pair of tiles: over the first tile's terms, then the second's
-        const uint32_t npair = (ntile + 1u) >> 1;
-        for (uint32_t e = tid; e < npair * 2u * kMaxTerms; e += blockDim.x) {
-          const uint32_t p = e / (2u * kMaxTerms), l = e % (2u * kMaxTerms);
-          uint32_t c = 0;
-          for (uint32_t t = 0; t <= l; ++t) {
-            const uint32_t i = 2u * p + t / kMaxTerms, j = t % kMaxTerms;
-            if (i < ntile) c += rng[(i + 1u) * kMaxTerms + j] - rng[i * kMaxTerms + j];
-          }
-          cum[e] = c;
+        // tile boundaries of the chunk, every term: rng[i][j] = bounds_j[tile0 + i]
+        for (uint32_t e = tid; e < (ntile + 1u) * kMaxTerms; e += blockDim.x) {
+          const uint32_t i = e / kMaxTerms, j = e % kMaxTerms;
+          uint32_t v = 0;
+          if (j < qd.n_terms)
+            v = reinterpret_cast<const uint32_t*>(args->jterms[qd.first_term + j].bounds)[tile0 + i];
+          rng[e] = v;
         }
-      } else {
+        join_prologue(smem, qd, args->qterms, args->jterms);   // (its barrier publishes rng too)
+        // per tile: the inclusive prefix of the terms' entry counts (what join_begin splits)
         for (uint32_t e = tid; e < ntile * kMaxTerms; e += blockDim.x) {
           const uint32_t i = e / kMaxTerms, j = e % kMaxTerms;
           uint32_t c = 0;

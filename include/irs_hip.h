@@ -382,6 +382,39 @@ typedef enum irs_hip_scorer_kind {
  * addition to ABI 12: a non-phrase kind with the flag was IRS_HIP_EINVAL before. */
 #define IRS_HIP_GROUP_ALT IRS_HIP_PHRASE_ALT
 
+/* OR-ed into the `kind` of an included IRS_HIP_OP_OR or IRS_HIP_OP_MINMATCH entry: one more REQUIRED
+ * member of the clause opened by the nearest preceding included entry without the flag — an Or
+ * whose children are by_term filters and Ands of by_term, `(a AND b) OR c` (Or::prepare prepares
+ * every child on its own with ctx.boost x child boost, an And child becomes a conjunction, the Or a
+ * disjunction or min-match disjunction over the children; boolean_filter.cpp:150-210,
+ * boolean_query.cpp:60-145 and :212-247, conjunction.hpp:436-490, disjunction.hpp:1411-1467).  A
+ * clause is one child of the Or (a plain by_term child is a clause of one).  Per segment, minus its
+ * deleted docs:
+ *   a clause matches d iff every one of its entries holds d; a clause with an absent entry
+ *   (IRS_HIP_NO_TERM or no docs) is empty in that segment;
+ *   d matches iff at least max(1, min_match) clauses match it (IRS_HIP_OP_OR: one); total hits
+ *   counts these docs;
+ *   score(d) = the sum, over the clauses matching d, of the sum of their entries' scores (SUM at
+ *   both levels).
+ * Boosts are the callers': each entry's c0 carries its term boost x And boost x Or boost; a zero
+ * boost matches with score 0.  A term may stand in several clauses: it scores once per matched
+ * clause that holds it and is decoded once.  Under IRS_HIP_OP_MINMATCH `min_match` counts CLAUSES:
+ * 0 is IRS_HIP_EUNSUPPORTED as for every MINMATCH query, and a query with fewer non-empty clauses
+ * than min_match (more than it has clauses, too) is empty in that segment.
+ * IRS_HIP_EINVAL: the flag on the first included entry, on an IRS_HIP_EXCLUDE entry, on an AND,
+ * PHRASE or MULTITERM entry.  IRS_HIP_EUNSUPPORTED: more than IRS_HIP_MAX_TERMS included entries;
+ * a `merge` other than SUM; IRS_HIP_EXCLUDE entries; and what an entry scored from decoded streams
+ * cannot be: a frequency above 255 in its term, a scorer outside the table family (BM1's constant
+ * is taken) or more than 4 distinct (kind, norm_const, norm_length), wide or legacy norm columns.
+ * Such a query runs on k_clause_pilot / k_clause_score (irs_hip_batch_clause_units), over the
+ * streams the batch's joined units read, with 64-bit sums and a threshold of its own.  A batch that
+ * holds one refuses irs_hip_batch_set_doc_sets / _host, irs_hip_batch_set_comm and
+ * irs_hip_batch_match_sets* (IRS_HIP_EUNSUPPORTED); set_wand, set_path, set_paired_tiles and the
+ * tile size leave these units as they are; its other (non-phrase) queries give bit for bit what they
+ * give in a batch of their own.  A compatible addition to ABI 12: a kind with 0x1000 was
+ * IRS_HIP_EINVAL before (an unknown scorer). */
+#define IRS_HIP_CLAUSE_AND 0x1000
+
 /* One query term = the (term cookie, stats blob, boost) triple TermQuery::execute
  * hands to postings()/CompileScore (term_query.cpp:35-74), flattened. */
 typedef struct irs_hip_term_scorer {
@@ -837,6 +870,8 @@ int irs_hip_batch_stream_counts(irs_hip_batch* batch, uint32_t* distinct, uint32
 /* The batch's IRS_HIP_OP_MULTITERM units ((segment, query) pairs), whatever they hold in their
  * segment. */
 int irs_hip_batch_wide_units(irs_hip_batch* batch, uint32_t* units);
+/* ... and its units with IRS_HIP_CLAUSE_AND entries (k_clause_pilot / k_clause_score). */
+int irs_hip_batch_clause_units(irs_hip_batch* batch, uint32_t* units);
 /* Bound images: where a batch's plain disjunctions run on paired doc tiles, the kernel reads, per
  * (segment, term, scorer signature), a second array in posting order whose entries carry a 16-bit
  * upper bound of the posting's score factor instead of (tf, norm).  Images are made from the

@@ -166,12 +166,23 @@ struct by_phrase {
 // statistics; the Or's boost multiplies into each child's).  With a phrase: min_match_count <= 1,
 // merge SUM, at most IRS_HIP_MAX_PHRASE_TERMS words and terms in all (anything else:
 // not_supported); without terms in `subs` it is the phrase.
+// `clauses`: And-of-by_term children next to the by_terms of `subs` — a disjunction of clauses,
+// `(a AND b) OR c` (IRS_HIP_CLAUSE_AND; Or::prepare prepares every child on its own, an And child
+// becomes a conjunction: boolean_filter.cpp:150-210, boolean_query.cpp:60-145).  Children in that
+// order: subs, then clauses.  A clause of one term is that term; min_match_count counts children
+// (terms and clauses alike); a doc's score is the sum over its matching children.  Each term's
+// boost is multiplied by its And's and the Or's boosts, from the top down.  With clauses: merge SUM
+// at both levels, plain Ands of by_term (no groups, no phrases), no phrase next to them, at most
+// IRS_HIP_MAX_TERMS terms in all (anything else: not_supported); no Not children, no doc set, no
+// match sets (not_supported, as the ABI refuses them).
+struct And;
 struct Or {
   std::vector<by_term> subs;
   uint32_t min_match_count = 1;  // irs::Or::min_match_count()
   irs_hip_merge merge_type = IRS_HIP_MERGE_SUM;  // boolean_filter::merge_type()
   float boost = 1.f;   // multiplies into its terms' boosts (boolean_filter.cpp:153-154, 204)
   std::vector<by_phrase> phrases;
+  std::vector<And> clauses;
 };
 // irs::And of by_term children (`subs`) and Or-of-by_term children (`groups`: an And of Ors,
 // IRS_HIP_GROUP_ALT).  Children in that order: subs, then groups.  A group of one term is that term
@@ -340,7 +351,8 @@ std::vector<PreparedQuery> prepare(const std::vector<filter>& filters, const Sco
     if (const auto* t = std::get_if<by_term>(&f)) {
       q.op = IRS_HIP_OP_OR;
       q.terms.push_back(one(*t));
-    } else if (std::get_if<Or>(&f) && !std::get_if<Or>(&f)->phrases.empty()) {
+    } else if (std::get_if<Or>(&f) && !std::get_if<Or>(&f)->phrases.empty() &&
+               std::get_if<Or>(&f)->clauses.empty()) {   // (with And children: refused below)
       // a phrase or optional terms (Or::prepare prepares every child on its own,
       // boolean_filter.cpp:150-210; MakeDisjunction, disjunction.hpp:1411-1467): the phrase's words
       // with its ONE blob, then every by_term with its own statistics, flagged IRS_HIP_PHRASE_OPTIONAL
@@ -377,6 +389,47 @@ std::vector<PreparedQuery> prepare(const std::vector<filter>& filters, const Sco
         r.phrase_offset = 0;
         q.terms.push_back(r);
       }
+    } else if (std::get_if<Or>(&f) && !std::get_if<Or>(&f)->clauses.empty()) {
+      // a disjunction of clauses: every by_term with its own statistics, a clause's members after
+      // its first flagged IRS_HIP_CLAUSE_AND — unless no clause has two members: then the query is
+      // today's flat Or
+      const Or& o = *std::get_if<Or>(&f);
+      if (!o.phrases.empty())
+        throw not_supported(IRS_HIP_EUNSUPPORTED, "Or: a by_phrase next to an And child "
+                            "(a clause is a by_term or an And of by_term)");
+      if (o.merge_type != IRS_HIP_MERGE_SUM && o.subs.size() + o.clauses.size() > 1)
+        throw not_supported(IRS_HIP_EUNSUPPORTED, "Or: And children merge with SUM on the GPU path");
+      std::vector<std::vector<by_term>> clauses;
+      for (const auto& t : o.subs) clauses.push_back({by_term{t.term, o.boost * t.boost}});
+      bool any = false;
+      for (const And& c : o.clauses) {
+        if (!c.groups.empty())
+          throw not_supported(IRS_HIP_EUNSUPPORTED, "Or: an And child with an Or inside "
+                              "(a clause is an And of by_term)");
+        if (!c.phrases.empty())
+          throw not_supported(IRS_HIP_EUNSUPPORTED, "Or: an And child with a by_phrase inside "
+                              "(a clause is an And of by_term)");
+        if (c.subs.empty()) throw illegal_argument(IRS_HIP_EINVAL, "Or: an And child without terms");
+        if (c.subs.size() > 1 && c.merge_type != IRS_HIP_MERGE_SUM)
+          throw not_supported(IRS_HIP_EUNSUPPORTED, "Or: an And child merges with SUM on the GPU path");
+        const float mult = o.boost * c.boost;
+        clauses.emplace_back();
+        for (const auto& t : c.subs) clauses.back().push_back(by_term{t.term, mult * t.boost});
+        any = any || c.subs.size() > 1;
+      }
+      size_t total = 0;
+      for (const auto& c : clauses) total += c.size();
+      if (any && total > IRS_HIP_MAX_TERMS)
+        throw not_supported(IRS_HIP_EUNSUPPORTED, "Or: more than IRS_HIP_MAX_TERMS terms in its clauses");
+      q.op = o.min_match_count > 1 ? IRS_HIP_OP_MINMATCH : IRS_HIP_OP_OR;
+      q.min_match = o.min_match_count > 1 ? o.min_match_count : 0;
+      q.merge = IRS_HIP_MERGE_SUM;
+      for (const auto& c : clauses)
+        for (size_t i = 0; i < c.size(); ++i) {
+          irs_hip_term_scorer e = one(c[i]);
+          if (i) e.kind |= IRS_HIP_CLAUSE_AND;
+          q.terms.push_back(e);
+        }
     } else if (const auto* o = std::get_if<Or>(&f)) {
       q.op = o->min_match_count > 1 ? IRS_HIP_OP_MINMATCH : IRS_HIP_OP_OR;
       q.min_match = o->min_match_count > 1 ? o->min_match_count : 0;
@@ -484,6 +537,10 @@ std::vector<PreparedQuery> prepare(const std::vector<filter>& filters, const Sco
       for (const auto& t : m->terms) q.terms.push_back(one(by_term{t.term, m->boost * t.boost}));
     } else if (const auto* x = std::get_if<Exclusion>(&f)) {
       fill(q, x->incl);
+      for (const irs_hip_term_scorer& e : q.terms)
+        if ((e.kind & IRS_HIP_CLAUSE_AND) && (!x->excl.empty() || x->doc_set))
+          throw not_supported(IRS_HIP_EUNSUPPORTED, "Not children or a doc set around an Or with And "
+                              "children (its units read the streams every unit shares)");
       // behind the included entries: one IRS_HIP_EXCLUDE entry per excluded term, no scorer
       for (const by_term& t : x->excl) {
         irs_hip_term_scorer e{};
@@ -904,6 +961,15 @@ class QueryBatch {
   // last run decoded itself — the rest came out of the device's stream cache
   struct StreamCounts { uint32_t distinct = 0, decoded = 0; };
   // the batch's units of by_scored_terms / wide expansion queries (irs_hip_batch_wide_units)
+  uint32_t clause_units() const {   // ... of Ors with And children (irs_hip_batch_clause_units)
+    uint32_t total = 0;
+    for (const Part& part : part_) {
+      uint32_t n = 0;
+      if (part.h) check(irs_hip_batch_clause_units(part.h, &n), "irs_hip_batch_clause_units");
+      total += n;
+    }
+    return total;
+  }
   uint32_t wide_units() const {
     uint32_t total = 0;
     for (const Part& part : part_) {

@@ -5,7 +5,7 @@
 // the end, the waits of a batch: one function per thing a caller is about to touch (a run, a plan
 // stage, match sets, a setter's re-deal, a reader of the last run, destroy).  The run itself: run.h.
 // The unit lists and who fills them (units.h: commit_unit is create's only writer per unit):
-//   all_tile_units, all_conj_units, wide.units   commit_unit, fixed at create
+//   all_tile_units, all_conj_units, wide.units, clause.units   commit_unit, fixed at create
 //   blocks.units   a phrase batch: build_phrase_work at create; else deal_units, from all_conj_units
 //   any.units      build_any_work at create, from the grouped units commit_unit listed
 //   tiles.units, join.units   deal_units (ensure_scratch), from all_tile_units / all_conj_units
@@ -137,6 +137,18 @@ struct JoinWork {
 // their per-term records lie in join.d_jterms; nothing else of the batch counts them in (acc32,
 // count_precise, jt, tiles.any_and, all_tile_units, all_conj_units).
 struct WideWork {
+  std::vector<uint32_t> units;
+  bool on() const { return !units.empty(); }
+  DevBuf d_units;
+  uint32_t n_max = 0;   // doc tiles of the unit with the most
+  uint32_t n_min = 0;   // ... with the fewest, empty units aside (pilot stride)
+};
+
+// Ors of clauses (IRS_HIP_CLAUSE_AND; clauses.h, plan_clauses.h): the units, fixed at create, kept
+// apart from the rest of the batch exactly as the wide units are — their entries are streams of
+// JoinWork behind the joined and the wide units', their per-entry records lie in join.d_jterms, the
+// clause table rides in their DevQTerm rows (pad0: the need-mask of the row's clause).
+struct ClauseWork {
   std::vector<uint32_t> units;
   bool on() const { return !units.empty(); }
   DevBuf d_units;
@@ -338,6 +350,7 @@ struct irs_hip_batch {
   TileWork tiles;
   JoinWork join;
   WideWork wide;
+  ClauseWork clause;
   BlockWork blocks;
   AnyWork any;
   // A batch with optional terms (IRS_HIP_PHRASE_OPTIONAL): this batch is the PHRASE PASS; `opt` — a

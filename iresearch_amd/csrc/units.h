@@ -33,6 +33,7 @@ struct UnitShape {
   OpClass op = OpClass::kOr;
   bool variadic = false;   // a phrase with IRS_HIP_PHRASE_ALT members
   bool grouped = false;    // an And with IRS_HIP_GROUP_ALT members
+  bool clause = false;     // an Or / min-match Or with IRS_HIP_CLAUSE_AND members (clauses.h)
   Behind behind = Behind::kNone;
   bool phrase() const { return op == OpClass::kPhrase; }
   bool wide() const { return op == OpClass::kWide; }
@@ -77,6 +78,8 @@ struct Unit {
   uint64_t postings = 0, alg_bytes = 0;
   PhraseParts parts;
   // a grouped And: an entry without IRS_HIP_GROUP_ALT opens a group; bit g: group g has a present member
+  // (an Or of clauses: an entry without IRS_HIP_CLAUSE_AND opens a clause; bit g: every member of
+  // clause g is present)
   uint32_t n_groups = 0, groups_found = 0;
   uint32_t need = 1;         // unit_need: the present terms a doc must match, or kEmptyUnit
   // unit_run
@@ -97,7 +100,7 @@ struct UnitScratch {
   std::vector<DevQTerm> row;          // the unit's present terms
   std::vector<double> smins;          // per present term: the smallest score of one posting
   std::vector<uint32_t> excl;         // the unit's present excluded terms
-  std::vector<uint32_t> row_group;    // per row of a grouped And: its group
+  std::vector<uint32_t> row_group;    // per row of a grouped And: its group; of an Or of clauses: its clause
 };
 
 // A scored multi-term query (IRS_HIP_OP_MULTITERM, wide.h): up to IRS_HIP_MAX_WIDE_TERMS entries
@@ -138,7 +141,8 @@ int unit_shape(const irs_hip_query& in, const irs_hip_term_scorer* terms, uint32
   if (uint64_t(in.first_term) + in.n_terms > n_entries) return IRS_HIP_EINVAL;
   const irs_hip_term_scorer* ents = terms + in.first_term;
   sh = UnitShape{};
-  while (sh.n_incl < in.n_terms && ents[sh.n_incl].kind != IRS_HIP_EXCLUDE) ++sh.n_incl;
+  int32_t kinds = 0;   // every included entry's kind OR-ed together: the flags some entry carries
+  while (sh.n_incl < in.n_terms && ents[sh.n_incl].kind != IRS_HIP_EXCLUDE) kinds |= ents[sh.n_incl++].kind;
   sh.n_excl = in.n_terms - sh.n_incl;
   auto flagged = [&](int32_t flag) {
     bool any = false;
@@ -149,12 +153,17 @@ int unit_shape(const irs_hip_query& in, const irs_hip_term_scorer* terms, uint32
   sh.variadic = in.op == IRS_HIP_OP_PHRASE && flagged(IRS_HIP_PHRASE_ALT);
   if (sh.variadic && sh.n_incl > IRS_HIP_MAX_PHRASE_ENTRIES) return IRS_HIP_EUNSUPPORTED;
   sh.op = OpClass(in.op);
+  // an Or of clauses (IRS_HIP_CLAUSE_AND members): clause_shape_ok states what create takes
+  sh.clause = (kinds & IRS_HIP_CLAUSE_AND) != 0;
+  if (sh.clause && clause_shape_ok(in, ents, sh.n_incl, sh.n_excl) == IRS_HIP_EINVAL) return IRS_HIP_EINVAL;
   if ((in.op != IRS_HIP_OP_OR && in.op != IRS_HIP_OP_AND && in.op != IRS_HIP_OP_MINMATCH && !sh.phrase() && !sh.wide()) ||
       sh.n_incl == 0 || in.merge > IRS_HIP_MERGE_MIN || (sh.phrase() && in.merge != IRS_HIP_MERGE_SUM) ||
-      (!sh.wide() && sh.n_incl > IRS_HIP_MAX_TERMS) || sh.n_excl > IRS_HIP_MAX_EXCLUDED || in.k == 0 ||
+      (!sh.wide() && !sh.clause && sh.n_incl > IRS_HIP_MAX_TERMS) || sh.n_excl > IRS_HIP_MAX_EXCLUDED || in.k == 0 ||
       in.k > IRS_HIP_MAX_K)
     return IRS_HIP_EINVAL;
   sh.n_words = sh.n_incl;
+  if (sh.clause)
+    if (const int rc = clause_shape_ok(in, ents, sh.n_incl, sh.n_excl)) return rc;
   if (sh.wide())
     if (const int rc = wide_shape_ok(in, sh)) return rc;
   if (sh.phrase())
@@ -231,12 +240,25 @@ int unit_rows(const irs_hip_term_scorer* ents, const irs_hip_segment* seg, Unit&
   s.row.clear();
   s.smins.clear();
   s.row_group.clear();
+  // an Or of clauses: a clause with an absent member is empty in this segment — none of its entries
+  // is a row (bit c of `dead`)
+  uint32_t clause_of[IRS_HIP_MAX_TERMS];   // (written and read for such a unit only)
+  uint32_t dead = 0;
+  if (sh.clause) {
+    u.n_groups = clause_of_entries(ents, sh.n_incl, clause_of);
+    for (uint32_t j = 0; j < sh.n_incl; ++j) {
+      const uint32_t t = ents[j].term;
+      if (t == IRS_HIP_NO_TERM || (t < seg->dev.num_terms && seg->terms[t].docs_count == 0)) dead |= 1u << clause_of[j];
+    }
+    u.groups_found = ((1u << u.n_groups) - 1u) & ~dead;
+  }
   for (uint32_t j = 0; j < sh.n_incl; ++j) {
     const irs_hip_term_scorer& ts = ents[j];
     const bool behind = sh.phrase() && j >= sh.n_words;   // (a required or an optional term)
     const bool optional = behind && sh.behind == Behind::kOptional;   // (no part of the phrase: absent, it is dropped)
     const int32_t kind = sh.phrase() ? (ts.kind & ~(IRS_HIP_PHRASE_ALT | IRS_HIP_PHRASE_REQUIRED | IRS_HIP_PHRASE_OPTIONAL))
-                         : sh.grouped ? (ts.kind & ~IRS_HIP_GROUP_ALT) : ts.kind;
+                         : sh.grouped ? (ts.kind & ~IRS_HIP_GROUP_ALT)
+                         : sh.clause ? (ts.kind & ~IRS_HIP_CLAUSE_AND) : ts.kind;
     if (sh.grouped && !(ts.kind & IRS_HIP_GROUP_ALT)) ++u.n_groups;
     if (sh.phrase())
       if (const int rc = u.parts.enter(ents, j, (ts.kind & IRS_HIP_PHRASE_ALT) != 0, optional)) return rc;
@@ -260,8 +282,12 @@ int unit_rows(const irs_hip_term_scorer* ents, const irs_hip_segment* seg, Unit&
     if (qt.term == IRS_HIP_NO_TERM || seg->terms[qt.term].docs_count == 0) {
       // (a phrase / grouped conjunction: an absent member is dropped; a part / group without
       // a present one empties the unit, unit_need)
-      if (!sh.phrase() && !sh.grouped) u.absent = true;
+      if (!sh.phrase() && !sh.grouped && !sh.clause) u.absent = true;
       continue;
+    }
+    if (sh.clause) {
+      if ((dead >> clause_of[j]) & 1u) continue;
+      s.row_group.push_back(clause_of[j]);
     }
     if (sh.grouped) {
       u.groups_found |= 1u << (u.n_groups - 1u);
@@ -309,6 +335,9 @@ int unit_need(const irs_hip_query& in, Unit& u, UnitScratch& s) {
   const UnitShape& sh = u.shape;
   const uint32_t n_rows = uint32_t(s.row.size());
   u.need = 1;
+  // an Or of clauses: min_match counts the clauses (MinMatchQuery::execute over the children)
+  const uint32_t n_live = sh.clause ? uint32_t(__builtin_popcount(u.groups_found)) : n_rows;
+  const uint32_t n_subs = sh.clause ? u.n_groups : sh.n_incl;
   switch (sh.op) {
     case OpClass::kOr: break;
     case OpClass::kAnd:
@@ -318,7 +347,7 @@ int unit_need(const irs_hip_query& in, Unit& u, UnitScratch& s) {
       // Or::prepare turns min_match_count == 0 into the all-docs filter
       // (boolean_filter.cpp:213): not a posting-list query, not on this path
       if (in.min_match == 0) return IRS_HIP_EUNSUPPORTED;
-      u.need = (in.min_match > sh.n_incl || in.min_match > n_rows) ? kEmptyUnit : in.min_match;
+      u.need = (in.min_match > n_subs || in.min_match > n_live) ? kEmptyUnit : in.min_match;
       break;
     case OpClass::kWide: u.need = in.min_match > n_rows ? kEmptyUnit : in.min_match; break;
     case OpClass::kPhrase:
@@ -380,6 +409,14 @@ void unit_run(const irs_hip_query& in, const irs_hip_segment* seg, Unit& u, Unit
     // the unit's own 64-bit sums whatever min_match is
     run = kRunWide;
     op_need = u.need;
+  } else if (sh.clause) {
+    // lane j = row j of k_clause_pilot / k_clause_score; every row carries the need-mask of its
+    // clause (DevQTerm::pad0), `need` counts clauses
+    run = kRunClause;
+    op_need = u.need;
+    uint32_t masks[IRS_HIP_MAX_TERMS] = {};
+    clause_masks(s.row_group.data(), row.size(), masks);
+    for (size_t r = 0; r < row.size(); ++r) row[r].pad0 = masks[r];
   } else if (sh.grouped) {   // always block driven (conj_any.h), whatever the number of rows
     if (!row.empty()) u.group_opens = sort_groups(seg, u.n_groups, s);
     run = kRunConj;
@@ -404,7 +441,7 @@ void unit_run(const irs_hip_query& in, const irs_hip_segment* seg, Unit& u, Unit
   // disjunction.hpp:338-351) resp. with the zeroed score buffer (block_disjunction
   // :1308-1351): two sub-iterators -> min where both match, else 0; more (or the
   // min-match block disjunction) -> 0 for every doc.
-  uint32_t merge = row.size() > 1 ? in.merge : uint32_t(IRS_HIP_MERGE_SUM);
+  uint32_t merge = row.size() > 1 && !sh.clause ? in.merge : uint32_t(IRS_HIP_MERGE_SUM);
   bool min_both = false;
   if (merge == IRS_HIP_MERGE_MIN && run != kRunConj) {
     if (run == kRunTiles && row.size() == 2) {
@@ -421,7 +458,7 @@ void unit_run(const irs_hip_query& in, const irs_hip_segment* seg, Unit& u, Unit
   // match counts in the low bits of a 32-bit accumulator (join.h COUNT) round every posting
   // to 16 fixed-point units (+-8): relative to any doc's score that is at most
   // 8 * upper / (2^29 * min_score) — allowed while it stays below 2e-6
-  u.count_precise = !sh.wide() && row.size() <= kJoinCountTerms && u.min_score > 0.0 && u.upper > 0.0 &&
+  u.count_precise = !sh.wide() && !sh.clause && row.size() <= kJoinCountTerms && u.min_score > 0.0 && u.upper > 0.0 &&
                     u.upper / u.min_score <= 125.0;
 }
 
@@ -458,14 +495,14 @@ int unit_scale(Unit& u, bool has_rows) {
   if (!(u.upper > 0.0 && std::isfinite(u.upper))) return IRS_HIP_EUNSUPPORTED;
   u.bin_scale = float(double(kBins) / u.upper);
   // (irs_hip_batch_set_comm) the bound every segment of the index computes alike
-  if (u.same_bound && !sh.phrase() && !sh.wide() && u.upper_all > 0.0 &&
+  if (u.same_bound && !sh.phrase() && !sh.wide() && !sh.clause && u.upper_all > 0.0 &&
       u.upper_all * (1.0 + 1e-6) >= u.upper && std::isfinite(u.upper_all))
     u.shared_upper = u.upper_all * (1.0 + 1e-6);
   (void)std::frexp(u.upper, &u.exp);
   if (u.exp < -60 || u.exp > 60) return IRS_HIP_EUNSUPPORTED;
   // (grouped units score in floats, block driven: the flat units' accumulators are theirs)
-  // (wide units carry 64-bit sums of their own and never ask)
-  u.acc64 = !sh.grouped && !sh.wide() && (!(u.min_score > 0.0) || u.upper / u.min_score > 1000.0);
+  // (wide units and Ors of clauses carry 64-bit sums of their own and never ask)
+  u.acc64 = !sh.grouped && !sh.wide() && !sh.clause && (!(u.min_score > 0.0) || u.upper / u.min_score > 1000.0);
   return IRS_HIP_OK;
 }
 
@@ -510,6 +547,8 @@ void commit_unit(irs_hip_batch* b, uint32_t q, const irs_hip_query& in, const ir
     if (has_rows) b->blocks.opens[q] = u.parts.opens;
   } else if (sh.wide()) {
     b->wide.units.push_back(q);
+  } else if (sh.clause) {
+    b->clause.units.push_back(q);
   } else if (sh.grouped) {
     if (has_rows) {
       b->any.opens[q] = u.group_opens;
@@ -524,16 +563,16 @@ void commit_unit(irs_hip_batch* b, uint32_t q, const irs_hip_query& in, const ir
   if (u.acc64) b->acc32 = false;
   b->postings += u.postings;
   b->qterms.insert(b->qterms.end(), s.row.begin(), s.row.end());
-  if (!sh.wide()) b->jt = std::max(b->jt, dq.n_terms);   // (the plan table's term slots)
+  if (!sh.wide() && !sh.clause) b->jt = std::max(b->jt, dq.n_terms);   // (the plan table's term slots)
   b->k_max = std::max(b->k_max, in.k);
 }
 
 // Where every flat unit allows 32-bit accumulators (b->acc32, final behind the loop): 2^(30-exp)
-// units instead of commit_unit's 2^(29-exp) high words.  Wide units keep their 64-bit sums.
+// units instead of commit_unit's 2^(29-exp) high words.  Wide units and Ors of clauses keep their 64-bit sums.
 void widen_fixed_point(irs_hip_batch* b) {
   if (!b->acc32) return;
   for (DevQuery& dq : b->queries) {
-    if (unit_is_wide(dq)) continue;
+    if (unit_is_wide(dq) || unit_is_clause(dq)) continue;
     dq.fx_mul = std::ldexp(dq.fx_mul, 1);
     dq.fx_inv = std::ldexp(dq.fx_inv, 31);
   }

@@ -26,7 +26,7 @@ from dataclasses import dataclass, field, replace
 import numpy as np
 
 from . import _lib
-from ._lib import (EXCLUDE, HIT, NO_TERM, OP_AND, OP_MINMATCH, OP_MULTITERM, OP_OR, OP_PHRASE, PHRASE_ALT, PHRASE_OPTIONAL, PHRASE_REQUIRED, QUERY, SCORE_BM1, SCORE_BM15, SCORE_BM25,
+from ._lib import (EXCLUDE, HIT, NO_TERM, OP_AND, OP_MINMATCH, OP_MULTITERM, OP_OR, OP_PHRASE, PHRASE_ALT, PHRASE_OPTIONAL, PHRASE_REQUIRED, CLAUSE_AND, QUERY, SCORE_BM1, SCORE_BM15, SCORE_BM25,
                    SCORE_TFIDF, SCORE_TFIDF_NORM, TERM_META, TERM_SCORER, SegmentDesc)
 
 f32 = np.float32
@@ -106,6 +106,9 @@ MERGE_SUM, MERGE_MAX, MERGE_MIN = 0, 1, 2
 class Or:
     """irs::Or; min_match > 1 is Or::min_match_count() (boolean_filter.hpp); `merge` its
     merge_type(); `boost` multiplies into the boosts of its terms (boolean_filter.cpp:153-154, 204).
+    An Or of by_term and And-of-by_term children — a disjunction of clauses, `(a AND b) OR c`
+    (IRS_HIP_CLAUSE_AND; min_match counts the children, merge SUM, at most 16 terms in all) — is
+    taken by prepare(..., and_clauses=True).
     An Or of ONE by_phrase of plain terms and by_term children — a phrase or optional terms,
     `"new york" hotel cheap` (IRS_HIP_PHRASE_OPTIONAL; min_match <= 1, merge SUM, at most 8 words
     and terms in all) — is taken by prepare(..., optional_terms=True)."""
@@ -381,6 +384,78 @@ def and_groups(flt, mult=1.0):
     return groups
 
 
+def _and_members(flt, mult):
+    """(term, boost product) of every by_term under an And that is a clause of an Or (nested SUM Ands
+    flattened; a one-term And is its term)."""
+    if flt.op != OP_AND:
+        raise ValueError("an And child with op %d inside an Or is not on the GPU path" % flt.op)
+    if not flt.subs:
+        raise ValueError("an And without children inside an Or")
+    if flt.merge != MERGE_SUM and len(flt.subs) > 1:
+        raise ValueError("an And inside an Or merges with SUM on the GPU path (MAX / MIN clauses are "
+                         "not built)")
+    mult = f32(f32(mult) * f32(flt.boost))
+    out = []
+    for s in flt.subs:
+        if type(s) is by_term:
+            out.append((s.term, f32(mult * f32(s.boost))))
+        elif type(s) is And:
+            out += _and_members(s, mult)
+        elif isinstance(s, Or):
+            raise ValueError("an And child of an Or with an Or inside ((a AND (b OR c)) OR d) is not on "
+                             "the GPU path: a clause is an And of by_term")
+        elif isinstance(s, Not):
+            raise ValueError("an And child of an Or with a Not inside ((a AND NOT b) OR c) is not on "
+                             "the GPU path: a clause is an And of by_term")
+        elif isinstance(s, by_phrase):
+            raise ValueError("an And child of an Or with a by_phrase inside is not on the GPU path: a "
+                             "clause is an And of by_term")
+        else:
+            raise ValueError("%s inside an And child of an Or is not on the GPU path" % type(s).__name__)
+    return out
+
+
+def or_clauses(flt, mult=1.0):
+    """The clauses of an Or whose children are by_term, And of by_term and SUM Ors of those,
+    normalised: a by_term child is a clause of one, so is a one-term And (the single node case,
+    boolean_filter.cpp:152-155); nested SUM Ands are flattened into their clause; an Or child with
+    min_match <= 1 that merges with SUM is flattened into its parent where that parent's min_match
+    is <= 1 too (an Or of ONE child is that child under any parent).  Each member is (term, boost):
+    term boost x And boosts x Or boosts, multiplied from the top in float32 as prepare() hands
+    ctx.boost down (boolean_filter.cpp:153-154, 204).  Anything else raises ValueError."""
+    if not flt.subs:
+        raise ValueError("an Or without children")
+    if flt.merge != MERGE_SUM and len(flt.subs) > 1:
+        raise ValueError("an Or with And children merges with SUM on the GPU path (MAX / MIN over "
+                         "clauses are not built)")
+    mult = f32(f32(mult) * f32(flt.boost))
+    clauses = []
+    for s in flt.subs:
+        if type(s) is by_term:
+            clauses.append([(s.term, f32(mult * f32(s.boost)))])
+        elif type(s) is And:
+            clauses.append(_and_members(s, mult))
+        elif type(s) is Or:
+            one = len(s.subs) == 1
+            if s.min_match > 1 or (flt.min_match > 1 and not one):
+                raise ValueError("an Or child of an Or is flattened into it only where both have "
+                                 "min_match <= 1: a min-match over nested Ors is not on the GPU path")
+            if s.merge != MERGE_SUM and not one:
+                raise ValueError("an Or child of an Or merges with SUM on the GPU path")
+            clauses += or_clauses(s, mult)
+        elif isinstance(s, Not):
+            raise ValueError("an Or with a Not child matches all docs but some (zero-score fill, "
+                             "boolean_filter.cpp:120-127): not on the GPU path")
+        elif isinstance(s, by_phrase):
+            raise ValueError("a by_phrase next to an And child in an Or ((a AND b) OR \"c d\") is not on "
+                             "the GPU path: a clause is a by_term or an And of by_term")
+        else:
+            raise ValueError("%s inside an Or is not on the GPU path" % type(s).__name__)
+    if sum(len(c) for c in clauses) > _lib.MAX_TERMS:
+        raise ValueError("an Or has at most %d terms in all its clauses" % _lib.MAX_TERMS)
+    return clauses
+
+
 def _terms_of(flt):
     if isinstance(flt, Not):
         raise ValueError("Not is taken by prepare() only (as a child of an And), not here")
@@ -412,6 +487,9 @@ class PreparedQuery:
     optional: list | None = None   # OP_PHRASE: True for an entry that is an optional term — a by_term
                                    # child of the Or that holds the phrase (IRS_HIP_PHRASE_OPTIONAL),
                                    # carrying its own scorer; None: no Or around the phrase
+    clause: list | None = None     # OP_OR / OP_MINMATCH: True for an entry that is one more required
+                                   # member of the clause before it (IRS_HIP_CLAUSE_AND) — an Or with
+                                   # And children, min_match counting clauses; None: a flat Or
 
 
 # ------------------------------------------------------------------ segment --
@@ -580,7 +658,9 @@ class QueryArrays:
             alts = p.alts if p.alts is not None else [False] * len(p.terms)
             reqs = p.required if p.required is not None else [False] * len(p.terms)
             opts = p.optional if p.optional is not None else [False] * len(p.terms)
-            for t, (kind, c0, nc, nl), off, alt, req, opt in zip(p.terms, p.scorers, offs, alts, reqs, opts):
+            more = p.clause if p.clause is not None else [False] * len(p.terms)
+            for t, (kind, c0, nc, nl), off, alt, req, opt, cl in zip(p.terms, p.scorers, offs, alts, reqs, opts, more):
+                kind = kind | CLAUSE_AND if cl else kind
                 kind = kind | PHRASE_ALT if alt else kind   # (GROUP_ALT for an And: the same bit)
                 kind = kind | PHRASE_REQUIRED if req else kind
                 kind = kind | PHRASE_OPTIONAL if opt else kind
@@ -697,6 +777,9 @@ def prepare_filters(filters, scorer, segment_stats, segs, k):
                     raise ValueError("a by_phrase inside an And (a phrase plus required terms, "
                                      "IRS_HIP_PHRASE_REQUIRED) is taken by prepare(), not by the "
                                      "array path prepare_filters")
+                if cls is Or and any(isinstance(s, (And, Or)) for s in subs):
+                    raise ValueError("an Or with And children (IRS_HIP_CLAUSE_AND) is taken by "
+                                     "prepare(..., and_clauses=True), not by the array path prepare_filters")
                 raise ValueError("only flat Or/And of by_term are on the array path: an And with "
                                  "Or children is taken by prepare()")
             op = flt.op
@@ -1011,6 +1094,13 @@ class QueryBatch:
                    "irs_hip_batch_stream_counts")
         return d.value, n.value
 
+    def clause_units(self) -> int:
+        """irs_hip_batch_clause_units: the batch's units of Ors with And children
+        (IRS_HIP_CLAUSE_AND: k_clause_pilot / k_clause_score)."""
+        n = C.c_uint32()
+        _lib.check(self.L, self.L.irs_hip_batch_clause_units(self.handle, C.byref(n)), "irs_hip_batch_clause_units")
+        return n.value
+
     def wide_units(self) -> int:
         """irs_hip_batch_wide_units: the batch's units of by_terms / wide expansion queries
         (IRS_HIP_OP_MULTITERM), (segment, query) pairs."""
@@ -1162,7 +1252,7 @@ class SegmentStats:
     docs_count: np.ndarray  # per term ordinal: term_meta::docs_count
 
 
-def prepare(filters, scorer, segment_stats, required_terms=False, optional_terms=False):
+def prepare(filters, scorer, segment_stats, required_terms=False, optional_terms=False, and_clauses=False):
     """filter::prepare for a list of filters against ALL segments: statistics are
     index-global (term_filter.cpp:102-125): D = sum docs_with_field,
     d = sum docs_count of the term, avgdl from the summed field frequency.
@@ -1172,7 +1262,10 @@ def prepare(filters, scorer, segment_stats, required_terms=False, optional_terms
     change until they ask for it.
     optional_terms=True: Or([by_phrase, by_term...]) — a phrase or optional terms,
     IRS_HIP_PHRASE_OPTIONAL — is taken, also as the one included child of And([Or([...]), Not(...)]).
-    Off by default in the same way."""
+    Off by default in the same way.
+    and_clauses=True: Or([And([by_term...]), by_term, Or([...])...]) — an Or with And children, a
+    disjunction of clauses, IRS_HIP_CLAUSE_AND (or_clauses) — is taken.  Off by default in the same
+    way: without it such an Or is refused as it always was."""
     dwf = sum(s.docs_with_field for s in segment_stats)
     ttf = sum(s.total_term_freq for s in segment_stats)
     out = []
@@ -1180,14 +1273,20 @@ def prepare(filters, scorer, segment_stats, required_terms=False, optional_terms
         flt, doc_set = split_doc_set(flt)
         if doc_set is not None:
             # (the doc set is no part of what is prepared: no score, no statistic)
-            p = prepare([flt], scorer, segment_stats, required_terms, optional_terms)[0]
+            p = prepare([flt], scorer, segment_stats, required_terms, optional_terms, and_clauses)[0]
+            if p.clause is not None:
+                raise ValueError("a by_doc_set on an Or with And children is not on the GPU path "
+                                 "(its units read the streams every unit shares)")
             p.doc_set = doc_set
             out.append(p)
             continue
         flt, excluded = split_exclusions(flt)
         if excluded:
             # (the excluded part is prepared without scorers: no score, no statistic)
-            p = prepare([flt], scorer, segment_stats, required_terms, optional_terms)[0]
+            p = prepare([flt], scorer, segment_stats, required_terms, optional_terms, and_clauses)[0]
+            if p.clause is not None:
+                raise ValueError("Not around an Or with And children (((a AND b) OR c) AND NOT d) is "
+                                 "not on the GPU path")
             p.excluded = [int(t) for t in excluded]
             out.append(p)
             continue
@@ -1222,6 +1321,9 @@ def prepare(filters, scorer, segment_stats, required_terms=False, optional_terms
             continue
         if type(flt) is And and (flt.boost != 1.0 or any(type(s) is not by_term for s in flt.subs)):
             out.append(_prepare_groups(flt, scorer, segment_stats, dwf, ttf))
+            continue
+        if and_clauses and type(flt) is Or and any(type(s) is not by_term for s in flt.subs):
+            out.append(_prepare_clauses(flt, scorer, segment_stats, dwf, ttf))
             continue
         op, subs = _terms_of(flt)
         mult = float(getattr(flt, "boost", 1.0)) if type(flt) is not by_term else 1.0
@@ -1357,6 +1459,23 @@ def _prepare_groups(flt, scorer, segment_stats, dwf, ttf):
             alts.append(i > 0)
     return PreparedQuery(OP_AND, terms, scorers, int(flt.min_match), merge=int(flt.merge),
                          alts=alts if any(alts) else None)
+
+
+def _prepare_clauses(flt, scorer, segment_stats, dwf, ttf):
+    """prepare() of an Or with And children (Or::prepare prepares every child on its own,
+    boolean_filter.cpp:150-210): per-term statistics as for any by_term, the boost product per
+    member; every member after a clause's first flagged IRS_HIP_CLAUSE_AND; min_match counts
+    clauses.  A tree whose clauses all have one member is a flat Or, sent as one."""
+    clauses = or_clauses(flt)
+    terms, scorers, more = [], [], []
+    for c in clauses:
+        for i, (t, boost) in enumerate(c):
+            dwt = sum(int(st.docs_count[t]) for st in segment_stats if 0 <= t < len(st.docs_count))
+            terms.append(t)
+            scorers.append(scorer.term_scorer(scorer.collect(dwf, dwt, ttf), boost))
+            more.append(i > 0)
+    return PreparedQuery(flt.op, terms, scorers, int(flt.min_match), merge=MERGE_SUM,
+                         clause=more if any(more) else None)
 
 
 def variadic_slots(parts, segment_stats):

@@ -13,7 +13,8 @@ terms (And([by_phrase, by_term...])) or optional terms (Or([by_phrase, by_term..
 round runs
 Ands of Or groups (with exclusions, wand on and off; every third over two segments in one batch)
 and by_terms queries of 17..64 entries (IRS_HIP_OP_MULTITERM) mixed into a batch of the round's
-ordinary filters.
+ordinary filters, and likewise Ors with And children (IRS_HIP_CLAUSE_AND: 1-8 clauses, 2-16 entries,
+any min_match) against the per-clause composition of tests/test_or_clauses.py.
 With --doc-sets every round also restricts a random subset of its units to random doc sets
 (irs_hip_batch_set_doc_sets) at densities 0, 0.001, 0.5 and 1, on a path picked at random, and
 compares each against the oracle's run on the segment with the set's complement deleted as well.
@@ -221,6 +222,58 @@ def wide_round(sr, seg, filters, scorer, k, st, rng, max_rank):
     return len(mixed)
 
 
+def clause_round(sr, seg, filters, scorer, k, st, rng, max_rank, term):
+    """Ors with And children (IRS_HIP_CLAUSE_AND, k_clause_pilot / k_clause_score): 1-8 clauses of
+    1-4 members (frequent, rare and absent ranks, boosts with zeros at all three levels, a nested SUM
+    Or now and then, min_match 1 .. clauses + 1) interleaved with some of the round's ordinary
+    filters: the clause ones against the oracle composed per clause (tests/test_or_clauses.py), the
+    ordinary ones bit for bit what a batch without them gives."""
+    import test_or_clauses as tc
+    from iresearch_amd import _lib, search
+    from iresearch_amd.search import And, Or
+    boost = lambda: float(rng.choice([1.0, 1.0, 0.25, 0.5, 2.0, 4.0, 0.0]))   # noqa: E731
+    made = []
+    for _ in range(6):
+        subs, left = [], 16
+        for _ in range(int(rng.integers(1, 9))):
+            n = min(left, int(rng.integers(1, 5)))
+            if n == 0:
+                break
+            left -= n
+            members = [term() for _ in range(n)]
+            subs.append(members[0] if n == 1 else And(members, boost=boost()))
+        if not any(type(s) is And for s in subs):   # (at least one clause of two: a clause query)
+            subs[0] = And([subs[0], term()])
+        mm = int(rng.choice([1, 1, 2, int(rng.integers(1, len(subs) + 2))]))
+        if mm <= 1 and len(subs) > 2 and rng.integers(0, 3) == 0:   # the tail as a nested SUM Or
+            subs = subs[:-2] + [Or(subs[-2:], boost=boost())]
+        made.append(Or(subs, min_match=mm, boost=float(rng.choice([1.0, 1.0, 1.5]))))
+    mixed = []
+    for i, f in enumerate(made):
+        mixed += [f] + filters[i:i + 1]
+    at_c = [i for i, f in enumerate(mixed) if any(f is m for m in made)]
+    at_o = [i for i in range(len(mixed)) if i not in at_c]
+    path = int(rng.choice([_lib.PATH_AUTO, _lib.PATH_ITEMS, _lib.PATH_JOINED]))
+    try:
+        b = sr.batch(search.prepare(mixed, scorer, st, and_clauses=True), k).set_path(path)
+    except _lib.IrsHipError as e:   # (a frequency above 255 in one of the lists: not on this path)
+        assert e.status == _lib.EUNSUPPORTED, e
+        return 0
+    if rng.integers(0, 3) == 0:
+        b.configure(cand_cap=max(k, 64))
+    h, c, t = (x.copy() for x in b.run().results())
+    assert b.clause_units() == len(made)
+    b.close()
+    if at_o:
+        pb = sr.batch(search.prepare([mixed[i] for i in at_o], scorer, st), k).set_path(path)
+        ph, pc, pt = pb.run().results()
+        assert np.array_equal(h[at_o], ph) and np.array_equal(c[at_o], pc) and np.array_equal(t[at_o], pt), "mixed batch"
+        pb.close()
+    for q in at_c:
+        tc.check(mixed[q], k, h[q], c[q], t[q], *tc.expected(seg, mixed[q], scorer))
+    return len(mixed)
+
+
 def match_round(b, seg, filters, totals, excl=None):
     """Unscored execution of the same batch (irs_hip_batch_match_sets): every unit's set bit for bit
     against the oracle (tests/test_match_sets.py want_set), the counts against the scored totals.
@@ -378,6 +431,7 @@ def main():
             # And of Or groups (k_conj_any), every round; over two segments every third
             queries += grouped_round(sr, seg, scorer, k, st, rng, max_rank, term, merge, rounds % 3 == 2, L)
             queries += wide_round(sr, seg, filters, scorer, k, st, rng, max_rank)
+            queries += clause_round(sr, seg, filters, scorer, k, st, rng, max_rank, term)
             if rounds % 3 == 0:   # the same results through page-locked host memory, a run later
                 hh, hc, ht = b.run().results_to_host().host_results()
                 assert np.array_equal(hc, counts) and np.array_equal(ht, totals), "host results: counts"

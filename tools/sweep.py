@@ -32,6 +32,12 @@ def main():
                     help="terms per query; --op terms and --op or take a comma list (17,32,50,64): each is "
                          "timed on the same index, one line per count, then exits")
     ap.add_argument("--min-match", type=int, default=1, help="--op terms: by_terms_options::min_match")
+    ap.add_argument("--clauses", default="",
+                    help="--op or: comma list of SPECs, each the clause sizes of an Or with And children over "
+                         "the --terms entries of every query (IRS_HIP_CLAUSE_AND: k_clause_pilot / "
+                         "k_clause_score) — 2+1+1 is one two-term clause and two single terms, 2x8 is eight "
+                         "clauses of two; the sizes add up to --terms.  Times each on the same entry lists "
+                         "(those of --op terms at the same --terms) and exits")
     ap.add_argument("--layout", type=int, default=1, help="0 = scalar (1_5), 1 = simd4 (1_5simd)")
     ap.add_argument("--scorer", default="bm25", choices=["bm25", "tfidf", "bm15"])
     ap.add_argument("--lib", default=None, help="alternative build of libirs_hip.so (A/B runs)")
@@ -107,6 +113,43 @@ def main():
     scorer = {"bm25": BM25(), "tfidf": TFIDF(True), "bm15": BM25(1.2, 0.0)}[args.scorer]
     st = search.SegmentStats(seg.docs_with_field, seg.total_term_freq,
                              np.asarray(seg.metas["docs_count"]))
+    if args.clauses:
+        # one line per SPEC: the rows of --op terms at the same --terms, cut into clauses
+        if args.op != "or" or len(term_counts) > 1:
+            raise SystemExit("--clauses goes with --op or and one --terms")
+        _, stride = (int(x) for x in args.configs.split(",")[0].split(":"))
+        for spec in args.clauses.split(","):
+            sizes = []
+            for part in spec.split("+"):
+                size, _, times = part.partition("x")
+                sizes += [int(size)] * (int(times) if times else 1)
+            if sum(sizes) != args.terms or min(sizes) < 1:
+                raise SystemExit("--clauses %s: the clause sizes add up to --terms %d" % (spec, args.terms))
+            fl = []
+            for row in ranks:
+                at, subs = 0, []
+                for size in sizes:
+                    members = [by_term(int(r) - 1) for r in row[at:at + size]]
+                    subs.append(members[0] if size == 1 else And(members))
+                    at += size
+                fl.append(Or(subs, min_match=args.min_match))
+            b = sr.batch(search.prepare(fl, scorer, [st], and_clauses=True), args.k).configure(0, stride, 0).profile(True)
+            b.run()
+            _, _, totals = b.results()
+            ms = []
+            t0 = time.perf_counter()
+            for _ in range(args.steps):
+                b.run()
+                ms.append(b.timings())
+            dt = (time.perf_counter() - t0) / args.steps
+            avg = np.mean(ms, axis=0)
+            alg, post = b.work()
+            print("or terms=%d clauses=%s min_match=%d  clause units %d  step %.2f ms  plan %.2f pilot %.2f score %.2f "
+                  "select %.2f  %.1f M postings  streams (distinct, decoded) %s  hits/query mean %.0f  reruns=%d" % (
+                      args.terms, spec, args.min_match, b.clause_units(), dt * 1e3, *avg, post / 1e6,
+                      b.stream_counts(), float(np.mean(totals)), b.reruns()), flush=True)
+            b.close()
+        sys.exit(0)
     if args.op == "terms" or len(term_counts) > 1:
         # one line per term count: by_terms on the wide kernels (k_wide_pilot / k_wide_score in the
         # pilot / score stages) or the Or of as many by_terms on the paths it takes today

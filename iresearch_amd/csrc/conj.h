@@ -14,13 +14,12 @@
 //      largest block-max score among its blocks overlapping the lead block's doc range; a
 //      bound below the threshold bin (from the pilot pass) skips the lead block — nothing is
 //      decoded;
-//   1. the lead block is decoded: 128 ascending docs and their frequencies into LDS;
-//   2. for every other term, cheapest first: binary search of the block directory for the
-//      first block reaching the lead block's first doc, then 64 directory entries per step, a
-//      lane each, tested against the docs still alive ("is any of them in (previous last,
-//      last]"); only blocks that pass are decoded, and each decoded posting looks its doc up
-//      among the lead docs (binary search in LDS): a hit leaves the term's frequency in the
-//      term's row.  A term that leaves no doc alive ends the block;
+//   1. the lead block is decoded: 128 ascending docs and their frequencies into LDS, the lead
+//      frame (lead.h) over their doc range;
+//   2. for every other term, cheapest first: from the first block reaching the lead block's first
+//      doc (k_conj_seek) the blocks that can hold a doc still alive are decoded (follow_list,
+//      lead.h), and each decoded posting looks its doc up among the lead docs: a hit leaves the
+//      term's frequency in the term's row.  A term that leaves no doc alive ends the block;
 //   3. docs every term reached are the conjunction.  Only THEY are scored — as the reference
 //      scores a doc after converge() has accepted it (conjunction.hpp:176-187): their norm is
 //      read, the per-term scores are summed in cost order (the order the reference's
@@ -31,7 +30,7 @@
 // the matches instead (k_conj_threshold turns the histogram into the threshold bin).
 #pragma once
 #include "gpu_rt.h"
-#include "phrase.h"
+#include "lead.h"
 #include "score.h"
 
 namespace irs_hip {
@@ -245,29 +244,6 @@ k_wand_skip0(DevSegment seg, const uint64_t* skip_at /*[term] absolute offset of
   }
 }
 
-// Doc block `e` of a term, from the packed image when both parts live there (one funnel
-// shift + one bit-field extract per value), else from `.doc` (any framing).
-template<int LAYOUT>
-__device__ __forceinline__ void decode_dir_block(const DevSegment& seg, uint64_t doc_start,
-                                                 uint32_t bits, uint32_t off, uint32_t aoff,
-                                                 uint32_t base, unsigned lane, uint32_t& d0,
-                                                 uint32_t& d1, uint32_t& f0, uint32_t& f1) {
-  const uint32_t dbits = bits & 0xFFu, fbits = bits >> 8;
-  if (pk_both(dbits, fbits)) {
-    const uint64_t pl = reinterpret_cast<uint64_t>(seg.pk) + (uint64_t(aoff) << 4);
-    uint64_t da, db, fa, fb;
-    raw_load_packed_g<LAYOUT>(pl, dbits, lane, da, db);
-    raw_load_packed_g<LAYOUT>(pl + 16u * dbits, fbits, lane, fa, fb);
-    uint32_t x0, x1;
-    extract_fast<LAYOUT>(da, db, dbits, lane, x0, x1);
-    extract_fast<LAYOUT>(fa, fb, fbits, lane, f0, f1);
-    d1 = base + wave::inclusive_scan(x0 + x1);
-    d0 = d1 - x1;
-  } else {
-    decode_block<LAYOUT, true>(seg.doc + doc_start + off, dbits, fbits, base, lane, d0, d1, f0, f1);
-  }
-}
-
 // Conjunction::Score2 / ScoreN (conjunction.hpp:105-126): the first sub-score, then the
 // filter's merger over the others (SumMerger / MaxMerger / MinMerger, scorer.hpp:390-423).
 __device__ __forceinline__ float merge_scores(uint32_t merge, bool first, float acc, float s) {
@@ -280,14 +256,9 @@ __device__ __forceinline__ float merge_scores(uint32_t merge, bool first, float 
 constexpr uint32_t kConjWaves = 4;  // wavefronts (= lead blocks) per workgroup
 constexpr uint32_t kConjRows = 4;   // frequency rows per wavefront (terms scored per flush)
 
-// LDS of one wavefront.  The lead block's doc range [dlo, dhi] is cut into kConjBuckets buckets of
-// 2^s docs (s = 0 when the range is that small).  Per bucket: the entry index of its FIRST lead
-// doc (`first`, 0 = none) — "is this decoded posting's doc a lead doc, and which" is one byte
-// read, a walk over the bucket's lead docs (1.1 on average) and a compare, where a search of the
-// sorted docs walks seven dependent reads (round 6: the search ran for ~every decoded block of a
-// sparse lead, a third of the kernel's instructions); "has every earlier term reached it" is
-// cnt[].  And one BIT per bucket in doc-range bitmaps: "does this block of the other term hold a
-// doc still alive" is two prefix-count reads for a directory entry.
+// LDS of one wavefront: the lead frame of lead.h (docs, `first`, three bitmaps: what the current
+// term reaches is alive for the next), the frequency rows, and per lead doc "has every earlier term
+// reached it": cnt[].
 struct ConjWave {
   uint32_t docs[kBlock];
   float score[kBlock];
@@ -311,14 +282,8 @@ k_conj(ConjArgs A, uint32_t pilot) {
   const unsigned lane = tid & 63u;
   const uint32_t wv = wave::uniform(tid >> 6);
   // one lead item per wavefront: record e (pilot pass: the sampled items' records)
-  uint32_t e = blockIdx.x * kConjWaves + wv;
-  if (pilot) {
-    if (e >= A.n_pilot) return;
-    const PhraseWg w = A.wgs[e];
-    e = wave::uniform(A.unit_items[w.unit] + w.first_item);
-  } else if (e >= A.n_items) {
-    return;
-  }
+  const uint32_t e = lead_item_of(A, pilot, kConjWaves);
+  if (e == kNoItem) return;
   // (wave-uniform records are read with scalar loads, at the point of use)
   const ConjItem R = wave::sload<ConjItem>(reinterpret_cast<uint64_t>(A.recs) + uint64_t(e) * sizeof(ConjItem));
   const uint32_t unit = R.unit, item = R.item & kConjItemBlock;
@@ -392,31 +357,12 @@ k_conj(ConjArgs A, uint32_t pilot) {
   uint32_t n = kBlock;
   uint32_t bytes = 0;   // (wave-uniform) encoded bytes of the blocks this wavefront decodes
   const bool counting = !pilot && A.touched != nullptr;   // (irs_hip_batch_profile bit 1)
-  auto block_bytes = [](uint32_t bits) {   // header bytes + payloads (all-equal: ~1 byte of vint)
-    const uint32_t db = bits & 0xFFu, fb = bits >> 8;
-    return 2u + (db ? 16u * db : 1u) + (fb ? 16u * fb : 1u);
-  };
   uint32_t ld_d[2], ld_e[2];   // this lane's two lead docs and their entry indices
   bool live[2];                // ... and whether they are docs of the conjunction at all
   uint32_t sub_lo = 0;         // first posting of the block that is this item's (a piece: > 0)
   {
-    uint32_t f[2], estep;
-    if (item < ld.nblk) {
-      decode_dir_block<LAYOUT>(seg, ld.doc_start, R.bits, R.off, R.aoff, R.base, lane, ld_d[0],
-                               ld_d[1], f[0], f[1]);
-      if (counting) bytes += block_bytes(R.bits);
-      ld_e[0] = 2u * lane;
-      estep = 1u;
-    } else {
-      n = ld.n;
-      ld_d[0] = lane < n ? seg.tail_docs[ld.tail_row + lane] : 0u;
-      ld_d[1] = lane + 64u < n ? seg.tail_docs[ld.tail_row + lane + 64u] : 0u;
-      f[0] = lane < n ? seg.tail_freqs[ld.tail_row + lane] : 0u;
-      f[1] = lane + 64u < n ? seg.tail_freqs[ld.tail_row + lane + 64u] : 0u;
-      ld_e[0] = lane;
-      estep = 64u;
-    }
-    ld_e[1] = ld_e[0] + estep;
+    uint32_t f[2];
+    n = lead_decode<LAYOUT>(seg, ld, R, item, lane, counting, bytes, ld_d, ld_e, f);
     if (split_lg) {   // (wave-uniform) this item's piece of the block: its postings move to the front
       const uint32_t per = (n + (1u << split_lg) - 1u) >> split_lg;
       sub_lo = piece * per;
@@ -447,8 +393,7 @@ k_conj(ConjArgs A, uint32_t pilot) {
         W.bm[k][2u * lane + 1u] = 0u;
       }
     }
-    static_assert(kConjBuckets == 64u * 16u, "one 16-byte store per lane clears `first`");
-    reinterpret_cast<ConjQuad*>(W.first)[lane] = ConjQuad{0u, 0u, 0u, 0u};
+    lead_first_clear(W.first, lane);
   }
   // the docs every one of the terms [g0, g1) reached (and every earlier one) get those terms'
   // scores: norm read here, once per flush, for these docs only — they are postings of the lead
@@ -484,42 +429,22 @@ k_conj(ConjArgs A, uint32_t pilot) {
     lead_skipped(A, unit, counting, bytes, lane);
     return;
   }
-  const uint32_t dlo = wave::uniform(docs[0]), dhi = wave::uniform(docs[n - 1]);
-  // bucket of a doc: (doc - dlo) >> s, below 32 * kConjWords
-  const uint32_t span = dhi - dlo;
-  const uint32_t s = span < kConjBuckets ? 0u
-                     : 32u - uint32_t(__builtin_clz(span)) - (5u + uint32_t(__builtin_ctz(kConjWords)));
+  const LeadFrame fr = lead_frame(docs, n);
   const bool masked = qd.dead != nullptr;   // (wave-uniform)
 #pragma unroll
   for (int h = 0; h < 2; ++h) {
     if (ld_e[h] < n) {
-      const uint32_t bk = (ld_d[h] - dlo) >> s;
+      const uint32_t bk = fr.bucket(ld_d[h]);
       atomicOr(&W.bm[0][bk >> 5], 1u << (bk & 31u));
       // (what the first other term may reach is the LIVE lead docs: bm[2], free until the third
       // term marks into it)
       if (masked && live[h]) atomicOr(&W.bm[2][bk >> 5], 1u << (bk & 31u));
-      // the bucket's first lead doc (entries are in doc order: its predecessor lies in another)
-      if (ld_e[h] == 0u || ((docs[ld_e[h] - 1u] - dlo) >> s) != bk) W.first[bk] = uint8_t(ld_e[h] + 1u);
     }
   }
+  lead_first_fill(fr, W.first, docs, ld_d, ld_e, n);
   wave::sync();
-  // bits in the words before word w (lane: words 2*lane, 2*lane+1; [kConjWords] = all)
-  auto prefix = [&](const uint32_t* bmap, uint8_t* pre) {
-    uint32_t p0 = 0, p1 = 0;
-    if (lane < kConjWords / 2u) {
-      p0 = uint32_t(__builtin_popcount(bmap[2u * lane]));
-      p1 = uint32_t(__builtin_popcount(bmap[2u * lane + 1u]));
-    }
-    const uint32_t incl = wave::inclusive_scan(p0 + p1);
-    if (lane < kConjWords / 2u) {
-      pre[2u * lane] = uint8_t(incl - p0 - p1);
-      pre[2u * lane + 1u] = uint8_t(incl - p1);
-    }
-    if (lane == kConjWords / 2u - 1u) pre[kConjWords] = uint8_t(incl);
-    wave::sync();
-    return wave::read_lane(incl, 63);
-  };
-  prefix(W.bm[0], W.lpre);
+  bitmap_prefix(W.bm[0], W.lpre, lane);
+  wave::sync();
 
   // ---- 2. the other terms, cheapest first
   for (uint32_t i = 1; i < m; ++i) {
@@ -541,126 +466,44 @@ k_conj(ConjArgs A, uint32_t pilot) {
         mark[2u * lane + 1u] = 0u;
       }
       apre = W.apre;
-      if (prefix(alive, W.apre) == 0u) {   // no doc reached by every term so far: done
+      const uint32_t left = bitmap_prefix(alive, W.apre, lane);
+      wave::sync();
+      if (left == 0u) {   // no doc reached by every term so far: done
         if (!pilot && A.touched && lane == 0)
           atomicAdd(&A.touched[2u * unit], static_cast<unsigned long long>(bytes));
         return;
       }
     }
-    // alive bits in the buckets below x, 0 <= x <= 32 * kConjWords
-    auto alive_below = [&](uint32_t x) {
-      return uint32_t(apre[x >> 5]) + uint32_t(__builtin_popcount(alive[x >> 5] & ((1u << (x & 31u)) - 1u)));
-    };
     // a decoded posting of term i: is its doc one of the lead docs still alive?
     auto put = [&](uint32_t doc, uint32_t f) {
-      const uint32_t x = doc - dlo;
-      if (f == 0 || x > span) return;
-      const uint32_t bk = x >> s;
-      const uint32_t t = lead_index(W.first, docs, n, bk, s, doc);
+      const uint32_t x = doc - fr.dlo;
+      if (f == 0 || x > fr.span) return;
+      const uint32_t bk = x >> fr.s;
+      const uint32_t t = lead_index(W.first, docs, n, bk, fr.s, doc);
       // (a lead doc every earlier term reached: deleted lead docs count 0 and stay out)
       if (t == n || cnt[t] != i) return;
       row[t] = f;
       cnt[t] = uint8_t(i + 1u);
       if (i + 1u < m) atomicOr(&mark[bk >> 5], 1u << (bk & 31u));   // (alive for the next term)
     };
-    if (tl.nblk) {
-      // (integer addresses: loads through the global address space, see raw_load_packed_g)
+    uint32_t b_first = seek[i - 1u];
+    if (piece && tl.nblk) {   // (wave-uniform) the seek row is the whole lead block's: this piece starts
+      // further on — the first block of term i whose last doc reaches the piece's first doc, by a
+      // 64-ary search of the directory's last docs (one load per lane and round)
       const uint64_t last_at = reinterpret_cast<uint64_t>(seg.blk_last + tl.dir_off);
-      const uint64_t dir_at = reinterpret_cast<uint64_t>(seg.blk_dir + tl.dir_off);
-      const uint64_t pk_at = reinterpret_cast<uint64_t>(seg.pk);
-      uint32_t b_first = seek[i - 1u];
-      if (piece) {   // (wave-uniform) the seek row is the whole lead block's: this piece starts
-        // further on — the first block of term i whose last doc reaches the piece's first doc, by a
-        // 64-ary search of the directory's last docs (one load per lane and round)
-        uint32_t hi = tl.nblk;
-        while (hi - b_first > 64u) {
-          const uint32_t step = (hi - b_first + 63u) / 64u;
-          const uint32_t p = b_first + lane * step;
-          const uint32_t v = p < hi ? wave::gload_u32(last_at, p * 4u) : 0xFFFFFFFFu;
-          const uint64_t ge = wave::ballot(v >= dlo);
-          const uint32_t j = ge ? uint32_t(__builtin_ctzll(ge)) : 64u;
-          const uint32_t reach = b_first + j * step;   // (j < 64: block `reach` reaches dlo)
-          if (j < 64u && reach < hi) hi = reach;
-          if (j) b_first += (j - 1u) * step + 1u;
-        }
-      }
-      for (uint32_t b0 = b_first; b0 < tl.nblk; b0 += 64) {
-        const uint32_t bl = b0 + lane;
-        const bool valid = bl < tl.nblk;
-        // the block's last doc AND its directory record in one round trip (the record also
-        // holds the preceding block's last doc): the kernel is a chain of dependent loads —
-        // fetching the record only for the blocks that turn out to be wanted made it one longer
-        const uint32_t lst = valid ? wave::gload_u32(last_at, bl * 4u) : 0xFFFFFFFFu;
-        BlkDir d{};
-        if (valid) {
-          uint32_t w[4];
-          wave::gload_u32x4(dir_at, bl * uint32_t(sizeof(BlkDir)), w);
-          d = BlkDir{w[0], w[1], w[2], w[3]};
-        }
-        // the block holds docs in (prv, lst], prv = the preceding block's lst
-        const uint32_t prv = bl ? d.prev_last : 0u;
-        const bool reach = valid && prv < dhi && lst >= dlo;
-        // some doc every earlier term reached lies in a bucket touching (prv, lst]
-        bool want = false;
-        if (reach) {
-          const uint32_t x0 = prv + 1u > dlo ? prv + 1u - dlo : 0u;
-          const uint32_t x1 = (lst < dhi ? lst : dhi) - dlo;
-          want = alive_below((x1 >> s) + 1u) > alive_below(x0 >> s);
-        }
-        uint64_t mask = wave::ballot(want);
-        const bool more = wave::ballot(valid && prv >= dhi) == 0;  // no block started behind dhi yet
-        while (mask) {
-          const uint32_t k = uint32_t(__builtin_ctzll(mask));
-          mask &= mask - 1;
-          const uint32_t kbits = wave::read_lane(d.bits, k);
-          if (counting) bytes += block_bytes(kbits);
-          // two wanted blocks at a time where both live in the packed image: their payload
-          // loads are in flight together (one round trip for the pair)
-          if (mask && pk_both(kbits & 0xFFu, kbits >> 8)) {
-            const uint32_t k2 = uint32_t(__builtin_ctzll(mask));
-            const uint32_t kbits2 = wave::read_lane(d.bits, k2);
-            if (pk_both(kbits2 & 0xFFu, kbits2 >> 8)) {
-              mask &= mask - 1;
-              if (counting) bytes += block_bytes(kbits2);
-              const uint64_t pl1 = pk_at + (uint64_t(wave::read_lane(d.aoff, k)) << 4);
-              const uint64_t pl2 = pk_at + (uint64_t(wave::read_lane(d.aoff, k2)) << 4);
-              uint64_t da1, db1, fa1, fb1, da2, db2, fa2, fb2;
-              raw_load_packed_g<LAYOUT>(pl1, kbits & 0xFFu, lane, da1, db1);
-              raw_load_packed_g<LAYOUT>(pl1 + 16u * (kbits & 0xFFu), kbits >> 8, lane, fa1, fb1);
-              raw_load_packed_g<LAYOUT>(pl2, kbits2 & 0xFFu, lane, da2, db2);
-              raw_load_packed_g<LAYOUT>(pl2 + 16u * (kbits2 & 0xFFu), kbits2 >> 8, lane, fa2, fb2);
-              uint32_t x0, x1, f0, f1;
-              extract_fast<LAYOUT>(da1, db1, kbits & 0xFFu, lane, x0, x1);
-              extract_fast<LAYOUT>(fa1, fb1, kbits >> 8, lane, f0, f1);
-              uint32_t d1 = wave::read_lane(d.prev_last, k) + wave::inclusive_scan(x0 + x1);
-              put(d1 - x1, f0);
-              put(d1, f1);
-              extract_fast<LAYOUT>(da2, db2, kbits2 & 0xFFu, lane, x0, x1);
-              extract_fast<LAYOUT>(fa2, fb2, kbits2 >> 8, lane, f0, f1);
-              d1 = wave::read_lane(d.prev_last, k2) + wave::inclusive_scan(x0 + x1);
-              put(d1 - x1, f0);
-              put(d1, f1);
-              continue;
-            }
-          }
-          uint32_t d0, d1, f0, f1;
-          decode_dir_block<LAYOUT>(seg, tl.doc_start, kbits, wave::read_lane(d.off, k),
-                                   wave::read_lane(d.aoff, k), wave::read_lane(d.prev_last, k),
-                                   lane, d0, d1, f0, f1);
-          put(d0, f0);
-          put(d1, f1);
-        }
-        if (!more) break;
+      uint32_t hi = tl.nblk;
+      while (hi - b_first > 64u) {
+        const uint32_t step = (hi - b_first + 63u) / 64u;
+        const uint32_t p = b_first + lane * step;
+        const uint32_t v = p < hi ? wave::gload_u32(last_at, p * 4u) : 0xFFFFFFFFu;
+        const uint64_t ge = wave::ballot(v >= fr.dlo);
+        const uint32_t j = ge ? uint32_t(__builtin_ctzll(ge)) : 64u;
+        const uint32_t reach = b_first + j * step;   // (j < 64: block `reach` reaches dlo)
+        if (j < 64u && reach < hi) hi = reach;
+        if (j) b_first += (j - 1u) * step + 1u;
       }
     }
-    if (tl.n && tl.first_doc <= dhi && tl.last_doc >= dlo) {  // vint tail / single doc
-      const uint32_t t0 = lane < tl.n ? seg.tail_docs[tl.tail_row + lane] : 0u;
-      const uint32_t t1 = lane + 64u < tl.n ? seg.tail_docs[tl.tail_row + lane + 64u] : 0u;
-      const uint32_t g0 = lane < tl.n ? seg.tail_freqs[tl.tail_row + lane] : 0u;
-      const uint32_t g1 = lane + 64u < tl.n ? seg.tail_freqs[tl.tail_row + lane + 64u] : 0u;
-      put(t0, g0);
-      put(t1, g1);
-    }
+    follow_list<LAYOUT, false, true>(seg, tl, b_first, fr, alive, apre, counting, bytes, lane, put);
     wave::sync();
   }
 
@@ -695,15 +538,7 @@ k_conj(ConjArgs A, uint32_t pilot) {
       if (pilot) atomicAdd(&A.hist[uint64_t(unit) * kBins + bin], 1u);
       else cand = bin >= bs;
     }
-    // one reservation per wavefront for all its candidates of this pass
-    const uint64_t cm = wave::ballot(cand);
-    if (cm) {
-      uint32_t base = 0;
-      if (lane == 0) base = atomicAdd(&A.cand_count[unit], uint32_t(__builtin_popcountll(cm)));
-      base = wave::read_lane(base, 0);
-      const uint32_t slot = base + uint32_t(__builtin_popcountll(cm & below));
-      if (cand && slot < A.cand_cap) A.cands[uint64_t(unit) * A.cand_cap + slot] = make_key(v, doc);
-    }
+    emit_candidates(A, unit, cand, v, doc, lane);
   }
   if (!pilot && lane == 0 && total) A.item_hits[e] = total;
 }

@@ -24,8 +24,8 @@
 //     the And's merge over the groups.
 // Block-max pruning is not applied (A.wand is ignored): grouped units run exhaustively.
 //
-// k_conj, k_vphrase and the other block-driven kernels are left as they are: the decode steps
-// below repeat theirs rather than sharing them.
+// The lead frame, the alive bitmap rebuilt from the lanes and the walk over a member's blocks are
+// lead.h's.
 #pragma once
 #include "conj.h"
 #include "vphrase.h"
@@ -46,14 +46,8 @@ __device__ __forceinline__ void conj_any_item(const ConjArgs& A, const uint32_t*
   const uint32_t tid = threadIdx.x;
   const unsigned lane = tid & 63u;
   const uint32_t wv = wave::uniform(tid >> 6);
-  uint32_t e = blockIdx.x * kConjWaves + wv;
-  if (pilot) {
-    if (e >= A.n_pilot) return;
-    const PhraseWg w = A.wgs[e];
-    e = wave::uniform(A.unit_items[w.unit] + w.first_item);
-  } else if (e >= A.n_items) {
-    return;
-  }
+  const uint32_t e = lead_item_of(A, pilot, kConjWaves);
+  if (e == kNoItem) return;
   const ConjItem R = wave::sload<ConjItem>(reinterpret_cast<uint64_t>(A.recs) + uint64_t(e) * sizeof(ConjItem));
   const uint32_t unit = R.unit, item = R.item & kConjItemBlock, j = (R.item >> 24) & 0xFu;
   const DevQuery qd = wave::sload<DevQuery>(reinterpret_cast<uint64_t>(A.queries) + uint64_t(unit) * sizeof(DevQuery));
@@ -66,13 +60,7 @@ __device__ __forceinline__ void conj_any_item(const ConjArgs& A, const uint32_t*
   auto term_tail = [&](uint32_t i) { return wave::sload<DevTail>(tl_at + i * sizeof(DevTail)); };
   auto term_q = [&](uint32_t i) { return wave::sload<DevQTerm>(qt_at + i * sizeof(DevQTerm)); };
   const uint32_t opens = wave::uniform(opens_of[unit]) | 1u;
-  // rows [group_lo(r), group_end(r)) form the group of row r
-  auto group_lo = [&](uint32_t r) { return 31u - uint32_t(__builtin_clz(opens & ((2u << r) - 1u))); };
-  auto group_end = [&](uint32_t r) {
-    const uint32_t above = opens & ~((2u << r) - 1u) & ((1u << m) - 1u);
-    return above ? uint32_t(__builtin_ctz(above)) : m;
-  };
-  const uint32_t lead_lo = group_lo(j), lead_end = group_end(j);
+  const uint32_t lead_lo = group_lo(opens, j), lead_end = group_end(opens, j, m);
   const DevTail ld = term_tail(j);
   const uint32_t bs = pilot ? 0u : A.bstar[unit];
   AnyWave& W = s_wave[wv];
@@ -83,30 +71,11 @@ __device__ __forceinline__ void conj_any_item(const ConjArgs& A, const uint32_t*
   uint32_t n = kBlock;
   uint32_t bytes = 0;
   const bool counting = !pilot && A.touched != nullptr;
-  auto block_bytes = [](uint32_t bits) {
-    const uint32_t db = bits & 0xFFu, fb = bits >> 8;
-    return 2u + (db ? 16u * db : 1u) + (fb ? 16u * fb : 1u);
-  };
   uint32_t ld_d[2], ld_e[2];
   bool alive[2];   // the lane's lead entries still in the running (docs of the segment, not masked)
   {
-    uint32_t f[2], estep;
-    if (item < ld.nblk) {
-      decode_dir_block<LAYOUT>(seg, ld.doc_start, R.bits, R.off, R.aoff, R.base, lane, ld_d[0],
-                               ld_d[1], f[0], f[1]);
-      if (counting) bytes += block_bytes(R.bits);
-      ld_e[0] = 2u * lane;
-      estep = 1u;
-    } else {
-      n = ld.n;
-      ld_d[0] = lane < n ? seg.tail_docs[ld.tail_row + lane] : 0u;
-      ld_d[1] = lane + 64u < n ? seg.tail_docs[ld.tail_row + lane + 64u] : 0u;
-      f[0] = lane < n ? seg.tail_freqs[ld.tail_row + lane] : 0u;
-      f[1] = lane + 64u < n ? seg.tail_freqs[ld.tail_row + lane + 64u] : 0u;
-      ld_e[0] = lane;
-      estep = 64u;
-    }
-    ld_e[1] = ld_e[0] + estep;
+    uint32_t f[2];
+    n = lead_decode<LAYOUT>(seg, ld, R, item, lane, counting, bytes, ld_d, ld_e, f);
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       const uint32_t idx = ld_e[h];
@@ -114,8 +83,7 @@ __device__ __forceinline__ void conj_any_item(const ConjArgs& A, const uint32_t*
       alive[h] = idx < n && !(qd.dead && doc_dead(qd.dead, ld_d[h]));
       for (uint32_t i = 0; i < m; ++i) W.tf[i][idx] = (i == j && alive[h]) ? f[h] : 0u;
     }
-    static_assert(kConjBuckets == 64u * 16u, "one 16-byte store per lane clears `first`");
-    reinterpret_cast<ConjQuad*>(W.first)[lane] = ConjQuad{0u, 0u, 0u, 0u};
+    lead_first_clear(W.first, lane);
   }
   wave::sync();
   if (n == 0) return;
@@ -123,48 +91,13 @@ __device__ __forceinline__ void conj_any_item(const ConjArgs& A, const uint32_t*
     lead_skipped(A, unit, counting, bytes, lane);
     return;
   }
-  const uint32_t dlo = wave::uniform(docs[0]), dhi = wave::uniform(docs[n - 1]);
-  const uint32_t span = dhi - dlo;
-  const uint32_t s = span < kConjBuckets ? 0u
-                     : 32u - uint32_t(__builtin_clz(span)) - (5u + uint32_t(__builtin_ctz(kConjWords)));
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    if (ld_e[h] < n) {
-      const uint32_t bk = (ld_d[h] - dlo) >> s;
-      if (ld_e[h] == 0u || ((docs[ld_e[h] - 1u] - dlo) >> s) != bk) W.first[bk] = uint8_t(ld_e[h] + 1u);
-    }
-  }
+  const LeadFrame fr = lead_frame(docs, n);
+  lead_first_fill(fr, W.first, docs, ld_d, ld_e, n);
   // the alive bitmap from the lanes' alive entries, and its prefix counts: number of alive buckets
   auto rebuild = [&]() {
-    if (lane < (kConjWords + 4u) / 2u) {
-      W.bm[2u * lane] = 0u;
-      W.bm[2u * lane + 1u] = 0u;
-    }
+    const uint32_t left = alive_rebuild(fr, W.bm, W.apre, ld_d, alive, lane);
     wave::sync();
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      if (alive[h]) {
-        const uint32_t bk = (ld_d[h] - dlo) >> s;
-        atomicOr(&W.bm[bk >> 5], 1u << (bk & 31u));
-      }
-    }
-    wave::sync();
-    uint32_t p0 = 0, p1 = 0;
-    if (lane < kConjWords / 2u) {
-      p0 = uint32_t(__builtin_popcount(W.bm[2u * lane]));
-      p1 = uint32_t(__builtin_popcount(W.bm[2u * lane + 1u]));
-    }
-    const uint32_t incl = wave::inclusive_scan(p0 + p1);
-    if (lane < kConjWords / 2u) {
-      W.apre[2u * lane] = uint8_t(incl - p0 - p1);
-      W.apre[2u * lane + 1u] = uint8_t(incl - p1);
-    }
-    if (lane == kConjWords / 2u - 1u) W.apre[kConjWords] = uint8_t(incl);
-    wave::sync();
-    return wave::read_lane(incl, 63);
-  };
-  auto alive_below = [&](uint32_t x) {
-    return uint32_t(W.apre[x >> 5]) + uint32_t(__builtin_popcount(W.bm[x >> 5] & ((1u << (x & 31u)) - 1u)));
+    return left;
   };
 
   // ---- 2. one row: the blocks of its list that can hold an alive doc (k_conj step 2), decoded; a
@@ -172,59 +105,14 @@ __device__ __forceinline__ void conj_any_item(const ConjArgs& A, const uint32_t*
   auto decode_row = [&](uint32_t i) {
     const DevTail tl = term_tail(i);
     auto put = [&](uint32_t doc, uint32_t f) {
-      const uint32_t x = doc - dlo;
-      if (f == 0 || x > span) return;
-      const uint32_t t = lead_index(W.first, docs, n, x >> s, s, doc);
+      const uint32_t x = doc - fr.dlo;
+      if (f == 0 || x > fr.span) return;
+      const uint32_t t = lead_index(W.first, docs, n, x >> fr.s, fr.s, doc);
       if (t == n) return;
       W.tf[i][t] = f;
     };
-    if (tl.nblk) {
-      const uint64_t last_at = reinterpret_cast<uint64_t>(seg.blk_last + tl.dir_off);
-      const uint64_t dir_at = reinterpret_cast<uint64_t>(seg.blk_dir + tl.dir_off);
-      const uint32_t b_first = seek[i < j ? i : i - 1u];
-      for (uint32_t b0 = b_first; b0 < tl.nblk; b0 += 64) {
-        const uint32_t bl = b0 + lane;
-        const bool valid = bl < tl.nblk;
-        const uint32_t lst = valid ? wave::gload_u32(last_at, bl * 4u) : 0xFFFFFFFFu;
-        BlkDir d{};
-        if (valid) {
-          uint32_t w[4];
-          wave::gload_u32x4(dir_at, bl * uint32_t(sizeof(BlkDir)), w);
-          d = BlkDir{w[0], w[1], w[2], w[3]};
-        }
-        const uint32_t prv = bl ? d.prev_last : 0u;   // the block holds docs in (prv, lst]
-        const bool reach = valid && prv < dhi && lst >= dlo;
-        bool want = false;
-        if (reach) {
-          const uint32_t x0 = prv + 1u > dlo ? prv + 1u - dlo : 0u;
-          const uint32_t x1 = (lst < dhi ? lst : dhi) - dlo;
-          want = alive_below((x1 >> s) + 1u) > alive_below(x0 >> s);
-        }
-        uint64_t mask = wave::ballot(want);
-        const bool more = wave::ballot(valid && prv >= dhi) == 0;
-        while (mask) {
-          const uint32_t k = uint32_t(__builtin_ctzll(mask));
-          mask &= mask - 1;
-          const uint32_t kbits = wave::read_lane(d.bits, k);
-          if (counting) bytes += block_bytes(kbits);
-          uint32_t d0, d1, f0, f1;
-          decode_dir_block<LAYOUT>(seg, tl.doc_start, kbits, wave::read_lane(d.off, k),
-                                   wave::read_lane(d.aoff, k), wave::read_lane(d.prev_last, k),
-                                   lane, d0, d1, f0, f1);
-          put(d0, f0);
-          put(d1, f1);
-        }
-        if (!more) break;
-      }
-    }
-    if (tl.n && tl.first_doc <= dhi && tl.last_doc >= dlo) {  // vint tail / single doc
-      const uint32_t t0 = lane < tl.n ? seg.tail_docs[tl.tail_row + lane] : 0u;
-      const uint32_t t1 = lane + 64u < tl.n ? seg.tail_docs[tl.tail_row + lane + 64u] : 0u;
-      const uint32_t g0 = lane < tl.n ? seg.tail_freqs[tl.tail_row + lane] : 0u;
-      const uint32_t g1 = lane + 64u < tl.n ? seg.tail_freqs[tl.tail_row + lane + 64u] : 0u;
-      put(t0, g0);
-      put(t1, g1);
-    }
+    follow_list<LAYOUT, false, false>(seg, tl, seek[i < j ? i : i - 1u], fr, W.bm, W.apre, counting, bytes,
+                                     lane, put);
   };
   auto quit = [&]() {   // no doc left: what was decoded is counted
     if (counting && lane == 0) atomicAdd(&A.touched[2u * unit], static_cast<unsigned long long>(bytes));
@@ -245,7 +133,7 @@ __device__ __forceinline__ void conj_any_item(const ConjArgs& A, const uint32_t*
   }
   // b. every other group, cheapest first: alive = docs one of its members holds
   for (uint32_t lo = 0; lo < m;) {
-    const uint32_t end = group_end(lo);
+    const uint32_t end = group_end(opens, lo, m);
     if (lo != lead_lo) {
       if (rebuild() == 0u) return quit();
       for (uint32_t r = lo; r < end; ++r) decode_row(r);
@@ -284,7 +172,7 @@ __device__ __forceinline__ void conj_any_item(const ConjArgs& A, const uint32_t*
                           : (item < ld.nblk ? seg.pnorm[(ld.dir_off + item) * kBlock + sl]
                                             : seg.tail_norms[ld.tail_row + sl]);
       for (uint32_t lo = 0; lo < m;) {
-        const uint32_t end = group_end(lo);
+        const uint32_t end = group_end(opens, lo, m);
         float g = 0.f;
         for (uint32_t r = lo; r < end; ++r) {
           const uint32_t f = W.tf[r][sl];
@@ -297,14 +185,7 @@ __device__ __forceinline__ void conj_any_item(const ConjArgs& A, const uint32_t*
       if (pilot) atomicAdd(&A.hist[uint64_t(unit) * kBins + bin], 1u);
       else cand = bin >= bs;
     }
-    const uint64_t cm = wave::ballot(cand);
-    if (cm) {
-      uint32_t base = 0;
-      if (lane == 0) base = atomicAdd(&A.cand_count[unit], uint32_t(__builtin_popcountll(cm)));
-      base = wave::read_lane(base, 0);
-      const uint32_t slot = base + uint32_t(__builtin_popcountll(cm & below));
-      if (cand && slot < A.cand_cap) A.cands[uint64_t(unit) * A.cand_cap + slot] = make_key(v, doc);
-    }
+    emit_candidates(A, unit, cand, v, doc, lane);
   }
   if (pilot) return;
   if (lane == 0 && total) A.item_hits[e] = total;

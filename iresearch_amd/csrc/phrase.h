@@ -15,8 +15,11 @@
 // sum is precomputed at open (DevSegment::blk_pos), inside the block one wavefront scan
 // gives the rest.  So the conjunction of the phrase's terms is formed from the doc blocks
 // alone (k_phrase below), with (P, tf) riding along, and only docs holding ALL phrase terms
-// ever touch the position stream.
+// ever touch the position stream.  What k_phrase shares with the other block-driven kernels — the
+// lead item's records and the doc-block decoders — is in lead.h, which also describes the lead frame
+// and the follower walk; phrase_item keeps its own text of those two (see there for why).
 #pragma once
+#include "lead.h"
 #include "score.h"
 
 namespace irs_hip {
@@ -37,47 +40,6 @@ __device__ __forceinline__ uint32_t packed_at(const uint8_t* payload, uint32_t b
   }
   const uint32_t bit = j * bits;
   return uint32_t(wave::load_u64(payload + 4u * (bit >> 5)) >> (bit & 31u)) & mask;
-}
-
-// decode_block (decode.h) for a field with positions: absolute docs d0/d1 and frequencies
-// f0/f1 of postings 2*lane, 2*lane+1, and `before` = sum of the frequencies of the block's
-// postings in front of 2*lane (where this lane's positions start inside the block).  The two
-// prefix sums run as one interleaved chain.
-template<int LAYOUT>
-__device__ __forceinline__ void decode_block_pos(const uint8_t* blk, uint32_t dbits,
-                                                 uint32_t fbits, uint32_t base, unsigned lane,
-                                                 uint32_t& d0, uint32_t& d1, uint32_t& f0,
-                                                 uint32_t& f1, uint32_t& before) {
-  uint32_t x0, x1;
-  const uint32_t size = read_block_pair<LAYOUT>(blk, dbits, lane, x0, x1);
-  read_block_pair<LAYOUT>(blk + size, fbits, lane, f0, f1);
-  uint32_t dsum = x0 + x1, fsum = f0 + f1;
-  wave::inclusive_scan2(dsum, fsum);
-  d1 = base + dsum;
-  d0 = d1 - x1;
-  before = fsum - f0 - f1;
-}
-
-// The same from the packed-payload image (both parts 1..31-bit packed, pk_both()):
-// 16-byte aligned payloads, one funnel shift + one bit-field extract per value, as k_score's
-// hot loop reads them.
-template<int LAYOUT>
-__device__ __forceinline__ void decode_packed_pos(const uint8_t* pl, uint32_t dbits,
-                                                  uint32_t fbits, uint32_t base, unsigned lane,
-                                                  uint32_t& d0, uint32_t& d1, uint32_t& f0,
-                                                  uint32_t& f1, uint32_t& before) {
-  uint64_t da, db, fa, fb;
-  const uint64_t at = reinterpret_cast<uint64_t>(pl);
-  raw_load_packed_g<LAYOUT>(at, dbits, lane, da, db);
-  raw_load_packed_g<LAYOUT>(at + 16u * dbits, fbits, lane, fa, fb);
-  uint32_t x0, x1;
-  extract_fast<LAYOUT>(da, db, dbits, lane, x0, x1);
-  extract_fast<LAYOUT>(fa, fb, fbits, lane, f0, f1);
-  uint32_t dsum = x0 + x1, fsum = f0 + f1;
-  wave::inclusive_scan2(dsum, fsum);
-  d1 = base + dsum;
-  d0 = d1 - x1;
-  before = fsum - f0 - f1;
 }
 
 // Position delta number `idx` of a term (what position::next adds to value_, :1624-1626).
@@ -242,22 +204,6 @@ k_pos_directory(DevSegment seg, DevPosTerm* pterms, uint32_t* pblk_off, uint8_t*
   }
 }
 
-// (P, tf) of the tail postings this lane owns: entries `lane` and `lane + 64` of the
-// decoded tail (or the single doc).  base = positions in front of the tail.
-__device__ __forceinline__ void tail_pidx(const DevSegment& seg, uint32_t row, uint32_t n,
-                                          uint32_t base, unsigned lane, uint32_t (&doc)[2],
-                                          uint32_t (&tf)[2], uint32_t (&pidx)[2]) {
-  tf[0] = lane < n ? seg.tail_freqs[row + lane] : 0u;
-  tf[1] = lane + 64u < n ? seg.tail_freqs[row + lane + 64u] : 0u;
-  doc[0] = lane < n ? seg.tail_docs[row + lane] : 0u;
-  doc[1] = lane + 64u < n ? seg.tail_docs[row + lane + 64u] : 0u;
-  const uint32_t ia = wave::inclusive_scan(tf[0]);
-  const uint32_t ta = wave::bcast(ia, 63);
-  const uint32_t ib = wave::inclusive_scan(tf[1]);
-  pidx[0] = base + ia - tf[0];
-  pidx[1] = base + ta + ib - tf[1];
-}
-
 // Bit-exact test surface: every position of every doc of one term, doc after doc
 // (what draining the position attribute behind doc_iterator::next yields).
 // grid.x = nblk + 1 wave-sized items, kWaves per workgroup (as k_decode_term).
@@ -295,14 +241,6 @@ k_decode_positions(DevSegment seg, uint32_t term, uint32_t* out) {
 // ------------------------------------------------------------ query time --
 
 constexpr uint32_t kPhraseWaves = 4;  // wavefronts (= lead blocks) per workgroup
-constexpr uint32_t kConjWords = 32;   // 32-bit words of a wavefront's doc-range bitmaps: 1024 buckets
-constexpr uint32_t kConjBuckets = 32u * kConjWords;
-
-// One entry of a pilot list: a sampled lead item of a unit.
-struct PhraseWg {
-  uint32_t unit;        // (segment, query) execution unit
-  uint32_t first_item;  // index of the lead item
-};
 
 // #{i < n : sorted[i] <= x}, knowing that it lies in [a, b]
 __device__ __forceinline__ uint32_t count_le(const uint32_t* sorted, uint32_t a, uint32_t b,
@@ -314,162 +252,6 @@ __device__ __forceinline__ uint32_t count_le(const uint32_t* sorted, uint32_t a,
   return a;
 }
 
-// ---- block-driven execution (irs::And in conj.h, by_phrase below): shared pieces
-
-// A wavefront's bucket table (conj.h ConjWave::first): the entry index (< n) of lead doc `doc` of
-// bucket bk, or n: not a lead doc
-__device__ __forceinline__ uint32_t lead_index(const uint8_t* first, const uint32_t* docs, uint32_t n,
-                                               uint32_t bk, uint32_t s, uint32_t doc) {
-  uint32_t t = first[bk];
-  if (!t) return n;
-  --t;
-  if (s) {   // (wave-uniform) a bucket may hold several lead docs, in entry order
-    while (docs[t] < doc && t + 1u < n) ++t;
-  }
-  return docs[t] == doc ? t : n;
-}
-struct alignas(16) ConjQuad {   // 16 bytes cleared at once
-  uint32_t x, y, z, w;
-};
-
-// One lead item (a 128-posting block of the conjunction's rarest term, or its decoded vint
-// tail), everything its wavefront needs to start decoding — written by the pre-pass so that
-// the wavefront's first load is this record (one scalar load) instead of a chain of dependent
-// ones (unit -> query -> term record -> directory words).
-// A lead block whose docs spread over many blocks of the other terms (a rare lead against frequent
-// terms: the reference's AndHighLow) is cut into 2^lg lead items of 128 >> lg consecutive postings:
-// one wavefront would decode up to 128 blocks per other term one after the other, a chain of
-// dependent loads with nobody to overlap it.
-constexpr uint32_t kConjItemBlock = 0xFFFFFFu;   // ConjItem::item: block index (nblk <= 2^24)
-constexpr uint32_t kConjSplitMax = 4;            //   | piece << 24 | lg << 28: 16 pieces at most
-struct alignas(32) ConjItem {
-  uint32_t unit;
-  uint32_t item;    // block index in the lead's list; == its nblk: the vint tail (+ piece, lg above)
-  uint32_t base;    // doc the block's first delta is relative to (formats_10.cpp:636)
-  uint32_t r_lo;    // the item's docs lie in [r_lo, r_hi] (from the directory)
-  uint32_t r_hi;
-  uint32_t aoff;    // block in the packed-payload image, 16-byte units
-  uint32_t bits;    // header bytes: dbits | fbits << 8
-  uint32_t off;     // block in `.doc`, relative to the term's doc_start
-};
-static_assert(sizeof(ConjItem) == 32, "one s_load_dwordx8 per lead item");
-
-// Pre-pass, one thread per lead item of every conjunction: the item's record, and where the
-// other terms start for it — the binary search of a term's block directory for the first
-// block reaching the lead item's first doc, SkipReader::Seek (skip_list.hpp:208-249), done
-// once per (lead item, term) by ONE THREAD (inside k_conj a wavefront would walk the same
-// dependent chain 64 lanes wide).  seek[(item_base + item) * (jt - 1) + slot of term i among the non-lead terms].
-__global__ void __launch_bounds__(kThreads)
-k_conj_seek(const DevSegment* segs, const DevQuery* queries, const DevTail* tails, uint32_t jt,
-            const uint32_t* conj_units, const uint32_t* item_base /*[n_conj + 1]*/,
-            uint32_t n_conj, const uint32_t* lead_of /*[unit] slot of the lead term; null: 0*/,
-            const uint32_t* split_lg /*[n_conj] log2 of the pieces per lead block; null: 0*/,
-            uint32_t* seek, ConjItem* recs) {
-  const uint32_t t = blockIdx.x * kThreads + threadIdx.x;
-  if (t >= item_base[n_conj]) return;
-  uint32_t lo = 0, hi = n_conj;   // the unit whose items hold t: last c with item_base[c] <= t
-  while (hi - lo > 1) {
-    const uint32_t mid = (lo + hi) >> 1;
-    if (item_base[mid] <= t) lo = mid; else hi = mid;
-  }
-  const uint32_t lg = split_lg ? split_lg[lo] : 0u;
-  const uint32_t unit = conj_units[lo], item = (t - item_base[lo]) >> lg;
-  const uint32_t piece = (t - item_base[lo]) & ((1u << lg) - 1u);
-  const DevQuery qd = queries[unit];
-  const DevSegment& seg = segs[qd.seg];
-  const DevTail* tl = tails + uint64_t(unit) * jt;
-  const uint32_t lead = lead_of ? lead_of[unit] : 0u;
-  const DevTail ld = tl[lead];
-  ConjItem r{};
-  r.unit = unit;
-  r.item = item | (piece << 24) | (lg << 28);
-  if (item < ld.nblk) {
-    const uint64_t e = ld.dir_off + item;
-    r.base = item ? seg.blk_last[e - 1] : kDocMin;
-    r.r_lo = item ? r.base + 1u : kDocMin;
-    r.r_hi = seg.blk_last[e];
-    r.aoff = seg.blk_aoff[e];
-    r.bits = seg.blk_bits[e];
-    r.off = seg.blk_off[e];
-  } else {
-    r.r_lo = ld.first_doc;
-    r.r_hi = ld.last_doc;
-  }
-  recs[t] = r;
-  for (uint32_t i = 0; i < qd.n_terms; ++i) {   // row: the other terms in slot order
-    if (i == lead) continue;
-    const uint32_t* last = seg.blk_last + tl[i].dir_off;
-    uint32_t a = 0, b = tl[i].nblk;  // lower_bound(last, r_lo)
-    while (a < b) {
-      const uint32_t mid = (a + b) >> 1;
-      if (last[mid] < r.r_lo) a = mid + 1; else b = mid;
-    }
-    seek[uint64_t(t) * (jt - 1u) + (i < lead ? i : i - 1u)] = a;
-  }
-}
-
-struct ConjArgs {
-  const DevSegment* segs;
-  const DevQuery* queries;
-  const DevQTerm* qterms;
-  const PhraseWg* wgs;          // pilot pass: {unit, lead item} per wavefront (the sampled items)
-  uint32_t n_pilot;             // entries of the pilot list
-  uint32_t n_items;             // full pass: lead items of all conjunctions (= records)
-  const DevTail* tails;         // [unit][jt] (k_plan)
-  const uint32_t* bstar;        // threshold bin per unit (0 = none)
-  const uint32_t* seek;         // k_conj_seek
-  const ConjItem* recs;         // k_conj_seek
-  const uint32_t* unit_items;   // [nq] first record of the unit's lead items (conj units)
-  const uint32_t* lead_of;      // [nq] by_phrase: slot of the unit's lead (rarest) term
-  uint64_t* cands;
-  uint32_t* cand_count;
-  unsigned long long* hits;
-  uint32_t* item_hits;          // [n_items] matches of every lead item (full pass; zeroed per run):
-                                // a store instead of an atomic on the unit's counter — one hot
-                                // address per unit kept every wavefront resident until its atomic
-                                // had come back (1.6 of 6.4 ms per 1000 AND-2 queries);
-                                // k_conj_hits adds them up
-  unsigned long long* touched;  // [unit][2]: `.doc` + norm bytes actually decoded / read (full
-                                // pass; per unit: one hot address would serialise the atomics);
-                                // null unless the batch counts (irs_hip_batch_profile bit 1)
-  uint32_t* hist;               // [unit][kBins], pilot pass only
-  uint32_t jt;
-  uint32_t cand_cap;
-  uint32_t pilot_stride;        // pilot pass: lead items {phase, phase + P, ...}
-  uint32_t wand;                // prune lead blocks by block-max bounds
-  uint32_t* pruned;             // [unit] set when a lead block was skipped (k_select's underflow check)
-  // doc sets (irs_hip_batch_doc_set_stats), counted like `touched` (null unless the batch counts):
-  // lead pieces of the units whose mask comes from a doc set (`restricted`: [unit] bytes), and how
-  // many of them held no doc the mask leaves
-  unsigned long long* leads;    // [2]
-  const uint8_t* restricted;
-};
-
-// A lead piece of a masked unit, decoded, none of whose docs the mask leaves (one wave-uniform
-// ballot of the lanes' `live`) ends there — nothing of it can match: no other term is sought or
-// decoded, no position read; its hit count, candidate slots and pilot contribution stay zero.  What
-// an exhausted `alive` bitmap tells a few steps later (and all a unit masked by deletions or
-// exclusions alone ever sees of this: the same results); a doc set empties whole doc ranges.
-// lead_skipped: what such a piece leaves behind in a counting run.  Its atomics sit on the path
-// that ends the wavefront, nowhere else: a write to memory in front of the kernels' other loads
-// would turn their scalar loads into vector loads (the compiler could no longer take the tables for
-// unwritten) — which is why the pieces themselves are counted by k_count_leads, not here.
-__device__ __forceinline__ void lead_skipped(const ConjArgs& A, uint32_t unit, bool counting, uint32_t bytes,
-                                             unsigned lane) {
-  if (counting && lane == 0) {
-    atomicAdd(&A.touched[2u * unit], static_cast<unsigned long long>(bytes));
-    if (A.leads && A.restricted[unit]) atomicAdd(&A.leads[1], 1ull);
-  }
-}
-// A counting run of a batch with doc sets: the lead pieces (records) of its restricted units
-__global__ void __launch_bounds__(kThreads)
-k_count_leads(const ConjItem* recs, uint32_t n, const uint8_t* restricted, unsigned long long* leads) {
-  const uint32_t i = blockIdx.x * kThreads + threadIdx.x;
-  const bool on = i < n && restricted[recs[i].unit];
-  const uint32_t c = uint32_t(__builtin_popcountll(wave::ballot(on)));
-  if ((threadIdx.x & 63u) == 0 && c) atomicAdd(&leads[0], static_cast<unsigned long long>(c));
-}
-
 
 // by_phrase, block driven.  The conjunction PhraseIterator::next runs first
 // (phrase_iterator.hpp:590-596) is bounded by its rarest member — the reason Conjunction
@@ -477,13 +259,12 @@ k_count_leads(const ConjItem* recs, uint32_t n, const uint8_t* restricted, unsig
 // the others seek().  Here ONE WAVEFRONT owns one 128-posting block (or the vint tail)
 // of the lead term (its record and the other terms' start blocks come from k_conj_seek):
 //   1. it decodes the lead block: 128 ascending docs into LDS and into a bitmap over the
-//      block's doc range (conj.h: ConjWave), (P, tf) of each into the lead's row;
+//      block's doc range (the lead frame, lead.h), (P, tf) of each into the lead's row;
 //   2. for every other term it finds the blocks that can hold one of the docs every term
-//      so far reached — what seek() does through the skip list (skip_list.hpp:208-249): 64
-//      directory entries per step, a lane each, tested against the alive bitmap ("is any of
-//      them in (previous last, last]": two prefix-count reads); only the blocks that pass are
-//      decoded, and each decoded posting tests its doc's bit: a hit leaves (P, tf) in the
-//      term's row at the doc's rank and marks the doc alive for the next term;
+//      so far reached — what seek() does through the skip list (skip_list.hpp:208-249) — and
+//      decodes them (the walk of follow_list, lead.h, here with position numbers AND two blocks in
+//      flight); each decoded posting looks its doc up among the lead docs: a hit leaves (P, tf) in
+//      the term's row at the doc's rank and marks the doc alive for the next term;
 //   3. docs that every term reached are the conjunction's matches: compacted, one lane each
 //      merges the terms' position lists (FixedPhraseFrequency::NextPosition,
 //      phrase_iterator.hpp:109-151): phrase frequency = #{p in first term : p + off_i in
@@ -508,7 +289,7 @@ struct PhraseWave {
   uint32_t docs[kBlock];
   uint32_t pidx[MT][kBlock];          // first position number of the doc in term i's list
   uint32_t tf[MT][kBlock];            // its frequency there (0: the term has not reached the doc)
-  alignas(16) uint8_t first[kConjBuckets];   // bucket -> 1 + entry index of its first lead doc (conj.h)
+  alignas(16) uint8_t first[kConjBuckets];   // bucket -> 1 + entry index of its first lead doc (lead.h)
   uint32_t bm[3][kConjWords + 4];     // bitmaps over [dlo, dhi]: lead docs, alive / marked
   uint8_t lpre[kConjWords + 4];       // lead-bitmap bits in the words before word w
   uint8_t apre[kConjWords + 4];       // the same for the alive bitmap of the current term
@@ -597,10 +378,6 @@ __device__ __forceinline__ void phrase_item(const ConjArgs& A, uint32_t pilot /*
   uint32_t n = kBlock;
   uint32_t bytes = 0;   // (wave-uniform) encoded bytes of the doc blocks this wavefront decodes
   const bool counting = !pilot && A.touched != nullptr;   // (irs_hip_batch_profile bit 1)
-  auto block_bytes = [](uint32_t bits) {
-    const uint32_t db = bits & 0xFFu, fb = bits >> 8;
-    return 2u + (db ? 16u * db : 1u) + (fb ? 16u * fb : 1u);
-  };
   uint32_t ld_d[2], ld_e[2];
   bool live[2];   // the lane's lead docs that are docs of the segment at all (not deleted)
   {
@@ -649,8 +426,7 @@ __device__ __forceinline__ void phrase_item(const ConjArgs& A, uint32_t pilot /*
         W.bm[k][2u * lane + 1u] = 0u;
       }
     }
-    static_assert(kConjBuckets == 64u * 16u, "one 16-byte store per lane clears `first`");
-    reinterpret_cast<ConjQuad*>(W.first)[lane] = ConjQuad{0u, 0u, 0u, 0u};
+    lead_first_clear(W.first, lane);
   }
   wave::sync();
   if (qd.dead && wave::ballot(live[0] || live[1]) == 0) {   // (wave-uniform) no lead doc is left

@@ -24,9 +24,10 @@
 // Alive sets are kept per doc in the lanes (two lead entries each); the bucket bitmap that steers
 // the block selection is rebuilt from them after every step.
 //
-// The fixed kernels (k_phrase2 / k_phrase) are left as they are, instruction for instruction: the
-// follower decode below repeats theirs rather than sharing it (sharing changed their register
-// allocation).  A batch with any variadic unit runs all of its phrase units here.
+// The lead frame, the alive bitmap rebuilt from the lanes and the walk over a member's blocks are
+// lead.h's.  The fixed kernels (k_phrase2 / k_phrase) keep their own text of the walk, two wanted
+// blocks at a time: sharing it changed how they run (lead.h).  A batch with any variadic unit runs all
+// of its phrase units here.
 #pragma once
 #include "phrase.h"
 
@@ -109,14 +110,8 @@ __device__ __forceinline__ void vphrase_item(const ConjArgs& A, const uint32_t* 
   const uint32_t tid = threadIdx.x;
   const unsigned lane = tid & 63u;
   const uint32_t wv = wave::uniform(tid >> 6);
-  uint32_t e = blockIdx.x * kPhraseWaves + wv;
-  if (pilot) {
-    if (e >= A.n_pilot) return;
-    const PhraseWg w = A.wgs[e];
-    e = wave::uniform(A.unit_items[w.unit] + w.first_item);
-  } else if (e >= A.n_items) {
-    return;
-  }
+  const uint32_t e = lead_item_of(A, pilot, kPhraseWaves);
+  if (e == kNoItem) return;
   const ConjItem R = wave::sload<ConjItem>(reinterpret_cast<uint64_t>(A.recs) + uint64_t(e) * sizeof(ConjItem));
   const uint32_t unit = R.unit, item = R.item & kConjItemBlock, j = (R.item >> 24) & 0xFu;
   const DevQuery qd = wave::sload<DevQuery>(reinterpret_cast<uint64_t>(A.queries) + uint64_t(unit) * sizeof(DevQuery));
@@ -127,14 +122,8 @@ __device__ __forceinline__ void vphrase_item(const ConjArgs& A, const uint32_t* 
   auto term_tail = [&](uint32_t i) { return wave::sload<DevTail>(tl_at + i * sizeof(DevTail)); };
   const uint32_t opens = wave::uniform(opens_of[unit]) | 1u;
   const uint32_t n_parts = uint32_t(__builtin_popcount(opens));
-  // rows [part_lo(r), part_end(r)) form the part of row r
-  auto part_lo = [&](uint32_t r) { return 31u - uint32_t(__builtin_clz(opens & ((2u << r) - 1u))); };
-  auto part_end = [&](uint32_t r) {
-    const uint32_t above = opens & ~((2u << r) - 1u) & ((1u << m) - 1u);
-    return above ? uint32_t(__builtin_ctz(above)) : m;
-  };
-  const uint32_t lead_lo = part_lo(j), lead_end = part_end(j);
-  const uint32_t first_end = part_end(0);   // rows of P_0, whose positions are counted
+  const uint32_t lead_lo = group_lo(opens, j), lead_end = group_end(opens, j, m);
+  const uint32_t first_end = group_end(opens, 0u, m);   // rows of P_0, whose positions are counted
   const DevTail ld = term_tail(j);
   const DevQTerm qt = A.qterms[qd.first_term];  // the phrase's scorer rides on every entry
   const uint32_t bs = (MATCH || pilot) ? 0u : A.bstar[unit];
@@ -151,37 +140,11 @@ __device__ __forceinline__ void vphrase_item(const ConjArgs& A, const uint32_t* 
   uint32_t n = kBlock;
   uint32_t bytes = 0;
   const bool counting = !pilot && A.touched != nullptr;
-  auto block_bytes = [](uint32_t bits) {
-    const uint32_t db = bits & 0xFFu, fb = bits >> 8;
-    return 2u + (db ? 16u * db : 1u) + (fb ? 16u * fb : 1u);
-  };
   uint32_t ld_d[2], ld_e[2];
   bool alive[2];   // the lane's lead entries still in the running (docs of the segment, not masked)
   {
-    uint32_t f[2], p[2], estep;
-    if (item < ld.nblk) {
-      const uint64_t eb = ld.dir_off + item;
-      if (counting) bytes += block_bytes(R.bits);
-      uint32_t before;
-      if (pk_both(R.bits & 0xFFu, R.bits >> 8)) {
-        decode_packed_pos<LAYOUT>(seg.pk + (uint64_t(R.aoff) << 4), R.bits & 0xFFu, R.bits >> 8,
-                                  R.base, lane, ld_d[0], ld_d[1], f[0], f[1], before);
-      } else {
-        decode_block_pos<LAYOUT>(seg.doc + ld.doc_start + R.off, R.bits & 0xFFu, R.bits >> 8,
-                                 R.base, lane, ld_d[0], ld_d[1], f[0], f[1], before);
-      }
-      p[0] = seg.blk_pos[eb] - seg.blk_pos[ld.dir_off] + before;
-      p[1] = p[0] + f[0];
-      ld_e[0] = 2u * lane;
-      estep = 1u;
-    } else {
-      n = ld.n;
-      const uint32_t base = seg.blk_pos[ld.dir_off + ld.nblk] - seg.blk_pos[ld.dir_off];
-      tail_pidx(seg, ld.tail_row, n, base, lane, ld_d, f, p);
-      ld_e[0] = lane;
-      estep = 64u;
-    }
-    ld_e[1] = ld_e[0] + estep;
+    uint32_t f[2], p[2];
+    n = lead_decode_pos<LAYOUT>(seg, ld, R, item, lane, counting, bytes, ld_d, ld_e, f, p);
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       const uint32_t idx = ld_e[h];
@@ -192,56 +155,20 @@ __device__ __forceinline__ void vphrase_item(const ConjArgs& A, const uint32_t* 
         W.tf[i][idx] = (i == j && alive[h]) ? f[h] : 0u;
       }
     }
-    static_assert(kConjBuckets == 64u * 16u, "one 16-byte store per lane clears `first`");
-    reinterpret_cast<ConjQuad*>(W.first)[lane] = ConjQuad{0u, 0u, 0u, 0u};
+    lead_first_clear(W.first, lane);
   }
   wave::sync();
   if (qd.dead && wave::ballot(alive[0] || alive[1]) == 0) {   // (wave-uniform) no lead doc is left
     lead_skipped(A, unit, counting, bytes, lane);
     return;
   }
-  const uint32_t dlo = wave::uniform(docs[0]), dhi = wave::uniform(docs[n - 1]);
-  const uint32_t span = dhi - dlo;
-  const uint32_t s = span < kConjBuckets ? 0u
-                     : 32u - uint32_t(__builtin_clz(span)) - (5u + uint32_t(__builtin_ctz(kConjWords)));
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    if (ld_e[h] < n) {
-      const uint32_t bk = (ld_d[h] - dlo) >> s;
-      if (ld_e[h] == 0u || ((docs[ld_e[h] - 1u] - dlo) >> s) != bk) W.first[bk] = uint8_t(ld_e[h] + 1u);
-    }
-  }
+  const LeadFrame fr = lead_frame(docs, n);
+  lead_first_fill(fr, W.first, docs, ld_d, ld_e, n);
   // the alive bitmap from the lanes' alive entries, and its prefix counts: number of alive buckets
   auto rebuild = [&]() {
-    if (lane < (kConjWords + 4u) / 2u) {
-      W.bm[2u * lane] = 0u;
-      W.bm[2u * lane + 1u] = 0u;
-    }
+    const uint32_t left = alive_rebuild(fr, W.bm, W.apre, ld_d, alive, lane);
     wave::sync();
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      if (alive[h]) {
-        const uint32_t bk = (ld_d[h] - dlo) >> s;
-        atomicOr(&W.bm[bk >> 5], 1u << (bk & 31u));
-      }
-    }
-    wave::sync();
-    uint32_t p0 = 0, p1 = 0;
-    if (lane < kConjWords / 2u) {
-      p0 = uint32_t(__builtin_popcount(W.bm[2u * lane]));
-      p1 = uint32_t(__builtin_popcount(W.bm[2u * lane + 1u]));
-    }
-    const uint32_t incl = wave::inclusive_scan(p0 + p1);
-    if (lane < kConjWords / 2u) {
-      W.apre[2u * lane] = uint8_t(incl - p0 - p1);
-      W.apre[2u * lane + 1u] = uint8_t(incl - p1);
-    }
-    if (lane == kConjWords / 2u - 1u) W.apre[kConjWords] = uint8_t(incl);
-    wave::sync();
-    return wave::read_lane(incl, 63);
-  };
-  auto alive_below = [&](uint32_t x) {
-    return uint32_t(W.apre[x >> 5]) + uint32_t(__builtin_popcount(W.bm[x >> 5] & ((1u << (x & 31u)) - 1u)));
+    return left;
   };
 
   // ---- 2. one row: the blocks of its list that can hold an alive doc (k_phrase step 2), decoded;
@@ -249,70 +176,15 @@ __device__ __forceinline__ void vphrase_item(const ConjArgs& A, const uint32_t* 
   auto decode_row = [&](uint32_t i) {
     const DevTail tl = term_tail(i);
     auto put = [&](uint32_t doc, uint32_t f, uint32_t p) {
-      const uint32_t x = doc - dlo;
-      if (f == 0 || x > span) return;
-      const uint32_t t = lead_index(W.first, docs, n, x >> s, s, doc);
+      const uint32_t x = doc - fr.dlo;
+      if (f == 0 || x > fr.span) return;
+      const uint32_t t = lead_index(W.first, docs, n, x >> fr.s, fr.s, doc);
       if (t == n) return;
       W.pidx[i][t] = p;
       W.tf[i][t] = f;
     };
-    if (tl.nblk) {
-      const uint64_t last_at = reinterpret_cast<uint64_t>(seg.blk_last + tl.dir_off);
-      const uint64_t dir_at = reinterpret_cast<uint64_t>(seg.blk_dir + tl.dir_off);
-      const uint64_t pos_at = reinterpret_cast<uint64_t>(seg.blk_pos + tl.dir_off);
-      const uint32_t pos0 = seg.blk_pos[tl.dir_off];
-      const uint32_t b_first = seek[i < j ? i : i - 1u];
-      for (uint32_t b0 = b_first; b0 < tl.nblk; b0 += 64) {
-        const uint32_t bl = b0 + lane;
-        const bool valid = bl < tl.nblk;
-        const uint32_t lst = valid ? wave::gload_u32(last_at, bl * 4u) : 0xFFFFFFFFu;
-        BlkDir d{};
-        uint32_t pos_l = 0;
-        if (valid) {
-          uint32_t w[4];
-          wave::gload_u32x4(dir_at, bl * uint32_t(sizeof(BlkDir)), w);
-          d = BlkDir{w[0], w[1], w[2], w[3]};
-          pos_l = wave::gload_u32(pos_at, bl * 4u);
-        }
-        const uint32_t prv = bl ? d.prev_last : 0u;   // the block holds docs in (prv, lst]
-        const bool reach = valid && prv < dhi && lst >= dlo;
-        bool want = false;
-        if (reach) {
-          const uint32_t x0 = prv + 1u > dlo ? prv + 1u - dlo : 0u;
-          const uint32_t x1 = (lst < dhi ? lst : dhi) - dlo;
-          want = alive_below((x1 >> s) + 1u) > alive_below(x0 >> s);
-        }
-        uint64_t mask = wave::ballot(want);
-        const bool more = wave::ballot(valid && prv >= dhi) == 0;
-        while (mask) {
-          const uint32_t k = uint32_t(__builtin_ctzll(mask));
-          mask &= mask - 1;
-          const uint32_t bits = wave::read_lane(d.bits, k);
-          if (counting) bytes += block_bytes(bits);
-          const uint32_t base = wave::read_lane(d.prev_last, k);
-          uint32_t d0, d1, f0, f1, before;
-          const uint32_t dbits = bits & 0xFFu, fbits = bits >> 8;
-          if (pk_both(dbits, fbits)) {
-            decode_packed_pos<LAYOUT>(seg.pk + (uint64_t(wave::read_lane(d.aoff, k)) << 4), dbits,
-                                      fbits, base, lane, d0, d1, f0, f1, before);
-          } else {
-            decode_block_pos<LAYOUT>(seg.doc + tl.doc_start + wave::read_lane(d.off, k), dbits,
-                                     fbits, base, lane, d0, d1, f0, f1, before);
-          }
-          const uint32_t p0 = wave::read_lane(pos_l, k) - pos0 + before;
-          put(d0, f0, p0);
-          put(d1, f1, p0 + f0);
-        }
-        if (!more) break;
-      }
-    }
-    if (tl.n && tl.first_doc <= dhi && tl.last_doc >= dlo) {  // vint tail / single doc
-      const uint32_t base = seg.blk_pos[tl.dir_off + tl.nblk] - seg.blk_pos[tl.dir_off];
-      uint32_t d[2], f[2], p[2];
-      tail_pidx(seg, tl.tail_row, tl.n, base, lane, d, f, p);
-      put(d[0], f[0], p[0]);
-      put(d[1], f[1], p[1]);
-    }
+    follow_list<LAYOUT, true, false>(seg, tl, seek[i < j ? i : i - 1u], fr, W.bm, W.apre, counting, bytes,
+                                     lane, put);
   };
   auto quit = [&]() {   // no doc left: what was decoded is counted
     if (counting && lane == 0) atomicAdd(&A.touched[2u * unit], static_cast<unsigned long long>(bytes));
@@ -333,7 +205,7 @@ __device__ __forceinline__ void vphrase_item(const ConjArgs& A, const uint32_t* 
   }
   // b. every other part: alive = docs one of its members holds
   for (uint32_t lo = 0; lo < m;) {
-    const uint32_t end = part_end(lo);
+    const uint32_t end = group_end(opens, lo, m);
     if (lo != lead_lo) {
       if (rebuild() == 0u) return quit();
       for (uint32_t r = lo; r < end; ++r) decode_row(r);
@@ -431,14 +303,7 @@ __device__ __forceinline__ void vphrase_item(const ConjArgs& A, const uint32_t* 
         ++my_hits;
       }
     }
-    const uint64_t cm = wave::ballot(cand);
-    if (cm) {
-      uint32_t base = 0;
-      if (lane == 0) base = atomicAdd(&A.cand_count[unit], uint32_t(__builtin_popcountll(cm)));
-      base = wave::read_lane(base, 0);
-      const uint32_t slot = base + uint32_t(__builtin_popcountll(cm & below));
-      if (cand && slot < A.cand_cap) A.cands[uint64_t(unit) * A.cand_cap + slot] = make_key(score, doc);
-    }
+    emit_candidates(A, unit, cand, score, doc, lane);
   }
   if constexpr (MATCH) {
     my_hits = wave::reduce_add(my_hits);

@@ -23,7 +23,7 @@ using irs_hip::DevQuery;
 using irs_hip::DevTail;
 
 // The records the block-driven and joined kernels read with sload<T> live in headers that
-// carry those kernels (phrase.h: ConjItem; join.h: StreamRec, JoinWg).  sload<T> depends on T
+// carry those kernels (lead.h: ConjItem; join.h: StreamRec, JoinWg).  sload<T> depends on T
 // through its size and alignment only: same-shaped stand-ins here, and the test module
 // compares both numbers with the declarations in those headers.
 struct alignas(32) ConjItemShape { uint32_t w[8]; };

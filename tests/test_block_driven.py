@@ -294,6 +294,50 @@ def case_phrase_pilot_misled(L, layout=synth.LAYOUT_SIMD4):
         sr.close()
 
 
+# ------------------------------------------- the blocks the follower walk decodes --
+
+def case_walk_touched(L, layout=synth.LAYOUT_SIMD4):
+    """Which blocks follow_list (lead.h) decodes, pinned by the bytes a counting run reports.  Term 0
+    holds every doc: each of its blocks is all-equal in docs and in frequencies, 2 header bytes + 1
+    + 1.  Term 1 is its first block alone.  A lead of one block, docs step, 2 * step, ..., 128 * step,
+    ends on the LAST doc of block `step` - 1 of term 0: exactly `step` blocks of term 0 hold a lead
+    doc and the next one starts right behind dhi.  Against term 1 the same lead decodes one such
+    block, so the two runs differ by (step - 1) * 4 bytes whatever the lead block itself costs.
+    step = 16: two docs per bucket, one directory round; step = 80: 80 wanted blocks, a second
+    round.  A block decoded twice, or the block behind dhi, shows as 4 bytes more.  (Lead blocks
+    uncut: a piece decodes the lead block again.)"""
+    n_docs = 128 * 90
+    dense = np.arange(1, n_docs + 1, dtype=np.uint32)
+    steps = (16, 80)
+    lists = [(dense, np.ones(dense.size, np.uint32)), (dense[:128], np.ones(128, np.uint32))]
+    for step in steps:
+        d = step * np.arange(1, 129, dtype=np.uint32)
+        lists.append((d, np.ones(d.size, np.uint32)))
+    seg = synth.segment_from_lists(lists, n_docs, layout, norms=False)
+    sr = search.SegmentReader.from_synth(seg, L=L)
+    st = [parity.segment_stats(seg)]
+
+    def doc_bytes(flt, hits):
+        b = sr.batch(search.prepare([flt], TFIDF(False), st), 200).set_path(_lib.PATH_ITEMS).profile(3)
+        h, c, tot = b.run().results()
+        assert int(tot[0]) == hits and b.path() == _lib.PATH_ITEMS and b.reruns() == 0, (flt, int(tot[0]))
+        parity.check_single_segment(seg, [flt], TFIDF(False), 200, h, c, tot)
+        got, positions = b.touched()
+        b.close()
+        assert positions == 0
+        return got
+    os.environ["IRS_HIP_CONJ_SPLIT_LOG2"] = "0"
+    try:
+        for t, step in enumerate(steps, start=2):
+            whole = doc_bytes(And([by_term(t), by_term(0)]), 128)
+            one = doc_bytes(And([by_term(t), by_term(1)]), 128 // step)
+            print("walk touched: step %d, %d bytes against every doc, %d against its first block" % (step, whole, one))
+            assert whole - one == (step - 1) * 4, (step, whole, one)
+    finally:
+        os.environ.pop("IRS_HIP_CONJ_SPLIT_LOG2", None)
+    sr.close()
+
+
 # ------------------------------------------------------- candidate overflow --
 
 def _overflow_segments(L, layout, sizes, seed, missing=None):
@@ -481,6 +525,11 @@ def test_phrase_pilot_misled_emulated(simlib, layout):
     case_phrase_pilot_misled(simlib, layout)
 
 
+@pytest.mark.parametrize("layout", [synth.LAYOUT_SIMD4, synth.LAYOUT_SCALAR])
+def test_walk_touched_emulated(simlib, layout):
+    case_walk_touched(simlib, layout)
+
+
 def test_conj_overflow_emulated(simlib):
     case_conj_overflow(simlib)
 
@@ -524,6 +573,12 @@ def test_conj_pruned_only_gpu(gpulib, layout, capfd):
 @pytest.mark.parametrize("layout", [synth.LAYOUT_SIMD4, synth.LAYOUT_SCALAR])
 def test_phrase_pilot_misled_gpu(gpulib, layout):
     case_phrase_pilot_misled(gpulib, layout)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("layout", [synth.LAYOUT_SIMD4, synth.LAYOUT_SCALAR])
+def test_walk_touched_gpu(gpulib, layout):
+    case_walk_touched(gpulib, layout)
 
 
 @pytest.mark.gpu

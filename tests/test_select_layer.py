@@ -35,7 +35,7 @@ SRC = PROBE / "select_probe.hip"
 SIM_SO = PROBE / "libselect_probe_sim.so"
 HIP_SO = PROBE / "libselect_probe_hip.so"
 CSRC = ROOT / "iresearch_amd" / "csrc"
-HEADERS = ("kernels.h", "score.h", "join.h", "phrase.h", "conj.h", "types.h")
+HEADERS = ("kernels.h", "score.h", "join.h", "lead.h", "phrase.h", "conj.h", "types.h")
 
 u32, u64, f32 = np.uint32, np.uint64, np.float32
 

@@ -418,7 +418,7 @@ def _constants():
 
 def _record_sizes():
     sizes = {}
-    for h in ("types.h", "phrase.h", "join.h"):
+    for h in ("types.h", "lead.h", "phrase.h", "join.h"):
         for name, n in re.findall(r"static_assert\(sizeof\((\w+)\)\s*==\s*(\d+)", (CSRC / h).read_text()):
             sizes[name] = int(n)
     # (no static_assert in types.h for these: what the probe compiled, test_probe_records_... compares)
@@ -589,7 +589,7 @@ def test_probe_records_have_the_kernels_shapes(probe_sim):
     """sload<T> sees T's size and alignment only; ConjItem / StreamRec / JoinWg are stand-ins in
     the probe (their headers carry kernels): both numbers against the declarations."""
     sizes = _record_sizes()
-    text = "".join((CSRC / h).read_text() for h in ("types.h", "phrase.h", "join.h"))
+    text = "".join((CSRC / h).read_text() for h in ("types.h", "lead.h", "phrase.h", "join.h"))
     for i, name in enumerate(SLOAD_TYPES):
         assert probe_sim.wp_sload_size(i) == sizes[name], name
         assert re.search(r"struct (alignas\(\d+\) )?%s \{" % name, text), name

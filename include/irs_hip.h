@@ -363,6 +363,41 @@ typedef enum irs_hip_scorer_kind {
  * took 0x800 | kind for an unknown scorer under every op). */
 #define IRS_HIP_PHRASE_OPTIONAL 0x800
 
+/* OR-ed into the `kind` of an included IRS_HIP_OP_PHRASE entry: that entry is the FIRST WORD OF A
+ * FURTHER PHRASE — the query is the irs::And of its phrases, plus its required terms, minus its
+ * excluded terms, `+"new york" +"real estate"` (And::prepare -> make_conjunction over
+ * PhraseIterators and term iterators: boolean_filter.cpp:150-210, boolean_query.cpp:60-145,
+ * conjunction.hpp:436-490).  Entry order in [first_term, first_term + n_terms):
+ *   [words of phrase 1] [words of phrase 2, the first with this flag] ... [by_term children,
+ *   IRS_HIP_PHRASE_REQUIRED] [IRS_HIP_EXCLUDE entries]
+ * Every phrase has at least 2 words and the included entries are at most IRS_HIP_MAX_PHRASE_TERMS in
+ * all (so at most four phrases; more entries: IRS_HIP_EUNSUPPORTED); up to IRS_HIP_MAX_EXCLUDED
+ * excluded entries.  The phrase_offsets of a phrase are relative to its own first word, which
+ * carries 0.  The words of ONE phrase carry one scorer (that phrase's FixedPrepareCollect blob, its
+ * boost x the And's); different phrases may carry different values and kinds.
+ * IRS_HIP_EINVAL: the flag under another op; on entry 0; on an entry that also carries
+ * IRS_HIP_PHRASE_ALT, IRS_HIP_PHRASE_REQUIRED, IRS_HIP_PHRASE_OPTIONAL or is IRS_HIP_EXCLUDE; a
+ * flagged entry with phrase_offset != 0; a phrase of one word; the flag behind an
+ * IRS_HIP_PHRASE_REQUIRED entry; words of one phrase with differing scorer values; a merge other
+ * than IRS_HIP_MERGE_SUM.  IRS_HIP_EUNSUPPORTED: more than IRS_HIP_MAX_PHRASE_TERMS included
+ * entries; an IRS_HIP_PHRASE_ALT or IRS_HIP_PHRASE_OPTIONAL entry anywhere in such a query; such a
+ * query in a batch that also holds variadic phrases or queries with optional terms, in either
+ * order; a segment without positions.  Per segment:
+ *   d matches iff every phrase has phrase frequency pf_i(d) > 0, every required term holds d, d is
+ *   not deleted, lies in the unit's doc set if one is given, and no excluded term holds it;
+ *   score(d) = the float32 sum over the And's children of s_phrase_i(tf = pf_i(d), norm(d)) resp.
+ *   s_j(tf_j(d), norm(d)), the children in cost order as Conjunction sorts them
+ *   (conjunction.hpp:450-453): a phrase costs the smallest docs_count of its words, a term its
+ *   docs_count; ties in entry order — the rule IRS_HIP_PHRASE_REQUIRED states for one phrase.
+ * An absent word or required term (IRS_HIP_NO_TERM or no docs) empties the query in that segment;
+ * an absent excluded term changes nothing.  total_hits = the matching docs.  Such a query may share
+ * a batch with plain phrases and with phrases plus required terms: the whole batch then runs on
+ * k_phrases_and (irs_hip_batch_phrase_conj_units), a query with one phrase giving bit for bit what
+ * it gives in a batch without such a query; every batch control behaves as for a batch with
+ * required terms.  A query without the flag is untouched by all of this.  A compatible addition to
+ * ABI 12: a kind with 0x2000 was IRS_HIP_EINVAL before (an unknown scorer). */
+#define IRS_HIP_PHRASE_NEXT 0x2000
+
 /* The same bit OR-ed into the `kind` of an included IRS_HIP_OP_AND entry: one more member of the
  * group opened by the nearest preceding included entry without the flag — an And whose children
  * are Ors of by_term (And::prepare -> make_conjunction over the children, an Or child being its
@@ -872,6 +907,8 @@ int irs_hip_batch_stream_counts(irs_hip_batch* batch, uint32_t* distinct, uint32
 int irs_hip_batch_wide_units(irs_hip_batch* batch, uint32_t* units);
 /* ... and its units with IRS_HIP_CLAUSE_AND entries (k_clause_pilot / k_clause_score). */
 int irs_hip_batch_clause_units(irs_hip_batch* batch, uint32_t* units);
+/* ... and its units with an IRS_HIP_PHRASE_NEXT entry (several phrases in one And; k_phrases_and). */
+int irs_hip_batch_phrase_conj_units(irs_hip_batch* batch, uint32_t* units);
 /* Bound images: where a batch's plain disjunctions run on paired doc tiles, the kernel reads, per
  * (segment, term, scorer signature), a second array in posting order whose entries carry a 16-bit
  * upper bound of the posting's score factor instead of (tf, norm).  Images are made from the

@@ -200,6 +200,11 @@ struct And {
   std::vector<Or> groups;
   float boost = 1.f;
   std::vector<by_phrase> phrases;
+  // `phrases` may hold TWO TO FOUR phrases of plain terms, each of two words or more —
+  // `+"new york" +"real estate"` (IRS_HIP_PHRASE_NEXT: each phrase's words with its own blob, the
+  // first word of every further phrase flagged; `subs` may be empty) — when this is set; unset, two
+  // phrases are not_supported as they always were
+  bool phrase_conjunction = false;
 };
 // irs::And of ONE included filter and Not(by_term) children (boolean_filter.cpp:92-135,
 // boolean_query.cpp:121-141): the included filter's matches minus every doc of an excluded term —
@@ -440,34 +445,47 @@ std::vector<PreparedQuery> prepare(const std::vector<filter>& filters, const Sco
       // boolean_filter.cpp:150-210): the phrase's words with its ONE blob, then every by_term with
       // its own statistics, flagged IRS_HIP_PHRASE_REQUIRED
       const And& a = *std::get_if<And>(&f);
-      if (a.phrases.size() > 1)
+      // (phrase_conjunction: two to four phrases, IRS_HIP_PHRASE_NEXT on the first word of every
+      // phrase but the first, each phrase with its OWN blob; required terms may follow or not)
+      if (a.phrases.size() > 1 && !a.phrase_conjunction)
         throw not_supported(IRS_HIP_EUNSUPPORTED, "And: two phrases (ONE by_phrase plus by_terms is taken)");
-      const by_phrase& p = a.phrases[0];
-      if (!p.members.empty())
-        throw not_supported(IRS_HIP_EUNSUPPORTED, "And: a variadic by_phrase with required terms "
-                            "(ONE by_phrase of plain terms plus by_terms is taken)");
+      if (a.phrases.size() > 4)
+        throw not_supported(IRS_HIP_EUNSUPPORTED, "And: more than four phrases");
+      size_t n_words = 0;
+      for (const by_phrase& p : a.phrases) {
+        if (!p.members.empty())
+          throw not_supported(IRS_HIP_EUNSUPPORTED, "And: a variadic by_phrase with required terms "
+                              "(ONE by_phrase of plain terms plus by_terms is taken)");
+        n_words += p.terms.size();
+      }
       if (!a.groups.empty())
         throw not_supported(IRS_HIP_EUNSUPPORTED, "And: an Or group next to a by_phrase "
                             "(ONE by_phrase plus by_terms is taken)");
       if (a.merge_type != IRS_HIP_MERGE_SUM)
         throw not_supported(IRS_HIP_EUNSUPPORTED, "And: a by_phrase child merges with SUM on the GPU path");
-      if (a.subs.empty())
+      if (a.subs.empty() && a.phrases.size() == 1)
         throw illegal_argument(IRS_HIP_EINVAL, "And: a by_phrase alone is that phrase (send the by_phrase)");
-      if (p.terms.size() < 2)
-        throw illegal_argument(IRS_HIP_EINVAL, "And: a by_phrase of one term is a by_term");
-      if (!p.offsets.empty() && (p.offsets.size() != p.terms.size() || p.offsets[0] != 0))
-        throw illegal_argument(IRS_HIP_EINVAL, "by_phrase: offsets are relative to the first term");
-      if (p.terms.size() + a.subs.size() > IRS_HIP_MAX_PHRASE_TERMS)
+      for (const by_phrase& p : a.phrases) {
+        if (p.terms.size() < 2)
+          throw illegal_argument(IRS_HIP_EINVAL, "And: a by_phrase of one term is a by_term");
+        if (!p.offsets.empty() && (p.offsets.size() != p.terms.size() || p.offsets[0] != 0))
+          throw illegal_argument(IRS_HIP_EINVAL, "by_phrase: offsets are relative to the first term");
+      }
+      if (n_words + a.subs.size() > IRS_HIP_MAX_PHRASE_TERMS)
         throw not_supported(IRS_HIP_EUNSUPPORTED, "And: more than IRS_HIP_MAX_PHRASE_TERMS phrase words "
                             "and required terms");
       q.op = IRS_HIP_OP_PHRASE;
-      TermStats st;  // ONE blob for the phrase, from its own words (FixedPrepareCollect)
-      for (uint32_t t : p.terms) scorer.collect(st, dwf, docs_with_term(t), ttf);
-      irs_hip_term_scorer e = scorer.term_scorer(st, a.boost * p.boost);
-      for (size_t i = 0; i < p.terms.size(); ++i) {
-        e.term = p.terms[i];
-        e.phrase_offset = p.offsets.empty() ? uint32_t(i) : p.offsets[i];
-        q.terms.push_back(e);
+      for (const by_phrase& p : a.phrases) {
+        TermStats st;  // ONE blob per phrase, from its own words (FixedPrepareCollect)
+        for (uint32_t t : p.terms) scorer.collect(st, dwf, docs_with_term(t), ttf);
+        irs_hip_term_scorer e = scorer.term_scorer(st, a.boost * p.boost);
+        for (size_t i = 0; i < p.terms.size(); ++i) {
+          irs_hip_term_scorer w = e;
+          w.term = p.terms[i];
+          w.phrase_offset = p.offsets.empty() ? uint32_t(i) : p.offsets[i];
+          if (i == 0 && &p != &a.phrases[0]) w.kind |= IRS_HIP_PHRASE_NEXT;
+          q.terms.push_back(w);
+        }
       }
       for (const auto& t : a.subs) {
         irs_hip_term_scorer r = one(by_term{t.term, a.boost * t.boost});
@@ -961,6 +979,15 @@ class QueryBatch {
   // last run decoded itself — the rest came out of the device's stream cache
   struct StreamCounts { uint32_t distinct = 0, decoded = 0; };
   // the batch's units of by_scored_terms / wide expansion queries (irs_hip_batch_wide_units)
+  uint32_t phrase_conj_units() const {   // ... of several phrases in one And (irs_hip_batch_phrase_conj_units)
+    uint32_t total = 0;
+    for (const auto& part : part_) {
+      uint32_t n = 0;
+      if (part.h) check(irs_hip_batch_phrase_conj_units(part.h, &n), "irs_hip_batch_phrase_conj_units");
+      total += n;
+    }
+    return total;
+  }
   uint32_t clause_units() const {   // ... of Ors with And children (irs_hip_batch_clause_units)
     uint32_t total = 0;
     for (const Part& part : part_) {

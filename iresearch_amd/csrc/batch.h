@@ -181,6 +181,13 @@ struct BlockWork {
   bool optional = false;
   std::vector<uint32_t> n_phrase;
   DevBuf d_n_phrase;
+  // ... or several phrases in one And (IRS_HIP_PHRASE_NEXT in any unit: every phrase unit of the
+  // batch runs on k_phrases_and, phrases.h): n_phrase as above (all word rows), and per unit bit r of
+  // `phrase_opens` set = row r opens a phrase; they go out in d_opens, which a variadic batch —
+  // never one of these — fills with its parts' words
+  bool several = false;
+  uint32_t n_several = 0;   // units with the flag (irs_hip_batch_phrase_conj_units)
+  std::vector<uint32_t> phrase_opens;
   DevBuf d_pilot;             // the lead items the pilot pass samples, {unit, item} each
   uint32_t n_pilot = 0, pilot_stride = 0;
 };

@@ -27,6 +27,7 @@
 #include "kernels.h"
 #include "phrase.h"
 #include "vphrase.h"
+#include "phrases.h"
 #include "score.h"
 #include "conj.h"
 #include "conj_any.h"
@@ -579,6 +580,7 @@ static int batch_create_multi_impl(irs_hip_segment* const* segs, uint32_t n_segs
   b->groups.upper.assign(nq, 0.0);
   b->blocks.opens.assign(nq, 0);
   b->blocks.n_phrase.assign(nq, 0);
+  b->blocks.phrase_opens.assign(nq, 0);
   b->any.opens.assign(nq, 0);
   b->qterms.reserve(size_t(n_entries) * n_segs);
   b->excl.unit_first.assign(1, 0u);
@@ -1384,6 +1386,13 @@ int irs_hip_batch_clause_units(irs_hip_batch* b, uint32_t* units) {
   return settled(b, [&]() -> int {
     if (!b || !units) return IRS_HIP_EINVAL;
     *units = uint32_t(b->clause.units.size());
+    return IRS_HIP_OK;
+  });
+}
+int irs_hip_batch_phrase_conj_units(irs_hip_batch* b, uint32_t* units) {
+  return settled(b, [&]() -> int {
+    if (!b || !units) return IRS_HIP_EINVAL;
+    *units = b->blocks.n_several;
     return IRS_HIP_OK;
   });
 }

@@ -11,10 +11,12 @@
 //   k_phrase_and_match ... with required terms (IRS_HIP_PHRASE_REQUIRED: phrase_item's REQ form),
 //   k_vphrase_match ... and of vphrase_item (vphrase.h, variadic phrases): phrase frequency > 0
 //                   sets the doc's bit in the unit's zeroed row
+//   k_phrases_and_match (phrases.h) several phrases in one And: every phrase's frequency > 0
 #pragma once
 #include "kernels.h"
 #include "phrase.h"
 #include "vphrase.h"
+#include "phrases.h"
 
 namespace irs_hip {
 

@@ -121,9 +121,14 @@ int build_phrase_work(irs_hip_batch* b) {
   const int rc = stage_lead_items(b, b->blocks, b->blocks.d_lead_of, lead_of);
   b->blocks.n_phrase_wgs = (b->blocks.n_items + kPhraseWaves - 1) / kPhraseWaves;
   // (required terms: the lead above is the rarest of the phrase words AND the required terms)
-  if (rc == IRS_HIP_OK && (b->blocks.required || b->blocks.optional) &&
+  if (rc == IRS_HIP_OK && (b->blocks.required || b->blocks.optional || b->blocks.several) &&
       (!b->blocks.d_n_phrase.alloc(uint64_t(b->nq) * 4) ||
        !b->up.copy(b->blocks.d_n_phrase.p, b->blocks.n_phrase.data(), uint64_t(b->nq) * 4)))
+    return IRS_HIP_ENOMEM;
+  // (several phrases in one And: ... and which rows open a phrase)
+  if (rc == IRS_HIP_OK && b->blocks.several &&
+      (!b->blocks.d_opens.alloc(uint64_t(b->nq) * 4) ||
+       !b->up.copy(b->blocks.d_opens.p, b->blocks.phrase_opens.data(), uint64_t(b->nq) * 4)))
     return IRS_HIP_ENOMEM;
   return rc;
 }
@@ -282,6 +287,8 @@ bool launch_conj(irs_hip_batch* b, rt::stream_t st) {
 // threshold bins -> full pass.
 // REQ: a batch with required terms (IRS_HIP_PHRASE_REQUIRED), every unit on k_phrase_and.
 // REQ == kPhraseOpt: a batch with optional terms (IRS_HIP_PHRASE_OPTIONAL), every unit on k_phrase_or.
+// REQ == kPhraseSeveral: a batch with several phrases in one And (IRS_HIP_PHRASE_NEXT), every unit on
+// k_phrases_and (phrases.h).
 template<int LAYOUT, int MT, int REQ = 0>
 bool launch_phrase(irs_hip_batch* b, rt::stream_t st) {
   if (b->blocks.n_phrase_wgs == 0) return true;  // no query has all its terms in its segment
@@ -303,7 +310,11 @@ bool launch_phrase(irs_hip_batch* b, rt::stream_t st) {
     p.wgs = b->blocks.d_pilot.as<PhraseWg>();
     p.n_pilot = b->blocks.n_pilot;
     p.touched = nullptr;
-    if constexpr (REQ == kPhraseOpt) {
+    if constexpr (REQ == kPhraseSeveral) {
+      RT_LAUNCH((k_phrases_and<LAYOUT, MT>), (b->blocks.n_pilot + kPhraseWaves - 1) / kPhraseWaves,
+                kPhraseWaves * 64, 0, st, p, b->blocks.d_n_phrase.as<uint32_t>(),
+                b->blocks.d_opens.as<uint32_t>(), 1u);
+    } else if constexpr (REQ == kPhraseOpt) {
       RT_LAUNCH((k_phrase_or<LAYOUT, MT>), (b->blocks.n_pilot + kPhraseWaves - 1) / kPhraseWaves,
                 kPhraseWaves * 64, 0, st, p, b->blocks.d_n_phrase.as<uint32_t>(),
                 b->d_taken.as<uint32_t>(), 2u * b->taken_words, 1u);
@@ -322,7 +333,10 @@ bool launch_phrase(irs_hip_batch* b, rt::stream_t st) {
             b->d_queries.as<DevQuery>(), b->blocks.d_units.as<uint32_t>(),
             b->blocks.d_items.as<uint32_t>(), b->blocks.d_hist.as<uint32_t>(), stride,
             b->estimate ? kPilotMargin : 0u, b->d_bstar.as<uint32_t>(), min_bins(b));
-  if constexpr (REQ == kPhraseOpt) {
+  if constexpr (REQ == kPhraseSeveral) {
+    RT_LAUNCH((k_phrases_and<LAYOUT, MT>), b->blocks.n_phrase_wgs, kPhraseWaves * 64, 0, st, a,
+              b->blocks.d_n_phrase.as<uint32_t>(), b->blocks.d_opens.as<uint32_t>(), 0u);
+  } else if constexpr (REQ == kPhraseOpt) {
     RT_LAUNCH((k_phrase_or<LAYOUT, MT>), b->blocks.n_phrase_wgs, kPhraseWaves * 64, 0, st, a,
               b->blocks.d_n_phrase.as<uint32_t>(), b->d_taken.as<uint32_t>(), 2u * b->taken_words, 0u);
   } else if constexpr (REQ) {
@@ -375,6 +389,9 @@ bool launch_vphrase(irs_hip_batch* b, rt::stream_t st) {
 template<int LAYOUT>
 bool launch_phrase_terms(irs_hip_batch* b, rt::stream_t st) {
   if (b->blocks.variadic) return launch_vphrase<LAYOUT>(b, st);
+  if (b->blocks.several)   // (with or without required terms: every unit on k_phrases_and)
+    return b->jt <= 4 ? launch_phrase<LAYOUT, 4, kPhraseSeveral>(b, st)
+                      : launch_phrase<LAYOUT, int(kPhraseMaxTerms), kPhraseSeveral>(b, st);
   if (b->blocks.required)
     return b->jt <= 4 ? launch_phrase<LAYOUT, 4, kPhraseReq>(b, st)
                       : launch_phrase<LAYOUT, int(kPhraseMaxTerms), kPhraseReq>(b, st);

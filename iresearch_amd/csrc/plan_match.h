@@ -85,6 +85,16 @@ static bool launch_phrase_match(irs_hip_batch* b, rt::stream_t st, uint32_t* set
             w.d_units.as<uint32_t>(), w.d_item_base.as<uint32_t>(), uint32_t(w.units.size()),
             w.d_lead_of.as<uint32_t>(), static_cast<const uint32_t*>(nullptr), w.d_seek.as<uint32_t>(),
             w.d_recs.as<ConjItem>());
+  if (w.several) {   // (a batch with several phrases in one And: every unit on k_phrases_and_match)
+    if (b->jt <= 4) {
+      RT_LAUNCH((k_phrases_and_match<LAYOUT, 4>), w.n_phrase_wgs, kPhraseWaves * 64, 0, st, a,
+                w.d_n_phrase.as<uint32_t>(), w.d_opens.as<uint32_t>(), sets32, words32, counts);
+    } else {
+      RT_LAUNCH((k_phrases_and_match<LAYOUT, int(kPhraseMaxTerms)>), w.n_phrase_wgs, kPhraseWaves * 64, 0, st, a,
+                w.d_n_phrase.as<uint32_t>(), w.d_opens.as<uint32_t>(), sets32, words32, counts);
+    }
+    return rt::last_error_ok();
+  }
   if (w.required) {   // (a batch with required terms: every unit on the REQ form)
     if (b->jt <= 4) {
       RT_LAUNCH((k_phrase_and_match<LAYOUT, 4>), w.n_phrase_wgs, kPhraseWaves * 64, 0, st, a,

@@ -35,6 +35,10 @@ struct UnitShape {
   bool grouped = false;    // an And with IRS_HIP_GROUP_ALT members
   bool clause = false;     // an Or / min-match Or with IRS_HIP_CLAUSE_AND members (clauses.h)
   Behind behind = Behind::kNone;
+  // an And of several phrases (IRS_HIP_PHRASE_NEXT, phrases.h): bit j of `opens` = entry j opens a
+  // phrase (bit 0 always); a unit with rows has a row per entry, so these are its rows too
+  bool several = false;
+  uint32_t n_phrases = 1, opens = 1;
   bool phrase() const { return op == OpClass::kPhrase; }
   bool wide() const { return op == OpClass::kWide; }
 };
@@ -134,6 +138,52 @@ int phrase_behind(const irs_hip_term_scorer* ents, UnitShape& sh) {
   return IRS_HIP_OK;
 }
 
+// A chain of phrases (IRS_HIP_PHRASE_NEXT on the first word of every phrase but the first): the
+// words of phrase 1, of phrase 2, ..., then required terms.  This is where the flag is interpreted;
+// phrase_behind, which follows, sees the words of all phrases as the words in front of the
+// required terms.  A query without the flag passes untouched.
+int phrase_chain(const irs_hip_term_scorer* ents, UnitShape& sh) {
+  constexpr int32_t kBehind = IRS_HIP_PHRASE_REQUIRED | IRS_HIP_PHRASE_OPTIONAL;
+  constexpr int32_t kFlags = kBehind | IRS_HIP_PHRASE_ALT | IRS_HIP_PHRASE_NEXT;
+  sh.opens = 1;
+  sh.n_phrases = 1;
+  int32_t kinds = 0;
+  for (uint32_t j = 0; j < sh.n_incl; ++j) kinds |= ents[j].kind;
+  sh.several = (kinds & IRS_HIP_PHRASE_NEXT) != 0;
+  if (!sh.several) return IRS_HIP_OK;
+  uint32_t first = 0;       // the current phrase's first entry
+  bool behind = false;      // a required / optional entry has been seen
+  for (uint32_t j = 0; j <= sh.n_incl; ++j) {
+    const bool end = j == sh.n_incl;
+    const int32_t kind = end ? 0 : ents[j].kind;
+    const bool next = (kind & IRS_HIP_PHRASE_NEXT) != 0;
+    if (next && (j == 0 || behind || (kind & (kBehind | IRS_HIP_PHRASE_ALT)) ||
+                 (kind & ~kFlags) == IRS_HIP_EXCLUDE || ents[j].phrase_offset != 0))
+      return IRS_HIP_EINVAL;
+    // the current phrase ends in front of the next one, of the first entry behind the words, of
+    // the end: a phrase of one word is none
+    if (!behind && (end || next || (kind & kBehind))) {
+      if (j - first < 2) return IRS_HIP_EINVAL;
+      // its words carry ONE scorer: the phrase's stats blob
+      for (uint32_t x = first + 1; x < j; ++x) {
+        const irs_hip_term_scorer &a = ents[first], &w = ents[x];
+        if ((a.kind & ~kFlags) != (w.kind & ~kFlags) || a.c0 != w.c0 || a.norm_const != w.norm_const ||
+            a.norm_length != w.norm_length)
+          return IRS_HIP_EINVAL;
+      }
+    }
+    if (next) {
+      sh.opens |= 1u << j;
+      ++sh.n_phrases;
+      first = j;
+    }
+    behind = behind || (kind & kBehind) != 0;
+  }
+  if (sh.n_incl > IRS_HIP_MAX_PHRASE_TERMS || (kinds & (IRS_HIP_PHRASE_ALT | IRS_HIP_PHRASE_OPTIONAL)))
+    return IRS_HIP_EUNSUPPORTED;
+  return IRS_HIP_OK;
+}
+
 // Shape of query `in` in one segment.  Reads the query, the segment's entries `terms` and its term
 // table; fills `sh` and `excl` (the present excluded terms); writes nothing of the batch.
 int unit_shape(const irs_hip_query& in, const irs_hip_term_scorer* terms, uint32_t n_entries,
@@ -158,6 +208,7 @@ int unit_shape(const irs_hip_query& in, const irs_hip_term_scorer* terms, uint32
   if (sh.clause && clause_shape_ok(in, ents, sh.n_incl, sh.n_excl) == IRS_HIP_EINVAL) return IRS_HIP_EINVAL;
   if ((in.op != IRS_HIP_OP_OR && in.op != IRS_HIP_OP_AND && in.op != IRS_HIP_OP_MINMATCH && !sh.phrase() && !sh.wide()) ||
       sh.n_incl == 0 || in.merge > IRS_HIP_MERGE_MIN || (sh.phrase() && in.merge != IRS_HIP_MERGE_SUM) ||
+      (!sh.phrase() && (kinds & IRS_HIP_PHRASE_NEXT)) ||
       (!sh.wide() && !sh.clause && sh.n_incl > IRS_HIP_MAX_TERMS) || sh.n_excl > IRS_HIP_MAX_EXCLUDED || in.k == 0 ||
       in.k > IRS_HIP_MAX_K)
     return IRS_HIP_EINVAL;
@@ -166,6 +217,8 @@ int unit_shape(const irs_hip_query& in, const irs_hip_term_scorer* terms, uint32
     if (const int rc = clause_shape_ok(in, ents, sh.n_incl, sh.n_excl)) return rc;
   if (sh.wide())
     if (const int rc = wide_shape_ok(in, sh)) return rc;
+  if (sh.phrase())
+    if (const int rc = phrase_chain(ents, sh)) return rc;
   if (sh.phrase())
     if (const int rc = phrase_behind(ents, sh)) return rc;
   // a grouped conjunction: an And whose entries with IRS_HIP_GROUP_ALT are more members of the
@@ -256,7 +309,8 @@ int unit_rows(const irs_hip_term_scorer* ents, const irs_hip_segment* seg, Unit&
     const irs_hip_term_scorer& ts = ents[j];
     const bool behind = sh.phrase() && j >= sh.n_words;   // (a required or an optional term)
     const bool optional = behind && sh.behind == Behind::kOptional;   // (no part of the phrase: absent, it is dropped)
-    const int32_t kind = sh.phrase() ? (ts.kind & ~(IRS_HIP_PHRASE_ALT | IRS_HIP_PHRASE_REQUIRED | IRS_HIP_PHRASE_OPTIONAL))
+    const int32_t kind = sh.phrase() ? (ts.kind & ~(IRS_HIP_PHRASE_ALT | IRS_HIP_PHRASE_REQUIRED | IRS_HIP_PHRASE_OPTIONAL |
+                                                  IRS_HIP_PHRASE_NEXT))
                          : sh.grouped ? (ts.kind & ~IRS_HIP_GROUP_ALT)
                          : sh.clause ? (ts.kind & ~IRS_HIP_CLAUSE_AND) : ts.kind;
     if (sh.grouped && !(ts.kind & IRS_HIP_GROUP_ALT)) ++u.n_groups;
@@ -312,13 +366,17 @@ int unit_rows(const irs_hip_term_scorer* ents, const irs_hip_segment* seg, Unit&
 }
 
 // k_vphrase takes no required or optional terms, k_phrase_and no variadic parts, a batch runs on
-// k_phrase_and or on k_phrase_or: the units so far (BlockWork's flags, commit_unit) and this one
+// k_phrase_and or on k_phrase_or; k_phrases_and (several phrases in one And) takes plain phrases
+// and required terms, no variadic parts, no optional terms: the units so far (BlockWork's flags,
+// commit_unit) and this one
 int phrase_kernel_rule(const irs_hip_batch* b, const UnitShape& sh) {
   if (!sh.phrase()) return IRS_HIP_OK;
   const bool variadic = b->blocks.variadic || sh.variadic;
   const bool required = b->blocks.required || sh.behind == Behind::kRequired;
   const bool optional = b->blocks.optional || sh.behind == Behind::kOptional;
-  return (variadic && (required || optional)) || (required && optional) ? IRS_HIP_EUNSUPPORTED : IRS_HIP_OK;
+  const bool several = b->blocks.several || sh.several;
+  return (variadic && (required || optional || several)) || (optional && (required || several))
+             ? IRS_HIP_EUNSUPPORTED : IRS_HIP_OK;
 }
 
 // How many of the (present) terms a doc must match.  Or: 1.  And: all, and one absent term empties
@@ -351,8 +409,10 @@ int unit_need(const irs_hip_query& in, Unit& u, UnitScratch& s) {
       break;
     case OpClass::kWide: u.need = in.min_match > n_rows ? kEmptyUnit : in.min_match; break;
     case OpClass::kPhrase:
+      // (several phrases: every word is a part, so an absent word of any phrase empties the unit;
+      // one scorer per PHRASE was checked on the entries, phrase_chain)
       u.need = u.parts.complete() ? 1u : kEmptyUnit;
-      for (uint32_t r = 0; r < u.parts.word_rows; ++r) {
+      for (uint32_t r = 0; r < u.parts.word_rows && !sh.several; ++r) {
         const DevQTerm& qt = s.row[r];
         if (qt.kind != s.row[0].kind || qt.c0 != s.row[0].c0 || qt.norm_const != s.row[0].norm_const ||
             qt.norm_length != s.row[0].norm_length)
@@ -545,6 +605,9 @@ void commit_unit(irs_hip_batch* b, uint32_t q, const irs_hip_query& in, const ir
     b->blocks.optional = b->blocks.optional || sh.behind == Behind::kOptional;
     b->blocks.n_phrase[q] = u.parts.word_rows;
     if (has_rows) b->blocks.opens[q] = u.parts.opens;
+    b->blocks.several = b->blocks.several || sh.several;
+    if (sh.several) ++b->blocks.n_several;
+    if (has_rows) b->blocks.phrase_opens[q] = sh.opens;   // (one phrase: bit 0)
   } else if (sh.wide()) {
     b->wide.units.push_back(q);
   } else if (sh.clause) {

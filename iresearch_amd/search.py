@@ -26,7 +26,7 @@ from dataclasses import dataclass, field, replace
 import numpy as np
 
 from . import _lib
-from ._lib import (EXCLUDE, HIT, NO_TERM, OP_AND, OP_MINMATCH, OP_MULTITERM, OP_OR, OP_PHRASE, PHRASE_ALT, PHRASE_OPTIONAL, PHRASE_REQUIRED, CLAUSE_AND, QUERY, SCORE_BM1, SCORE_BM15, SCORE_BM25,
+from ._lib import (EXCLUDE, HIT, NO_TERM, OP_AND, OP_MINMATCH, OP_MULTITERM, OP_OR, OP_PHRASE, PHRASE_ALT, PHRASE_NEXT, PHRASE_OPTIONAL, PHRASE_REQUIRED, CLAUSE_AND, QUERY, SCORE_BM1, SCORE_BM15, SCORE_BM25,
                    SCORE_TFIDF, SCORE_TFIDF_NORM, TERM_META, TERM_SCORER, SegmentDesc)
 
 f32 = np.float32
@@ -127,7 +127,9 @@ class And:
     """irs::And of by_term and Or-of-by_term children (the Ors are groups: IRS_HIP_GROUP_ALT), or of
     ONE by_phrase of plain terms and by_term children — a phrase plus required terms,
     `+"new york" +hotel` (IRS_HIP_PHRASE_REQUIRED; merge SUM, at most 8 words and terms in all;
-    prepare(..., required_terms=True));
+    prepare(..., required_terms=True)), or of two to four such phrases and by_term children —
+    `+"new york" +"real estate"` (IRS_HIP_PHRASE_NEXT; merge SUM, at most 8 words and terms in all;
+    prepare(..., phrase_conjunctions=True));
     Not children exclude docs either way; `boost` multiplies into the boosts of its children."""
     subs: list
     op: int = OP_AND
@@ -170,8 +172,9 @@ class by_phrase:
     phrase, VariadicPrepareCollect); `offsets[i]` = position of part i relative to the first
     (default: consecutive words).  A phrase of plain terms may also be a child of an And, next to
     by_term children (required terms) and Nots (prepare(..., required_terms=True)), or of an Or
-    next to by_term children (optional terms, prepare(..., optional_terms=True)); not next to
-    another phrase."""
+    next to by_term children (optional terms, prepare(..., optional_terms=True)).  Up to four
+    phrases of plain terms may stand in one And (prepare(..., phrase_conjunctions=True)); two
+    phrases in one Or are not taken."""
     terms: list
     offsets: list | None = None
     boost: float = 1.0
@@ -490,6 +493,9 @@ class PreparedQuery:
     clause: list | None = None     # OP_OR / OP_MINMATCH: True for an entry that is one more required
                                    # member of the clause before it (IRS_HIP_CLAUSE_AND) — an Or with
                                    # And children, min_match counting clauses; None: a flat Or
+    opens: list | None = None      # OP_PHRASE: True for an entry that is the first word of a FURTHER
+                                   # phrase of the And (IRS_HIP_PHRASE_NEXT): the words of phrase 1, of
+                                   # phrase 2, ..., then the required terms; None: one phrase
 
 
 # ------------------------------------------------------------------ segment --
@@ -659,8 +665,11 @@ class QueryArrays:
             reqs = p.required if p.required is not None else [False] * len(p.terms)
             opts = p.optional if p.optional is not None else [False] * len(p.terms)
             more = p.clause if p.clause is not None else [False] * len(p.terms)
-            for t, (kind, c0, nc, nl), off, alt, req, opt, cl in zip(p.terms, p.scorers, offs, alts, reqs, opts, more):
+            nxts = p.opens if p.opens is not None else [False] * len(p.terms)
+            for t, (kind, c0, nc, nl), off, alt, req, opt, cl, nxt in zip(p.terms, p.scorers, offs, alts, reqs, opts,
+                                                                         more, nxts):
                 kind = kind | CLAUSE_AND if cl else kind
+                kind = kind | PHRASE_NEXT if nxt else kind
                 kind = kind | PHRASE_ALT if alt else kind   # (GROUP_ALT for an And: the same bit)
                 kind = kind | PHRASE_REQUIRED if req else kind
                 kind = kind | PHRASE_OPTIONAL if opt else kind
@@ -772,6 +781,10 @@ def prepare_filters(filters, scorer, segment_stats, segs, k):
                                                any(not isinstance(s, by_term) for s in subs)):
                 if any(isinstance(s, Not) for s in subs):
                     raise ValueError("Not is taken by prepare() (IRS_HIP_EXCLUDE), not by the "
+                                     "array path prepare_filters")
+                if cls is And and sum(isinstance(s, by_phrase) for s in subs) > 1:
+                    raise ValueError("several by_phrase children of an And (IRS_HIP_PHRASE_NEXT) are "
+                                     "taken by prepare(..., phrase_conjunctions=True), not by the "
                                      "array path prepare_filters")
                 if any(isinstance(s, by_phrase) for s in subs):
                     raise ValueError("a by_phrase inside an And (a phrase plus required terms, "
@@ -1101,6 +1114,14 @@ class QueryBatch:
         _lib.check(self.L, self.L.irs_hip_batch_clause_units(self.handle, C.byref(n)), "irs_hip_batch_clause_units")
         return n.value
 
+    def phrase_conj_units(self) -> int:
+        """irs_hip_batch_phrase_conj_units: the batch's units of several phrases in one And
+        (IRS_HIP_PHRASE_NEXT: k_phrases_and), (segment, query) pairs."""
+        n = C.c_uint32()
+        _lib.check(self.L, self.L.irs_hip_batch_phrase_conj_units(self.handle, C.byref(n)),
+                   "irs_hip_batch_phrase_conj_units")
+        return n.value
+
     def wide_units(self) -> int:
         """irs_hip_batch_wide_units: the batch's units of by_terms / wide expansion queries
         (IRS_HIP_OP_MULTITERM), (segment, query) pairs."""
@@ -1252,7 +1273,8 @@ class SegmentStats:
     docs_count: np.ndarray  # per term ordinal: term_meta::docs_count
 
 
-def prepare(filters, scorer, segment_stats, required_terms=False, optional_terms=False, and_clauses=False):
+def prepare(filters, scorer, segment_stats, required_terms=False, optional_terms=False, and_clauses=False,
+            phrase_conjunctions=False):
     """filter::prepare for a list of filters against ALL segments: statistics are
     index-global (term_filter.cpp:102-125): D = sum docs_with_field,
     d = sum docs_count of the term, avgdl from the summed field frequency.
@@ -1265,7 +1287,10 @@ def prepare(filters, scorer, segment_stats, required_terms=False, optional_terms
     Off by default in the same way.
     and_clauses=True: Or([And([by_term...]), by_term, Or([...])...]) — an Or with And children, a
     disjunction of clauses, IRS_HIP_CLAUSE_AND (or_clauses) — is taken.  Off by default in the same
-    way: without it such an Or is refused as it always was."""
+    way: without it such an Or is refused as it always was.
+    phrase_conjunctions=True: And([by_phrase, by_phrase..., by_term..., Not(...)...]) — two to four
+    phrases in one And, plus required terms, IRS_HIP_PHRASE_NEXT — is taken.  Off by default in the
+    same way: without it two phrases in one And are refused as they always were."""
     dwf = sum(s.docs_with_field for s in segment_stats)
     ttf = sum(s.total_term_freq for s in segment_stats)
     out = []
@@ -1273,7 +1298,8 @@ def prepare(filters, scorer, segment_stats, required_terms=False, optional_terms
         flt, doc_set = split_doc_set(flt)
         if doc_set is not None:
             # (the doc set is no part of what is prepared: no score, no statistic)
-            p = prepare([flt], scorer, segment_stats, required_terms, optional_terms, and_clauses)[0]
+            p = prepare([flt], scorer, segment_stats, required_terms, optional_terms, and_clauses,
+                        phrase_conjunctions)[0]
             if p.clause is not None:
                 raise ValueError("a by_doc_set on an Or with And children is not on the GPU path "
                                  "(its units read the streams every unit shares)")
@@ -1283,7 +1309,8 @@ def prepare(filters, scorer, segment_stats, required_terms=False, optional_terms
         flt, excluded = split_exclusions(flt)
         if excluded:
             # (the excluded part is prepared without scorers: no score, no statistic)
-            p = prepare([flt], scorer, segment_stats, required_terms, optional_terms, and_clauses)[0]
+            p = prepare([flt], scorer, segment_stats, required_terms, optional_terms, and_clauses,
+                        phrase_conjunctions)[0]
             if p.clause is not None:
                 raise ValueError("Not around an Or with And children (((a AND b) OR c) AND NOT d) is "
                                  "not on the GPU path")
@@ -1311,6 +1338,10 @@ def prepare(filters, scorer, segment_stats, required_terms=False, optional_terms
             continue
         if type(flt) is Or and optional_terms and any(isinstance(s, by_phrase) for s in flt.subs):
             out.append(_prepare_phrase_or(flt, scorer, segment_stats, dwf, ttf))
+            continue
+        if (phrase_conjunctions and type(flt) is And and flt.op == OP_AND and
+                sum(isinstance(s, by_phrase) for s in flt.subs) > 1):
+            out.append(_prepare_phrases_and(flt, scorer, segment_stats, dwf, ttf))
             continue
         if isinstance(flt, (Or, And)) and any(isinstance(s, by_phrase) for s in flt.subs):
             if type(flt) is And and not required_terms:
@@ -1398,6 +1429,54 @@ def _prepare_phrase_and(flt, scorer, segment_stats, dwf, ttf):
         scorers.append(scorer.term_scorer(scorer.collect(dwf, dwt, ttf), f32(mult * f32(s.boost))))
     return PreparedQuery(OP_PHRASE, terms, scorers, 0, [int(o) for o in ph.offsets] + [0] * len(others),
                          required=[False] * len(ph.terms) + [True] * len(others))
+
+
+def _prepare_phrases_and(flt, scorer, segment_stats, dwf, ttf):
+    """prepare() of And([by_phrase, by_phrase..., by_term...]) — several phrases in one And, plus
+    required terms (And::prepare -> make_conjunction over the children, boolean_filter.cpp:150-210):
+    every phrase gets its OWN FixedPrepareCollect blob from its own words, every by_term its own
+    statistics; the And's boost multiplies into every child's in float32.  Entries: the words of
+    phrase 1, of phrase 2 (its first word with IRS_HIP_PHRASE_NEXT), ..., then the required terms
+    (IRS_HIP_PHRASE_REQUIRED).  What is taken: 2-4 phrases of plain terms, each of at least two
+    words, 0 or more by_term children, merge SUM, at most 8 words and terms in all (Not children
+    were split off before)."""
+    taken = ("an And takes 2-4 by_phrase children of plain terms (two words or more each) plus "
+             "by_term children (and Not children), merged with SUM, at most %d words and terms in all"
+             % _lib.MAX_PHRASE_TERMS)
+    phrases = [s for s in flt.subs if isinstance(s, by_phrase)]
+    others = [s for s in flt.subs if not isinstance(s, by_phrase)]
+    if any(ph.variadic for ph in phrases):
+        raise ValueError("a variadic by_phrase next to another phrase is not on the GPU path: " + taken)
+    for s in others:
+        if type(s) is Or:
+            raise ValueError("an Or group next to by_phrase children is not on the GPU path: " + taken)
+        if type(s) is not by_term:
+            raise ValueError("%s next to by_phrase children is not on the GPU path: %s" % (type(s).__name__, taken))
+    if flt.merge != MERGE_SUM:
+        raise ValueError("an And with by_phrase children merges with SUM on the GPU path "
+                         "(MAX / MIN over phrases and terms are not built)")
+    if any(len(ph.terms) < 2 for ph in phrases):
+        raise ValueError("a by_phrase of one term is a by_term: " + taken)
+    if len(phrases) > 4:
+        raise ValueError("more than four phrases in one And are not on the GPU path: " + taken)
+    if sum(len(ph.terms) for ph in phrases) + len(others) > _lib.MAX_PHRASE_TERMS:
+        raise ValueError("phrases plus required terms have at most %d entries in all" % _lib.MAX_PHRASE_TERMS)
+    mult = f32(flt.boost)
+    terms, scorers, offsets, opens = [], [], [], []
+    for i, ph in enumerate(phrases):
+        one = _phrase_scorer(ph, f32(mult * f32(ph.boost)), scorer, segment_stats, dwf, ttf)
+        terms += list(ph.terms)
+        scorers += [one] * len(ph.terms)
+        offsets += [int(o) for o in ph.offsets]
+        opens += [i > 0] + [False] * (len(ph.terms) - 1)
+    n_words = len(terms)
+    for s in others:
+        dwt = sum(int(st.docs_count[s.term]) for st in segment_stats if 0 <= s.term < len(st.docs_count))
+        terms.append(s.term)
+        scorers.append(scorer.term_scorer(scorer.collect(dwf, dwt, ttf), f32(mult * f32(s.boost))))
+    return PreparedQuery(OP_PHRASE, terms, scorers, 0, offsets + [0] * len(others),
+                         required=([False] * n_words + [True] * len(others)) if others else None,
+                         opens=opens + [False] * len(others))
 
 
 def _prepare_phrase_or(flt, scorer, segment_stats, dwf, ttf):

@@ -384,6 +384,40 @@ def main():
                 tpa.check(f, k, rh[q], rc[q], rt[q], *tpa.expected(seg, f, scorer))
             rb.close()
             queries += len(rf)
+            # several phrases in one And (IRS_HIP_PHRASE_NEXT): 2-4 phrases of 2-3 frequent words
+            # within 8 entries, some with a required term or a Not, next to units of one phrase,
+            # against the composition of tests/test_phrases_and.py (the oracle's run of every phrase)
+            import test_phrases_and as tps
+            pf = []
+            for i in range(8):
+                left, phs = 8, []
+                for _ in range(int(rng.integers(2, 5))):
+                    nw = int(rng.integers(2, 4))
+                    if left - nw < 0:
+                        break
+                    left -= nw
+                    offs = np.concatenate([[0], np.cumsum(rng.integers(1, 3, nw - 1))])
+                    phs.append(by_phrase([int(x) for x in rng.integers(0, 8, nw)], [int(o) for o in offs],
+                                         boost=1.0 if i % 3 else 1.5))
+                subs = list(phs)   # (the first two always fit: at most 3 + 3 of 8 entries)
+                if left > 0 and i % 2:
+                    subs.append(by_term(int(rng.integers(0, max_rank)), 0.75))
+                if i % 4 == 0:
+                    subs.append(Not(by_term(int(rng.integers(0, max_rank)))))
+                pf.append(And([subs[j] for j in rng.permutation(len(subs))], boost=2.5 if i % 5 == 0 else 1.0))
+            pf += rf[:2] + filters[:2]
+            pb = sr.batch(tps.prepare(pf, scorer, st), k)
+            assert pb.phrase_conj_units() == 8
+            ph_, pc_, pt_ = (x.copy() for x in pb.run().results())
+            pexp = [tps.expected(seg, f, scorer) for f in pf]
+            for q, f in enumerate(pf):
+                tps.check(f, k, ph_[q], pc_[q], pt_[q], *pexp[q])
+            psets, pcounts = pb.match_sets()
+            for q, f in enumerate(pf):
+                assert np.array_equal(tps._bits(psets[q], seg.num_docs + 1), pexp[q][1]), ("match set", f)
+                assert int(pcounts[q]) == int(pexp[q][1].sum()), ("match count", f)
+            pb.close()
+            queries += len(pf)
             # a phrase or optional terms (IRS_HIP_PHRASE_OPTIONAL): Or([by_phrase, by_term...]), some
             # with a Not, against the composition of tests/test_phrase_or.py (the oracle's phrase run
             # and its disjunction of the optional terms); the match sets are the union

@@ -58,6 +58,10 @@ def main():
                          "plain phrase of the same words.  --op and: every term becomes an Or group of N "
                          "members from the same rank range (IRS_HIP_GROUP_ALT); 1 = the plain And.  "
                          "Times each and exits")
+    ap.add_argument("--phrases", default="",
+                    help="--op phrase: comma list N,...: And of N phrases (IRS_HIP_PHRASE_NEXT; 2..4 with "
+                         "--terms 2) — every query's own phrase and those of the N-1 queries behind it; "
+                         "1 = the plain phrases.  Times each and exits")
     ap.add_argument("--required", default="",
                     help="--op phrase: comma list N,...: And([phrase, N by_terms]) — the same phrases with "
                          "N required terms each (IRS_HIP_PHRASE_REQUIRED), drawn from --lo-rank..--hi-rank; "
@@ -272,6 +276,30 @@ def main():
                   "select %.2f)  hits/query mean %.1f  reruns=%d"
                   % (n_req, dt * 1e3, dt * 1e3 * 1000 / len(rf), *avg, float(np.mean(totals)), b.reruns()),
                   flush=True)
+            b.close()
+        sys.exit(0)
+    if args.phrases and args.op == "phrase":
+        for n_ph in (int(x) for x in args.phrases.split(",")):
+            # query q: its own phrase and those of the n_ph - 1 queries behind it, in one And
+            pf = []
+            for q in range(len(ranks)):
+                phs = [by_phrase([int(r) - 1 for r in ranks[(q + j) % len(ranks)]]) for j in range(n_ph)]
+                pf.append(And(phs) if n_ph > 1 else phs[0])
+            b = sr.batch(search.prepare(pf, scorer, [st], phrase_conjunctions=True), args.k).profile(True)
+            b.run()
+            _, _, totals = b.results()
+            ms = []
+            t0 = time.perf_counter()
+            for _ in range(args.steps):
+                b.run()
+                b.results()
+                ms.append(b.timings())
+            dt = (time.perf_counter() - t0) / args.steps
+            avg = np.mean(ms, axis=0)
+            print("phrases=%d  step %.2f ms  = %.2f ms per 1000 queries  (plan %.2f pilot %.2f score %.2f "
+                  "select %.2f)  hits/query mean %.1f  reruns=%d  conj units %d"
+                  % (n_ph, dt * 1e3, dt * 1e3 * 1000 / len(pf), *avg, float(np.mean(totals)), b.reruns(),
+                     b.phrase_conj_units()), flush=True)
             b.close()
         sys.exit(0)
     if args.alts and args.op == "phrase":

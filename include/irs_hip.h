@@ -398,6 +398,41 @@ typedef enum irs_hip_scorer_kind {
  * ABI 12: a kind with 0x2000 was IRS_HIP_EINVAL before (an unknown scorer). */
 #define IRS_HIP_PHRASE_NEXT 0x2000
 
+/* OR-ed into the `kind` of an included IRS_HIP_OP_PHRASE entry: that entry is the FIRST WORD OF AN
+ * ALTERNATIVE PHRASE — the query is the irs::Or of its phrases, minus its excluded terms,
+ * `"new york" OR "los angeles"` (Or::prepare prepares every child on its own,
+ * boolean_filter.cpp:150-210; MakeDisjunction over PhraseIterators: basic_disjunction for two,
+ * small_disjunction for up to five, disjunction.hpp:1411-1467, :208-350, :374-).  Entry order in
+ * [first_term, first_term + n_terms):
+ *   [words of phrase 1] [words of phrase 2, the first with this flag] ... [IRS_HIP_EXCLUDE entries]
+ * Two to four phrases, each of at least 2 plain words, the included entries at most
+ * IRS_HIP_MAX_PHRASE_TERMS in all; up to IRS_HIP_MAX_EXCLUDED excluded entries.  The phrase_offsets
+ * of a phrase are relative to its own first word, which carries 0.  The words of ONE phrase carry one
+ * scorer (that phrase's FixedPrepareCollect blob, its boost x the Or's); different phrases may carry
+ * different values and kinds.
+ * IRS_HIP_EINVAL: the flag under another op; on entry 0; on an IRS_HIP_EXCLUDE entry; a flagged
+ * entry with phrase_offset != 0; a phrase of one word; words of one phrase with differing scorer
+ * values; a merge other than IRS_HIP_MERGE_SUM.  IRS_HIP_EUNSUPPORTED: more than
+ * IRS_HIP_MAX_PHRASE_TERMS included entries; an IRS_HIP_PHRASE_ALT, IRS_HIP_PHRASE_REQUIRED,
+ * IRS_HIP_PHRASE_OPTIONAL or IRS_HIP_PHRASE_NEXT entry anywhere in such a query; such a query in a
+ * batch that also holds a query with one of those four flags, in either order (plain phrases may
+ * share the batch); a segment without positions.  Per segment:
+ *   a phrase with an absent word (IRS_HIP_NO_TERM or no docs) is dropped in that segment — the other
+ *   phrases go on matching; every phrase dropped: the unit is empty;
+ *   d matches iff some present phrase has phrase frequency pf_i(d) > 0, d is not deleted, lies in the
+ *   unit's doc set if one is given, and no excluded term holds it;
+ *   score(d) = the float32 sum, in entry order, over the phrases with pf_i(d) > 0 of
+ *   s_phrase_i(tf = pf_i(d), norm(d)); the sum starts from the first such phrase's value;
+ *   total_hits = the matching docs, each counted once.
+ * An absent excluded term changes nothing.  A batch with such a query runs all its phrase units on
+ * k_phrases_or (irs_hip_batch_phrase_disj_units), a plain phrase giving bit for bit what it gives in a
+ * batch without such a query; every batch control (doc sets, comm, shared threshold, min scores,
+ * configure) behaves as for a batch of plain phrases.  irs_hip_batch_set_wand leaves these units
+ * unpruned: a lead piece could be skipped only against a bound on the whole unit's score, and none is
+ * kept per block.  A query without the flag is untouched by all of this.  A compatible addition to
+ * ABI 12: a kind with 0x4000 was IRS_HIP_EINVAL before (an unknown scorer). */
+#define IRS_HIP_PHRASE_OR 0x4000
+
 /* The same bit OR-ed into the `kind` of an included IRS_HIP_OP_AND entry: one more member of the
  * group opened by the nearest preceding included entry without the flag — an And whose children
  * are Ors of by_term (And::prepare -> make_conjunction over the children, an Or child being its
@@ -909,6 +944,8 @@ int irs_hip_batch_wide_units(irs_hip_batch* batch, uint32_t* units);
 int irs_hip_batch_clause_units(irs_hip_batch* batch, uint32_t* units);
 /* ... and its units with an IRS_HIP_PHRASE_NEXT entry (several phrases in one And; k_phrases_and). */
 int irs_hip_batch_phrase_conj_units(irs_hip_batch* batch, uint32_t* units);
+/* ... and its units with an IRS_HIP_PHRASE_OR entry (several phrases in one Or; k_phrases_or). */
+int irs_hip_batch_phrase_disj_units(irs_hip_batch* batch, uint32_t* units);
 /* Bound images: where a batch's plain disjunctions run on paired doc tiles, the kernel reads, per
  * (segment, term, scorer signature), a second array in posting order whose entries carry a 16-bit
  * upper bound of the posting's score factor instead of (tf, norm).  Images are made from the

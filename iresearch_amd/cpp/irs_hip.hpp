@@ -183,6 +183,12 @@ struct Or {
   float boost = 1.f;   // multiplies into its terms' boosts (boolean_filter.cpp:153-154, 204)
   std::vector<by_phrase> phrases;
   std::vector<And> clauses;
+  // `phrases` may hold TWO TO FOUR phrases of plain terms, each of two words or more, and `subs`
+  // nothing — `"new york" OR "los angeles"` (IRS_HIP_PHRASE_OR: each phrase's words with its own
+  // blob, the first word of every further phrase flagged; min_match_count <= 1, merge SUM, at most
+  // IRS_HIP_MAX_PHRASE_TERMS words in all) — when this is set; unset, two phrases are not_supported
+  // as they always were
+  bool phrase_disjunction = false;
 };
 // irs::And of by_term children (`subs`) and Or-of-by_term children (`groups`: an And of Ors,
 // IRS_HIP_GROUP_ALT).  Children in that order: subs, then groups.  A group of one term is that term
@@ -362,8 +368,47 @@ std::vector<PreparedQuery> prepare(const std::vector<filter>& filters, const Sco
       // boolean_filter.cpp:150-210; MakeDisjunction, disjunction.hpp:1411-1467): the phrase's words
       // with its ONE blob, then every by_term with its own statistics, flagged IRS_HIP_PHRASE_OPTIONAL
       const Or& o = *std::get_if<Or>(&f);
-      if (o.phrases.size() > 1)
+      if (o.phrases.size() > 1 && !o.phrase_disjunction)
         throw not_supported(IRS_HIP_EUNSUPPORTED, "Or: two phrases (ONE by_phrase plus by_terms is taken)");
+      if (o.phrases.size() > 1) {
+        // several phrases in one Or (phrase_disjunction; MakeDisjunction over PhraseIterators):
+        // IRS_HIP_PHRASE_OR on the first word of every phrase but the first, each phrase with its
+        // OWN blob, nothing behind the words
+        if (o.phrases.size() > 4) throw not_supported(IRS_HIP_EUNSUPPORTED, "Or: more than four phrases");
+        if (!o.subs.empty())
+          throw not_supported(IRS_HIP_EUNSUPPORTED, "Or: a by_term next to several phrases "
+                              "(2-4 by_phrases of plain terms and nothing else are taken)");
+        if (o.min_match_count > 1)
+          throw not_supported(IRS_HIP_EUNSUPPORTED, "Or: by_phrase children with min_match_count > 1");
+        if (o.merge_type != IRS_HIP_MERGE_SUM)
+          throw not_supported(IRS_HIP_EUNSUPPORTED, "Or: by_phrase children merge with SUM on the GPU path");
+        size_t n_words = 0;
+        for (const by_phrase& p : o.phrases) {
+          if (!p.members.empty())
+            throw not_supported(IRS_HIP_EUNSUPPORTED, "Or: a variadic by_phrase next to another phrase");
+          if (p.terms.size() < 2)
+            throw illegal_argument(IRS_HIP_EINVAL, "Or: a by_phrase of one term is a by_term");
+          if (!p.offsets.empty() && (p.offsets.size() != p.terms.size() || p.offsets[0] != 0))
+            throw illegal_argument(IRS_HIP_EINVAL, "by_phrase: offsets are relative to the first term");
+          n_words += p.terms.size();
+        }
+        if (n_words > IRS_HIP_MAX_PHRASE_TERMS)
+          throw not_supported(IRS_HIP_EUNSUPPORTED, "Or: more than IRS_HIP_MAX_PHRASE_TERMS phrase words");
+        q.op = IRS_HIP_OP_PHRASE;
+        for (const by_phrase& p : o.phrases) {
+          TermStats st;  // ONE blob per phrase, from its own words (FixedPrepareCollect)
+          for (uint32_t t : p.terms) scorer.collect(st, dwf, docs_with_term(t), ttf);
+          const irs_hip_term_scorer e = scorer.term_scorer(st, o.boost * p.boost);
+          for (size_t i = 0; i < p.terms.size(); ++i) {
+            irs_hip_term_scorer w = e;
+            w.term = p.terms[i];
+            w.phrase_offset = p.offsets.empty() ? uint32_t(i) : p.offsets[i];
+            if (i == 0 && &p != &o.phrases[0]) w.kind |= IRS_HIP_PHRASE_OR;
+            q.terms.push_back(w);
+          }
+        }
+        return;
+      }
       const by_phrase& p = o.phrases[0];
       if (!p.members.empty())
         throw not_supported(IRS_HIP_EUNSUPPORTED, "Or: a variadic by_phrase with optional terms "
@@ -984,6 +1029,15 @@ class QueryBatch {
     for (const auto& part : part_) {
       uint32_t n = 0;
       if (part.h) check(irs_hip_batch_phrase_conj_units(part.h, &n), "irs_hip_batch_phrase_conj_units");
+      total += n;
+    }
+    return total;
+  }
+  uint32_t phrase_disj_units() const {   // ... of several phrases in one Or (irs_hip_batch_phrase_disj_units)
+    uint32_t total = 0;
+    for (const auto& part : part_) {
+      uint32_t n = 0;
+      if (part.h) check(irs_hip_batch_phrase_disj_units(part.h, &n), "irs_hip_batch_phrase_disj_units");
       total += n;
     }
     return total;

@@ -188,6 +188,11 @@ struct BlockWork {
   bool several = false;
   uint32_t n_several = 0;   // units with the flag (irs_hip_batch_phrase_conj_units)
   std::vector<uint32_t> phrase_opens;
+  // ... or several phrases in one Or (IRS_HIP_PHRASE_OR in any unit: every phrase unit of the batch
+  // runs on k_phrases_or, phrases_or.h): `phrase_opens` over the rows of the PRESENT phrases, in
+  // d_opens; every phrase leads with its rarest row, the unit's lead rows as a mask in d_lead_rows
+  bool disj = false;
+  uint32_t n_disj = 0;      // units with the flag (irs_hip_batch_phrase_disj_units)
   DevBuf d_pilot;             // the lead items the pilot pass samples, {unit, item} each
   uint32_t n_pilot = 0, pilot_stride = 0;
 };

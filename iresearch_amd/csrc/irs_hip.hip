@@ -28,6 +28,7 @@
 #include "phrase.h"
 #include "vphrase.h"
 #include "phrases.h"
+#include "phrases_or.h"
 #include "score.h"
 #include "conj.h"
 #include "conj_any.h"
@@ -1393,6 +1394,13 @@ int irs_hip_batch_phrase_conj_units(irs_hip_batch* b, uint32_t* units) {
   return settled(b, [&]() -> int {
     if (!b || !units) return IRS_HIP_EINVAL;
     *units = b->blocks.n_several;
+    return IRS_HIP_OK;
+  });
+}
+int irs_hip_batch_phrase_disj_units(irs_hip_batch* b, uint32_t* units) {
+  return settled(b, [&]() -> int {
+    if (!b || !units) return IRS_HIP_EINVAL;
+    *units = b->blocks.n_disj;
     return IRS_HIP_OK;
   });
 }

@@ -12,11 +12,14 @@
 //   k_vphrase_match ... and of vphrase_item (vphrase.h, variadic phrases): phrase frequency > 0
 //                   sets the doc's bit in the unit's zeroed row
 //   k_phrases_and_match (phrases.h) several phrases in one And: every phrase's frequency > 0
+//   k_phrases_or_match (phrases_or.h) several phrases in one Or: some phrase's frequency > 0, the
+//                   doc set and counted by the item that owns it
 #pragma once
 #include "kernels.h"
 #include "phrase.h"
 #include "vphrase.h"
 #include "phrases.h"
+#include "phrases_or.h"
 
 namespace irs_hip {
 

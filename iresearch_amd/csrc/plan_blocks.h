@@ -92,11 +92,53 @@ int build_vphrase_work(irs_hip_batch* b) {
   return rc;
 }
 
+// k_phrases_or work (phrases_or.h) of a batch with several phrases in one Or: EVERY present phrase of
+// a unit leads with its own rarest row (the first such one on ties); the unit's lead items are the
+// blocks (+ tail / single doc) of each phrase's lead row, phrase after phrase.  The lead rows are
+// not contiguous: d_lead_rows carries them as a mask (bit r = row r leads its phrase), which
+// k_phrases_or_seek turns into records and seek rows; d_opens says which rows open a phrase.
+int build_phrases_or_work(irs_hip_batch* b) {
+  BlockWork& w = b->blocks;
+  std::vector<uint32_t> lead_mask(b->nq, 0);
+  for (uint32_t u = 0; u < b->nq; ++u) {
+    const DevQuery& dq = b->queries[u];
+    if (!dq.n_terms) continue;
+    const irs_hip_segment* sg = b->segs[dq.seg];
+    const uint32_t opens = w.phrase_opens[u] | 1u;
+    uint32_t items = 0;
+    for (uint32_t lo = 0; lo < dq.n_terms;) {
+      uint32_t end = lo + 1;
+      while (end < dq.n_terms && !((opens >> end) & 1u)) ++end;
+      uint32_t best = 0xFFFFFFFFu, lead = lo, k = 0;
+      for (uint32_t r = lo; r < end; ++r) {
+        const DevTerm& t = sg->terms[b->qterms[dq.first_term + r].term];
+        if (t.docs_count < best) {
+          best = t.docs_count;
+          k = t.nblk + ((t.docs_count == 1 || t.tail_n) ? 1u : 0u);
+          lead = r;
+        }
+      }
+      lead_mask[u] |= 1u << lead;
+      items += k;
+      lo = end;
+    }
+    w.units.push_back(u);
+    w.items.push_back(items);
+  }
+  if (w.units.empty()) return IRS_HIP_OK;   // (no query has a phrase with all its words in its segment)
+  if (!w.d_opens.alloc(uint64_t(b->nq) * 4) || !b->up.copy(w.d_opens.p, w.phrase_opens.data(), uint64_t(b->nq) * 4))
+    return IRS_HIP_ENOMEM;
+  const int rc = stage_lead_items(b, w, w.d_lead_rows, lead_mask);
+  w.n_phrase_wgs = (w.n_items + kPhraseWaves - 1) / kPhraseWaves;
+  return rc;
+}
+
 // k_phrase work of a phrase batch, built at create: the lead term of a unit is its rarest one; one
 // wavefront per 128-posting block of it (+ one for its vint tail / single doc); records and start
 // blocks of the other terms written by k_conj_seek every run
 int build_phrase_work(irs_hip_batch* b) {
   if (b->blocks.variadic) return build_vphrase_work(b);
+  if (b->blocks.disj) return build_phrases_or_work(b);
   std::vector<uint32_t> lead_of(b->nq, 0);
   for (uint32_t u = 0; u < b->nq; ++u) {
     const DevQuery& dq = b->queries[u];
@@ -352,6 +394,42 @@ bool launch_phrase(irs_hip_batch* b, rt::stream_t st) {
             b->d_hits.as<unsigned long long>());
   return rt::last_error_ok();
 }
+// Several phrases in one Or (k_phrases_or<LAYOUT, MT>, phrases_or.h): the same stages — pilot list,
+// threshold, full pass, hit counts — with the lead items of every phrase; records and seek rows from
+// k_phrases_or_seek.
+template<int LAYOUT, int MT>
+bool launch_phrases_or(irs_hip_batch* b, rt::stream_t st) {
+  if (b->blocks.n_phrase_wgs == 0) return true;
+  const uint32_t stride = b->stride_eff;
+  if (!ensure_pilot_list(b, b->blocks, stride, st) || !rt::dmemset(b->blocks.d_hist.p, 0, b->blocks.d_hist.n, st) ||
+      !rt::dmemset(b->blocks.d_item_hits.p, 0, b->blocks.d_item_hits.n, st))
+    return false;
+  ConjArgs a = block_args(b, b->blocks, stride);
+  const uint32_t* opens = b->blocks.d_opens.as<uint32_t>();
+  RT_LAUNCH(k_phrases_or_seek, (b->blocks.n_items + kThreads - 1) / kThreads, kThreads, 0, st,
+            b->d_segs.as<DevSegment>(), b->d_queries.as<DevQuery>(), b->d_tails.as<DevTail>(),
+            b->jt, b->blocks.d_units.as<uint32_t>(), b->blocks.d_item_base.as<uint32_t>(),
+            uint32_t(b->blocks.units.size()), b->blocks.d_lead_rows.as<uint32_t>(),
+            b->blocks.d_seek.as<uint32_t>(), b->blocks.d_recs.as<ConjItem>());
+  count_leads(b->blocks, a, st);
+  if (b->blocks.n_pilot) {
+    ConjArgs p = a;
+    p.wgs = b->blocks.d_pilot.as<PhraseWg>();
+    p.n_pilot = b->blocks.n_pilot;
+    p.touched = nullptr;
+    RT_LAUNCH((k_phrases_or<LAYOUT, MT>), (b->blocks.n_pilot + kPhraseWaves - 1) / kPhraseWaves,
+              kPhraseWaves * 64, 0, st, p, opens, 1u);
+  }
+  RT_LAUNCH(k_conj_threshold, uint32_t(b->blocks.units.size()), 64, 0, st,
+            b->d_queries.as<DevQuery>(), b->blocks.d_units.as<uint32_t>(),
+            b->blocks.d_items.as<uint32_t>(), b->blocks.d_hist.as<uint32_t>(), stride,
+            b->estimate ? kPilotMargin : 0u, b->d_bstar.as<uint32_t>(), min_bins(b));
+  RT_LAUNCH((k_phrases_or<LAYOUT, MT>), b->blocks.n_phrase_wgs, kPhraseWaves * 64, 0, st, a, opens, 0u);
+  RT_LAUNCH(k_conj_hits, uint32_t(b->blocks.units.size()), 64, 0, st, b->blocks.d_units.as<uint32_t>(),
+            b->blocks.d_item_base.as<uint32_t>(), b->blocks.d_item_hits.as<uint32_t>(),
+            b->d_hits.as<unsigned long long>());
+  return rt::last_error_ok();
+}
 // Variadic phrases (k_vphrase): the same stages, with the items of every lead member.
 template<int LAYOUT>
 bool launch_vphrase(irs_hip_batch* b, rt::stream_t st) {
@@ -389,6 +467,8 @@ bool launch_vphrase(irs_hip_batch* b, rt::stream_t st) {
 template<int LAYOUT>
 bool launch_phrase_terms(irs_hip_batch* b, rt::stream_t st) {
   if (b->blocks.variadic) return launch_vphrase<LAYOUT>(b, st);
+  if (b->blocks.disj)   // (every unit on k_phrases_or)
+    return b->jt <= 4 ? launch_phrases_or<LAYOUT, 4>(b, st) : launch_phrases_or<LAYOUT, int(kPhraseMaxTerms)>(b, st);
   if (b->blocks.several)   // (with or without required terms: every unit on k_phrases_and)
     return b->jt <= 4 ? launch_phrase<LAYOUT, 4, kPhraseSeveral>(b, st)
                       : launch_phrase<LAYOUT, int(kPhraseMaxTerms), kPhraseSeveral>(b, st);

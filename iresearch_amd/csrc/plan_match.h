@@ -79,6 +79,20 @@ static bool launch_phrase_match(irs_hip_batch* b, rt::stream_t st, uint32_t* set
               w.d_opens.as<uint32_t>(), sets32, words32, counts);
     return rt::last_error_ok();
   }
+  if (w.disj) {   // (a batch with several phrases in one Or: every unit on k_phrases_or_match)
+    RT_LAUNCH(k_phrases_or_seek, (w.n_items + kThreads - 1) / kThreads, kThreads, 0, st,
+              b->d_segs.as<DevSegment>(), b->d_queries.as<DevQuery>(), b->d_tails.as<DevTail>(), b->jt,
+              w.d_units.as<uint32_t>(), w.d_item_base.as<uint32_t>(), uint32_t(w.units.size()),
+              w.d_lead_rows.as<uint32_t>(), w.d_seek.as<uint32_t>(), w.d_recs.as<ConjItem>());
+    if (b->jt <= 4) {
+      RT_LAUNCH((k_phrases_or_match<LAYOUT, 4>), w.n_phrase_wgs, kPhraseWaves * 64, 0, st, a,
+                w.d_opens.as<uint32_t>(), sets32, words32, counts);
+    } else {
+      RT_LAUNCH((k_phrases_or_match<LAYOUT, int(kPhraseMaxTerms)>), w.n_phrase_wgs, kPhraseWaves * 64, 0, st, a,
+                w.d_opens.as<uint32_t>(), sets32, words32, counts);
+    }
+    return rt::last_error_ok();
+  }
   a.lead_of = w.d_lead_of.as<uint32_t>();
   RT_LAUNCH(k_conj_seek, (w.n_items + kThreads - 1) / kThreads, kThreads, 0, st,
             b->d_segs.as<DevSegment>(), b->d_queries.as<DevQuery>(), b->d_tails.as<DevTail>(), b->jt,

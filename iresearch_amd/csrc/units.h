@@ -39,6 +39,9 @@ struct UnitShape {
   // phrase (bit 0 always); a unit with rows has a row per entry, so these are its rows too
   bool several = false;
   uint32_t n_phrases = 1, opens = 1;
+  // an Or of several phrases (IRS_HIP_PHRASE_OR, phrases_or.h): n_phrases and `opens` as above, over
+  // the ENTRIES — a phrase with an absent word has no rows (unit_rows: Unit::disj_opens)
+  bool disj = false;
   bool phrase() const { return op == OpClass::kPhrase; }
   bool wide() const { return op == OpClass::kWide; }
 };
@@ -85,6 +88,7 @@ struct Unit {
   // (an Or of clauses: an entry without IRS_HIP_CLAUSE_AND opens a clause; bit g: every member of
   // clause g is present)
   uint32_t n_groups = 0, groups_found = 0;
+  uint32_t disj_opens = 0;   // an Or of phrases: bit r = row r opens a (present) phrase
   uint32_t need = 1;         // unit_need: the present terms a doc must match, or kEmptyUnit
   // unit_run
   int32_t op = 0;
@@ -184,6 +188,44 @@ int phrase_chain(const irs_hip_term_scorer* ents, UnitShape& sh) {
   return IRS_HIP_OK;
 }
 
+// Alternative phrases (IRS_HIP_PHRASE_OR on the first word of every phrase but the first): the words
+// of phrase 1, of phrase 2, ..., nothing behind them but excluded terms.  This is where the flag is
+// interpreted; a query without it passes untouched.
+int phrase_alternatives(const irs_hip_term_scorer* ents, UnitShape& sh) {
+  constexpr int32_t kOthers = IRS_HIP_PHRASE_REQUIRED | IRS_HIP_PHRASE_OPTIONAL | IRS_HIP_PHRASE_ALT | IRS_HIP_PHRASE_NEXT;
+  constexpr int32_t kFlags = kOthers | IRS_HIP_PHRASE_OR;
+  int32_t kinds = 0;
+  for (uint32_t j = 0; j < sh.n_incl; ++j) kinds |= ents[j].kind;
+  sh.disj = (kinds & IRS_HIP_PHRASE_OR) != 0;
+  if (!sh.disj) return IRS_HIP_OK;
+  sh.opens = 1;
+  sh.n_phrases = 1;
+  uint32_t first = 0;       // the current phrase's first entry
+  for (uint32_t j = 0; j <= sh.n_incl; ++j) {
+    const bool end = j == sh.n_incl;
+    const bool next = !end && (ents[j].kind & IRS_HIP_PHRASE_OR) != 0;
+    if (next && (j == 0 || (ents[j].kind & ~kFlags) == IRS_HIP_EXCLUDE || ents[j].phrase_offset != 0))
+      return IRS_HIP_EINVAL;
+    if (end || next) {   // the current phrase ends here: a phrase of one word is none
+      if (j - first < 2) return IRS_HIP_EINVAL;
+      // its words carry ONE scorer: the phrase's stats blob
+      for (uint32_t x = first + 1; x < j; ++x) {
+        const irs_hip_term_scorer &a = ents[first], &w = ents[x];
+        if ((a.kind & ~kFlags) != (w.kind & ~kFlags) || a.c0 != w.c0 || a.norm_const != w.norm_const ||
+            a.norm_length != w.norm_length)
+          return IRS_HIP_EINVAL;
+      }
+    }
+    if (next) {
+      sh.opens |= 1u << j;
+      ++sh.n_phrases;
+      first = j;
+    }
+  }
+  if (sh.n_incl > IRS_HIP_MAX_PHRASE_TERMS || (kinds & kOthers)) return IRS_HIP_EUNSUPPORTED;
+  return IRS_HIP_OK;
+}
+
 // Shape of query `in` in one segment.  Reads the query, the segment's entries `terms` and its term
 // table; fills `sh` and `excl` (the present excluded terms); writes nothing of the batch.
 int unit_shape(const irs_hip_query& in, const irs_hip_term_scorer* terms, uint32_t n_entries,
@@ -208,7 +250,7 @@ int unit_shape(const irs_hip_query& in, const irs_hip_term_scorer* terms, uint32
   if (sh.clause && clause_shape_ok(in, ents, sh.n_incl, sh.n_excl) == IRS_HIP_EINVAL) return IRS_HIP_EINVAL;
   if ((in.op != IRS_HIP_OP_OR && in.op != IRS_HIP_OP_AND && in.op != IRS_HIP_OP_MINMATCH && !sh.phrase() && !sh.wide()) ||
       sh.n_incl == 0 || in.merge > IRS_HIP_MERGE_MIN || (sh.phrase() && in.merge != IRS_HIP_MERGE_SUM) ||
-      (!sh.phrase() && (kinds & IRS_HIP_PHRASE_NEXT)) ||
+      (!sh.phrase() && (kinds & (IRS_HIP_PHRASE_NEXT | IRS_HIP_PHRASE_OR))) ||
       (!sh.wide() && !sh.clause && sh.n_incl > IRS_HIP_MAX_TERMS) || sh.n_excl > IRS_HIP_MAX_EXCLUDED || in.k == 0 ||
       in.k > IRS_HIP_MAX_K)
     return IRS_HIP_EINVAL;
@@ -218,6 +260,8 @@ int unit_shape(const irs_hip_query& in, const irs_hip_term_scorer* terms, uint32
   if (sh.wide())
     if (const int rc = wide_shape_ok(in, sh)) return rc;
   if (sh.phrase())
+    if (const int rc = phrase_alternatives(ents, sh)) return rc;
+  if (sh.phrase() && !sh.disj)
     if (const int rc = phrase_chain(ents, sh)) return rc;
   if (sh.phrase())
     if (const int rc = phrase_behind(ents, sh)) return rc;
@@ -305,12 +349,28 @@ int unit_rows(const irs_hip_term_scorer* ents, const irs_hip_segment* seg, Unit&
     }
     u.groups_found = ((1u << u.n_groups) - 1u) & ~dead;
   }
+  // an Or of phrases: a phrase with an absent word is dropped in this segment the same way — none of
+  // its entries is a row (bit j of `gone`: entry j belongs to such a phrase)
+  uint32_t gone = 0;
+  if (sh.disj) {
+    for (uint32_t lo = 0; lo < sh.n_incl;) {
+      uint32_t end = lo + 1;
+      while (end < sh.n_incl && !((sh.opens >> end) & 1u)) ++end;
+      bool absent = false;
+      for (uint32_t j = lo; j < end; ++j) {
+        const uint32_t t = ents[j].term;
+        absent = absent || t == IRS_HIP_NO_TERM || (t < seg->dev.num_terms && seg->terms[t].docs_count == 0);
+      }
+      if (absent) gone |= ((1u << end) - 1u) & ~((1u << lo) - 1u);
+      lo = end;
+    }
+  }
   for (uint32_t j = 0; j < sh.n_incl; ++j) {
     const irs_hip_term_scorer& ts = ents[j];
     const bool behind = sh.phrase() && j >= sh.n_words;   // (a required or an optional term)
     const bool optional = behind && sh.behind == Behind::kOptional;   // (no part of the phrase: absent, it is dropped)
     const int32_t kind = sh.phrase() ? (ts.kind & ~(IRS_HIP_PHRASE_ALT | IRS_HIP_PHRASE_REQUIRED | IRS_HIP_PHRASE_OPTIONAL |
-                                                  IRS_HIP_PHRASE_NEXT))
+                                                  IRS_HIP_PHRASE_NEXT | IRS_HIP_PHRASE_OR))
                          : sh.grouped ? (ts.kind & ~IRS_HIP_GROUP_ALT)
                          : sh.clause ? (ts.kind & ~IRS_HIP_CLAUSE_AND) : ts.kind;
     if (sh.grouped && !(ts.kind & IRS_HIP_GROUP_ALT)) ++u.n_groups;
@@ -343,6 +403,10 @@ int unit_rows(const irs_hip_term_scorer* ents, const irs_hip_segment* seg, Unit&
       if ((dead >> clause_of[j]) & 1u) continue;
       s.row_group.push_back(clause_of[j]);
     }
+    if (sh.disj) {
+      if ((gone >> j) & 1u) continue;
+      if ((sh.opens >> j) & 1u) u.disj_opens |= 1u << s.row.size();
+    }
     if (sh.grouped) {
       u.groups_found |= 1u << (u.n_groups - 1u);
       s.row_group.push_back(u.n_groups - 1u);
@@ -367,7 +431,8 @@ int unit_rows(const irs_hip_term_scorer* ents, const irs_hip_segment* seg, Unit&
 
 // k_vphrase takes no required or optional terms, k_phrase_and no variadic parts, a batch runs on
 // k_phrase_and or on k_phrase_or; k_phrases_and (several phrases in one And) takes plain phrases
-// and required terms, no variadic parts, no optional terms: the units so far (BlockWork's flags,
+// and required terms, no variadic parts, no optional terms; k_phrases_or (several phrases in one Or)
+// plain phrases only: the units so far (BlockWork's flags,
 // commit_unit) and this one
 int phrase_kernel_rule(const irs_hip_batch* b, const UnitShape& sh) {
   if (!sh.phrase()) return IRS_HIP_OK;
@@ -375,7 +440,10 @@ int phrase_kernel_rule(const irs_hip_batch* b, const UnitShape& sh) {
   const bool required = b->blocks.required || sh.behind == Behind::kRequired;
   const bool optional = b->blocks.optional || sh.behind == Behind::kOptional;
   const bool several = b->blocks.several || sh.several;
-  return (variadic && (required || optional || several)) || (optional && (required || several))
+  // (k_phrases_or — several phrases in one Or — takes plain phrases and nothing else)
+  const bool disj = b->blocks.disj || sh.disj;
+  return (variadic && (required || optional || several)) || (optional && (required || several)) ||
+                 (disj && (variadic || required || optional || several))
              ? IRS_HIP_EUNSUPPORTED : IRS_HIP_OK;
 }
 
@@ -411,8 +479,9 @@ int unit_need(const irs_hip_query& in, Unit& u, UnitScratch& s) {
     case OpClass::kPhrase:
       // (several phrases: every word is a part, so an absent word of any phrase empties the unit;
       // one scorer per PHRASE was checked on the entries, phrase_chain)
-      u.need = u.parts.complete() ? 1u : kEmptyUnit;
-      for (uint32_t r = 0; r < u.parts.word_rows && !sh.several; ++r) {
+      // (an Or of phrases: the rows of its present phrases; none present empties it)
+      u.need = (sh.disj ? !s.row.empty() : u.parts.complete()) ? 1u : kEmptyUnit;
+      for (uint32_t r = 0; r < u.parts.word_rows && !sh.several && !sh.disj; ++r) {
         const DevQTerm& qt = s.row[r];
         if (qt.kind != s.row[0].kind || qt.c0 != s.row[0].c0 || qt.norm_const != s.row[0].norm_const ||
             qt.norm_length != s.row[0].norm_length)
@@ -607,7 +676,9 @@ void commit_unit(irs_hip_batch* b, uint32_t q, const irs_hip_query& in, const ir
     if (has_rows) b->blocks.opens[q] = u.parts.opens;
     b->blocks.several = b->blocks.several || sh.several;
     if (sh.several) ++b->blocks.n_several;
-    if (has_rows) b->blocks.phrase_opens[q] = sh.opens;   // (one phrase: bit 0)
+    if (has_rows) b->blocks.phrase_opens[q] = sh.disj ? u.disj_opens : sh.opens;   // (one phrase: bit 0)
+    b->blocks.disj = b->blocks.disj || sh.disj;
+    if (sh.disj) ++b->blocks.n_disj;
   } else if (sh.wide()) {
     b->wide.units.push_back(q);
   } else if (sh.clause) {

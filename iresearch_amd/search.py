@@ -26,7 +26,7 @@ from dataclasses import dataclass, field, replace
 import numpy as np
 
 from . import _lib
-from ._lib import (EXCLUDE, HIT, NO_TERM, OP_AND, OP_MINMATCH, OP_MULTITERM, OP_OR, OP_PHRASE, PHRASE_ALT, PHRASE_NEXT, PHRASE_OPTIONAL, PHRASE_REQUIRED, CLAUSE_AND, QUERY, SCORE_BM1, SCORE_BM15, SCORE_BM25,
+from ._lib import (EXCLUDE, HIT, NO_TERM, OP_AND, OP_MINMATCH, OP_MULTITERM, OP_OR, OP_PHRASE, PHRASE_ALT, PHRASE_NEXT, PHRASE_OPTIONAL, PHRASE_OR, PHRASE_REQUIRED, CLAUSE_AND, QUERY, SCORE_BM1, SCORE_BM15, SCORE_BM25,
                    SCORE_TFIDF, SCORE_TFIDF_NORM, TERM_META, TERM_SCORER, SegmentDesc)
 
 f32 = np.float32
@@ -173,8 +173,8 @@ class by_phrase:
     (default: consecutive words).  A phrase of plain terms may also be a child of an And, next to
     by_term children (required terms) and Nots (prepare(..., required_terms=True)), or of an Or
     next to by_term children (optional terms, prepare(..., optional_terms=True)).  Up to four
-    phrases of plain terms may stand in one And (prepare(..., phrase_conjunctions=True)); two
-    phrases in one Or are not taken."""
+    phrases of plain terms may stand in one And (prepare(..., phrase_conjunctions=True)) or in
+    one Or (prepare(..., phrase_disjunctions=True))."""
     terms: list
     offsets: list | None = None
     boost: float = 1.0
@@ -496,6 +496,9 @@ class PreparedQuery:
     opens: list | None = None      # OP_PHRASE: True for an entry that is the first word of a FURTHER
                                    # phrase of the And (IRS_HIP_PHRASE_NEXT): the words of phrase 1, of
                                    # phrase 2, ..., then the required terms; None: one phrase
+    or_opens: list | None = None   # OP_PHRASE: True for an entry that is the first word of an
+                                   # ALTERNATIVE phrase of the Or (IRS_HIP_PHRASE_OR): the words of
+                                   # phrase 1, of phrase 2, ...; None: one phrase
 
 
 # ------------------------------------------------------------------ segment --
@@ -666,10 +669,12 @@ class QueryArrays:
             opts = p.optional if p.optional is not None else [False] * len(p.terms)
             more = p.clause if p.clause is not None else [False] * len(p.terms)
             nxts = p.opens if p.opens is not None else [False] * len(p.terms)
-            for t, (kind, c0, nc, nl), off, alt, req, opt, cl, nxt in zip(p.terms, p.scorers, offs, alts, reqs, opts,
-                                                                         more, nxts):
+            ors = p.or_opens if p.or_opens is not None else [False] * len(p.terms)
+            for t, (kind, c0, nc, nl), off, alt, req, opt, cl, nxt, orr in zip(p.terms, p.scorers, offs, alts, reqs,
+                                                                              opts, more, nxts, ors):
                 kind = kind | CLAUSE_AND if cl else kind
                 kind = kind | PHRASE_NEXT if nxt else kind
+                kind = kind | PHRASE_OR if orr else kind
                 kind = kind | PHRASE_ALT if alt else kind   # (GROUP_ALT for an And: the same bit)
                 kind = kind | PHRASE_REQUIRED if req else kind
                 kind = kind | PHRASE_OPTIONAL if opt else kind
@@ -785,6 +790,10 @@ def prepare_filters(filters, scorer, segment_stats, segs, k):
                 if cls is And and sum(isinstance(s, by_phrase) for s in subs) > 1:
                     raise ValueError("several by_phrase children of an And (IRS_HIP_PHRASE_NEXT) are "
                                      "taken by prepare(..., phrase_conjunctions=True), not by the "
+                                     "array path prepare_filters")
+                if cls is Or and sum(isinstance(s, by_phrase) for s in subs) > 1:
+                    raise ValueError("several by_phrase children of an Or (IRS_HIP_PHRASE_OR) are "
+                                     "taken by prepare(..., phrase_disjunctions=True), not by the "
                                      "array path prepare_filters")
                 if any(isinstance(s, by_phrase) for s in subs):
                     raise ValueError("a by_phrase inside an And (a phrase plus required terms, "
@@ -1122,6 +1131,14 @@ class QueryBatch:
                    "irs_hip_batch_phrase_conj_units")
         return n.value
 
+    def phrase_disj_units(self) -> int:
+        """irs_hip_batch_phrase_disj_units: the batch's units of several phrases in one Or
+        (IRS_HIP_PHRASE_OR: k_phrases_or), (segment, query) pairs."""
+        n = C.c_uint32()
+        _lib.check(self.L, self.L.irs_hip_batch_phrase_disj_units(self.handle, C.byref(n)),
+                   "irs_hip_batch_phrase_disj_units")
+        return n.value
+
     def wide_units(self) -> int:
         """irs_hip_batch_wide_units: the batch's units of by_terms / wide expansion queries
         (IRS_HIP_OP_MULTITERM), (segment, query) pairs."""
@@ -1274,7 +1291,7 @@ class SegmentStats:
 
 
 def prepare(filters, scorer, segment_stats, required_terms=False, optional_terms=False, and_clauses=False,
-            phrase_conjunctions=False):
+            phrase_conjunctions=False, phrase_disjunctions=False):
     """filter::prepare for a list of filters against ALL segments: statistics are
     index-global (term_filter.cpp:102-125): D = sum docs_with_field,
     d = sum docs_count of the term, avgdl from the summed field frequency.
@@ -1290,7 +1307,11 @@ def prepare(filters, scorer, segment_stats, required_terms=False, optional_terms
     way: without it such an Or is refused as it always was.
     phrase_conjunctions=True: And([by_phrase, by_phrase..., by_term..., Not(...)...]) — two to four
     phrases in one And, plus required terms, IRS_HIP_PHRASE_NEXT — is taken.  Off by default in the
-    same way: without it two phrases in one And are refused as they always were."""
+    same way: without it two phrases in one And are refused as they always were.
+    phrase_disjunctions=True: Or([by_phrase, by_phrase...]) — two to four phrases in one Or,
+    IRS_HIP_PHRASE_OR — is taken, also as the one included child of And([Or([...]), Not(...)...,
+    by_doc_set(r)]).  Off by default in the same way: without it two phrases in one Or are refused as
+    they always were."""
     dwf = sum(s.docs_with_field for s in segment_stats)
     ttf = sum(s.total_term_freq for s in segment_stats)
     out = []
@@ -1299,7 +1320,7 @@ def prepare(filters, scorer, segment_stats, required_terms=False, optional_terms
         if doc_set is not None:
             # (the doc set is no part of what is prepared: no score, no statistic)
             p = prepare([flt], scorer, segment_stats, required_terms, optional_terms, and_clauses,
-                        phrase_conjunctions)[0]
+                        phrase_conjunctions, phrase_disjunctions)[0]
             if p.clause is not None:
                 raise ValueError("a by_doc_set on an Or with And children is not on the GPU path "
                                  "(its units read the streams every unit shares)")
@@ -1310,7 +1331,7 @@ def prepare(filters, scorer, segment_stats, required_terms=False, optional_terms
         if excluded:
             # (the excluded part is prepared without scorers: no score, no statistic)
             p = prepare([flt], scorer, segment_stats, required_terms, optional_terms, and_clauses,
-                        phrase_conjunctions)[0]
+                        phrase_conjunctions, phrase_disjunctions)[0]
             if p.clause is not None:
                 raise ValueError("Not around an Or with And children (((a AND b) OR c) AND NOT d) is "
                                  "not on the GPU path")
@@ -1335,6 +1356,9 @@ def prepare(filters, scorer, segment_stats, required_terms=False, optional_terms
             one = _phrase_scorer(flt, flt.boost, scorer, segment_stats, dwf, ttf)
             out.append(PreparedQuery(OP_PHRASE, list(flt.terms), [one] * len(flt.terms), 0,
                                      [int(o) for o in flt.offsets]))
+            continue
+        if phrase_disjunctions and type(flt) is Or and sum(isinstance(s, by_phrase) for s in flt.subs) > 1:
+            out.append(_prepare_phrases_or(flt, scorer, segment_stats, dwf, ttf))
             continue
         if type(flt) is Or and optional_terms and any(isinstance(s, by_phrase) for s in flt.subs):
             out.append(_prepare_phrase_or(flt, scorer, segment_stats, dwf, ttf))
@@ -1477,6 +1501,45 @@ def _prepare_phrases_and(flt, scorer, segment_stats, dwf, ttf):
     return PreparedQuery(OP_PHRASE, terms, scorers, 0, offsets + [0] * len(others),
                          required=([False] * n_words + [True] * len(others)) if others else None,
                          opens=opens + [False] * len(others))
+
+
+def _prepare_phrases_or(flt, scorer, segment_stats, dwf, ttf):
+    """prepare() of Or([by_phrase, by_phrase...]) — several phrases in one Or (Or::prepare prepares
+    every child on its own, boolean_filter.cpp:150-210; MakeDisjunction over PhraseIterators,
+    disjunction.hpp:1411-1467): every phrase gets its OWN FixedPrepareCollect blob from its own
+    words; the Or's boost multiplies into every phrase's in float32.  Entries: the words of phrase 1,
+    of phrase 2 (its first word with IRS_HIP_PHRASE_OR), ...  What is taken: 2-4 phrases of plain
+    terms, each of at least two words, nothing else, min_match <= 1, merge SUM, at most 8 words in
+    all (Not children and a by_doc_set were split off before)."""
+    taken = ("an Or takes 2-4 by_phrase children of plain terms (two words or more each) and nothing "
+             "else, min_match <= 1, merged with SUM, at most %d words in all" % _lib.MAX_PHRASE_TERMS)
+    phrases = [s for s in flt.subs if isinstance(s, by_phrase)]
+    others = [s for s in flt.subs if not isinstance(s, by_phrase)]
+    if any(ph.variadic for ph in phrases):
+        raise ValueError("a variadic by_phrase next to another phrase in an Or is not on the GPU path: " + taken)
+    for s in others:
+        raise ValueError("%s next to several by_phrase children of an Or is not on the GPU path: %s"
+                         % (type(s).__name__, taken))
+    if flt.min_match > 1:
+        raise ValueError("an Or of by_phrase children with min_match > 1 is not on the GPU path: " + taken)
+    if flt.merge != MERGE_SUM:
+        raise ValueError("an Or of by_phrase children merges with SUM on the GPU path "
+                         "(MAX / MIN over phrases are not built)")
+    if any(len(ph.terms) < 2 for ph in phrases):
+        raise ValueError("a by_phrase of one term is a by_term: " + taken)
+    if len(phrases) > 4:
+        raise ValueError("more than four phrases in one Or are not on the GPU path: " + taken)
+    if sum(len(ph.terms) for ph in phrases) > _lib.MAX_PHRASE_TERMS:
+        raise ValueError("the phrases of an Or have at most %d words in all" % _lib.MAX_PHRASE_TERMS)
+    mult = f32(flt.boost)
+    terms, scorers, offsets, opens = [], [], [], []
+    for i, ph in enumerate(phrases):
+        one = _phrase_scorer(ph, f32(mult * f32(ph.boost)), scorer, segment_stats, dwf, ttf)
+        terms += list(ph.terms)
+        scorers += [one] * len(ph.terms)
+        offsets += [int(o) for o in ph.offsets]
+        opens += [i > 0] + [False] * (len(ph.terms) - 1)
+    return PreparedQuery(OP_PHRASE, terms, scorers, 0, offsets, or_opens=opens)
 
 
 def _prepare_phrase_or(flt, scorer, segment_stats, dwf, ttf):

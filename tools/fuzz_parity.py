@@ -418,6 +418,37 @@ def main():
                 assert int(pcounts[q]) == int(pexp[q][1].sum()), ("match count", f)
             pb.close()
             queries += len(pf)
+            # several phrases in one Or (IRS_HIP_PHRASE_OR): 2-4 phrases of 2-3 frequent words within
+            # 8 entries, some under a Not, next to plain phrases, against the composition of
+            # tests/test_phrases_or.py (the oracle's run of every phrase); the match sets are the union
+            import test_phrases_or as tpo
+            from iresearch_amd.search import Or
+            of = []
+            for i in range(8):
+                left, phs = 8, []
+                for _ in range(int(rng.integers(2, 5))):
+                    nw = int(rng.integers(2, 4))
+                    if left - nw < 0:
+                        break
+                    left -= nw
+                    offs = np.concatenate([[0], np.cumsum(rng.integers(1, 3, nw - 1))])
+                    phs.append(by_phrase([int(x) for x in rng.integers(0, 8 if i % 4 else max_rank, nw)],
+                                         [int(o) for o in offs], boost=1.0 if i % 3 else 1.5))
+                flt = Or(phs, boost=2.5 if i % 5 == 0 else 1.0)
+                of.append(And([flt, Not(by_term(int(rng.integers(0, max_rank))))]) if i % 4 == 1 else flt)
+            of += filters[:2]
+            ob = sr.batch(tpo.prepare(of, scorer, st), k)
+            assert ob.phrase_disj_units() == 8
+            oh_, oc_, ot_ = (x.copy() for x in ob.run().results())
+            oexp = [tpo.expected(seg, f, scorer) for f in of]
+            for q, f in enumerate(of):
+                tpo.check(f, k, oh_[q], oc_[q], ot_[q], *oexp[q])
+            osets, ocounts = ob.match_sets()
+            for q, f in enumerate(of):
+                assert np.array_equal(tpo._bits(osets[q], seg.num_docs + 1), oexp[q][1]), ("match set", f)
+                assert int(ocounts[q]) == int(oexp[q][1].sum()), ("match count", f)
+            ob.close()
+            queries += len(of)
             # a phrase or optional terms (IRS_HIP_PHRASE_OPTIONAL): Or([by_phrase, by_term...]), some
             # with a Not, against the composition of tests/test_phrase_or.py (the oracle's phrase run
             # and its disjunction of the optional terms); the match sets are the union

@@ -62,6 +62,11 @@ def main():
                     help="--op phrase: comma list N,...: And of N phrases (IRS_HIP_PHRASE_NEXT; 2..4 with "
                          "--terms 2) — every query's own phrase and those of the N-1 queries behind it; "
                          "1 = the plain phrases.  Times each and exits")
+    ap.add_argument("--or-phrases", default="",
+                    help="--op phrase: comma list N,...: Or of N phrases (IRS_HIP_PHRASE_OR; 2..4 with "
+                         "--terms 2) — every query's own phrase and those of the N-1 queries behind it; "
+                         "1 = the plain phrases, whose per-query times are the yardstick: the sum over a "
+                         "query's phrases run alone.  Times each and exits")
     ap.add_argument("--required", default="",
                     help="--op phrase: comma list N,...: And([phrase, N by_terms]) — the same phrases with "
                          "N required terms each (IRS_HIP_PHRASE_REQUIRED), drawn from --lo-rank..--hi-rank; "
@@ -300,6 +305,42 @@ def main():
                   "select %.2f)  hits/query mean %.1f  reruns=%d  conj units %d"
                   % (n_ph, dt * 1e3, dt * 1e3 * 1000 / len(pf), *avg, float(np.mean(totals)), b.reruns(),
                      b.phrase_conj_units()), flush=True)
+            b.close()
+        sys.exit(0)
+    if args.or_phrases and args.op == "phrase":
+        from iresearch_amd.search import Or
+        hits_alone = None
+        for n_ph in (int(x) for x in args.or_phrases.split(",")):
+            # query q: its own phrase and those of the n_ph - 1 queries behind it, in one Or
+            pf = []
+            for q in range(len(ranks)):
+                phs = [by_phrase([int(r) - 1 for r in ranks[(q + j) % len(ranks)]]) for j in range(n_ph)]
+                pf.append(Or(phs) if n_ph > 1 else phs[0])
+            b = sr.batch(search.prepare(pf, scorer, [st], phrase_disjunctions=True), args.k).profile(True)
+            b.run()
+            _, _, totals = b.results()
+            totals = np.asarray(totals, np.int64).reshape(-1)
+            if n_ph == 1:
+                hits_alone = totals
+            ms = []
+            t0 = time.perf_counter()
+            for _ in range(args.steps):
+                b.run()
+                b.results()
+                ms.append(b.timings())
+            dt = (time.perf_counter() - t0) / args.steps
+            avg = np.mean(ms, axis=0)
+            shared = ""
+            if hits_alone is not None and n_ph > 1:
+                # the phrases' own hits minus the union's: a doc that p phrases match counts p - 1 times
+                # (two phrases: the docs both match)
+                alone = sum(np.roll(hits_alone, -j) for j in range(n_ph))
+                shared = "  matches beyond a doc's first phrase: %d in all, in %d queries" % (
+                    int((alone - totals).sum()), int(((alone - totals) > 0).sum()))
+            print("or-phrases=%d  step %.2f ms  = %.2f ms per 1000 queries  (plan %.2f pilot %.2f score %.2f "
+                  "select %.2f)  hits/query mean %.1f  reruns=%d  disj units %d%s"
+                  % (n_ph, dt * 1e3, dt * 1e3 * 1000 / len(pf), *avg, float(np.mean(totals)), b.reruns(),
+                     b.phrase_disj_units(), shared), flush=True)
             b.close()
         sys.exit(0)
     if args.alts and args.op == "phrase":

@@ -485,6 +485,56 @@ typedef enum irs_hip_scorer_kind {
  * IRS_HIP_EINVAL before (an unknown scorer). */
 #define IRS_HIP_CLAUSE_AND 0x1000
 
+/* The `kind` of a NODE ENTRY: IRS_HIP_TREE_NODE | node op [| IRS_HIP_EXCLUDE].  A query whose entries
+ * hold at least one node entry is a TREE QUERY — a boolean filter nested to any depth over by_term
+ * leaves: `a AND (b OR (c AND d))`, `(a AND NOT b) OR c`, `+a +(b c d)~2` (And::prepare / Or::prepare
+ * prepare every child on its own with ctx.boost x child boost, boolean_filter.cpp:55-312; an And
+ * becomes a conjunction with its Not children as an exclusion, an Or a disjunction or min-match
+ * disjunction: boolean_query.cpp:127-247, conjunction.hpp:436-490, disjunction.hpp:1411-1467,
+ * exclusion.hpp).
+ *   query.op      IRS_HIP_OP_OR, IRS_HIP_OP_AND or IRS_HIP_OP_MINMATCH: the ROOT's operator, and
+ *                 query.min_match the root's
+ *   entries       [first_term, first_term + n_terms): the root's children in prefix order; n_terms
+ *                 counts every entry, node entries included
+ *   a leaf        an ordinary scorer entry (by_term)
+ *   a negated leaf  an IRS_HIP_EXCLUDE entry (Not(by_term)); under the tree flag it may stand wherever
+ *                 a direct child of an And may, not only behind the included entries
+ *   a node entry  opens a subtree: kind = IRS_HIP_TREE_NODE | node op (one of the three op values,
+ *                 in the low byte), | IRS_HIP_EXCLUDE for Not(subtree); phrase_offset =
+ *                 span | (min_match << 16), span = the entries of the subtree that follow the node
+ *                 entry, min_match that of an IRS_HIP_OP_MINMATCH node (0 on the others); term, c0
+ *                 and the norm fields are ignored
+ * Per segment, minus its deleted docs, bottom up:
+ *   a positive leaf matches the docs of its term; an absent term (IRS_HIP_NO_TERM or no docs)
+ *   matches nothing;
+ *   an And matches d iff every positive child matches d and no negated child does;
+ *   an Or matches d iff at least max(1, min_match) of its children match d;
+ *   d is a hit iff the root matches it; total hits counts these docs;
+ *   score(d) is summed from the root down: a matching node contributes the scores of its positive
+ *   children that match d — for an Or or min-match node EVERY matching child, not only min_match of
+ *   them; negated children contribute nothing (SUM at every level).
+ * So an And with an absent member is empty in that segment, an Or drops it, a min-match with too few
+ * present children is empty, a Not of an absent term has no effect.  Boosts are the callers': a
+ * leaf's c0 carries its boost times every ancestor's; a zero boost matches with score 0.  The same
+ * term in two branches scores once per matching branch and is decoded once.
+ * IRS_HIP_EINVAL: a span of 0 or one that runs past its parent; a node op outside the three; a
+ * nonzero min_match on a node that is not IRS_HIP_OP_MINMATCH; a negated child of an Or / MINMATCH
+ * node entry; a node entry under IRS_HIP_OP_PHRASE or IRS_HIP_OP_MULTITERM; the flag together with
+ * any other flag but IRS_HIP_EXCLUDE, or any other flag on a leaf of such a query.
+ * IRS_HIP_EUNSUPPORTED: more than 16 leaves (positive and negated together) or more than 15 node
+ * entries; a `merge` other than SUM; an And (root or node) without a positive child; a negated
+ * child of a root Or / MINMATCH; min_match 0 on a MINMATCH root or node, as for every MINMATCH
+ * query; and what an entry scored from decoded streams cannot be (IRS_HIP_CLAUSE_AND above), the
+ * frequencies of a negated leaf's term included.
+ * Such a query runs on k_tree_pilot / k_tree_score (irs_hip_batch_tree_units), over the streams the
+ * batch's joined units read, with 64-bit sums and a threshold of its own.  A batch that holds one
+ * refuses irs_hip_batch_set_doc_sets / _host, irs_hip_batch_set_comm and irs_hip_batch_match_sets*
+ * (IRS_HIP_EUNSUPPORTED); set_wand, set_path, set_paired_tiles and the tile size leave these units
+ * as they are; its other (non-phrase) queries give bit for bit what they give in a batch of their
+ * own.  A query without a node entry is validated exactly as before.  A compatible addition to
+ * ABI 12: a kind with 0x8000 was IRS_HIP_EINVAL before (an unknown scorer). */
+#define IRS_HIP_TREE_NODE 0x8000
+
 /* One query term = the (term cookie, stats blob, boost) triple TermQuery::execute
  * hands to postings()/CompileScore (term_query.cpp:35-74), flattened. */
 typedef struct irs_hip_term_scorer {
@@ -942,6 +992,8 @@ int irs_hip_batch_stream_counts(irs_hip_batch* batch, uint32_t* distinct, uint32
 int irs_hip_batch_wide_units(irs_hip_batch* batch, uint32_t* units);
 /* ... and its units with IRS_HIP_CLAUSE_AND entries (k_clause_pilot / k_clause_score). */
 int irs_hip_batch_clause_units(irs_hip_batch* batch, uint32_t* units);
+/* ... and its units of tree queries (IRS_HIP_TREE_NODE entries: k_tree_pilot / k_tree_score). */
+int irs_hip_batch_tree_units(irs_hip_batch* batch, uint32_t* units);
 /* ... and its units with an IRS_HIP_PHRASE_NEXT entry (several phrases in one And; k_phrases_and). */
 int irs_hip_batch_phrase_conj_units(irs_hip_batch* batch, uint32_t* units);
 /* ... and its units with an IRS_HIP_PHRASE_OR entry (several phrases in one Or; k_phrases_or). */

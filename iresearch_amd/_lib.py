@@ -27,6 +27,7 @@ PHRASE_OPTIONAL = 0x800   # ... into a phrase entry's kind: a by_term child of t
 CLAUSE_AND = 0x1000   # ... into an Or / min-match entry's kind: one more required member of the clause before it
 PHRASE_NEXT = 0x2000   # ... into a phrase entry's kind: the first word of a further phrase of the And
 PHRASE_OR = 0x4000   # ... into a phrase entry's kind: the first word of an alternative phrase of the Or
+TREE_NODE = 0x8000   # the kind of a node entry: TREE_NODE | node op [| EXCLUDE]; phrase_offset = span | min_match << 16
 NO_TERM = 0xFFFFFFFF
 NO_DOC_SET = 0xFFFFFFFF   # row_of_unit of an unrestricted unit (irs_hip_batch_set_doc_sets)
 PATH_AUTO, PATH_ITEMS, PATH_JOINED = 0, 1, 2
@@ -103,6 +104,7 @@ SYMBOLS = (
     "irs_hip_device_trim",
     "irs_hip_device_set_stream_cache", "irs_hip_device_stream_cache_stats",
     "irs_hip_batch_stream_counts", "irs_hip_batch_wide_units", "irs_hip_batch_clause_units",
+    "irs_hip_batch_tree_units",
     "irs_hip_batch_phrase_conj_units", "irs_hip_batch_phrase_disj_units",
     "irs_hip_batch_image_counts", "irs_hip_device_image_count", "irs_hip_join_bound_rule",
     "irs_hip_batch_rescore_paths", "irs_hip_join_half_rule", "irs_hip_join_half_probe",
@@ -208,6 +210,7 @@ def bind(L: C.CDLL) -> C.CDLL:
     L.irs_hip_batch_stream_counts.restype = C.c_int
     L.irs_hip_batch_wide_units.argtypes, L.irs_hip_batch_wide_units.restype = [vp, P(u32)], C.c_int
     L.irs_hip_batch_clause_units.argtypes, L.irs_hip_batch_clause_units.restype = [vp, P(u32)], C.c_int
+    L.irs_hip_batch_tree_units.argtypes, L.irs_hip_batch_tree_units.restype = [vp, P(u32)], C.c_int
     L.irs_hip_batch_phrase_conj_units.argtypes, L.irs_hip_batch_phrase_conj_units.restype = [vp, P(u32)], C.c_int
     L.irs_hip_batch_phrase_disj_units.argtypes, L.irs_hip_batch_phrase_disj_units.restype = [vp, P(u32)], C.c_int
     L.irs_hip_batch_image_counts.argtypes = [vp, P(u32), P(u32)]

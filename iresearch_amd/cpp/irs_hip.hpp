@@ -175,8 +175,49 @@ struct by_phrase {
 // at both levels, plain Ands of by_term (no groups, no phrases), no phrase next to them, at most
 // IRS_HIP_MAX_TERMS terms in all (anything else: not_supported); no Not children, no doc set, no
 // match sets (not_supported, as the ABI refuses them).
+// A boolean filter nested to any depth over by_term leaves — `a AND (b OR (c AND d))`,
+// `(a AND NOT b) OR c`, `+a +(b c d)~2` (IRS_HIP_TREE_NODE; And::prepare / Or::prepare prepare every
+// child on its own: boolean_filter.cpp:55-312, boolean_query.cpp:127-247, exclusion.hpp).  Built with
+// And::tree / Or::tree / BoolTree::leaf / BoolTree::negated.  An And matches where every positive
+// child does and no negated one; an Or where at least max(1, min_match_count) children do; a doc's
+// score is summed from the root down over the matching positive children of matching nodes (for an
+// Or EVERY matching child).  Each leaf's boost is multiplied by every ancestor's, from the top down;
+// merge SUM at every level.  prepare() writes the filter as it stands: the root's children in prefix
+// order, every inner And / Or a node entry, Not(by_term) an IRS_HIP_EXCLUDE entry where it stands,
+// Not(Not(f)) as f; a filter of one level is the flat query it is.  not_supported: more than
+// IRS_HIP_MAX_TERMS leaves (Nots included) or 15 inner nodes, a Not child of an Or, an And of only
+// Nots, a Not at the top, min_match_count 0; illegal_argument: a node without children.  No doc set,
+// no match sets (not_supported, as the ABI refuses them).
+struct BoolTree {
+  enum class Kind { kTerm, kAnd, kOr, kNot };
+  Kind kind = Kind::kTerm;
+  by_term term;                  // kTerm
+  std::vector<BoolTree> subs;    // kAnd / kOr: the children; kNot: the one filter it negates
+  uint32_t min_match_count = 1;  // kOr
+  float boost = 1.f;             // kAnd / kOr
+  static BoolTree leaf(uint32_t term, float boost = 1.f) {
+    BoolTree t;
+    t.term = by_term{term, boost};
+    return t;
+  }
+  static BoolTree negated(BoolTree f) {
+    BoolTree t;
+    t.kind = Kind::kNot;
+    t.subs.push_back(std::move(f));
+    return t;
+  }
+};
 struct And;
 struct Or {
+  // Or::tree({...}, min_match_count, boost): an Or node of a BoolTree
+  static BoolTree tree(std::vector<BoolTree> subs, uint32_t min_match_count = 1, float boost = 1.f) {
+    BoolTree t;
+    t.kind = BoolTree::Kind::kOr;
+    t.subs = std::move(subs);
+    t.min_match_count = min_match_count;
+    t.boost = boost;
+    return t;
+  }
   std::vector<by_term> subs;
   uint32_t min_match_count = 1;  // irs::Or::min_match_count()
   irs_hip_merge merge_type = IRS_HIP_MERGE_SUM;  // boolean_filter::merge_type()
@@ -201,6 +242,14 @@ struct Or {
 // With a phrase: at least one term in `subs`, no `groups`, merge SUM, at most
 // IRS_HIP_MAX_PHRASE_TERMS words and terms in all (anything else: not_supported).
 struct And {
+  // And::tree({...}, boost): an And node of a BoolTree
+  static BoolTree tree(std::vector<BoolTree> subs, float boost = 1.f) {
+    BoolTree t;
+    t.kind = BoolTree::Kind::kAnd;
+    t.subs = std::move(subs);
+    t.boost = boost;
+    return t;
+  }
   std::vector<by_term> subs;
   irs_hip_merge merge_type = IRS_HIP_MERGE_SUM;
   std::vector<Or> groups;
@@ -245,7 +294,7 @@ struct Exclusion {
   std::vector<by_term> excl;   // at most IRS_HIP_MAX_EXCLUDED
   std::optional<by_doc_set> doc_set;   // the And's by_doc_set child (next to its Nots, or alone)
 };
-using filter = std::variant<by_term, Or, And, by_phrase, Exclusion, by_scored_terms>;
+using filter = std::variant<by_term, Or, And, by_phrase, Exclusion, by_scored_terms, BoolTree>;
 
 // What by_term::prepare reads from one segment without touching postings.
 struct SegmentStats {
@@ -586,9 +635,84 @@ std::vector<PreparedQuery> prepare(const std::vector<filter>& filters, const Sco
     }
     if (q.terms.empty()) throw illegal_argument(IRS_HIP_EINVAL, "empty filter");
   };
+  // A BoolTree: the root's children in prefix order (struct BoolTree above)
+  auto tree = [&](PreparedQuery& q, const BoolTree& root) {
+    using K = BoolTree::Kind;
+    auto unwrap = [](const BoolTree* f, bool* neg) {
+      *neg = false;
+      while (f->kind == K::kNot) {
+        if (f->subs.size() != 1) throw illegal_argument(IRS_HIP_EINVAL, "Not: one filter");
+        f = &f->subs[0];
+        *neg = !*neg;
+      }
+      return f;
+    };
+    uint32_t n_leaves = 0, n_nodes = 0;
+    std::function<void(const BoolTree&, float, std::vector<irs_hip_term_scorer>&)> children =
+        [&](const BoolTree& node, float mult, std::vector<irs_hip_term_scorer>& out) {
+          if (node.subs.empty()) throw illegal_argument(IRS_HIP_EINVAL, "a boolean node without children");
+          if (node.kind == K::kOr && node.min_match_count == 0)
+            throw not_supported(IRS_HIP_EUNSUPPORTED, "Or: min_match_count 0 matches all docs");
+          mult *= node.boost;
+          uint32_t n_pos = 0;
+          for (const BoolTree& s : node.subs) {
+            bool neg = false;
+            const BoolTree* f = unwrap(&s, &neg);
+            if (neg && node.kind != K::kAnd)
+              throw not_supported(IRS_HIP_EUNSUPPORTED, "Or: a Not child matches all docs but some");
+            n_pos += neg ? 0u : 1u;
+            irs_hip_term_scorer e{};
+            if (f->kind == K::kTerm) {
+              ++n_leaves;
+              if (neg) {
+                e.term = f->term.term;
+                e.kind = IRS_HIP_EXCLUDE;
+              } else {
+                e = one(by_term{f->term.term, mult * f->term.boost});
+              }
+              out.push_back(e);
+              continue;
+            }
+            ++n_nodes;
+            std::vector<irs_hip_term_scorer> inner;
+            children(*f, neg ? 1.f : mult, inner);
+            const bool mm = f->kind == K::kOr && f->min_match_count > 1;
+            e.term = IRS_HIP_NO_TERM;
+            e.kind = IRS_HIP_TREE_NODE | (f->kind == K::kAnd ? IRS_HIP_OP_AND : mm ? IRS_HIP_OP_MINMATCH : IRS_HIP_OP_OR) |
+                     (neg ? IRS_HIP_EXCLUDE : 0);
+            e.phrase_offset = uint32_t(inner.size()) | ((mm ? std::min<uint32_t>(f->min_match_count, 0xFFFFu) : 0u) << 16);
+            out.push_back(e);
+            out.insert(out.end(), inner.begin(), inner.end());
+          }
+          if (node.kind == K::kAnd && n_pos == 0)
+            throw not_supported(IRS_HIP_EUNSUPPORTED, "And: only Not children match all docs but some");
+        };
+    bool neg = false;
+    const BoolTree* top = unwrap(&root, &neg);
+    if (neg) throw not_supported(IRS_HIP_EUNSUPPORTED, "a filter of only Not matches all docs but some");
+    if (top->kind == K::kTerm) {
+      q.op = IRS_HIP_OP_OR;
+      q.terms.push_back(one(top->term));
+      return;
+    }
+    children(*top, 1.f, q.terms);
+    if (n_leaves > IRS_HIP_MAX_TERMS)
+      throw not_supported(IRS_HIP_EUNSUPPORTED, "a nested boolean filter: more than IRS_HIP_MAX_TERMS leaves");
+    if (n_nodes > IRS_HIP_MAX_TERMS - 1u)
+      throw not_supported(IRS_HIP_EUNSUPPORTED, "a nested boolean filter: more than 15 inner nodes");
+    const bool mm = top->kind == K::kOr && top->min_match_count > 1;
+    q.op = top->kind == K::kAnd ? IRS_HIP_OP_AND : mm ? IRS_HIP_OP_MINMATCH : IRS_HIP_OP_OR;
+    q.min_match = mm ? top->min_match_count : 0;
+    q.merge = IRS_HIP_MERGE_SUM;
+    if (n_nodes == 0)   // one level: the flat query it is, its excluded entries behind the included ones
+      std::stable_partition(q.terms.begin(), q.terms.end(),
+                            [](const irs_hip_term_scorer& e) { return e.kind != IRS_HIP_EXCLUDE; });
+  };
   for (const filter& f : filters) {
     PreparedQuery q;
-    if (const auto* m = std::get_if<by_scored_terms>(&f)) {
+    if (const auto* t = std::get_if<BoolTree>(&f)) {
+      tree(q, *t);
+    } else if (const auto* m = std::get_if<by_scored_terms>(&f)) {
       // statistics per term exactly as for an Or of by_terms
       if (m->terms.empty()) throw illegal_argument(IRS_HIP_EINVAL, "by_scored_terms: no terms");
       if (m->terms.size() > IRS_HIP_MAX_WIDE_TERMS)
@@ -1038,6 +1162,15 @@ class QueryBatch {
     for (const auto& part : part_) {
       uint32_t n = 0;
       if (part.h) check(irs_hip_batch_phrase_disj_units(part.h, &n), "irs_hip_batch_phrase_disj_units");
+      total += n;
+    }
+    return total;
+  }
+  uint32_t tree_units() const {   // ... of nested boolean filters (irs_hip_batch_tree_units)
+    uint32_t total = 0;
+    for (const Part& part : part_) {
+      uint32_t n = 0;
+      if (part.h) check(irs_hip_batch_tree_units(part.h, &n), "irs_hip_batch_tree_units");
       total += n;
     }
     return total;

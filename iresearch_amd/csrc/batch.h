@@ -5,7 +5,7 @@
 // the end, the waits of a batch: one function per thing a caller is about to touch (a run, a plan
 // stage, match sets, a setter's re-deal, a reader of the last run, destroy).  The run itself: run.h.
 // The unit lists and who fills them (units.h: commit_unit is create's only writer per unit):
-//   all_tile_units, all_conj_units, wide.units, clause.units   commit_unit, fixed at create
+//   all_tile_units, all_conj_units, wide.units, clause.units, tree.units   commit_unit, fixed at create
 //   blocks.units   a phrase batch: build_phrase_work at create; else deal_units, from all_conj_units
 //   any.units      build_any_work at create, from the grouped units commit_unit listed
 //   tiles.units, join.units   deal_units (ensure_scratch), from all_tile_units / all_conj_units
@@ -152,6 +152,19 @@ struct ClauseWork {
   std::vector<uint32_t> units;
   bool on() const { return !units.empty(); }
   DevBuf d_units;
+  uint32_t n_max = 0;   // doc tiles of the unit with the most
+  uint32_t n_min = 0;   // ... with the fewest, empty units aside (pilot stride)
+};
+
+// Tree queries (IRS_HIP_TREE_NODE; tree.h, plan_tree.h): the units, fixed at create, kept apart from
+// the rest of the batch exactly as the clause units are — their leaves are streams of JoinWork behind
+// the joined, the wide and the clause units', their per-row records lie in join.d_jterms, a row's
+// DevQTerm::pad0 names its leaf; `nodes`: kTreeMaxNodes records per unit, in the order of `units`.
+struct TreeWork {
+  std::vector<uint32_t> units;
+  std::vector<TreeNode> nodes;
+  bool on() const { return !units.empty(); }
+  DevBuf d_units, d_nodes;
   uint32_t n_max = 0;   // doc tiles of the unit with the most
   uint32_t n_min = 0;   // ... with the fewest, empty units aside (pilot stride)
 };
@@ -363,6 +376,7 @@ struct irs_hip_batch {
   JoinWork join;
   WideWork wide;
   ClauseWork clause;
+  TreeWork tree;
   BlockWork blocks;
   AnyWork any;
   // A batch with optional terms (IRS_HIP_PHRASE_OPTIONAL): this batch is the PHRASE PASS; `opt` — a

@@ -36,6 +36,7 @@
 #include "wide.h"
 #include "clauses.h"
 #include "clause_shape.h"
+#include "tree.h"
 #include "excl.h"
 #include "match.h"
 
@@ -50,6 +51,7 @@ using namespace irs_hip;
 #include "plan_any.h"
 #include "plan_wide.h"
 #include "plan_clauses.h"
+#include "plan_tree.h"
 #include "plan_join.h"
 #include "plan_match.h"
 #include "units.h"
@@ -131,6 +133,8 @@ bool size_units(irs_hip_batch* b, uint64_t* first_words, uint64_t* item_bound) {
   b->wide.n_min = 0xFFFFFFFFu;
   b->clause.n_max = 0;
   b->clause.n_min = 0xFFFFFFFFu;
+  b->tree.n_max = 0;
+  b->tree.n_min = 0xFFFFFFFFu;
   std::vector<uint8_t> is_join(b->nq, 0);
   for (uint32_t u : b->join.units) is_join[u] = 1;
   for (uint32_t u = 0; u < b->nq; ++u) {
@@ -141,6 +145,10 @@ bool size_units(irs_hip_batch* b, uint64_t* first_words, uint64_t* item_bound) {
     }
     if (unit_is_clause(dq)) {   // (likewise)
       size_clause_unit(b, dq);
+      continue;
+    }
+    if (unit_is_tree(dq)) {   // (likewise)
+      size_tree_unit(b, dq);
       continue;
     }
     // (conjunctions are block driven unless they run as joined streams)
@@ -234,7 +242,7 @@ bool alloc_scratch(irs_hip_batch* b, uint64_t first_words, uint64_t item_bound) 
       !b->d_out_count.alloc(b->nq * sizeof(uint32_t)) || !b->tiles.d_work.alloc(16))
     return false;
   if (streams_on(b) && !build_streams(b)) return false;
-  if (!alloc_wide(b) || !alloc_clauses(b) || !build_groups(b)) return false;
+  if (!alloc_wide(b) || !alloc_clauses(b) || !alloc_tree(b) || !build_groups(b)) return false;
   if (!b->tiles.units.empty()) {
     if (!b->tiles.d_units.alloc(b->tiles.units.size() * 4) ||
         !b->up.copy(b->tiles.d_units.p, b->tiles.units.data(), b->tiles.units.size() * 4))
@@ -594,7 +602,7 @@ static int batch_create_multi_impl(irs_hip_segment* const* segs, uint32_t n_segs
     const irs_hip_term_scorer* terms = all_terms + size_t(q / nq_user) * n_entries;
     const irs_hip_query& in = queries[q % nq_user];
     Unit u;
-    int rc = unit_shape(in, terms, n_entries, seg, u.shape, scratch.excl);
+    int rc = unit_shape(in, terms, n_entries, seg, u.shape, scratch.excl, scratch.tab);
     if (rc != IRS_HIP_OK) return rc;
     const irs_hip_term_scorer* ents = terms + in.first_term;
     rc = phrase_only_rule(b, q, u.shape);
@@ -605,7 +613,7 @@ static int batch_create_multi_impl(irs_hip_segment* const* segs, uint32_t n_segs
     if (rc != IRS_HIP_OK) return rc;
     unit_run(in, seg, u, scratch);
     u.n_caches = assign_table_slots(scratch.row);
-    if (u.shape.wide() || u.shape.clause) rc = wide_terms_ok(seg, scratch.row);
+    if (u.shape.wide() || u.shape.clause || u.shape.tree) rc = wide_terms_ok(seg, scratch.row);
     if (rc == IRS_HIP_OK) rc = unit_scale(u, !scratch.row.empty());
     if (rc != IRS_HIP_OK) return rc;
     commit_unit(b, q, in, seg, u, scratch, grouped_units);
@@ -674,7 +682,7 @@ static int batch_set_shared_threshold_impl(irs_hip_batch* b, int enable) {
 static int batch_set_comm_impl(irs_hip_batch* b, irs_hip_comm* comm) {
   if (!b) return IRS_HIP_EINVAL;
   if (b->opt) return IRS_HIP_EUNSUPPORTED;   // (optional terms: two passes, one rank)
-  if (b->wide.on() || b->clause.on()) return IRS_HIP_EUNSUPPORTED;   // (wide units and Ors of clauses keep thresholds of their own)
+  if (b->wide.on() || b->clause.on() || b->tree.on()) return IRS_HIP_EUNSUPPORTED;   // (wide units, Ors of clauses and tree queries keep thresholds of their own)
   if (!quiet_for_setter(b)) return IRS_HIP_EHIP;
   if (comm && !b->groups.d_agree.p && !b->groups.d_agree.alloc(64)) return IRS_HIP_ENOMEM;
   b->comm = comm;
@@ -744,8 +752,8 @@ static int batch_set_doc_sets_impl(irs_hip_batch* b, const void* sets, bool host
   if (!b) return IRS_HIP_EINVAL;
   // (optional terms: the term pass's doc sets are the phrase pass's output)
   if (b->opt) return IRS_HIP_EUNSUPPORTED;
-  // (wide units and Ors of clauses read the streams every unit shares: a mask of their own cannot ride there)
-  if (b->wide.on() || b->clause.on()) return IRS_HIP_EUNSUPPORTED;
+  // (wide units, Ors of clauses and tree queries read the streams every unit shares: a mask of their own cannot ride there)
+  if (b->wide.on() || b->clause.on() || b->tree.on()) return IRS_HIP_EUNSUPPORTED;
   if (!rt::set_device(b->seg->device)) return IRS_HIP_EHIP;
   std::vector<uint32_t> rows;
   if (row_of_unit && n_rows) {
@@ -1404,6 +1412,13 @@ int irs_hip_batch_phrase_disj_units(irs_hip_batch* b, uint32_t* units) {
     return IRS_HIP_OK;
   });
 }
+int irs_hip_batch_tree_units(irs_hip_batch* b, uint32_t* units) {
+  return settled(b, [&]() -> int {
+    if (!b || !units) return IRS_HIP_EINVAL;
+    *units = uint32_t(b->tree.units.size());
+    return IRS_HIP_OK;
+  });
+}
 int irs_hip_batch_image_counts(irs_hip_batch* b, uint32_t* distinct, uint32_t* built) {
   return settled(b, [&]() -> int {
     if (!b || !b->ran) return IRS_HIP_EINVAL;
@@ -1523,15 +1538,15 @@ int irs_hip_batch_doc_set_stats(irs_hip_batch* b, uint64_t* tiles, uint64_t* til
 }
 int irs_hip_batch_match_sets(irs_hip_batch* b, uint64_t* sets, uint64_t n_words, uint64_t* counts) {
   return settled(b, [&] {
-    // (plan_match.h: 16 rows per unit, and no clauses)
-    if (b && (b->wide.on() || b->clause.on())) return int(IRS_HIP_EUNSUPPORTED);
+    // (plan_match.h: 16 rows per unit, no clauses and no trees)
+    if (b && (b->wide.on() || b->clause.on() || b->tree.on())) return int(IRS_HIP_EUNSUPPORTED);
     return batch_match_sets_impl(b, sets, nullptr, n_words, counts, nullptr, nullptr, false);
   });
 }
 int irs_hip_batch_match_sets_to_device(irs_hip_batch* b, void* d_sets, uint64_t n_words, void* d_counts,
                                        void* stream) {
   return settled(b, [&] {
-    if (b && (b->wide.on() || b->clause.on())) return int(IRS_HIP_EUNSUPPORTED);
+    if (b && (b->wide.on() || b->clause.on() || b->tree.on())) return int(IRS_HIP_EUNSUPPORTED);
     return batch_match_sets_impl(b, nullptr, d_sets, n_words, nullptr, d_counts,
                                  static_cast<rt::stream_t>(stream), true);
   });

@@ -135,9 +135,9 @@ void abandon_fills(irs_hip_batch* b) {
 
 bool join_half_ok(const irs_hip_batch* b);
 
-// Does the batch read decoded streams at all: units on joined streams, wide multi-term units or
-// Ors of clauses (wide.h, clauses.h: their terms are streams of the same set)
-bool streams_on(const irs_hip_batch* b) { return b->join.on() || b->wide.on() || b->clause.on(); }
+// Does the batch read decoded streams at all: units on joined streams, wide multi-term units, Ors
+// of clauses or tree queries (wide.h, clauses.h, tree.h: their terms are streams of the same set)
+bool streams_on(const irs_hip_batch* b) { return b->join.on() || b->wide.on() || b->clause.on() || b->tree.on(); }
 
 // The batch's distinct (segment, term) streams, k_join's work list and the per-(unit, term)
 // records of k_join_score.  Static per batch: built once.  Every stream is looked up in the
@@ -163,6 +163,7 @@ bool build_streams(irs_hip_batch* b) {
   std::vector<uint32_t> readers(b->join.units);
   readers.insert(readers.end(), b->wide.units.begin(), b->wide.units.end());
   readers.insert(readers.end(), b->clause.units.begin(), b->clause.units.end());
+  readers.insert(readers.end(), b->tree.units.begin(), b->tree.units.end());
   {
     size_t slots = 64;
     size_t n_keys = 0;
@@ -673,7 +674,7 @@ bool build_streams(irs_hip_batch* b) {
     w.pad2 = 0;
   }
   lap("  streams: per-term records");
-  for (uint32_t u : readers) {   // (a wide or clause unit's cs carries its own 64-bit scale: DevQuery::fx_mul)
+  for (uint32_t u : readers) {   // (a wide, clause or tree unit's cs carries its own 64-bit scale: DevQuery::fx_mul)
     DevQuery& dq = b->queries[u];
     const uint32_t rows = table_rows(dq.n_caches);
     for (uint32_t j = 0; j < dq.n_terms; ++j) {
@@ -689,7 +690,7 @@ bool build_streams(irs_hip_batch* b) {
       const bool general = qt.pad1 >= rows;
       jt.mode = (qt.cache_id * rows * 1024u) |
                 (general ? kJoinGeneral | (sqrt_kind(qt.kind) ? kJoinSqrt : 0u) : 0u);
-      if (qt.kind == kBM1) jt.mode = kWideConst;   // (wide and clause units only: joined units are of the table family)
+      if (qt.kind == kBM1) jt.mode = kWideConst;   // (wide, clause and tree units only: joined units are of the table family)
     }
   }
   // (the slack behind the last stream is only ever read by masked-off look-ahead: zero it once)
@@ -895,7 +896,7 @@ uint32_t* rescore_paths(irs_hip_batch* b) { return b->d_zeroed.as<uint32_t>() + 
 bool tail_ok(const irs_hip_batch* b) {
   if (!b->knobs.tail_stream || b->term_pass || b->phrase || b->opt || b->groups.n || b->comm) return false;
   if (!b->join.on() || b->join.n_plain != b->join.units.size()) return false;
-  if (!b->tiles.units.empty() || b->wide.on() || b->clause.on() || !b->blocks.units.empty() || !b->any.units.empty()) return false;
+  if (!b->tiles.units.empty() || b->wide.on() || b->clause.on() || b->tree.on() || !b->blocks.units.empty() || !b->any.units.empty()) return false;
   return join_half_ok(b) && b->join.img_on;
 }
 

@@ -120,6 +120,7 @@ static bool run_pilot(irs_hip_batch* b, rt::stream_t st) {
   if (b->join.on()) ok = ok && launch_join_pilot(b, st);
   if (b->wide.on()) ok = ok && launch_wide_pilot(b, st);
   if (b->clause.on()) ok = ok && launch_clause_pilot(b, st);
+  if (b->tree.on()) ok = ok && launch_tree_pilot(b, st);
   ok = ok && launch_group_threshold(b, st);
   if (tile_units_on(b))
     ok = ok && with_tile_kernel(b, [&](auto k) { return launch_pilot(b, st, k); });
@@ -153,6 +154,7 @@ static bool run_score(irs_hip_batch* b, rt::stream_t st, std::unique_lock<std::m
   if (b->join.on()) ok = ok && launch_join_score(b, st, end->tail ? &end->ts : nullptr);
   if (b->wide.on()) ok = ok && launch_wide_score(b, st);
   if (b->clause.on()) ok = ok && launch_clause_score(b, st);
+  if (b->tree.on()) ok = ok && launch_tree_score(b, st);
   if (!b->phrase) ok = ok && (simd ? launch_conj<kSimd4>(b, st) : launch_conj<kScalar>(b, st));
   if (!b->phrase) ok = ok && (simd ? launch_any<kSimd4>(b, st) : launch_any<kScalar>(b, st));
   return ok && run_mark(b, 2 * IRS_HIP_K_SCORE + 1, end->ts);

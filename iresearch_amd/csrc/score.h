@@ -211,12 +211,13 @@ __device__ __forceinline__ float from_fixed(ACC a, float fx_inv) {
 //               per-doc match counters (min-match); kRunConj — a conjunction, block by block of its
 //               rarest term (conj.h; a grouped one: conj_any.h) or on joined streams with match
 //               counts; kRunWide — a scored multi-term unit (wide.h); kRunClause — an Or of clauses
-//               (clauses.h; bits 8..15 count clauses)
+//               (clauses.h; bits 8..15 count clauses); kRunTree — a tree query (tree.h; bits 8..15:
+//               the records of its node table)
 //   bits 8..15  the matches a doc needs (0xFF: nothing of the segment can match)
 //   bits 16..17 the boolean filter's ScoreMergeType (scorer.hpp:224-236: 0 sum, 1 max, 2 min)
 //   bit 18      a kMin disjunction of two sub-iterators — a doc only one of them holds scores 0
 //               (disjunction.hpp:338-351)
-enum : uint32_t { kRunTiles = 0, kRunCount = 1, kRunConj = 2, kRunWide = 3, kRunClause = 4 };
+enum : uint32_t { kRunTiles = 0, kRunCount = 1, kRunConj = 2, kRunWide = 3, kRunClause = 4, kRunTree = 5 };
 enum : uint32_t { kScoreSum = 0, kScoreMax = 1, kScoreMin = 2 };
 __host__ __device__ __forceinline__ uint32_t query_run(int32_t op) { return uint32_t(op) & 0xFFu; }
 __host__ __device__ __forceinline__ uint32_t query_merge(int32_t op) { return (uint32_t(op) >> 16) & 3u; }

@@ -34,6 +34,9 @@ struct UnitShape {
   bool variadic = false;   // a phrase with IRS_HIP_PHRASE_ALT members
   bool grouped = false;    // an And with IRS_HIP_GROUP_ALT members
   bool clause = false;     // an Or / min-match Or with IRS_HIP_CLAUSE_AND members (clauses.h)
+  // a tree query (IRS_HIP_TREE_NODE entries, tree.h): n_incl counts its LEAVES, positive and negated
+  // (entry leaf_at[l] of UnitScratch::tab is leaf l), n_excl is 0 — the negated leaves are rows, no mask
+  bool tree = false;
   Behind behind = Behind::kNone;
   // an And of several phrases (IRS_HIP_PHRASE_NEXT, phrases.h): bit j of `opens` = entry j opens a
   // phrase (bit 0 always); a unit with rows has a row per entry, so these are its rows too
@@ -109,6 +112,7 @@ struct UnitScratch {
   std::vector<double> smins;          // per present term: the smallest score of one posting
   std::vector<uint32_t> excl;         // the unit's present excluded terms
   std::vector<uint32_t> row_group;    // per row of a grouped And: its group; of an Or of clauses: its clause
+  TreeTable tab;                      // a tree query's compiled node table and leaves (tree_shape.h)
 };
 
 // A scored multi-term query (IRS_HIP_OP_MULTITERM, wide.h): up to IRS_HIP_MAX_WIDE_TERMS entries
@@ -226,15 +230,33 @@ int phrase_alternatives(const irs_hip_term_scorer* ents, UnitShape& sh) {
   return IRS_HIP_OK;
 }
 
+// A tree query (some entry carries IRS_HIP_TREE_NODE): tree_compile states what create takes
+int tree_unit_shape(const irs_hip_query& in, const irs_hip_term_scorer* ents, UnitShape& sh,
+                    std::vector<uint32_t>& excl, TreeTable& tab) {
+  excl.clear();
+  sh = UnitShape{};
+  sh.tree = true;
+  if (in.k == 0 || in.k > IRS_HIP_MAX_K || in.merge > IRS_HIP_MERGE_MIN) return IRS_HIP_EINVAL;
+  if (const int rc = tree_compile(in, ents, tab)) return rc;
+  sh.op = OpClass(in.op);
+  sh.n_incl = sh.n_words = tab.n_leaves;
+  return IRS_HIP_OK;
+}
+
 // Shape of query `in` in one segment.  Reads the query, the segment's entries `terms` and its term
-// table; fills `sh` and `excl` (the present excluded terms); writes nothing of the batch.
+// table; fills `sh` and `excl` (the present excluded terms; a tree query: `tab`); writes nothing of
+// the batch.
 int unit_shape(const irs_hip_query& in, const irs_hip_term_scorer* terms, uint32_t n_entries,
-               const irs_hip_segment* seg, UnitShape& sh, std::vector<uint32_t>& excl) {
+               const irs_hip_segment* seg, UnitShape& sh, std::vector<uint32_t>& excl, TreeTable& tab) {
   if (uint64_t(in.first_term) + in.n_terms > n_entries) return IRS_HIP_EINVAL;
   const irs_hip_term_scorer* ents = terms + in.first_term;
   sh = UnitShape{};
   int32_t kinds = 0;   // every included entry's kind OR-ed together: the flags some entry carries
   while (sh.n_incl < in.n_terms && ents[sh.n_incl].kind != IRS_HIP_EXCLUDE) kinds |= ents[sh.n_incl++].kind;
+  // a node entry, among the included entries or behind the first IRS_HIP_EXCLUDE one: a tree query
+  int32_t behind = 0;
+  for (uint32_t j = sh.n_incl; j < in.n_terms; ++j) behind |= ents[j].kind;
+  if ((kinds | behind) & IRS_HIP_TREE_NODE) return tree_unit_shape(in, ents, sh, excl, tab);
   sh.n_excl = in.n_terms - sh.n_incl;
   auto flagged = [&](int32_t flag) {
     bool any = false;
@@ -365,8 +387,20 @@ int unit_rows(const irs_hip_term_scorer* ents, const irs_hip_segment* seg, Unit&
       lo = end;
     }
   }
+  // a tree query: its leaves, wherever they stand; a negated leaf is a row without a scorer of its
+  // own — it carries the scorer values of the tree's first positive leaf (one signature, one stream
+  // per term: plan_join.h build_streams) and a boost of 0
+  uint32_t tree_ref = 0;
+  while (sh.tree && tree_ref + 1u < sh.n_incl && ((s.tab.negated >> tree_ref) & 1u)) ++tree_ref;
   for (uint32_t j = 0; j < sh.n_incl; ++j) {
-    const irs_hip_term_scorer& ts = ents[j];
+    const bool negated = sh.tree && ((s.tab.negated >> j) & 1u);
+    irs_hip_term_scorer leaf{};
+    if (negated) {
+      leaf = ents[s.tab.leaf_at[tree_ref]];
+      leaf.term = ents[s.tab.leaf_at[j]].term;
+      leaf.c0 = 0.f;
+    }
+    const irs_hip_term_scorer& ts = negated ? leaf : sh.tree ? ents[s.tab.leaf_at[j]] : ents[j];
     const bool behind = sh.phrase() && j >= sh.n_words;   // (a required or an optional term)
     const bool optional = behind && sh.behind == Behind::kOptional;   // (no part of the phrase: absent, it is dropped)
     const int32_t kind = sh.phrase() ? (ts.kind & ~(IRS_HIP_PHRASE_ALT | IRS_HIP_PHRASE_REQUIRED | IRS_HIP_PHRASE_OPTIONAL |
@@ -383,6 +417,7 @@ int unit_rows(const irs_hip_term_scorer* ents, const irs_hip_segment* seg, Unit&
     qt.norm_length = ts.norm_length;
     qt.cache_id = kMaxCaches;
     qt.pad0 = (sh.phrase() && !behind) ? ts.phrase_offset : 0u;
+    if (sh.tree) qt.pad0 = j | (negated ? kTreeNegated : 0u);   // (the leaf's bit: an absent leaf keeps it and never sets it)
     if (ts.term != IRS_HIP_NO_TERM && ts.term >= seg->dev.num_terms) return IRS_HIP_EINVAL;
     // (a zero boost is legal: every posting then scores 0 — the fixed-point accumulators
     // still mark the doc as matched, and sums below kMaxTerms units come back as 0)
@@ -396,7 +431,7 @@ int unit_rows(const irs_hip_term_scorer* ents, const irs_hip_segment* seg, Unit&
     if (qt.term == IRS_HIP_NO_TERM || seg->terms[qt.term].docs_count == 0) {
       // (a phrase / grouped conjunction: an absent member is dropped; a part / group without
       // a present one empties the unit, unit_need)
-      if (!sh.phrase() && !sh.grouped && !sh.clause) u.absent = true;
+      if (!sh.phrase() && !sh.grouped && !sh.clause && !sh.tree) u.absent = true;
       continue;
     }
     if (sh.clause) {
@@ -415,7 +450,7 @@ int unit_rows(const irs_hip_term_scorer* ents, const irs_hip_segment* seg, Unit&
     const DevTerm& t = seg->terms[qt.term];
     qt.pad1 = t.tf_bound;
     s.smins.push_back(posting_smin(qt));
-    u.min_score = std::min(u.min_score, s.smins.back());
+    if (!negated) u.min_score = std::min(u.min_score, s.smins.back());
     const bool tfidf = qt.kind == kTfidf || qt.kind == kTfidfTiny || qt.kind == kTfidfWide || qt.kind == kTfidfLegacy;
     // (a phrase's frequency is at most the sum of the tf_bound of its first part's members; the
     // sum over every row of sqrt(tf_bound) bounds the square root of that, sqrt being subadditive)
@@ -461,6 +496,9 @@ int unit_need(const irs_hip_query& in, Unit& u, UnitScratch& s) {
   const UnitShape& sh = u.shape;
   const uint32_t n_rows = uint32_t(s.row.size());
   u.need = 1;
+  // a tree query: what a doc needs is its node table's to say (an And with an absent member, a
+  // min-match with too few present children: no doc's mask satisfies them)
+  if (sh.tree) return IRS_HIP_OK;
   // an Or of clauses: min_match counts the clauses (MinMatchQuery::execute over the children)
   const uint32_t n_live = sh.clause ? uint32_t(__builtin_popcount(u.groups_found)) : n_rows;
   const uint32_t n_subs = sh.clause ? u.n_groups : sh.n_incl;
@@ -546,6 +584,11 @@ void unit_run(const irs_hip_query& in, const irs_hip_segment* seg, Unit& u, Unit
     uint32_t masks[IRS_HIP_MAX_TERMS] = {};
     clause_masks(s.row_group.data(), row.size(), masks);
     for (size_t r = 0; r < row.size(); ++r) row[r].pad0 = masks[r];
+  } else if (sh.tree) {
+    // lane j = row j of k_tree_pilot / k_tree_score; every row carries its leaf's bit
+    // (DevQTerm::pad0, unit_rows), `need` counts the records of the unit's node table
+    run = kRunTree;
+    op_need = s.tab.n_nodes;
   } else if (sh.grouped) {   // always block driven (conj_any.h), whatever the number of rows
     if (!row.empty()) u.group_opens = sort_groups(seg, u.n_groups, s);
     run = kRunConj;
@@ -570,7 +613,7 @@ void unit_run(const irs_hip_query& in, const irs_hip_segment* seg, Unit& u, Unit
   // disjunction.hpp:338-351) resp. with the zeroed score buffer (block_disjunction
   // :1308-1351): two sub-iterators -> min where both match, else 0; more (or the
   // min-match block disjunction) -> 0 for every doc.
-  uint32_t merge = row.size() > 1 && !sh.clause ? in.merge : uint32_t(IRS_HIP_MERGE_SUM);
+  uint32_t merge = row.size() > 1 && !sh.clause && !sh.tree ? in.merge : uint32_t(IRS_HIP_MERGE_SUM);
   bool min_both = false;
   if (merge == IRS_HIP_MERGE_MIN && run != kRunConj) {
     if (run == kRunTiles && row.size() == 2) {
@@ -587,7 +630,7 @@ void unit_run(const irs_hip_query& in, const irs_hip_segment* seg, Unit& u, Unit
   // match counts in the low bits of a 32-bit accumulator (join.h COUNT) round every posting
   // to 16 fixed-point units (+-8): relative to any doc's score that is at most
   // 8 * upper / (2^29 * min_score) — allowed while it stays below 2e-6
-  u.count_precise = !sh.wide() && !sh.clause && row.size() <= kJoinCountTerms && u.min_score > 0.0 && u.upper > 0.0 &&
+  u.count_precise = !sh.wide() && !sh.clause && !sh.tree && row.size() <= kJoinCountTerms && u.min_score > 0.0 && u.upper > 0.0 &&
                     u.upper / u.min_score <= 125.0;
 }
 
@@ -624,14 +667,14 @@ int unit_scale(Unit& u, bool has_rows) {
   if (!(u.upper > 0.0 && std::isfinite(u.upper))) return IRS_HIP_EUNSUPPORTED;
   u.bin_scale = float(double(kBins) / u.upper);
   // (irs_hip_batch_set_comm) the bound every segment of the index computes alike
-  if (u.same_bound && !sh.phrase() && !sh.wide() && !sh.clause && u.upper_all > 0.0 &&
+  if (u.same_bound && !sh.phrase() && !sh.wide() && !sh.clause && !sh.tree && u.upper_all > 0.0 &&
       u.upper_all * (1.0 + 1e-6) >= u.upper && std::isfinite(u.upper_all))
     u.shared_upper = u.upper_all * (1.0 + 1e-6);
   (void)std::frexp(u.upper, &u.exp);
   if (u.exp < -60 || u.exp > 60) return IRS_HIP_EUNSUPPORTED;
   // (grouped units score in floats, block driven: the flat units' accumulators are theirs)
-  // (wide units and Ors of clauses carry 64-bit sums of their own and never ask)
-  u.acc64 = !sh.grouped && !sh.wide() && !sh.clause && (!(u.min_score > 0.0) || u.upper / u.min_score > 1000.0);
+  // (wide units, Ors of clauses and tree queries carry 64-bit sums of their own and never ask)
+  u.acc64 = !sh.grouped && !sh.wide() && !sh.clause && !sh.tree && (!(u.min_score > 0.0) || u.upper / u.min_score > 1000.0);
   return IRS_HIP_OK;
 }
 
@@ -683,6 +726,9 @@ void commit_unit(irs_hip_batch* b, uint32_t q, const irs_hip_query& in, const ir
     b->wide.units.push_back(q);
   } else if (sh.clause) {
     b->clause.units.push_back(q);
+  } else if (sh.tree) {
+    b->tree.units.push_back(q);
+    b->tree.nodes.insert(b->tree.nodes.end(), s.tab.node, s.tab.node + kTreeMaxNodes);
   } else if (sh.grouped) {
     if (has_rows) {
       b->any.opens[q] = u.group_opens;
@@ -697,16 +743,17 @@ void commit_unit(irs_hip_batch* b, uint32_t q, const irs_hip_query& in, const ir
   if (u.acc64) b->acc32 = false;
   b->postings += u.postings;
   b->qterms.insert(b->qterms.end(), s.row.begin(), s.row.end());
-  if (!sh.wide() && !sh.clause) b->jt = std::max(b->jt, dq.n_terms);   // (the plan table's term slots)
+  if (!sh.wide() && !sh.clause && !sh.tree) b->jt = std::max(b->jt, dq.n_terms);   // (the plan table's term slots)
   b->k_max = std::max(b->k_max, in.k);
 }
 
 // Where every flat unit allows 32-bit accumulators (b->acc32, final behind the loop): 2^(30-exp)
-// units instead of commit_unit's 2^(29-exp) high words.  Wide units and Ors of clauses keep their 64-bit sums.
+// units instead of commit_unit's 2^(29-exp) high words.  Wide units, Ors of clauses and tree
+// queries keep their 64-bit sums.
 void widen_fixed_point(irs_hip_batch* b) {
   if (!b->acc32) return;
   for (DevQuery& dq : b->queries) {
-    if (unit_is_wide(dq) || unit_is_clause(dq)) continue;
+    if (unit_is_wide(dq) || unit_is_clause(dq) || unit_is_tree(dq)) continue;
     dq.fx_mul = std::ldexp(dq.fx_mul, 1);
     dq.fx_inv = std::ldexp(dq.fx_inv, 31);
   }

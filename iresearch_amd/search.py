@@ -26,7 +26,7 @@ from dataclasses import dataclass, field, replace
 import numpy as np
 
 from . import _lib
-from ._lib import (EXCLUDE, HIT, NO_TERM, OP_AND, OP_MINMATCH, OP_MULTITERM, OP_OR, OP_PHRASE, PHRASE_ALT, PHRASE_NEXT, PHRASE_OPTIONAL, PHRASE_OR, PHRASE_REQUIRED, CLAUSE_AND, QUERY, SCORE_BM1, SCORE_BM15, SCORE_BM25,
+from ._lib import (EXCLUDE, HIT, NO_TERM, OP_AND, OP_MINMATCH, OP_MULTITERM, OP_OR, OP_PHRASE, PHRASE_ALT, PHRASE_NEXT, PHRASE_OPTIONAL, PHRASE_OR, PHRASE_REQUIRED, CLAUSE_AND, TREE_NODE, QUERY, SCORE_BM1, SCORE_BM15, SCORE_BM25,
                    SCORE_TFIDF, SCORE_TFIDF_NORM, TERM_META, TERM_SCORER, SegmentDesc)
 
 f32 = np.float32
@@ -459,6 +459,79 @@ def or_clauses(flt, mult=1.0):
     return clauses
 
 
+def boolean_tree(flt, mult=1.0):
+    """A nested filter of by_term / And / Or / Not, normalised for the tree encoding
+    (IRS_HIP_TREE_NODE).  Returns ("leaf", term, boost) or ("node", op, min_match, children), every
+    child a pair (negated, subtree):
+      a node of one positive child collapses into that child, its boost multiplied in (the single
+      node case, boolean_filter.cpp:152-155); an And child of an And is flattened into it; a SUM Or
+      child with min_match <= 1 is flattened into an Or with min_match <= 1; Not(Not(f)) is f
+      (optimize_not, boolean_filter.cpp:35-48).
+    A leaf's boost is its own times every ancestor's, multiplied from the top in float32 as prepare()
+    hands ctx.boost down (boolean_filter.cpp:153-154, 204); what stands under a Not scores nothing.
+    Anything else raises ValueError."""
+    if type(flt) is by_term:
+        return ("leaf", int(flt.term), f32(f32(mult) * f32(flt.boost)))
+    if isinstance(flt, Not):
+        raise ValueError("a filter of only Not matches all docs but some (zero-score fill): "
+                         "not on the GPU path")
+    if isinstance(flt, (by_phrase, by_terms, by_doc_set)):
+        raise ValueError("a %s inside a nested boolean filter is not on the GPU path: the leaves of a "
+                         "tree (IRS_HIP_TREE_NODE) are by_term" % type(flt).__name__)
+    if type(flt) not in (And, Or):
+        raise ValueError("%s inside a nested boolean filter is not on the GPU path" % type(flt).__name__)
+    if type(flt) is And and flt.op != OP_AND:
+        raise ValueError("an And child with op %d is not on the GPU path" % flt.op)
+    if not flt.subs:
+        raise ValueError("%s without children" % ("an And" if type(flt) is And else "an Or"))
+    if flt.merge != MERGE_SUM and len(flt.subs) > 1:
+        raise ValueError("a nested boolean filter merges with SUM at every level on the GPU path "
+                         "(MAX / MIN are not built)")
+    conj = type(flt) is And
+    if not conj and flt.min_match < 1:
+        raise ValueError("an Or with min_match 0 matches all docs (boolean_filter.cpp:213): not on the "
+                         "GPU path")
+    mult = f32(f32(mult) * f32(flt.boost))
+    children = []
+    for s in flt.subs:
+        f, neg = _unwrap_not(s)
+        if neg and not conj:
+            raise ValueError("an Or with a Not child matches all docs but some (zero-score fill, "
+                             "boolean_filter.cpp:120-127): not on the GPU path")
+        sub = boolean_tree(f, f32(1) if neg else mult)
+        if sub[0] == "node" and not neg and (
+                (conj and sub[1] == OP_AND) or
+                (not conj and flt.min_match <= 1 and sub[1] == OP_OR)):
+            children += sub[3]     # (same operator: flattened)
+        else:
+            children.append((neg, sub))
+    if conj and all(neg for neg, _ in children):
+        raise ValueError("an And of only Not children matches all docs but some (zero-score fill): "
+                         "not on the GPU path")
+    if len(children) == 1 and (conj or flt.min_match <= 1):
+        return children[0][1]
+    return ("node", OP_AND if conj else flt.op, 0 if conj or flt.min_match <= 1 else int(flt.min_match), children)
+
+
+def tree_entries(tree):
+    """The prefix form of a normalised tree's children: one item per entry — ("leaf", term, boost),
+    ("not", term) or ("node", op, span, min_match, negated), a node followed by the `span` entries
+    of its subtree.  (n_leaves, n_nodes) with it."""
+    out = []
+    n_leaves = n_nodes = 0
+    for neg, sub in tree[3]:
+        if sub[0] == "leaf":
+            out.append(("not", sub[1]) if neg else sub)
+            n_leaves += 1
+        else:
+            inner, nl, nn = tree_entries(sub)
+            out.append(("node", sub[1], len(inner), sub[2], neg))
+            out += inner
+            n_leaves += nl
+            n_nodes += nn + 1
+    return out, n_leaves, n_nodes
+
+
 def _terms_of(flt):
     if isinstance(flt, Not):
         raise ValueError("Not is taken by prepare() only (as a child of an And), not here")
@@ -493,6 +566,10 @@ class PreparedQuery:
     clause: list | None = None     # OP_OR / OP_MINMATCH: True for an entry that is one more required
                                    # member of the clause before it (IRS_HIP_CLAUSE_AND) — an Or with
                                    # And children, min_match counting clauses; None: a flat Or
+    tree: list | None = None       # a tree query (IRS_HIP_TREE_NODE): per entry None — a leaf with its
+                                   # scorer —, "not" — a negated leaf, an IRS_HIP_EXCLUDE entry where it
+                                   # stands — or (op, span, min_match, negated) — a node entry (its
+                                   # term is None); `op` / `min_match` are the root's; None: no tree
     opens: list | None = None      # OP_PHRASE: True for an entry that is the first word of a FURTHER
                                    # phrase of the And (IRS_HIP_PHRASE_NEXT): the words of phrase 1, of
                                    # phrase 2, ..., then the required terms; None: one phrase
@@ -670,8 +747,15 @@ class QueryArrays:
             more = p.clause if p.clause is not None else [False] * len(p.terms)
             nxts = p.opens if p.opens is not None else [False] * len(p.terms)
             ors = p.or_opens if p.or_opens is not None else [False] * len(p.terms)
-            for t, (kind, c0, nc, nl), off, alt, req, opt, cl, nxt, orr in zip(p.terms, p.scorers, offs, alts, reqs,
-                                                                              opts, more, nxts, ors):
+            tree = p.tree if p.tree is not None else [None] * len(p.terms)
+            for t, (kind, c0, nc, nl), off, alt, req, opt, cl, nxt, orr, nd in zip(p.terms, p.scorers, offs, alts, reqs,
+                                                                                  opts, more, nxts, ors, tree):
+                if nd == "not":          # a negated leaf where it stands: no scorer
+                    kind, c0, nc, nl, off = EXCLUDE, 0.0, 0.0, 0.0, 0
+                elif nd is not None:     # a node entry: its op, the entries of its subtree, its min_match
+                    n_op, span, mm, neg = nd
+                    kind, c0, nc, nl = TREE_NODE | n_op | (EXCLUDE if neg else 0), 0.0, 0.0, 0.0
+                    off = span | (mm << 16)
                 kind = kind | CLAUSE_AND if cl else kind
                 kind = kind | PHRASE_NEXT if nxt else kind
                 kind = kind | PHRASE_OR if orr else kind
@@ -801,7 +885,8 @@ def prepare_filters(filters, scorer, segment_stats, segs, k):
                                      "array path prepare_filters")
                 if cls is Or and any(isinstance(s, (And, Or)) for s in subs):
                     raise ValueError("an Or with And children (IRS_HIP_CLAUSE_AND) is taken by "
-                                     "prepare(..., and_clauses=True), not by the array path prepare_filters")
+                                     "prepare(..., and_clauses=True), deeper trees (IRS_HIP_TREE_NODE) by "
+                                     "prepare(..., boolean_trees=True), not by the array path prepare_filters")
                 raise ValueError("only flat Or/And of by_term are on the array path: an And with "
                                  "Or children is taken by prepare()")
             op = flt.op
@@ -1139,6 +1224,13 @@ class QueryBatch:
                    "irs_hip_batch_phrase_disj_units")
         return n.value
 
+    def tree_units(self) -> int:
+        """irs_hip_batch_tree_units: the batch's units of tree queries (IRS_HIP_TREE_NODE entries:
+        k_tree_pilot / k_tree_score)."""
+        n = C.c_uint32()
+        _lib.check(self.L, self.L.irs_hip_batch_tree_units(self.handle, C.byref(n)), "irs_hip_batch_tree_units")
+        return n.value
+
     def wide_units(self) -> int:
         """irs_hip_batch_wide_units: the batch's units of by_terms / wide expansion queries
         (IRS_HIP_OP_MULTITERM), (segment, query) pairs."""
@@ -1291,7 +1383,7 @@ class SegmentStats:
 
 
 def prepare(filters, scorer, segment_stats, required_terms=False, optional_terms=False, and_clauses=False,
-            phrase_conjunctions=False, phrase_disjunctions=False):
+            phrase_conjunctions=False, phrase_disjunctions=False, boolean_trees=False):
     """filter::prepare for a list of filters against ALL segments: statistics are
     index-global (term_filter.cpp:102-125): D = sum docs_with_field,
     d = sum docs_count of the term, avgdl from the summed field frequency.
@@ -1311,10 +1403,22 @@ def prepare(filters, scorer, segment_stats, required_terms=False, optional_terms
     phrase_disjunctions=True: Or([by_phrase, by_phrase...]) — two to four phrases in one Or,
     IRS_HIP_PHRASE_OR — is taken, also as the one included child of And([Or([...]), Not(...)...,
     by_doc_set(r)]).  Off by default in the same way: without it two phrases in one Or are refused as
-    they always were."""
+    they always were.
+    boolean_trees=True: a tree of by_term / And / Or (with min_match) / Not nested to any depth —
+    `a AND (b OR (c AND d))`, `(a AND NOT b) OR c`, IRS_HIP_TREE_NODE (boolean_tree) — is taken where
+    every other route, under the flags given, refuses it; a filter one of them takes keeps its route
+    and its bytes.  Off by default in the same way: without it every refusal stays as it was."""
     dwf = sum(s.docs_with_field for s in segment_stats)
     ttf = sum(s.total_term_freq for s in segment_stats)
     out = []
+    if boolean_trees:
+        for flt in filters:
+            try:
+                out += prepare([flt], scorer, segment_stats, required_terms, optional_terms, and_clauses,
+                               phrase_conjunctions, phrase_disjunctions)
+            except ValueError:
+                out.append(_prepare_tree(flt, scorer, segment_stats, dwf, ttf))
+        return out
     for flt in filters:
         flt, doc_set = split_doc_set(flt)
         if doc_set is not None:
@@ -1618,6 +1722,41 @@ def _prepare_clauses(flt, scorer, segment_stats, dwf, ttf):
             more.append(i > 0)
     return PreparedQuery(flt.op, terms, scorers, int(flt.min_match), merge=MERGE_SUM,
                          clause=more if any(more) else None)
+
+
+def _prepare_tree(flt, scorer, segment_stats, dwf, ttf):
+    """prepare() of a nested boolean filter the other routes refuse (And::prepare / Or::prepare
+    prepare every child on its own, boolean_filter.cpp:55-312): normalised (boolean_tree), then the
+    root's children in prefix order — per leaf the statistics of any by_term and its boost product,
+    a negated leaf without scorer, a node entry per inner node.  A tree that normalises to one level
+    is sent as the flat query it is."""
+    tree = boolean_tree(flt)
+    if tree[0] == "leaf":
+        tree = ("node", OP_OR, 0, [(False, tree)])
+    entries, n_leaves, n_nodes = tree_entries(tree)
+    if n_leaves > _lib.MAX_TERMS:
+        raise ValueError("a nested boolean filter has at most %d leaves in all, Nots included" % _lib.MAX_TERMS)
+    if n_nodes > _lib.MAX_TERMS - 1:
+        raise ValueError("a nested boolean filter has at most %d inner nodes below its root" % (_lib.MAX_TERMS - 1))
+
+    def one(t, boost):
+        dwt = sum(int(st.docs_count[t]) for st in segment_stats if 0 <= t < len(st.docs_count))
+        return scorer.term_scorer(scorer.collect(dwf, dwt, ttf), boost)
+
+    _, op, min_match, _ = tree
+    if n_nodes == 0:     # one level: a flat Or / And / min-match, the negated leaves behind it
+        leaves = [e for e in entries if e[0] == "leaf"]
+        return PreparedQuery(op, [e[1] for e in leaves], [one(e[1], e[2]) for e in leaves], min_match,
+                             merge=MERGE_SUM, excluded=[e[1] for e in entries if e[0] == "not"])
+    terms, scorers, marks = [], [], []
+    for e in entries:
+        if e[0] == "leaf":
+            terms.append(e[1]); scorers.append(one(e[1], e[2])); marks.append(None)
+        elif e[0] == "not":
+            terms.append(e[1]); scorers.append((EXCLUDE, f32(0), f32(0), f32(0))); marks.append("not")
+        else:
+            terms.append(None); scorers.append((0, f32(0), f32(0), f32(0))); marks.append(tuple(e[1:]))
+    return PreparedQuery(op, terms, scorers, min_match, merge=MERGE_SUM, tree=marks)
 
 
 def variadic_slots(parts, segment_stats):

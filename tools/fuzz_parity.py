@@ -14,7 +14,9 @@ round runs
 Ands of Or groups (with exclusions, wand on and off; every third over two segments in one batch)
 and by_terms queries of 17..64 entries (IRS_HIP_OP_MULTITERM) mixed into a batch of the round's
 ordinary filters, and likewise Ors with And children (IRS_HIP_CLAUSE_AND: 1-8 clauses, 2-16 entries,
-any min_match) against the per-clause composition of tests/test_or_clauses.py.
+any min_match) against the per-clause composition of tests/test_or_clauses.py, and random trees of
+And / Or / min-match / Not over up to 16 leaves (IRS_HIP_TREE_NODE, prepare(..., boolean_trees=True))
+against the per-leaf composition of tests/test_boolean_trees.py.
 With --doc-sets every round also restricts a random subset of its units to random doc sets
 (irs_hip_batch_set_doc_sets) at densities 0, 0.001, 0.5 and 1, on a path picked at random, and
 compares each against the oracle's run on the segment with the set's complement deleted as well.
@@ -274,6 +276,71 @@ def clause_round(sr, seg, filters, scorer, k, st, rng, max_rank, term):
     return len(mixed)
 
 
+def tree_round(sr, seg, filters, scorer, k, st, rng, max_rank, term):
+    """Nested boolean filters (IRS_HIP_TREE_NODE, k_tree_pilot / k_tree_score): trees of depth up to 4
+    over up to 16 leaves (frequent, rare and absent ranks; boosts with zeros on leaves and nodes; Nots
+    of leaves and of subtrees under Ands; min-match Ors with min_match 1 .. children + 1) interleaved
+    with some of the round's ordinary filters: the trees against the oracle composed per leaf
+    (tests/test_boolean_trees.py), the ordinary ones bit for bit what a batch without them gives.
+    Whatever another route takes keeps that route (prepare counts the trees)."""
+    import test_boolean_trees as tb
+    from iresearch_amd import _lib, search
+    from iresearch_amd.search import And, Not, Or
+    boost = lambda: float(rng.choice([1.0, 1.0, 0.25, 0.5, 2.0, 4.0, 0.0]))   # noqa: E731
+
+    def gen(d, top=False):
+        if d == 0 or (not top and rng.random() < 0.4):
+            return term()
+        kind = int(rng.integers(0, 5))
+        if kind < 2:
+            subs = [gen(d - 1) for _ in range(int(rng.integers(1, 4)))]
+            r = rng.random()
+            if r < 0.3:
+                subs.append(Not(term()))
+            elif r < 0.45:
+                subs.append(Not(gen(d - 1)))
+            return And(subs, boost=boost())
+        subs = [gen(d - 1) for _ in range(int(rng.integers(1, 5)))]
+        mm = 1 if kind < 4 else int(rng.integers(1, len(subs) + 2))
+        return Or(subs, min_match=mm, boost=boost())
+
+    made = []
+    while len(made) < 6:
+        f = gen(int(rng.integers(2, 5)), True)
+        if tb.n_leaves(f) > 16:
+            continue
+        try:
+            search.prepare([f], scorer, st, boolean_trees=True)
+        except ValueError:      # (more than 15 inner nodes)
+            continue
+        made.append(f)
+    mixed = []
+    for i, f in enumerate(made):
+        mixed += [f] + filters[i:i + 1]
+    at_t = [i for i, f in enumerate(mixed) if any(f is m for m in made)]
+    path = int(rng.choice([_lib.PATH_AUTO, _lib.PATH_ITEMS, _lib.PATH_JOINED]))
+    prep = search.prepare(mixed, scorer, st, boolean_trees=True)
+    at_o = [i for i, p in enumerate(prep) if p.tree is None]   # (a drawn tree another route takes is one of these)
+    try:
+        b = sr.batch(prep, k).set_path(path)
+    except _lib.IrsHipError as e:   # (a frequency above 255 in one of the lists: not on this path)
+        assert e.status == _lib.EUNSUPPORTED, e
+        return 0
+    if rng.integers(0, 3) == 0:
+        b.configure(cand_cap=max(k, 64))
+    h, c, t = (x.copy() for x in b.run().results())
+    assert b.tree_units() == len(prep) - len(at_o)
+    b.close()
+    if at_o:
+        pb = sr.batch([prep[i] for i in at_o], k).set_path(path)
+        ph, pc, pt = pb.run().results()
+        assert np.array_equal(h[at_o], ph) and np.array_equal(c[at_o], pc) and np.array_equal(t[at_o], pt), "mixed batch"
+        pb.close()
+    for q in at_t:
+        tb.check(mixed[q], k, h[q], c[q], t[q], *tb.expected(seg, mixed[q], scorer))
+    return len(mixed)
+
+
 def match_round(b, seg, filters, totals, excl=None):
     """Unscored execution of the same batch (irs_hip_batch_match_sets): every unit's set bit for bit
     against the oracle (tests/test_match_sets.py want_set), the counts against the scored totals.
@@ -497,6 +564,7 @@ def main():
             queries += grouped_round(sr, seg, scorer, k, st, rng, max_rank, term, merge, rounds % 3 == 2, L)
             queries += wide_round(sr, seg, filters, scorer, k, st, rng, max_rank)
             queries += clause_round(sr, seg, filters, scorer, k, st, rng, max_rank, term)
+            queries += tree_round(sr, seg, filters, scorer, k, st, rng, max_rank, term)
             if rounds % 3 == 0:   # the same results through page-locked host memory, a run later
                 hh, hc, ht = b.run().results_to_host().host_results()
                 assert np.array_equal(hc, counts) and np.array_equal(ht, totals), "host results: counts"

@@ -23,15 +23,23 @@ def main():
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--configs", default="4096:16")
     ap.add_argument("--nocheck", action="store_true")
-    ap.add_argument("--op", default="or", choices=["or", "and", "mm", "phrase", "terms"],
+    ap.add_argument("--op", default="or", choices=["or", "and", "mm", "phrase", "terms", "tree"],
                     help="Or / And / Or(min_match=terms-1) / by_phrase of --terms consecutive words / "
-                         "by_terms of --terms terms with --min-match (IRS_HIP_OP_MULTITERM, up to 64 terms)")
+                         "by_terms of --terms terms with --min-match (IRS_HIP_OP_MULTITERM, up to 64 terms) / "
+                         "nested boolean trees over the --terms entries of every query (--shape)")
     ap.add_argument("--lo-rank", type=int, default=16)
     ap.add_argument("--hi-rank", type=int, default=4096)
     ap.add_argument("--terms", default="8",
                     help="terms per query; --op terms and --op or take a comma list (17,32,50,64): each is "
                          "timed on the same index, one line per count, then exits")
     ap.add_argument("--min-match", type=int, default=1, help="--op terms: by_terms_options::min_match")
+    ap.add_argument("--shape", default="nest",
+                    help="--op tree: comma list of SHAPEs over the --terms entries of every query "
+                         "(IRS_HIP_TREE_NODE: k_tree_pilot / k_tree_score) — clause sizes as for --clauses "
+                         "(2+2+2+2: an Or of Ands, sent as a tree), nest: an Or of (a AND (b OR (c AND d))) over "
+                         "every four entries (depth 3), chain: a left-deep chain alternating And / Or over all "
+                         "of them (--terms 16: 16 leaves, 15 nodes), not: nest with every d negated.  Times each "
+                         "on the same entry lists (those of --op terms at the same --terms) and exits")
     ap.add_argument("--clauses", default="",
                     help="--op or: comma list of SPECs, each the clause sizes of an Or with And children over "
                          "the --terms entries of every query (IRS_HIP_CLAUSE_AND: k_clause_pilot / "
@@ -122,6 +130,57 @@ def main():
     scorer = {"bm25": BM25(), "tfidf": TFIDF(True), "bm15": BM25(1.2, 0.0)}[args.scorer]
     st = search.SegmentStats(seg.docs_with_field, seg.total_term_freq,
                              np.asarray(seg.metas["docs_count"]))
+    if args.op == "tree":
+        # one line per SHAPE: the rows of --op terms at the same --terms, put together as trees
+        if len(term_counts) > 1 or not 2 <= args.terms <= 16:
+            raise SystemExit("--op tree takes one --terms of 2..16")
+        _, stride = (int(x) for x in args.configs.split(",")[0].split(":"))
+
+        def tree_of(shape, row):
+            leaves = [by_term(int(r) - 1) for r in row]
+            if shape == "chain":
+                node = And(leaves[:2])
+                for i in range(2, len(leaves)):
+                    node = (Or if i % 2 == 0 else And)([node, leaves[i]])
+                return node
+            if shape in ("nest", "not"):
+                if len(leaves) % 4:
+                    raise SystemExit("--shape %s: --terms is a multiple of 4" % shape)
+                last = (lambda f: Not(f)) if shape == "not" else (lambda f: f)
+                quads = [And([q[0], Or([q[1], And([q[2], last(q[3])])])])
+                         for q in (leaves[i:i + 4] for i in range(0, len(leaves), 4))]
+                return quads[0] if len(quads) == 1 else Or(quads)
+            sizes = []
+            for part in shape.split("+"):
+                size, _, times = part.partition("x")
+                sizes += [int(size)] * (int(times) if times else 1)
+            if sum(sizes) != len(leaves) or min(sizes) < 1:
+                raise SystemExit("--shape %s: the clause sizes add up to --terms %d" % (shape, len(leaves)))
+            at, subs = 0, []
+            for size in sizes:
+                subs.append(leaves[at] if size == 1 else And(leaves[at:at + size]))
+                at += size
+            return Or(subs, min_match=args.min_match)
+
+        for shape in args.shape.split(","):
+            fl = [tree_of(shape, row) for row in ranks]
+            b = sr.batch(search.prepare(fl, scorer, [st], boolean_trees=True), args.k).configure(0, stride, 0).profile(True)
+            b.run()
+            _, _, totals = b.results()
+            ms = []
+            t0 = time.perf_counter()
+            for _ in range(args.steps):
+                b.run()
+                ms.append(b.timings())
+            dt = (time.perf_counter() - t0) / args.steps
+            avg = np.mean(ms, axis=0)
+            alg, post = b.work()
+            print("tree terms=%d shape=%s  tree units %d  step %.2f ms  plan %.2f pilot %.2f score %.2f "
+                  "select %.2f  %.1f M postings  streams (distinct, decoded) %s  hits/query mean %.0f  reruns=%d" % (
+                      args.terms, shape, b.tree_units(), dt * 1e3, *avg, post / 1e6,
+                      b.stream_counts(), float(np.mean(totals)), b.reruns()), flush=True)
+            b.close()
+        sys.exit(0)
     if args.clauses:
         # one line per SPEC: the rows of --op terms at the same --terms, cut into clauses
         if args.op != "or" or len(term_counts) > 1:

@@ -750,6 +750,195 @@ def case_streams(L, num_docs, max_rank):
     sr.close()
 
 
+CHUNK_TILES = 9                  # launch_tree_score: 17 tiles in cpq = 2 chunks of ceil(17 / 2)
+N_CHUNKS = 16 * TILE + 5         # 17 tiles, the last one nearly empty
+N_SHORT = TILE + 5               # 2 tiles: the second workgroup of such a unit has no tile
+HOT_TILES = (3, 12)              # one tile of chunk 0, one of chunk 1
+STAGE = 512                      # kWideCands: candidate staging slots per chunk
+
+
+def _chunk_lists(num_docs, seed):
+    """Terms 0 .. 5 of a segment whose matches are concentrated: a core of docs that hold terms 0 and 2
+    (tf 1 .. 30) — 1000 in each tile of HOT_TILES where the segment has them, 150 anywhere — of which
+    every second holds term 1, two of three term 3, two of five term 5 and every seventh term 4 (the
+    negated leaf); 60 docs in tile 0 that hold terms 0, 1, 2, 3, 5 at tf 200 .. 255 (the best of every
+    query: a pilot that counted tile 0 twice would take their bin); the docs at every CHUNK_TILES
+    border, the last doc of the first tile, the first of the second and the segment's last doc hold
+    0, 1, 2, 3, 5; beside the core every term holds 300 docs of its own."""
+    rng = np.random.default_rng(seed)
+    n_tiles = (num_docs + TILE - 1) // TILE
+    free = np.ones(num_docs + 1, bool)
+    free[0] = False
+    fixed = {TILE, TILE + 1, num_docs}
+    for t in range(CHUNK_TILES, n_tiles, CHUNK_TILES):
+        fixed |= {t * TILE, t * TILE + 1}             # the last doc of tile t - 1, the first of tile t
+    fixed = np.array(sorted(fixed), np.int64)
+    free[fixed] = False
+
+    def take(lo, hi, n):
+        ids = lo + np.nonzero(free[lo:hi])[0]
+        d = np.sort(rng.choice(ids, n, replace=False))
+        free[d] = False
+        return d
+    top = take(1, TILE, 60)
+    core = [take(1 + t * TILE, 1 + (t + 1) * TILE, 1000) for t in HOT_TILES if (t + 1) * TILE <= num_docs]
+    core = np.sort(np.concatenate(core + [take(1, num_docs + 1, 150)]))
+    i = np.arange(core.size)
+    member = {0: core, 1: core[i % 2 == 0], 2: core, 3: core[i % 3 != 0], 4: core[i % 7 == 0], 5: core[i % 5 < 2]}
+    lists = []
+    for t in range(6):
+        own = take(1, num_docs + 1, 300)
+        docs = [member[t], own] + ([fixed, top] if t != 4 else [])
+        tfs = [rng.integers(1, 31, member[t].size), rng.integers(1, 6, own.size)] + \
+            ([rng.integers(1, 31, fixed.size), rng.integers(200, 256, top.size)] if t != 4 else [])
+        d, f = np.concatenate(docs), np.concatenate(tfs)
+        order = np.argsort(d)
+        lists.append((d[order].astype(np.uint32), f[order].astype(np.uint32)))
+    return lists, fixed, top
+
+
+def case_chunks(L, layout):
+    """Units of more than kWideChunkTiles = 16 tiles: one segment of 16 * 12288 + 5 docs — 17 tiles,
+    cpq = 2 workgroups per unit, chunk_tiles = 9 — and in the same batch one of 12288 + 5 docs, 2 tiles,
+    whose second workgroup leaves at `tile0 >= n_tiles`.  Two filters with a Not leaf and a nested And
+    on _chunk_lists: more than 600 hits in tile 3 and in tile 12 (a chunk stages more than kWideCands =
+    512), hits at the last doc of tile 8 and the first of tile 9 (the chunk border) and at the segment's
+    last doc.  Without norms under TFIDF(False) and BM25(1.2, 0), once BM25() with norms.  Per scorer:
+    k = 4096 (every hit returned: doc sets compare exactly) and k = 100 at the default stride;
+    configure(0, 1, 0): 17 sampled tiles, the pilot's second round of kWideChunkTiles; the same with a
+    candidate buffer of 128 slots under zero boosts (every hit ties: all are candidates, overflow, one
+    re-run, the smallest doc ids)."""
+    sizes = (N_CHUNKS, N_SHORT)
+    built = [_chunk_lists(n, 61 + i) for i, n in enumerate(sizes)]
+    filters = [And([T(0), Or([T(1), And([T(2), T(3)])]), Not(T(4))]),
+               Or([And([T(0, 0.5), Not(T(4))]), And([T(2), Or([T(1, 2.0), And([T(3), T(5)])])])])]
+    zero = [And(f.subs, boost=0.0) if type(f) is And else Or(f.subs, boost=0.0) for f in filters]
+    assert all(refused(f) for f in filters)
+    for scorer, with_norms in ((TFIDF(False), False), (BM25(1.2, 0.0), False), (BM25(), True)):
+        segs = []
+        for (lists, _, _), n in zip(built, sizes):
+            norms = (np.arange(n, dtype=np.uint32) * 7 % 200 + 20).astype(np.uint8) if with_norms else False
+            segs.append(synth.segment_from_lists(lists, n, layout, norms=norms))
+        readers = [search.SegmentReader.from_synth(s, L=L) for s in segs]
+        stats = [parity.segment_stats(s) for s in segs]
+        per = [[expected(s, f, scorer, segs) for f in filters] for s in segs]
+        per0 = [[expected(s, f, scorer, segs) for f in zero] for s in segs]
+        for q in range(len(filters)):      # what the lists must give, by the oracle alone
+            sc, m = per[0][q]
+            tile_hits = [int(m[1 + t * TILE:1 + (t + 1) * TILE].sum()) for t in range(17)]
+            assert all(tile_hits[t] >= 600 for t in HOT_TILES), tile_hits
+            assert sum(tile_hits[:CHUNK_TILES]) > STAGE and sum(tile_hits[CHUNK_TILES:]) > STAGE, tile_hits
+            assert m[CHUNK_TILES * TILE] and m[CHUNK_TILES * TILE + 1] and m[N_CHUNKS] and tile_hits[16] >= 1
+            assert m[built[0][1]].all() and m[built[0][2]].all()
+            assert 100 < int(m.sum()) <= 4096 and 100 < int(per[1][q][1].sum()) <= 4096
+            assert per[1][q][1][N_SHORT] and per[1][q][1][TILE] and per[1][q][1][TILE + 1]
+            best = np.argsort(-sc, kind="stable")[:60]
+            assert set(best.tolist()) == set(built[0][2].tolist()), "the 60 docs of tile 0 are the best"
+        for flts, exp, k, stride, cap, reruns in ((filters, per, 4096, 0, 0, 0), (filters, per, 100, 0, 0, 0),
+                                                  (filters, per, 4096, 1, 0, 0), (filters, per, 100, 1, 0, 0),
+                                                  (zero, per0, 100, 1, 128, 1)):
+            prep = search.prepare(flts, scorer, stats, boolean_trees=True)
+            b = search.QueryBatch(readers, prep, k)
+            if stride or cap:
+                b.configure(0, stride, cap)
+            assert b.tree_units() == len(flts) * len(segs)
+            h, c, t = b.run().results()
+            assert b.reruns() == reruns, (k, stride, cap, b.reruns())
+            for s in range(len(segs)):
+                for q, flt in enumerate(flts):
+                    check(flt, k, h[s, q], c[s, q], t[s, q], *exp[s][q])
+                    n = int(c[s, q])
+                    if cap:     # every score ties: doc id order
+                        assert n == k and (h[s, q, :n]["score"] == 0).all()
+                        assert np.array_equal(h[s, q, :n]["doc"], np.nonzero(exp[s][q][1])[0][:k])
+                    elif k == 4096:
+                        assert n == int(exp[s][q][1].sum())
+                        assert np.array_equal(np.sort(h[s, q, :n]["doc"]), np.nonzero(exp[s][q][1])[0])
+            b.close()
+        for r in readers:
+            r.close()
+
+
+def case_min_scores(L, layout):
+    """irs::score::Min (irs_hip_batch_set_min_scores) on a tree batch: k_tree_pilot's min_bin,
+    k_tree_score's `v < thr` pre-filter on sums that still carry their scoring mask, k_select's exact
+    cut.  The hand lists (three tiles), k = 50, with and without set_wand(True).  The unrestricted run
+    is h0 (checked against the composed expectation); a threshold at the k-th score returns h0; at the
+    10th score exactly the prefix of h0 at or above it, ties included; at the float just above it the
+    correspondingly shorter prefix; 1e30 returns nothing; None returns h0 again.  Totals never change,
+    nothing re-runs.  chain16's best doc (ALL) scores through all 16 leaves.  With k candidate slots a
+    threshold nothing reaches stages nothing (no re-run), where the same batch without a threshold
+    overflows: the pilot's min_bin bounds the candidates."""
+    lists = hand_lists()
+    N = N_HAND
+    norms = (np.arange(N, dtype=np.uint32) * 7 % 200 + 20).astype(np.uint8)
+    seg = synth.segment_from_lists(lists, N, layout, norms=norms)
+    sr = search.SegmentReader.from_synth(seg, L=L)
+    st = [parity.segment_stats(seg)]
+    named = hand_queries()
+    names = ["nest", "andnot_or", "not_and", "mm_mixed", "twice", "chain16", "boosts", "short"]
+    filters = [named[n] for n in names]
+    k = 50
+    for scorer in (BM25(), TFIDF(True)):
+        exp = [expected(seg, f, scorer) for f in filters]
+        assert all(int(m.sum()) > k for _, m in exp[:-1])
+        c16 = names.index("chain16")
+        assert n_leaves(filters[c16]) == 16 and int(np.argmax(exp[c16][0])) == ALL
+        for wand in (False, True):
+            b = sr.batch(search.prepare(filters, scorer, st, boolean_trees=True), k)
+            assert b.tree_units() == len(filters)
+            b.set_wand(wand)
+            h0, c0, t0 = (x.copy() for x in b.run().results())
+            for q, flt in enumerate(filters):
+                check(flt, k, h0[q], c0[q], t0[q], *exp[q])
+            assert int(h0[c16, 0]["doc"]) == ALL
+            assert (c0 >= 10).all() and (h0[:, 9]["score"] > 0).all()
+
+            def run(ms):
+                b.set_min_scores(None if ms is None else np.asarray(ms, f32))
+                h, c, t = (x.copy() for x in b.run().results())
+                assert b.reruns() == 0
+                assert np.array_equal(t, t0), "a caller's threshold changes no total"
+                return h, c
+
+            def prefix(ms):
+                return np.array([int((h0[q, :int(c0[q])]["score"] >= ms[q]).sum()) for q in range(len(filters))])
+
+            def same_prefix(h, c, n, what):
+                assert np.array_equal(c, n), (what, c, n)
+                for q in range(len(filters)):
+                    assert np.array_equal(h[q, :n[q]], h0[q, :n[q]]), (what, names[q])
+            kth = np.array([h0[q, int(c0[q]) - 1]["score"] for q in range(len(filters))], f32)
+            tenth = h0[:, 9]["score"].astype(f32)
+            above = np.nextafter(tenth, f32(np.inf))
+            same_prefix(*run(kth), c0, "the k-th score")
+            n10, n_above = prefix(tenth), prefix(above)
+            assert (n10 >= 10).all() and (n_above < 10).all() and (n10 < c0).any() and (n_above > 0).any()
+            same_prefix(*run(tenth), n10, "the 10th score")
+            same_prefix(*run(above), n_above, "above the 10th score")
+            h, c = run(np.full(len(filters), 1e30, f32))
+            assert (c == 0).all()
+            same_prefix(*run(None), c0, "None")
+            b.close()
+            # k_tree_pilot's min_bin is what keeps the candidates few: with k candidate slots (the
+            # fewest configure takes) the run under a threshold nothing reaches stages nothing, and
+            # the same batch without a threshold — the pilot's own bin admits k docs and their
+            # bin-mates — overflows and runs again
+            b = sr.batch(search.prepare(filters, scorer, st, boolean_trees=True), k).configure(0, 0, k)
+            b.set_wand(wand)
+            b.set_min_scores(np.full(len(filters), 1e30, f32))
+            h, c, t = (x.copy() for x in b.run().results())
+            assert b.reruns() == 0, "the caller's bin bounds the candidates"
+            assert np.array_equal(t, t0) and (c == 0).all()
+            b.set_min_scores(None)
+            h, c, t = (x.copy() for x in b.run().results())
+            assert b.reruns() == 1, "without it the k slots overflow: the case above bites"
+            assert np.array_equal(t, t0)
+            same_prefix(h, c, c0, "None, k candidate slots")
+            b.close()
+    sr.close()
+
+
 # --------------------------------------------------------------- host only --
 
 def test_prepare_boolean_trees():
@@ -905,6 +1094,16 @@ def test_boolean_trees_streams_emulated(simlib):
     case_streams(simlib, 14_000, 64)
 
 
+@pytest.mark.parametrize("layout", [synth.LAYOUT_SIMD4, synth.LAYOUT_SCALAR])
+def test_boolean_trees_chunks_emulated(simlib, layout):
+    case_chunks(simlib, layout)
+
+
+@pytest.mark.parametrize("layout", [synth.LAYOUT_SIMD4, synth.LAYOUT_SCALAR])
+def test_boolean_trees_min_scores_emulated(simlib, layout):
+    case_min_scores(simlib, layout)
+
+
 # --------------------------------------------------------------------- GPU --
 
 @pytest.mark.gpu
@@ -941,3 +1140,15 @@ def test_boolean_trees_multi_gpu(gpulib):
 @pytest.mark.gpu
 def test_boolean_trees_streams_gpu(gpulib):
     case_streams(gpulib, 60_000, 128)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("layout", [synth.LAYOUT_SIMD4, synth.LAYOUT_SCALAR])
+def test_boolean_trees_chunks_gpu(gpulib, layout):
+    case_chunks(gpulib, layout)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("layout", [synth.LAYOUT_SIMD4, synth.LAYOUT_SCALAR])
+def test_boolean_trees_min_scores_gpu(gpulib, layout):
+    case_min_scores(gpulib, layout)

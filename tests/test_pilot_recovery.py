@@ -2,7 +2,7 @@
 (wide.h k_wide_pilot / k_wide_score), Ors of clauses (clauses.h k_clause_pilot / k_clause_score),
 grouped conjunctions (conj_any.h k_conj_any), a phrase plus required terms (k_phrase_and) and a phrase
 or optional terms (k_phrase_or, its term pass — a second batch of work items under doc sets — and
-k_union_topk).
+k_union_topk), and nested And / Or / Not trees (tree.h k_tree_pilot / k_tree_score).
 
 Every pilot samples part of its unit — doc tiles {phase, phase + P, ...} or lead items, phase =
 (unit * 7) % P, unit = segment * queries + query — and estimates the score bin that leaves about
@@ -31,13 +31,14 @@ import pytest
 
 import oracle
 import parity
+import test_boolean_trees as bt
 import test_multiterm as mt
 import test_nested_boolean as nb
 import test_or_clauses as oc
 import test_phrase_and as pa
 import test_phrase_or as po
 from iresearch_amd import search, synth
-from iresearch_amd.search import BM25, TFIDF, And, Or, by_phrase, by_term, by_terms
+from iresearch_amd.search import BM25, TFIDF, And, Not, Or, by_phrase, by_term, by_terms
 from test_block_driven import (MISLED_K, STRIDE, _misled_conj_segments, _misled_phrase_segment, _same,
                                _trace_status, pilot_phase)
 
@@ -143,10 +144,12 @@ def _cold_pair(rng, free, shared=2000, own=1000):
     return out
 
 
-def _tile_segments(L, layout, tiles, shift, k, nq=2, with3=None, seed=7):
+def _tile_segments(L, layout, tiles, shift, k, nq=2, with3=None, seed=7, hot_in2=None):
     """Per segment of tiles[s] full tiles: terms 0 .. nq - 1 = the hot lists of its units
     s * nq + q, terms 2 and 3 = _cold_pair (segment `with3` False: no term 3), term 4 = every hot doc
-    with frequency 1 (only where term 3 exists).  The hot docs hold none of the cold terms."""
+    with frequency 1 (only where term 3 exists).  The hot docs hold none of the cold terms — except
+    in a segment `hot_in2`: there term 2 holds every hot doc too (frequency 1) and there is no
+    term 4."""
     segs, readers = [], []
     for s, n_tiles in enumerate(tiles):
         rng = np.random.default_rng(seed + s)
@@ -156,6 +159,9 @@ def _tile_segments(L, layout, tiles, shift, k, nq=2, with3=None, seed=7):
         cold = _cold_pair(rng, free)
         if with3 is not None and not with3[s]:
             lists += cold[:1]
+        elif hot_in2 is not None and hot_in2[s]:
+            d2 = np.sort(np.concatenate([cold[0][0]] + [d for d, _ in lists])).astype(np.uint32)
+            lists += [(d2, np.ones(d2.size, np.uint32)), cold[1]]
         else:
             every = np.sort(np.concatenate([d for d, _ in lists])).astype(np.uint32)
             lists += cold + [(every, np.ones(every.size, np.uint32))]
@@ -182,7 +188,7 @@ def _close(readers):
 
 
 def _wide_counters(b):
-    return (b.wide_units(), b.clause_units(), b.path())
+    return (b.wide_units(), b.clause_units(), b.tree_units(), b.path())
 
 
 def _check_family(mod, segs, filters, scorer, k):
@@ -439,6 +445,206 @@ def case_underflow_then_overflow(L, layout, capfd):
     sr.close()
 
 
+# ------------------------------------------------------- doc tiles: tree units --
+
+def _tree_filters():
+    """(q AND (4 OR 2)) OR (2 AND 3): the hot list under a nested Or, beside a clause of the cold pair."""
+    return [Or([And([by_term(q), Or([by_term(4), by_term(2)])]), And([by_term(2), by_term(3)])]) for q in range(2)]
+
+
+def _has(seg, term):
+    m = np.zeros(seg.num_docs + 1, bool)
+    if term < len(seg.metas):
+        m[_docs_of(seg, term)] = True
+    return m
+
+
+def case_tree_misled(L, layout, capfd, tiles=(8,)):
+    """k_tree_pilot / k_tree_score (prepare(boolean_trees=True); without the keyword prepare refuses the
+    shape).  Or([And([q, Or([4, 2])]), And([2, 3])]) for q = 0, 1 on segments of 8 (9, 10) tiles of
+    12288 docs without norms, configure(0, 4, 0): tree_stride = min(4, 8 tiles / 2) = 4.  Term q holds
+    400 docs with tf 50 in each of the 2 tiles sampled for its unit s * 2 + q (320 in each of 3: unit 4,
+    10 tiles, phase 0), term 4 every hot doc (tf 1), terms 2 and 3 3000 docs with tf 1, 2000 of them
+    common.  k = 1000: the pilot wants need = ceil(3 * 1000 * 2 / 8) = 750 docs at or above its bin
+    (667 for 2 of 9 tiles, 900 for 3 of 10) and finds the 800 (960) hot ones; the full run lists those
+    800 (960) < k of 2800 (2960) matches — the hot docs plus the 2000 of `2 AND 3`: exactly one re-run,
+    every unit short of k (`2 units short of k`).
+    Three segments of 8, 9, 10 tiles: units with the phases 0, 3, 2, 1, 0, 3.  The middle segment has
+    matches of its own and a leaf absent all the same: it lacks term 4, and its term 2 holds the hot docs
+    too (tf 1) — they match through `q AND 2`, 800 + 2000 = 2800 per unit — so that all six phases show
+    in the count: `6 units short of k`.  Per segment against the composed expectation with index-global
+    statistics, and the merged top k as test_boolean_trees.case_multi has it.
+    Control: the hot tiles two tiles (half a stride) further, no re-run."""
+    k, nq = 1000, 2
+    filters = _tree_filters()
+    assert all(bt.refused(f) for f in filters)
+    hot_in2 = None if len(tiles) == 1 else [s == 1 for s in range(len(tiles))]
+    for shift, reruns in ((0, 1), (WIDE_STRIDE // 2, 0)):
+        segs, readers = _tile_segments(L, layout, tiles, shift, k, nq, hot_in2=hot_in2)
+        stats = [parity.segment_stats(s) for s in segs]
+        for s, seg in enumerate(segs):       # the numbers above, from the lists alone
+            n_tiles = tiles[s]
+            assert (len(seg.metas) == 4) == bool(hot_in2 and hot_in2[s])
+            both = _has(seg, 2) & _has(seg, 3)
+            assert int(both.sum()) == 2000
+            for q in range(nq):
+                hot = _has(seg, q)
+                sampled = _sampled(s * nq + q, n_tiles)
+                n_hot = {2: 800, 3: 960}[len(_sampled(s * nq + q, n_tiles, shift))]     # (_hot)
+                matched = (hot & (_has(seg, 4) | _has(seg, 2))) | both
+                assert int(hot.sum()) == n_hot < k and not (hot & both).any()
+                assert int(matched.sum()) == n_hot + 2000 > 2 * k
+                in_sample = sum(int(hot[1 + t * TILE:1 + (t + 1) * TILE].sum()) for t in sampled)
+                assert in_sample == (0 if shift else n_hot)
+                assert shift or pilot_need(k, len(sampled), n_tiles) <= in_sample
+        assert pilot_need(k, 2, 8) == 750 and pilot_need(k, 2, 9) == 667 and pilot_need(k, 3, 10) == 900
+        for scorer in SCORERS:
+            prep = search.prepare(filters, scorer, stats, boolean_trees=True)
+            per = [[bt.expected(seg, flt, scorer, segs) for flt in filters] for seg in segs]
+
+            def check(res):
+                h, c, t = res
+                for s in range(len(segs)):
+                    for q, flt in enumerate(filters):
+                        bt.check(flt, k, h[s, q], c[s, q], t[s, q], *per[s][q])
+                assert int(c.min()) == k and int(t.min()) >= 2800
+                if len(segs) > 1:
+                    merged = search.merge_topk_host([(h[i], c[i]) for i in range(len(segs))], k)
+                    for q in range(nq):
+                        allsc = np.concatenate([per[i][q][0][per[i][q][1]] for i in range(len(segs))])
+                        ref = np.sort(allsc)[::-1][:k]
+                        assert int(t[:, q].sum()) == allsc.size, q
+                        got = np.array([r[0] for r in merged[q]])
+                        assert len(got) == len(ref) == k
+                        assert np.allclose(got, ref, rtol=parity.REL_TOL, atol=0), q
+
+            def counters(b):
+                assert b.tree_units() == nq * len(segs)
+                return _wide_counters(b)
+            _misled(_maker(readers, prep, k, WIDE_STRIDE), len(segs) > 1, check, counters, capfd,
+                    reruns, [nq * len(segs)] * reruns, listed=(800, 2800) if reruns else None,
+                    what=("tree", tiles, shift, scorer))
+        _close(readers)
+
+
+def case_tree_uncounted(L, layout, capfd):
+    """What k_tree_pilot must leave out of its histogram; configure(0, 4, 0) on 8 tiles, no re-run.
+    Terms 0, 2, 3 hold 12000 random docs each (tf 1 .. 5): `0 AND (2 OR 3)`, the real branch R of every
+    filter, matches about 340 docs in every tile alike.  500 decoys in EVERY tile (1000 in any unit's
+    sample of 2 tiles) hold term 4 with tf 200 and terms 5 and 6 with tf 1, and no other term; term 1
+    holds 100 other docs.  k = 200, need = ceil(3 * 200 * 2 / 8) = 150 <= the ~680 sampled matches.  One
+    batch of four units (phases 0, 3, 2, 1):
+      * Or([And([4, 1]), R]): a decoy holds a leaf of an And whose sibling is missing;
+      * Or([And([4, Not(5)]), R]): a decoy is barred by a Not leaf;
+      * Or([And([4, Not(And([5, 6]))]), R]): ... by a Not(And(...)) subtree;
+      * Or([And([4, 1]), And([5, Or([6, 2])]), R]): a decoy is a hit through the cheap branch `5 AND 6`
+        and holds the tf-200 leaf of a branch that does not match: leaf 4 must not score, in the
+        histogram or in the result.
+    Scored through term 4 a decoy lies above every real match, and 1000 of them >= need: a pilot that
+    counted them so puts its bin above every match, 0 < k listed.
+      * deleted docs: case_tree_misled's lists and filters, the 800 hot docs of the sampled tiles
+        deleted (at tf 50, and at tf 200: a bin of their own above every live doc), 400 live hot docs
+        (tf 50) in each of the 6 other tiles; k = 1000.  No deleted doc returned, totals without them."""
+    rng = np.random.default_rng(5)
+    n_tiles, k = 8, 200
+    free = np.ones(n_tiles * TILE + 1, bool)
+    decoy = _decoys(rng, range(n_tiles), 500, free)
+    real = [_spread(rng, free, 12000, 5) for _ in range(3)]      # (`free`: no decoy among them)
+    few = _spread(rng, free, 100, 1)
+    for d, _ in real + [few]:
+        assert not np.isin(d, decoy[0]).any()
+    ones = (decoy[0], np.ones(decoy[0].size, np.uint32))
+    lists = [real[0], few, real[1], real[2], decoy, ones, ones]
+    seg = synth.segment_from_lists(lists, n_tiles * TILE, layout, norms=False)
+    sr = search.SegmentReader.from_synth(seg, L=L)
+    T = by_term
+    R = And([T(0), Or([T(2), T(3)])])
+    filters = [Or([And([T(4, 4.0), T(1)]), R]),
+               Or([And([T(4, 4.0), Not(T(5))]), R]),
+               Or([And([T(4, 4.0), Not(And([T(5), T(6)]))]), R]),
+               Or([And([T(4, 4.0), T(1)]), And([T(5), Or([T(6), T(2)])]), R])]
+    assert pilot_need(k, 2, n_tiles) == 150
+    for scorer in SCORERS:
+        lv = bt.Leaves(seg, scorer)
+        as4 = lv(4, np.float32(4))[1][decoy[0]]          # what a decoy would score through term 4
+        cheap = lv(5, np.float32(1))[1] + lv(6, np.float32(1))[1]
+        for i, flt in enumerate(filters):
+            sc, m = bt.expected(seg, flt, scorer)
+            real_m = m.copy()
+            real_m[decoy[0]] = False
+            per_tile = [int(real_m[1 + t * TILE:1 + (t + 1) * TILE].sum()) for t in range(n_tiles)]
+            assert 2 * min(per_tile) >= pilot_need(k, 2, n_tiles) and sum(per_tile) > 4 * k, per_tile
+            assert as4.min() > sc[real_m].max(), "counted through term 4, the decoys lie above every real match"
+            if i < 3:
+                assert not m[decoy[0]].any()
+            else:
+                assert m[decoy[0]].all() and np.array_equal(sc[decoy[0]], cheap[decoy[0]])
+                assert (sc[decoy[0]] < as4).all() and (sc[decoy[0]] > 0).all()
+        _uncounted([sr], [seg], filters, scorer, k, bt, capfd, ("tree, decoys", scorer), boolean_trees=True)
+    sr.close()
+    k = 1000
+    filters = _tree_filters()
+    for masked_tf in (HOT_TF, DECOY_TF):
+        seg, sr, gone = _masked_hot_segment(L, layout, k, masked_tf)
+        both = _has(seg, 2) & _has(seg, 3)
+        live = []
+        for q in range(2):
+            m = (_has(seg, q) & (_has(seg, 4) | _has(seg, 2))) | both
+            m[gone] = False
+            live.append(int(m.sum()))
+        assert live == [2400 + 2000] * 2
+        for scorer in SCORERS:
+            ref = _uncounted([sr], [seg], filters, scorer, k, bt, capfd, ("tree, deleted", masked_tf, scorer), gone,
+                             boolean_trees=True)
+            assert [int(x) for x in ref[2][0]] == live, "the totals exclude the deleted docs"
+            assert [int(x) for x in ref[1][0]] == [k, k]
+        sr.close()
+
+
+def case_tree_under_then_over(L, layout, capfd):
+    """case_underflow_then_overflow on a tree filter.  case_tree_misled's hot lists and filters (8 tiles,
+    configure(0, 4, 0), k = 1000, need 750 <= 800 hot docs < k); term 2 holds 20000 docs with tf 1
+    (norms off: one score) apart from the hot docs, term 3 the same docs and 3000 more that hold
+    nothing else (`2 AND 3`: the 20000, all tied), term 4 every hot doc.  The first run lists 800 of
+    20800 matches: underflow.  recover_now's buffer is default_cand_cap = 16384 slots; the sound bin is
+    the ties', 20800 candidates: overflow, recover_overflow sizes the next buffer from the count.
+    results() is OK, the 200 places behind the hot docs are the smallest tied doc ids, reruns() == 1,
+    and a later batch on the same reader runs.  (The stride-1 reference gets 32768 candidate slots.)"""
+    k = 1000
+    rng = np.random.default_rng(37)
+    n_tiles = 8
+    free = np.ones(n_tiles * TILE + 1, bool)
+    lists = [_hot(rng, n_tiles, q, 0, free, k) for q in range(2)]
+    ids = np.nonzero(free)[0]
+    pick = rng.choice(ids[ids > 0], 23000, replace=False)
+    tied = np.sort(pick[:20000]).astype(np.uint32)
+    more = np.sort(pick).astype(np.uint32)
+    every = np.sort(np.concatenate([d for d, _ in lists])).astype(np.uint32)
+    assert tied.size > 16384 and every.size == 1600
+    lists += [(tied, np.ones(tied.size, np.uint32)), (more, np.ones(more.size, np.uint32)),
+              (every, np.ones(every.size, np.uint32))]
+    seg = synth.segment_from_lists(lists, n_tiles * TILE, layout, norms=False)
+    sr = search.SegmentReader.from_synth(seg, L=L)
+    filters = _tree_filters()
+    stats = [parity.segment_stats(seg)]
+    for scorer in SCORERS:
+        prep = search.prepare(filters, scorer, stats, boolean_trees=True)
+        ref = _misled(_maker([sr], prep, k, WIDE_STRIDE, ref_cap=32768), False,
+                      _check_family(bt, [seg], filters, scorer, k), _wide_counters, capfd, 1, [2],
+                      listed=(800, 20800), what=("tree: under, then over", scorer))
+        h, c, t = ref
+        for q in range(2):
+            assert int(c[0, q]) == k and int(t[0, q]) == 20800
+            assert set(h[0, q, :800]["doc"].tolist()) == set(lists[q][0].tolist())
+            assert np.array_equal(h[0, q, 800:k]["doc"], tied[:k - 800]), "tie order: smallest doc ids first"
+        later = sr.batch(prep, k)
+        lh, lc, lt = later.run().results()
+        assert later.tree_units() == 2
+        _same((lh[None], lc[None], lt[None]), ref, what="a later batch")
+        later.close()
+    sr.close()
+
+
 # ------------------------------------------------------ lead items: k_conj_any --
 
 def case_grouped_misled(L, layout, capfd, n_segs=1):
@@ -642,6 +848,24 @@ def test_underflow_then_overflow_emulated(simlib, capfd):
 
 
 @pytest.mark.parametrize("layout", LAYOUTS)
+def test_tree_misled_emulated(simlib, layout, capfd):
+    case_tree_misled(simlib, layout, capfd)
+
+
+def test_tree_misled_segments_emulated(simlib, capfd):
+    case_tree_misled(simlib, synth.LAYOUT_SIMD4, capfd, tiles=(8, 9, 10))
+
+
+@pytest.mark.parametrize("layout", LAYOUTS)
+def test_tree_uncounted_emulated(simlib, layout, capfd):
+    case_tree_uncounted(simlib, layout, capfd)
+
+
+def test_tree_under_then_over_emulated(simlib, capfd):
+    case_tree_under_then_over(simlib, synth.LAYOUT_SIMD4, capfd)
+
+
+@pytest.mark.parametrize("layout", LAYOUTS)
 def test_grouped_misled_emulated(simlib, layout, capfd):
     case_grouped_misled(simlib, layout, capfd)
 
@@ -694,6 +918,28 @@ def test_clause_uncounted_gpu(gpulib, layout, capfd):
 @pytest.mark.gpu
 def test_underflow_then_overflow_gpu(gpulib, capfd):
     case_underflow_then_overflow(gpulib, synth.LAYOUT_SIMD4, capfd)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("layout", LAYOUTS)
+def test_tree_misled_gpu(gpulib, layout, capfd):
+    case_tree_misled(gpulib, layout, capfd)
+
+
+@pytest.mark.gpu
+def test_tree_misled_segments_gpu(gpulib, capfd):
+    case_tree_misled(gpulib, synth.LAYOUT_SIMD4, capfd, tiles=(8, 9, 10))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("layout", LAYOUTS)
+def test_tree_uncounted_gpu(gpulib, layout, capfd):
+    case_tree_uncounted(gpulib, layout, capfd)
+
+
+@pytest.mark.gpu
+def test_tree_under_then_over_gpu(gpulib, capfd):
+    case_tree_under_then_over(gpulib, synth.LAYOUT_SIMD4, capfd)
 
 
 @pytest.mark.gpu

@@ -877,6 +877,44 @@ int irs_hip_batch_match_sets(irs_hip_batch* batch, uint64_t* sets, uint64_t n_wo
 int irs_hip_batch_match_sets_to_device(irs_hip_batch* batch, void* d_sets, uint64_t n_words,
                                        void* d_counts, void* stream);
 
+/* doc_iterator::seek(target) + score for docs the CALLER names (formats_10.cpp:2304-2365; a
+ * conjunction seeks its other children to the lead's doc, conjunction.hpp:207-223) — a compatible
+ * addition to ABI 12.  What a GPU-backed query needs to sit under a host conjunction whose other child
+ * this library never runs, and what scores the candidates another retriever returned.
+ * Unit u = segment * n_queries + query.  Unit u's docs are docs[offsets[u] .. offsets[u + 1]),
+ * strictly ascending, each in 1..num_docs of the unit's segment; `offsets` has n_units + 1 entries,
+ * offsets[0] == 0, non-decreasing (an empty list is allowed).
+ *   scores[i]   the score irs_hip_batch_run gives doc i under its unit, 0 where it does not match
+ *   matched[i]  1 / 0 (matched may be NULL)
+ * Matching and score are exactly what the unit's scored run defines for that doc: the segment's
+ * deleted docs, the unit's IRS_HIP_EXCLUDE entries and its doc set (irs_hip_batch_set_doc_sets) do
+ * not match; an absent term behaves as in a run (an And with one is empty, an Or drops it); the
+ * merge is the unit's (a kMin disjunction of three or more scores 0); a zero boost matches with
+ * score 0.  k, min scores, wand, the path, paired tiles, a shared threshold and a communicator play
+ * no part.  Like irs_hip_batch_match_sets the call may come before, after or without
+ * irs_hip_batch_run and leaves the batch's results, irs_hip_batch_reruns and later runs as they
+ * would have been.
+ * Units taken: every unit of at most IRS_HIP_MAX_TERMS rows — OR / AND / MINMATCH with SUM / MAX /
+ * MIN, IRS_HIP_GROUP_ALT, IRS_HIP_CLAUSE_AND, IRS_HIP_TREE_NODE, with or without IRS_HIP_EXCLUDE
+ * entries, on one or several segments.  Clause and tree units, whose runs sum 64-bit fixed point,
+ * are summed in float32 here: equal within the 1e-5 the scores are held to.
+ * IRS_HIP_EUNSUPPORTED: a batch that holds IRS_HIP_OP_PHRASE or IRS_HIP_OP_MULTITERM units; more
+ * than 2^31 docs in all.  IRS_HIP_EINVAL: a NULL batch, docs, offsets or scores; offsets[0] != 0;
+ * decreasing offsets; a doc of 0, a doc above its segment's num_docs, a list that does not ascend
+ * strictly.  Synchronous; the staging memory comes from the pool (IRS_HIP_ENOMEM). */
+int irs_hip_batch_score_docs(irs_hip_batch* batch, const uint32_t* docs, const uint64_t* offsets,
+                             float* scores, uint8_t* matched);
+/* The same on device memory (d_docs u32[n_docs], d_offsets u64[n_units + 1], d_scores f32[n_docs],
+ * d_matched u8[n_docs] or NULL), queued on `stream`; n_docs = offsets[n_units].  The host cannot
+ * validate what it does not read: the kernel reports every doc of 0 or above its segment's num_docs
+ * as unmatched, and every doc of a chunk (at most 128 consecutive docs of one list) that does not
+ * ascend strictly as unmatched; no address is ever formed from an unverified doc or offset —
+ * offsets that are not 0-based, non-decreasing and <= n_docs leave outputs unwritten, nothing more.
+ * The call returns IRS_HIP_OK in all these cases.  d_docs and d_offsets stay valid and unchanged
+ * until the stream has run the call. */
+int irs_hip_batch_score_docs_to_device(irs_hip_batch* batch, const void* d_docs, const void* d_offsets,
+                                       uint64_t n_docs, void* d_scores, void* d_matched, void* stream);
+
 /* Doc-set filters (a compatible addition to ABI 12): the units of a batch restricted to doc sets on
  * the device — the conjunction of a scored query with an UNSCORED child: the bitset_doc_iterator a
  * multi-term query builds from its unscored terms (multiterm_query.cpp:36-87, 133-166), a

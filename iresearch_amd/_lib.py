@@ -96,6 +96,7 @@ SYMBOLS = (
     "irs_hip_segment_wand_source",
     "irs_hip_batch_touched", "irs_hip_batch_unit_mask",
     "irs_hip_batch_match_sets", "irs_hip_batch_match_sets_to_device",
+    "irs_hip_batch_score_docs", "irs_hip_batch_score_docs_to_device",
     "irs_hip_batch_set_doc_sets", "irs_hip_batch_set_doc_sets_host", "irs_hip_batch_doc_set_stats",
     "irs_hip_comm_unique_id", "irs_hip_comm_init_rank", "irs_hip_comm_destroy",
     "irs_hip_comm_library",
@@ -188,6 +189,10 @@ def bind(L: C.CDLL) -> C.CDLL:
     L.irs_hip_batch_match_sets.restype = C.c_int
     L.irs_hip_batch_match_sets_to_device.argtypes = [vp, vp, u64, vp, vp]
     L.irs_hip_batch_match_sets_to_device.restype = C.c_int
+    L.irs_hip_batch_score_docs.argtypes = [vp, vp, vp, vp, vp]
+    L.irs_hip_batch_score_docs.restype = C.c_int
+    L.irs_hip_batch_score_docs_to_device.argtypes = [vp, vp, vp, u64, vp, vp, vp]
+    L.irs_hip_batch_score_docs_to_device.restype = C.c_int
     L.irs_hip_batch_set_doc_sets.argtypes = [vp, vp, u64, u64, vp]
     L.irs_hip_batch_set_doc_sets.restype = C.c_int
     L.irs_hip_batch_set_doc_sets_host.argtypes = [vp, vp, u64, u64, vp]

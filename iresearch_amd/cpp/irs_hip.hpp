@@ -1092,6 +1092,47 @@ class QueryBatch {
           "irs_hip_batch_match_sets_to_device");
     return *this;
   }
+  // doc_iterator::seek(target) + score for docs the caller names (irs_hip_batch_score_docs):
+  // docs[segment * n_queries + query] = strictly ascending doc ids of that segment.  Per doc the
+  // score run() gives it under its query (0 where it does not match) and whether it matches.
+  // Independent of run().  A batch with a by_phrase query: not_supported.
+  struct ScoredDocs {
+    std::vector<uint64_t> offsets;   // [units + 1]: unit u's answers are [offsets[u], offsets[u + 1])
+    std::vector<float> scores;
+    std::vector<uint8_t> matched;
+  };
+  ScoredDocs score_docs(const std::vector<std::vector<uint32_t>>& docs) {
+    const size_t units = size_t(n_segments_) * n_queries_;
+    if (docs.size() != units) throw illegal_argument(IRS_HIP_EINVAL, "score_docs: one doc list per (segment, query)");
+    if (part_[1].h) throw not_supported(IRS_HIP_EUNSUPPORTED, "score_docs: a batch with by_phrase queries");
+    ScoredDocs r;
+    r.offsets.assign(units + 1, 0);
+    for (size_t u = 0; u < units; ++u) r.offsets[u + 1] = r.offsets[u] + docs[u].size();
+    std::vector<uint32_t> flat;
+    flat.reserve(size_t(r.offsets[units]) + 1);
+    for (const auto& d : docs) flat.insert(flat.end(), d.begin(), d.end());
+    r.scores.assign(flat.size(), 0.f);
+    r.matched.assign(flat.size(), 0);
+    flat.push_back(0);   // (an empty call still hands over valid addresses)
+    r.scores.push_back(0.f);
+    r.matched.push_back(0);
+    // (all boolean: one device batch, its units in the caller's order)
+    check(irs_hip_batch_score_docs(single_part(), flat.data(), r.offsets.data(), r.scores.data(), r.matched.data()),
+          "irs_hip_batch_score_docs");
+    r.scores.pop_back();
+    r.matched.pop_back();
+    return r;
+  }
+  // ... on device memory, queued on `stream` (irs_hip_batch_score_docs_to_device): d_docs
+  // u32[n_docs], d_offsets u64[units + 1], d_scores f32[n_docs], d_matched u8[n_docs] or null; docs
+  // the host form refuses come back unmatched
+  QueryBatch& score_docs_to_device(const void* d_docs, const void* d_offsets, uint64_t n_docs, void* d_scores,
+                                   void* d_matched, void* stream = nullptr) {
+    if (part_[1].h) throw not_supported(IRS_HIP_EUNSUPPORTED, "score_docs: a batch with by_phrase queries");
+    check(irs_hip_batch_score_docs_to_device(single_part(), d_docs, d_offsets, n_docs, d_scores, d_matched, stream),
+          "irs_hip_batch_score_docs_to_device");
+    return *this;
+  }
   // The doc sets the queries' by_doc_set children name rows of (irs_hip_batch_set_doc_sets):
   // [n_rows][n_words] u64, bit = doc id (irs_hip_bit_union's layout), every segment of the batch
   // reading the same row for a query.  Device memory is BORROWED — valid and unchanged until the

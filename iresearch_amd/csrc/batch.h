@@ -260,6 +260,16 @@ struct MatchWork {
   uint32_t max_docs = 0;         // num_docs of the batch's largest segment
 };
 
+// Scores of caller-given docs (score_docs.h, plan_score_docs.h): the units as k_score_docs reads
+// them, built with the first irs_hip_batch_score_docs call (the rows and node records go out as
+// create left them); the host form's staging of the lists and results
+struct ScoreDocsWork {
+  bool built = false, sent = false;
+  std::vector<SdUnit> units;
+  std::vector<uint32_t> seg_docs;   // num_docs of every segment of the batch
+  DevBuf d_units, d_rows, d_nodes, d_docs, d_chunks, d_scores, d_matched;
+};
+
 // One threshold per query for its units on the batch's segments (irs_hip_batch_set_shared_threshold)
 // ... across ranks (irs_hip_batch_set_comm): the group histograms and the group sums are summed
 // over the communicator's ranks inside every run
@@ -300,6 +310,9 @@ struct RunSync {
   // the last irs_hip_batch_match_sets_to_device queued on some stream: it reads the exclusion masks
   // and the match tables
   Pending matched;
+  // the last irs_hip_batch_score_docs_to_device queued on some stream: it reads the exclusion masks
+  // and the score-docs tables
+  Pending docs_scored;
   Event uploaded;   // the first run's table uploads (the device's copy stream)
   Event prof[2 * IRS_HIP_K_COUNT];   // irs_hip_batch_profile: around every stage of a run
   PinBuf h_pin;                // page-locked staging for irs_hip_batch_results
@@ -391,6 +404,7 @@ struct irs_hip_batch {
   uint64_t taken_words = 0;
   ExclWork excl;
   MatchWork match;
+  ScoreDocsWork score_docs;
   Groups groups;
   RunSync sync;
 };
@@ -443,21 +457,24 @@ static bool run_status(const irs_hip_batch* b, uint32_t* status) {
 static bool quiesce(irs_hip_batch* b) {
   bool ok = b->sync.plan.sync();
   if (b->ran) ok = after_run(b) && ok;
-  return b->sync.matched.sync() && ok;
+  ok = b->sync.matched.sync() && ok;
+  return b->sync.docs_scored.sync() && ok;
 }
 
 // A plan stage is about to rewrite the plan tables and the masks on `st`: behind the batch's last
 // run (it reads them), a plan queued earlier and never used (it may run on ANOTHER stream), match
 // sets on another stream (they read the masks).
 static bool plan_get_behind(const irs_hip_batch* b, rt::stream_t st) {
-  return b->sync.done.wait(st) && b->sync.plan.wait(st) && b->sync.matched.wait(st);
+  return b->sync.done.wait(st) && b->sync.plan.wait(st) && b->sync.matched.wait(st) &&
+         b->sync.docs_scored.wait(st);
 }
 
 // Match sets are about to read the masks and the tables on `st`, and to rewrite the masks: behind a
 // plan stage and a run (they write the masks and may have the tables in flight) and an earlier
 // call's kernels on another stream.
 static bool match_get_behind(const irs_hip_batch* b, rt::stream_t st) {
-  return b->sync.plan.wait(st) && b->sync.done.wait(st) && b->sync.matched.wait(st);
+  return b->sync.plan.wait(st) && b->sync.done.wait(st) && b->sync.matched.wait(st) &&
+         b->sync.docs_scored.wait(st);
 }
 
 // A run is about to rewrite the batch's tables and outputs on `st`, and — a first run with tables
@@ -469,9 +486,11 @@ static bool match_get_behind(const irs_hip_batch* b, rt::stream_t st) {
 //   plan      a plan stage still queued — used by this run or made stale by a setter — reads and
 //             writes the tables this run uploads and rewrites: both streams
 //   matched   match sets on another stream read the masks and the tables: both streams
-// `host` and `matched` are settled here though only a stream waited: whatever touches these
-// buffers later — a run, a plan stage, match sets, a setter, destroy — gets behind this run's
-// `done`, which is recorded behind everything `st` has waited for.
+//   docs_scored  irs_hip_batch_score_docs_to_device on another stream reads the masks and the
+//             score-docs tables: both streams
+// `host`, `matched` and `docs_scored` are settled here though only a stream waited: whatever
+// touches these buffers later — a run, a plan stage, match sets, a score-docs call, a setter,
+// destroy — gets behind this run's `done`, which is recorded behind everything `st` has waited for.
 static bool run_get_behind(irs_hip_batch* b, rt::stream_t st, rt::stream_t* up_st) {
   RunSync& s = b->sync;
   if (!s.host.wait(st)) return false;
@@ -482,6 +501,8 @@ static bool run_get_behind(irs_hip_batch* b, rt::stream_t st, rt::stream_t* up_s
   if (*up_st && !s.plan.wait(*up_st)) return false;
   if (!s.matched.wait(st) || (*up_st && !s.matched.wait(*up_st))) return false;
   s.matched.settle();
+  if (!s.docs_scored.wait(st) || (*up_st && !s.docs_scored.wait(*up_st))) return false;
+  s.docs_scored.settle();
   return true;
 }
 
@@ -492,7 +513,7 @@ static bool run_get_behind(irs_hip_batch* b, rt::stream_t st, rt::stream_t* up_s
 static bool quiet_for_destroy(irs_hip_batch* b) {
   RunSync& s = b->sync;
   const bool ended = !b->ran || s.done.pending();
-  return s.done.sync() && s.plan.sync() && s.used.sync() && s.host.sync() && s.matched.sync() && ended;
+  return s.done.sync() && s.plan.sync() && s.used.sync() && s.host.sync() && s.matched.sync() && s.docs_scored.sync() && ended;
 }
 
 // A setter is about to change what the deal of the units depends on: the batch's device, and the

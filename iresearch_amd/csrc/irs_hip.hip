@@ -39,6 +39,7 @@
 #include "tree.h"
 #include "excl.h"
 #include "match.h"
+#include "score_docs.h"
 
 using namespace irs_hip;
 
@@ -54,6 +55,7 @@ using namespace irs_hip;
 #include "plan_tree.h"
 #include "plan_join.h"
 #include "plan_match.h"
+#include "plan_score_docs.h"
 #include "units.h"
 
 namespace {
@@ -797,6 +799,7 @@ static int batch_set_doc_sets_impl(irs_hip_batch* b, const void* sets, bool host
   x.set_words = x.sets_on() ? n_words : 0;
   if (!x.sets_on()) x.sets = nullptr;
   b->match.built = false;   // (the match units carry the masks' addresses)
+  b->score_docs.built = false;   // (and so do the score-docs units)
   deal_is_stale(b);
   const int rc2 = build_masks(b);
   return rc != IRS_HIP_OK ? rc : rc2;
@@ -1549,6 +1552,19 @@ int irs_hip_batch_match_sets_to_device(irs_hip_batch* b, void* d_sets, uint64_t 
     if (b && (b->wide.on() || b->clause.on() || b->tree.on())) return int(IRS_HIP_EUNSUPPORTED);
     return batch_match_sets_impl(b, nullptr, d_sets, n_words, nullptr, d_counts,
                                  static_cast<rt::stream_t>(stream), true);
+  });
+}
+int irs_hip_batch_score_docs(irs_hip_batch* b, const uint32_t* docs, const uint64_t* offsets, float* scores,
+                             uint8_t* matched) {
+  return settled(b, [&] {
+    return batch_score_docs_impl(b, docs, offsets, scores, matched, nullptr, nullptr, 0, nullptr, nullptr, nullptr, false);
+  });
+}
+int irs_hip_batch_score_docs_to_device(irs_hip_batch* b, const void* d_docs, const void* d_offsets, uint64_t n_docs,
+                                       void* d_scores, void* d_matched, void* stream) {
+  return settled(b, [&] {
+    return batch_score_docs_impl(b, nullptr, nullptr, nullptr, nullptr, d_docs, d_offsets, n_docs, d_scores,
+                                 d_matched, static_cast<rt::stream_t>(stream), true);
   });
 }
 int irs_hip_batch_plan(irs_hip_batch* b, void* stream) {

@@ -1180,6 +1180,52 @@ class QueryBatch:
             self.handle, d_sets, int(n_words), d_counts, stream), "irs_hip_batch_match_sets_to_device")
         return self
 
+    def score_docs(self, docs, offsets=None, matched=True):
+        """doc_iterator::seek + score for docs the caller names (irs_hip_batch_score_docs).  `docs`:
+        a list of arrays, one per unit (segment * n_queries + query), each strictly ascending doc
+        ids of the unit's segment — or one flat u32 array with `offsets` u64[units + 1].  Returns
+        (scores, matched) in the same shape: the score run() gives the doc under its unit (0 where
+        it does not match) and whether it matches; matched=False: (scores, None)."""
+        lists = offsets is None
+        if lists:
+            if len(docs) != self.nq:
+                raise ValueError("docs: one list per unit (%d)" % self.nq)
+            arrs = [np.ascontiguousarray(d, np.uint32).reshape(-1) for d in docs]
+            offsets = np.zeros(self.nq + 1, np.uint64)
+            np.cumsum([a.size for a in arrs], out=offsets[1:])
+            flat = np.concatenate(arrs) if arrs else np.zeros(0, np.uint32)
+        else:
+            flat = np.ascontiguousarray(docs, np.uint32).reshape(-1)
+            offsets = np.ascontiguousarray(offsets, np.uint64).reshape(-1)
+            if offsets.size != self.nq + 1:
+                raise ValueError("offsets: units + 1 entries (%d)" % (self.nq + 1))
+            if offsets.size and int(offsets[-1]) != flat.size:
+                raise ValueError("offsets[-1] != len(docs)")
+        flat = np.ascontiguousarray(flat, np.uint32)
+        n = max(flat.size, 1)   # (an empty call still hands over valid addresses)
+        buf = np.zeros(n, np.uint32)
+        buf[:flat.size] = flat
+        scores = np.zeros(n, np.float32)
+        hit = np.zeros(n, np.uint8) if matched else None
+        _lib.check(self.L, self.L.irs_hip_batch_score_docs(
+            self.handle, buf.ctypes.data, offsets.ctypes.data, scores.ctypes.data,
+            hit.ctypes.data if matched else None), "irs_hip_batch_score_docs")
+        scores = scores[:flat.size]
+        hit = hit[:flat.size].astype(bool) if matched else None
+        if not lists:
+            return scores, hit
+        cut = offsets[1:-1].astype(np.int64)
+        return np.split(scores, cut), (np.split(hit, cut) if matched else None)
+
+    def score_docs_to_device(self, d_docs, d_offsets, n_docs: int, d_scores, d_matched=None, stream=None):
+        """The same on device memory (irs_hip_batch_score_docs_to_device), queued on `stream`:
+        d_docs u32[n_docs], d_offsets u64[units + 1], d_scores f32[n_docs], d_matched u8[n_docs] or
+        None — device addresses.  Docs the host form refuses come back unmatched."""
+        _lib.check(self.L, self.L.irs_hip_batch_score_docs_to_device(
+            self.handle, d_docs, d_offsets, int(n_docs), d_scores, d_matched, stream),
+            "irs_hip_batch_score_docs_to_device")
+        return self
+
     def touched(self):
         """(`.doc` + norm bytes decoded, positions read) by the last run (And / by_phrase)."""
         a, p = C.c_uint64(), C.c_uint64()

@@ -330,6 +330,9 @@ def tree_round(sr, seg, filters, scorer, k, st, rng, max_rank, term):
         b.configure(cand_cap=max(k, 64))
     h, c, t = (x.copy() for x in b.run().results())
     assert b.tree_units() == len(prep) - len(at_o)
+    if len(at_t) == len(mixed):   # (every unit a drawn tree: each has its per-leaf composition)
+        exp = [tuple(np.asarray(x)[:seg.num_docs + 1] for x in tb.expected(seg, f, scorer)) for f in mixed]
+        score_docs_round(b, seg, rng, exp, h, c)
     b.close()
     if at_o:
         pb = sr.batch([prep[i] for i in at_o], k).set_path(path)
@@ -356,6 +359,24 @@ def match_round(b, seg, filters, totals, excl=None):
             want = tm.want_set(x, f, excl[q] if excl else [], segs)
             assert np.array_equal(tm.bits_of(sets[u], x.num_docs), want), ("match sets", i, q, f)
             assert int(counts[u]) == int(want.sum()), ("match sets: count", i, q, f)
+
+
+def score_docs_round(b, seg, rng, expected, hits, counts):
+    """irs_hip_batch_score_docs of the same batch: per unit a drawn doc list — random docs, and often
+    the run's own hits among them — against expected[q] = (score, matched) of ALL docs
+    (tests/test_score_docs.py check_list: matched bit for bit, scores to 1e-5, 0 where unmatched)."""
+    import test_score_docs as ts
+    per = []
+    for q in range(len(expected)):
+        docs = rng.choice(seg.num_docs, int(rng.integers(0, min(seg.num_docs, 600) + 1)), replace=False).astype(np.uint32) + 1
+        if rng.integers(0, 2):
+            docs = np.concatenate([docs, hits[q, :int(counts[q])]["doc"].astype(np.uint32)])
+        per.append(np.unique(docs))
+    sc, mt = b.score_docs(per)
+    for q, exp in enumerate(expected):
+        ts.check_list(("score docs", q), per[q], sc[q], mt[q], exp)
+        own = np.isin(per[q], hits[q, :int(counts[q])]["doc"])
+        assert mt[q][own].all(), ("score docs: a hit of the run does not match", q)
 
 
 def main():
@@ -556,6 +577,8 @@ def main():
             hits, counts, totals = (x.copy() for x in b.run().results())
             parity.check_single_segment(seg, filters, scorer, k, hits, counts, totals)
             match_round(b, seg, filters, totals)
+            import test_score_docs as ts
+            score_docs_round(b, seg, rng, [ts.want_flat(seg, f, [], scorer) for f in filters], hits, counts)
             if args.doc_sets:
                 queries += doc_set_round(sr, seg, filters, scorer, k, st, rng)
             if rounds % 3 == 1:   # irs::Not: some queries lose the docs of 1-2 excluded terms

@@ -88,6 +88,10 @@ def main():
                          "bitset + its count, and the counts alone) instead of run + results; the scored "
                          "step of the same batch and, for --op or, irs_hip_bit_union_counts over the "
                          "same term sets are timed next to it; then exits")
+    ap.add_argument("--score-docs", default="",
+                    help="comma list N,...: time irs_hip_batch_score_docs_to_device for N docs per query — once "
+                         "a uniform sample, once the run's own top N — beside the same batch's run "
+                         "(--op or | and | mm | tree); then exits")
     ap.add_argument("--doc-set", default="",
                     help="restrict every query to one doc set (irs_hip_batch_set_doc_sets): range:SHARE = a "
                          "contiguous doc range holding SHARE of the docs, random:SHARE = docs drawn uniformly, "
@@ -130,6 +134,64 @@ def main():
     scorer = {"bm25": BM25(), "tfidf": TFIDF(True), "bm15": BM25(1.2, 0.0)}[args.scorer]
     st = search.SegmentStats(seg.docs_with_field, seg.total_term_freq,
                              np.asarray(seg.metas["docs_count"]))
+    if args.score_docs:
+        # irs_hip_batch_score_docs_to_device beside the same batch's run: per N, a uniform sample of N
+        # docs per query and the run's own top N (sorted by doc); warm-up call, median of --steps
+        if args.op not in ("or", "and", "mm", "tree") or len(term_counts) > 1:
+            raise SystemExit("--score-docs goes with --op or | and | mm | tree and one --terms")
+        counts = [int(x) for x in args.score_docs.split(",")]
+        if min(counts) < 1 or max(counts) > _lib.MAX_K:
+            raise SystemExit("--score-docs N: 1..%d" % _lib.MAX_K)
+        flags = {}
+        if args.op == "tree":   # --shape nest: an Or of (a AND (b OR (c AND d))) over every four entries
+            if args.terms % 4:
+                raise SystemExit("--op tree --score-docs: --terms is a multiple of 4")
+            flags = {"boolean_trees": True}
+            filters = []
+            for row in ranks:
+                lv = [by_term(int(r) - 1) for r in row]
+                quads = [And([q[0], Or([q[1], And([q[2], q[3]])])]) for q in (lv[i:i + 4] for i in range(0, len(lv), 4))]
+                filters.append(quads[0] if len(quads) == 1 else Or(quads))
+        _, stride = (int(x) for x in args.configs.split(",")[0].split(":"))
+        b = sr.batch(search.prepare(filters, scorer, [st], **flags), max(args.k, max(counts))).configure(0, stride, 0)
+        b.set_async(False)   # (the whole run is queued when run() returns: a device synchronize times it)
+        b.run()
+        hits, cnt, totals = (x.copy() for x in b.results())
+        steps = max(args.steps, 5)
+
+        def median_ms(fn):
+            fn()
+            torch.cuda.synchronize()
+            ms = []
+            for _ in range(steps):
+                t0 = time.perf_counter()
+                fn()
+                torch.cuda.synchronize()
+                ms.append((time.perf_counter() - t0) * 1e3)
+            return float(np.median(ms)), float(np.min(ms))
+        run_ms = median_ms(lambda: b.run())
+        print("%s terms=%d  %d queries x %d docs  run (k=%d): median %.3f ms, min %.3f ms  hits/query mean %.0f" % (
+            args.op, args.terms, len(filters), args.docs, b.k, *run_ms, float(np.mean(totals))), flush=True)
+        rng = np.random.default_rng(synth.SEED + 6)
+        for n in counts:
+            lists = {"sample": [np.sort(rng.choice(args.docs, n, replace=False).astype(np.uint32) + 1) for _ in filters],
+                     "top": [np.sort(hits[q, :min(n, int(cnt[q]))]["doc"].astype(np.uint32)) for q in range(len(filters))]}
+            for name, per in lists.items():
+                offs = np.concatenate([[0], np.cumsum([p.size for p in per])]).astype(np.uint64)
+                flat = np.concatenate(per)
+                d_docs = torch.from_numpy(flat.view(np.int32)).cuda()
+                d_offs = torch.from_numpy(offs.view(np.int64)).cuda()
+                d_sc = torch.empty(flat.size, dtype=torch.float32, device="cuda")
+                d_mt = torch.empty(flat.size, dtype=torch.uint8, device="cuda")
+                ms = median_ms(lambda: b.score_docs_to_device(d_docs.data_ptr(), d_offs.data_ptr(), flat.size,
+                                                             d_sc.data_ptr(), d_mt.data_ptr()))
+                matched = int(d_mt.sum().item())
+                if name == "top" and not args.nocheck:
+                    assert matched == flat.size, "a hit of the run does not match"
+                print("  score_docs N=%-5d %-6s  %8d docs  matched %8d  median %.3f ms, min %.3f ms  (run / call %.2f)" % (
+                    n, name, flat.size, matched, *ms, run_ms[0] / ms[0]), flush=True)
+        b.close()
+        sys.exit(0)
     if args.op == "tree":
         # one line per SHAPE: the rows of --op terms at the same --terms, put together as trees
         if len(term_counts) > 1 or not 2 <= args.terms <= 16:

@@ -915,6 +915,73 @@ int irs_hip_batch_score_docs(irs_hip_batch* batch, const uint32_t* docs, const u
 int irs_hip_batch_score_docs_to_device(irs_hip_batch* batch, const void* d_docs, const void* d_offsets,
                                        uint64_t n_docs, void* d_scores, void* d_matched, void* stream);
 
+/* ByNestedFilter, the block join (core/search/nested_filter.{hpp,cpp}) — a compatible addition to
+ * ABI 12.  Child documents are stored in front of their parent; the batch's queries are the CHILD
+ * filter; the hits are the parents whose block of children satisfies a match rule, scored by a merge
+ * of their children's scores.
+ * Inputs.  Unit u = segment * n_queries + query, as everywhere.  d_parents: per segment of the batch
+ * one row of a device bitset, [n_segs][n_words] u64 in irs_hip_bit_union's layout (bit index = doc
+ * id); bit 0 and the bits above the segment's num_docs are ignored.
+ * Blocks.  P = the parent docs of the unit's segment, prev(p) = the largest parent below p (0 if
+ * none): the block of p is the docs in (prev(p), p) — ChildToParentJoin::FirstChildApprox /
+ * SeekInternal, nested_filter.cpp:165-186.  Docs above the last parent belong to nobody.
+ * The unit's child set C is what irs_hip_batch_match_sets returns for the unit — so without the
+ * segment's deleted docs, the unit's IRS_HIP_EXCLUDE terms and its doc set — with EVERY PARENT DOC
+ * REMOVED.  That is a definition made here: the reference assumes the child filter matches no
+ * parent, and its matchers disagree about what happens when it does (AnyMatcher::Accept :272-276
+ * skips such a hit, RangeMatcher / MinMatcher :393-440, :474-522 count it).
+ * Matching.  c(p) = |C ∩ block(p)|.  A parent is a hit iff it is not deleted in the segment and
+ * match_min <= c(p) <= match_max; match_max = IRS_HIP_NESTED_NO_MAX: no maximum.  A deleted parent
+ * still delimits blocks.
+ *   {0, 0}       kMatchNone :242-263   c(p) == 0; every hit scores none_boost
+ *   {1, none}    kMatchAny  :265-299   c(p) >= 1
+ *   {min, none}  MinMatcher :461-555   c(p) >= min; min == 0: every live parent
+ *   {min, max}   RangeMatcher :377-459 min <= c(p) <= max
+ * Score of a hit (except under {0, 0}): the merge (IRS_HIP_MERGE_SUM / MAX / MIN) over the scores of
+ * the children in C ∩ block(p), each what irs_hip_batch_score_docs gives it under the unit, merged in
+ * float32 in ascending doc order, the value starting from the first child's score (child_score(res)
+ * then merger(res, temp), :292-296, :426-436).  A hit with c(p) == 0 scores 0.  A quirk kept: under
+ * {0, none} the buffer starts from 0 (:477-485, :539-547) — SUM and MAX are unaffected, MIN scores 0
+ * for every parent.
+ * Results.  total_hits[u] = the hit parents; the top k is the unit's query's own k, ordered (score
+ * desc, doc asc).  k, min scores, wand, the path, paired tiles, a shared threshold and a communicator
+ * of the child batch play no part.  Like irs_hip_batch_match_sets the calls may come before, after or
+ * without irs_hip_batch_run and leave the batch's results, irs_hip_batch_reruns and later runs as
+ * they would have been.  Nothing is pruned (the reference prunes nothing either: :644).
+ * Not offered: the predicate form of `match` (PredMatcher), kNoop merges.
+ * IRS_HIP_EINVAL: a NULL batch, descriptor or d_parents; 64 * n_words <= num_docs of a segment of the
+ * batch or n_words > 2^26; match_min > match_max; a merge outside the three; a negative or non-finite
+ * none_boost; k_stride below the batch's largest k; every output NULL.  IRS_HIP_EUNSUPPORTED, all
+ * calls: what irs_hip_batch_match_sets refuses (IRS_HIP_OP_MULTITERM, IRS_HIP_CLAUSE_AND,
+ * IRS_HIP_TREE_NODE units); _topk in addition: what irs_hip_batch_score_docs refuses
+ * (IRS_HIP_OP_PHRASE units) — except under {0, 0}, which needs no child score; a unit with 2^31 or
+ * more hit parents, or children under them.  IRS_HIP_ENOMEM: the pool cannot serve the scratch (the
+ * child rows, [n_units][n_words] u64; for _topk the hit rows too, and per group of units the
+ * children's lists, their scores and the candidate keys: IRS_HIP_NESTED_SCRATCH_MB, read per call,
+ * default 256, bounds a group — a batch that exceeds it runs in several groups, never fails for it). */
+#define IRS_HIP_NESTED_NO_MAX 0xFFFFFFFFu
+typedef struct irs_hip_nested {
+  const void* d_parents;  /* device, [n_segs][n_words] u64; borrowed for the call */
+  uint64_t n_words;       /* 64 * n_words > num_docs of every segment of the batch, <= 2^26 */
+  uint32_t match_min, match_max;
+  uint32_t merge;         /* irs_hip_merge */
+  float none_boost;       /* used under {0, 0} only; >= 0 */
+} irs_hip_nested;
+/* The hit parents of every unit, unscored: rows [n_units][n_words] (every word written, those beyond
+ * the segment as 0) and / or their populations; either output may be NULL, not both.  Synchronous. */
+int irs_hip_batch_nested_sets(irs_hip_batch* batch, const irs_hip_nested* nested, uint64_t* sets,
+                              uint64_t* counts);
+/* The same into device memory (d_sets [n_units][n_words] u64, d_counts [n_units] u64), on `stream`,
+ * so that a nested filter chains into irs_hip_batch_set_doc_sets of a parent-level batch without the
+ * rows crossing to the host.  The child rows are scratch of the call: it returns when the stream has
+ * run it. */
+int irs_hip_batch_nested_sets_to_device(irs_hip_batch* batch, const irs_hip_nested* nested, void* d_sets,
+                                        void* d_counts, void* stream);
+/* The k best hit parents of every unit: hits[u * k_stride + i], counts[u], total_hits[u] (any of
+ * them may be NULL, not all).  Synchronous. */
+int irs_hip_batch_nested_topk(irs_hip_batch* batch, const irs_hip_nested* nested, irs_hip_hit* hits,
+                              uint32_t k_stride, uint32_t* counts, uint64_t* total_hits);
+
 /* Doc-set filters (a compatible addition to ABI 12): the units of a batch restricted to doc sets on
  * the device — the conjunction of a scored query with an UNSCORED child: the bitset_doc_iterator a
  * multi-term query builds from its unscored terms (multiterm_query.cpp:36-87, 133-166), a

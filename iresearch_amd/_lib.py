@@ -30,6 +30,7 @@ PHRASE_OR = 0x4000   # ... into a phrase entry's kind: the first word of an alte
 TREE_NODE = 0x8000   # the kind of a node entry: TREE_NODE | node op [| EXCLUDE]; phrase_offset = span | min_match << 16
 NO_TERM = 0xFFFFFFFF
 NO_DOC_SET = 0xFFFFFFFF   # row_of_unit of an unrestricted unit (irs_hip_batch_set_doc_sets)
+NESTED_NO_MAX = 0xFFFFFFFF   # irs_hip_nested.match_max: no maximum
 PATH_AUTO, PATH_ITEMS, PATH_JOINED = 0, 1, 2
 WAND_NONE, WAND_DIV_NORM, WAND_MAX_FREQ, WAND_MIN_NORM = 0, 1, 2, 3   # Scorer::WandType
 MAX_TERMS, MAX_K, MAX_PHRASE_TERMS, MAX_EXCLUDED = 16, 4096, 8, 16
@@ -62,6 +63,12 @@ class SegmentDesc(C.Structure):
         ("pos_features", C.c_uint32), ("norm_kind", C.c_uint32), ("wand_type", C.c_uint32),
         ("doc_mask", C.c_void_p), ("doc_mask_count", C.c_uint64),
     ]
+
+
+class Nested(C.Structure):
+    """irs_hip_nested: the parent rows and the match rule of irs_hip_batch_nested_*."""
+    _fields_ = [("d_parents", C.c_void_p), ("n_words", C.c_uint64), ("match_min", C.c_uint32),
+                ("match_max", C.c_uint32), ("merge", C.c_uint32), ("none_boost", C.c_float)]
 
 
 class StreamCacheStats(C.Structure):
@@ -97,6 +104,7 @@ SYMBOLS = (
     "irs_hip_batch_touched", "irs_hip_batch_unit_mask",
     "irs_hip_batch_match_sets", "irs_hip_batch_match_sets_to_device",
     "irs_hip_batch_score_docs", "irs_hip_batch_score_docs_to_device",
+    "irs_hip_batch_nested_sets", "irs_hip_batch_nested_sets_to_device", "irs_hip_batch_nested_topk",
     "irs_hip_batch_set_doc_sets", "irs_hip_batch_set_doc_sets_host", "irs_hip_batch_doc_set_stats",
     "irs_hip_comm_unique_id", "irs_hip_comm_init_rank", "irs_hip_comm_destroy",
     "irs_hip_comm_library",
@@ -193,6 +201,17 @@ def bind(L: C.CDLL) -> C.CDLL:
     L.irs_hip_batch_score_docs.restype = C.c_int
     L.irs_hip_batch_score_docs_to_device.argtypes = [vp, vp, vp, u64, vp, vp, vp]
     L.irs_hip_batch_score_docs_to_device.restype = C.c_int
+    L.irs_hip_batch_nested_sets.argtypes = [vp, P(Nested), vp, vp]
+    L.irs_hip_batch_nested_sets.restype = C.c_int
+    L.irs_hip_batch_nested_sets_to_device.argtypes = [vp, P(Nested), vp, vp, vp]
+    L.irs_hip_batch_nested_sets_to_device.restype = C.c_int
+    L.irs_hip_batch_nested_topk.argtypes = [vp, P(Nested), vp, u32, vp, vp]
+    L.irs_hip_batch_nested_topk.restype = C.c_int
+    L.irs_hip_device_alloc.argtypes, L.irs_hip_device_alloc.restype = [i32, u64, P(vp)], C.c_int
+    L.irs_hip_device_free.argtypes, L.irs_hip_device_free.restype = [i32, vp], None
+    L.irs_hip_device_upload.argtypes, L.irs_hip_device_upload.restype = [i32, vp, vp, u64], C.c_int
+    L.irs_hip_device_download.argtypes, L.irs_hip_device_download.restype = [i32, vp, vp, u64], C.c_int
+    L.irs_hip_device_sync.argtypes, L.irs_hip_device_sync.restype = [i32, vp], C.c_int
     L.irs_hip_batch_set_doc_sets.argtypes = [vp, vp, u64, u64, vp]
     L.irs_hip_batch_set_doc_sets.restype = C.c_int
     L.irs_hip_batch_set_doc_sets_host.argtypes = [vp, vp, u64, u64, vp]

@@ -813,6 +813,19 @@ class SegmentReader {
 
 // ---- a batch of prepared queries on one or several segments of one device -------------------
 class DeviceBuffer;
+// ByNestedOptions (nested_filter.hpp): how many children of a parent's block must match, and how
+// their scores merge into the parent's.  The predicate form of `match` and kNoop merges are not
+// offered.
+struct Match {
+  uint32_t min = 1, max = IRS_HIP_NESTED_NO_MAX;   // max == IRS_HIP_NESTED_NO_MAX: no maximum
+};
+inline constexpr Match kMatchNone{0, 0};
+inline constexpr Match kMatchAny{1, IRS_HIP_NESTED_NO_MAX};
+struct Nested {
+  Match match = kMatchAny;
+  irs_hip_merge merge_type = IRS_HIP_MERGE_SUM;
+  float none_boost = 1.f;   // the score of a hit under kMatchNone (the filter's boost)
+};
 class QueryBatch {
  public:
   struct Results {
@@ -1133,6 +1146,47 @@ class QueryBatch {
           "irs_hip_batch_score_docs_to_device");
     return *this;
   }
+  // ByNestedFilter (nested_filter.cpp; irs_hip_batch_nested_sets / _topk): the batch's queries are
+  // the CHILD filter, d_parents the parent docs of every segment as device bitsets
+  // [n_segments][n_words] u64 (bit = doc id; borrowed for the call).  nested_sets: the parents whose
+  // block of children satisfies opts.match, as rows [segment][query][n_words] and their populations;
+  // nested_topk: the k best of them per (segment, query), scored by opts.merge_type over their matching
+  // children's scores.  Queries that are all boolean or all by_phrase (one device batch); a by_phrase
+  // batch is scored under kMatchNone only.  Independent of run().
+  MatchSets nested_sets(const void* d_parents, uint64_t n_words, const Nested& opts = {}, bool sets = true) {
+    const irs_hip_nested d = nested_desc(d_parents, n_words, opts);
+    MatchSets r;
+    r.n_segments = n_segments_;
+    r.n_queries = n_queries_;
+    r.n_words = sets ? n_words : 0;
+    const size_t units = size_t(n_segments_) * n_queries_;
+    r.counts.resize(units);
+    if (sets) r.words.resize(units * n_words);
+    check(irs_hip_batch_nested_sets(single_part(), &d, sets ? r.words.data() : nullptr, r.counts.data()),
+          "irs_hip_batch_nested_sets");
+    return r;
+  }
+  QueryBatch& nested_sets_to_device(const void* d_parents, uint64_t n_words, const Nested& opts, void* d_sets,
+                                    void* d_counts, void* stream = nullptr) {
+    const irs_hip_nested d = nested_desc(d_parents, n_words, opts);
+    check(irs_hip_batch_nested_sets_to_device(single_part(), &d, d_sets, d_counts, stream),
+          "irs_hip_batch_nested_sets_to_device");
+    return *this;
+  }
+  Results nested_topk(const void* d_parents, uint64_t n_words, const Nested& opts = {}) {
+    const irs_hip_nested d = nested_desc(d_parents, n_words, opts);
+    Results r;
+    r.n_segments = n_segments_;
+    r.n_queries = n_queries_;
+    r.k = k_;
+    const size_t units = size_t(n_segments_) * n_queries_;
+    r.hits.resize(units * k_);
+    r.counts.resize(units);
+    r.total_hits.resize(units);
+    check(irs_hip_batch_nested_topk(single_part(), &d, r.hits.data(), k_, r.counts.data(), r.total_hits.data()),
+          "irs_hip_batch_nested_topk");
+    return r;
+  }
   // The doc sets the queries' by_doc_set children name rows of (irs_hip_batch_set_doc_sets):
   // [n_rows][n_words] u64, bit = doc id (irs_hip_bit_union's layout), every segment of the batch
   // reading the same row for a query.  Device memory is BORROWED — valid and unchanged until the
@@ -1172,6 +1226,16 @@ class QueryBatch {
   }
   // the one device batch of a list of queries that are all boolean or all by_phrase
   // (what search_sharded hands to irs_hip_batch_results_to_device)
+  static irs_hip_nested nested_desc(const void* d_parents, uint64_t n_words, const Nested& opts) {
+    irs_hip_nested d{};
+    d.d_parents = d_parents;
+    d.n_words = n_words;
+    d.match_min = opts.match.min;
+    d.match_max = opts.match.max;
+    d.merge = uint32_t(opts.merge_type);
+    d.none_boost = opts.none_boost;
+    return d;
+  }
   irs_hip_batch* single_part() const {
     if (part_[0].h && part_[1].h) throw not_supported(IRS_HIP_EUNSUPPORTED, "mixed boolean / phrase batch");
     return part_[0].h ? part_[0].h : part_[1].h;

@@ -40,6 +40,7 @@
 #include "excl.h"
 #include "match.h"
 #include "score_docs.h"
+#include "nested.h"
 
 using namespace irs_hip;
 
@@ -56,6 +57,7 @@ using namespace irs_hip;
 #include "plan_join.h"
 #include "plan_match.h"
 #include "plan_score_docs.h"
+#include "plan_nested.h"
 #include "units.h"
 
 namespace {
@@ -1566,6 +1568,19 @@ int irs_hip_batch_score_docs_to_device(irs_hip_batch* b, const void* d_docs, con
     return batch_score_docs_impl(b, nullptr, nullptr, nullptr, nullptr, d_docs, d_offsets, n_docs, d_scores,
                                  d_matched, static_cast<rt::stream_t>(stream), true);
   });
+}
+int irs_hip_batch_nested_sets(irs_hip_batch* b, const irs_hip_nested* nested, uint64_t* sets, uint64_t* counts) {
+  return settled(b, [&] { return batch_nested_sets_impl(b, nested, sets, counts, nullptr, nullptr, nullptr, false); });
+}
+int irs_hip_batch_nested_sets_to_device(irs_hip_batch* b, const irs_hip_nested* nested, void* d_sets, void* d_counts,
+                                        void* stream) {
+  return settled(b, [&] {
+    return batch_nested_sets_impl(b, nested, nullptr, nullptr, d_sets, d_counts, static_cast<rt::stream_t>(stream), true);
+  });
+}
+int irs_hip_batch_nested_topk(irs_hip_batch* b, const irs_hip_nested* nested, irs_hip_hit* hits, uint32_t k_stride,
+                              uint32_t* counts, uint64_t* total_hits) {
+  return settled(b, [&] { return batch_nested_topk_impl(b, nested, hits, k_stride, counts, total_hits); });
 }
 int irs_hip_batch_plan(irs_hip_batch* b, void* stream) {
   return settled(b, [&] { return batch_plan_impl(b, stream); });

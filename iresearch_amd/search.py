@@ -957,6 +957,42 @@ def prepare_filters(filters, scorer, segment_stats, segs, k):
     return QueryArrays(len(segs), queries, terms, k)
 
 
+class DeviceBuffer:
+    """Device memory by irs_hip_device_alloc / _upload / _download: what a caller without a HIP
+    toolchain of its own hands to the *_to_device calls.  `ptr` is the device address."""
+
+    def __init__(self, L, device: int, nbytes: int):
+        self.L, self.device, self.nbytes = L, int(device), int(nbytes)
+        p = C.c_void_p()
+        _lib.check(L, L.irs_hip_device_alloc(self.device, max(self.nbytes, 8), C.byref(p)), "irs_hip_device_alloc")
+        self.ptr = p.value
+
+    def upload(self, arr):
+        arr = np.ascontiguousarray(arr)
+        assert arr.nbytes <= self.nbytes
+        _lib.check(self.L, self.L.irs_hip_device_upload(self.device, self.ptr, arr.ctypes.data, arr.nbytes),
+                   "irs_hip_device_upload")
+        return self
+
+    def download(self, dtype, shape):
+        out = np.empty(shape, dtype)
+        assert out.nbytes <= self.nbytes
+        _lib.check(self.L, self.L.irs_hip_device_download(self.device, out.ctypes.data, self.ptr, out.nbytes),
+                   "irs_hip_device_download")
+        return out
+
+    def close(self):
+        if self.ptr:
+            self.L.irs_hip_device_free(self.device, self.ptr)
+            self.ptr = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:   # (interpreter shutdown: the library may be gone)
+            pass
+
+
 class QueryBatch:
     """A batch of prepared queries on one segment — or on several segments of one device
     at once (irs_hip_batch_create_multi): then every result array gets a leading segment
@@ -1225,6 +1261,76 @@ class QueryBatch:
             self.handle, d_docs, d_offsets, int(n_docs), d_scores, d_matched, stream),
             "irs_hip_batch_score_docs_to_device")
         return self
+
+    def _nested(self, parents, match, merge, none_boost, n_words=None):
+        """(irs_hip_nested, what keeps its parent rows alive): `parents` a numpy u64[n_segs][n_words]
+        array — uploaded for the call — or a device address with n_words."""
+        lo, hi = match
+        d = _lib.Nested()
+        d.match_min = int(lo)
+        d.match_max = _lib.NESTED_NO_MAX if hi is None else int(hi)
+        d.merge, d.none_boost = int(merge), float(none_boost)
+        if isinstance(parents, np.ndarray):
+            arr = np.ascontiguousarray(parents, np.uint64)
+            if arr.ndim == 1:
+                arr = arr.reshape(1, -1)
+            if arr.ndim != 2 or arr.shape[0] != len(self.segs):
+                raise ValueError("parents: u64[n_segs][n_words], a row per segment of the batch")
+            buf = DeviceBuffer(self.L, self.seg.device, arr.nbytes).upload(arr)
+            d.d_parents, d.n_words = buf.ptr, arr.shape[1]
+            return d, buf
+        if n_words is None:
+            raise ValueError("parents by device address: n_words")
+        d.d_parents, d.n_words = int(parents), int(n_words)
+        return d, None
+
+    def nested_sets(self, parents, match=(1, None), merge=MERGE_SUM, none_boost=0.0, sets=True, n_words=None):
+        """ByNestedFilter, unscored (irs_hip_batch_nested_sets): the batch's queries are the child
+        filter, `parents` the parent docs of every segment as bitsets (bit = doc id).  Returns
+        (sets u64[units][n_words] or None, counts u64[units]): the parents whose block of children
+        holds match = (min, max) of them (max None: no maximum; (0, 0): none; (1, None): any)."""
+        d, keep = self._nested(parents, match, merge, none_boost, n_words)
+        try:
+            out = np.empty((self.nq, int(d.n_words)), np.uint64) if sets else None
+            counts = np.empty(self.nq, np.uint64)
+            _lib.check(self.L, self.L.irs_hip_batch_nested_sets(
+                self.handle, C.byref(d), out.ctypes.data if sets else None, counts.ctypes.data),
+                "irs_hip_batch_nested_sets")
+        finally:
+            if keep is not None:
+                keep.close()
+        return out, counts
+
+    def nested_sets_to_device(self, parents, d_sets, d_counts, match=(1, None), merge=MERGE_SUM,
+                              none_boost=0.0, n_words=None, stream=None):
+        """The same into device memory (irs_hip_batch_nested_sets_to_device): d_sets
+        u64[units][n_words], d_counts u64[units], device addresses, either may be None — rows that
+        irs_hip_batch_set_doc_sets of a parent-level batch takes as they are."""
+        d, keep = self._nested(parents, match, merge, none_boost, n_words)
+        try:
+            _lib.check(self.L, self.L.irs_hip_batch_nested_sets_to_device(
+                self.handle, C.byref(d), d_sets, d_counts, stream), "irs_hip_batch_nested_sets_to_device")
+        finally:
+            if keep is not None:
+                keep.close()
+        return self
+
+    def nested_topk(self, parents, match=(1, None), merge=MERGE_SUM, none_boost=0.0, n_words=None):
+        """ByNestedFilter, scored (irs_hip_batch_nested_topk): (hits HIT[units][k], counts[units],
+        totals[units]) — every unit's k best hit parents, each scored by `merge` over its matching
+        children's scores ((0, 0): none_boost), ordered (score desc, doc asc)."""
+        d, keep = self._nested(parents, match, merge, none_boost, n_words)
+        try:
+            hits = np.zeros((self.nq, self.k), HIT)
+            counts = np.zeros(self.nq, np.uint32)
+            totals = np.zeros(self.nq, np.uint64)
+            _lib.check(self.L, self.L.irs_hip_batch_nested_topk(
+                self.handle, C.byref(d), hits.ctypes.data, self.k, counts.ctypes.data, totals.ctypes.data),
+                "irs_hip_batch_nested_topk")
+        finally:
+            if keep is not None:
+                keep.close()
+        return hits, counts, totals
 
     def touched(self):
         """(`.doc` + norm bytes decoded, positions read) by the last run (And / by_phrase)."""

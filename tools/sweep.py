@@ -92,6 +92,11 @@ def main():
                     help="comma list N,...: time irs_hip_batch_score_docs_to_device for N docs per query — once "
                          "a uniform sample, once the run's own top N — beside the same batch's run "
                          "(--op or | and | mm | tree); then exits")
+    ap.add_argument("--nested", default="",
+                    help="comma list B,...: ByNestedFilter with the queries as the child filter and every "
+                         "(B+1)-th doc a parent (B children per parent): times irs_hip_batch_nested_sets (rows + "
+                         "counts), nested_sets_to_device and nested_topk under kMatchAny / SUM beside the same "
+                         "batch's run (--op or | and); then exits")
     ap.add_argument("--doc-set", default="",
                     help="restrict every query to one doc set (irs_hip_batch_set_doc_sets): range:SHARE = a "
                          "contiguous doc range holding SHARE of the docs, random:SHARE = docs drawn uniformly, "
@@ -190,6 +195,51 @@ def main():
                     assert matched == flat.size, "a hit of the run does not match"
                 print("  score_docs N=%-5d %-6s  %8d docs  matched %8d  median %.3f ms, min %.3f ms  (run / call %.2f)" % (
                     n, name, flat.size, matched, *ms, run_ms[0] / ms[0]), flush=True)
+        b.close()
+        sys.exit(0)
+    if args.nested:
+        # the three nested calls beside the same batch's run: warm-up call, median of --steps; per B the
+        # parents are the docs B + 1, 2 (B + 1), ...
+        if args.op not in ("or", "and") or len(term_counts) > 1:
+            raise SystemExit("--nested goes with --op or | and and one --terms")
+        sizes = [int(x) for x in args.nested.split(",")]
+        if min(sizes) < 1:
+            raise SystemExit("--nested B: children per parent, 1 or more")
+        _, stride = (int(x) for x in args.configs.split(",")[0].split(":"))
+        b = sr.batch(search.prepare(filters, scorer, [st]), args.k).configure(0, stride, 0)
+        b.set_async(False)   # (the whole run is queued when run() returns: a device synchronize times it)
+        steps = max(args.steps, 5)
+
+        def median_ms(fn):
+            fn()
+            torch.cuda.synchronize()
+            ms = []
+            for _ in range(steps):
+                t0 = time.perf_counter()
+                fn()
+                torch.cuda.synchronize()
+                ms.append((time.perf_counter() - t0) * 1e3)
+            return float(np.median(ms)), float(np.min(ms))
+        run_ms = median_ms(lambda: b.run())
+        print("%s terms=%d  %d queries x %d docs  run (k=%d): median %.3f ms, min %.3f ms" % (
+            args.op, args.terms, len(filters), args.docs, b.k, *run_ms), flush=True)
+        nw = b.match_words()
+        d_sets = torch.empty((b.nq, nw), dtype=torch.int64, device="cuda")
+        d_counts = torch.empty(b.nq, dtype=torch.int64, device="cuda")
+        for bsz in sizes:
+            par = np.zeros(64 * nw, bool)
+            par[np.arange(bsz + 1, args.docs + 1, bsz + 1)] = True
+            d_par = torch.from_numpy(np.packbits(par, bitorder="little").view(np.int64)).cuda()
+            ptr = d_par.data_ptr()
+            host = median_ms(lambda: b.nested_sets(ptr, n_words=nw))
+            dev = median_ms(lambda: b.nested_sets_to_device(ptr, d_sets.data_ptr(), d_counts.data_ptr(), n_words=nw))
+            top = median_ms(lambda: b.nested_topk(ptr, n_words=nw))
+            totals = b.nested_topk(ptr, n_words=nw)[2]
+            if not args.nocheck:
+                assert np.array_equal(d_counts.cpu().numpy().astype(np.uint64), totals), "sets and top k disagree"
+            print("  nested B=%-4d %8d parents  hits/query mean %.0f  sets %.3f / %.3f ms  sets_to_device %.3f / %.3f ms  "
+                  "topk %.3f / %.3f ms  (median / min; run / topk %.2f)" % (
+                      bsz, int(par.sum()), float(np.mean(totals)), *host, *dev, *top, run_ms[0] / top[0]), flush=True)
         b.close()
         sys.exit(0)
     if args.op == "tree":
